@@ -32,6 +32,18 @@ over ranks.  The dominant kernel's launch duration is measured live with HIP eve
 it is launched on, and feeds `roofline`.  `cpu_baseline` times the reference's own CPU
 implementation (oracle/_ref when present, else the C restatement oracle/) on one host core over a
 bounded sample of the same workload shape (rank 0, N=1 only).
+
+Plain run and --full: `bench.py --gpus 1 --steps K --warmup W` does only what the headline needs -- it
+builds the engine, warms up, times the K steps and prints the result line (`value`, `ms_per_step`,
+`khz_per_utterance`, ...).  Its batch is three tiles of 16 utterances per CU (48 x CUs; 12 288 on an
+MI355X), the batch the real-time sweep settles on, so that the same arguments always time the same
+workload.  `--full` adds everything else as before: the real-time batch sweep (and times the batch
+it picks), `reference_definition`, `end_to_end`, `dropin_fp32`, `oversubscribed`, the socket-power
+reading, `roofline` and `cpu_baseline`.
+--dump-outputs DIR: after the timed steps, the samples of the last timed step (what a caller of the
+timed path receives, [batch][samples per step]) go to DIR/samples.npy as float32; above 64 MB, a
+fixed, seeded sample of utterances (their indices in DIR/samples_rows.npy).  Weights, conditioning
+and selectors are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -553,7 +565,8 @@ def free_port():
 
 
 def spawn_ranks(args):
-    """`python bench.py --gpus N` outside a launcher: re-execute under torch.distributed.run with N local ranks."""
+    """`python bench.py --gpus N` outside a launcher: run torch.distributed.run with N local ranks as a child process
+    (a fresh process, not an exec of this one, which may already have opened the GPU runtime) and exit with its status."""
     if args.backend == "nccl":
         import torch
         have = torch.cuda.device_count()
@@ -561,7 +574,8 @@ def spawn_ranks(args):
             sys.exit("bench.py: --gpus %d but only %d GPU(s) are visible" % (args.gpus, have))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)          # (a child killed by signal s: 128 + s, like a shell)
 
 
 def prove_world(dist, world, rank, local_rank, backend):
@@ -708,28 +722,57 @@ def power_reading(e, N, NTOT, B, sptr, seconds=3.0):
         return {"error": str(ex)[:200]}
 
 
+DUMP_MAX_BYTES = 64 << 20                     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, y, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: the samples of the last timed step, y [batch][samples] (integers), as out_dir/samples.npy in float32 (exact
+    for sample indices).  Above max_bytes, a fixed, seeded sample of utterances (rows) in ascending order, whose indices go to
+    out_dir/samples_rows.npy (float64); the two files together stay within max_bytes.  Returns the paths written."""
+    y = np.asarray(y)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    rows_keep = max(1, (max_bytes - 512) // (4 * y.shape[1] + 8))       # (float32 samples and a float64 index per row, two .npy headers)
+    if y.shape[0] > rows_keep:
+        rows = np.sort(np.random.default_rng(seed).choice(y.shape[0], size=rows_keep, replace=False))
+        y = y[rows]
+        paths.append(os.path.join(out_dir, "samples_rows.npy"))
+        np.save(paths[-1], rows.astype(np.float64))
+    paths.append(os.path.join(out_dir, "samples.npy"))
+    np.save(paths[-1], y.astype(np.float32))
+    return paths
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--batch", type=int, default=0, help="utterances per GPU (0 = find the max real-time batch)")
+    ap.add_argument("--batch", type=int, default=0, help="utterances per GPU (0 = 48 per CU; with --full, the real-time batch the sweep picks)")
     ap.add_argument("--samples", type=int, default=0, help="samples per step (0 = auto)")
     ap.add_argument("--config", default="headline", choices=["headline", "c5"],
                     help="c5: BASELINE configs[4], global batch 64 sharded over the ranks (8 x 8 on 8 GPUs)")
     ap.add_argument("--conditioning", default="packed", choices=["packed", "features"],
                     help="what the timed launches read: conditioning pre-packed in fragment order (the reference harness's setInputs outside "
                          "the timed region; the headline), or the upsampled features, the conditioning computed in the kernel (profiling aid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-power", action="store_true", help="skip the 3-second socket-power reading behind the timed steps")
-    ap.add_argument("--no-extras", action="store_true", help="skip reference_definition / end_to_end / oversubscribed")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the real-time batch sweep (the timed batch is the one it picks), "
+                         "reference_definition / end_to_end / dropin_fp32 / oversubscribed, socket power, roofline, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples of the last timed step to DIR/samples.npy (float32; a seeded sample of utterances above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
+    ap.add_argument("--no-power", action="store_true", help="(--full) skip the 3-second socket-power reading behind the timed steps")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip reference_definition / end_to_end / oversubscribed")
     ap.add_argument("--extras-budget", type=float, default=240.0,
-                    help="seconds of wall clock the entries beside the headline may take together; what does not fit is reported as skipped")
+                    help="(--full) seconds of wall clock the entries beside the headline may take together; what does not fit is "
+                         "reported as skipped")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for smoke runs)")
     ap.add_argument("--selftest-dist", action="store_true", help="launcher / rendezvous / gather plumbing only (no GPU)")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seed", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     t_main = time.perf_counter()
 
     def note(msg):                               # progress on stderr (stdout carries the one JSON line)
@@ -770,9 +813,9 @@ def main():
     from nv_wavenet_amd.sharding import gather_samples, shard_range
     w = make_weights()
     ncu = torch.cuda.get_device_properties(local_rank).multi_processor_count
-    extras = world == 1 and not args.no_extras and args.config == "headline"
+    extras = world == 1 and args.full and not args.no_extras and args.config == "headline"
 
-    # ---- workload: the largest per-GPU batch that stays real time (bounded bisection, rank 0) ----
+    # ---- workload: the largest per-GPU batch that stays real time (bounded bisection, rank 0; --full only) ----
     sweep = {}
     max_rt = [None, None]                 # the largest real-time batch of the sweep and its kHz per utterance (rank 0)
     c3_b16_khz = None
@@ -781,6 +824,8 @@ def main():
         assert B > 0, "more ranks than utterances"
     elif args.batch:
         B = args.batch
+    elif not args.full:
+        B = 48 * ncu                      # three tiles per CU on every CU: the real-time batch the sweep below settles on
     else:
         choice = torch.zeros(1, dtype=torch.int64, device="cuda")
         if rank == 0:
@@ -1035,7 +1080,7 @@ def main():
     ybuf = [torch.zeros(B, NTOT, dtype=torch.int32, device="cuda") for _ in range(2)]
     stream = torch.cuda.current_stream()
     sptr = stream.cuda_stream
-    gathered_rows = [0]
+    gathered = [None]                           # (world > 1) the last finished gather: [total_batch][N]
     total_batch = 64 if args.config == "c5" else B * world
 
     pending = []
@@ -1045,7 +1090,7 @@ def main():
         # the gather of step i overlaps the kernel of step i+1 (RCCL runs on its own stream); the gather
         # of step i-2 read the buffer this step overwrites, so it is completed first
         while len(pending) > 1:
-            gathered_rows[0] = pending.pop(0)().shape[0]
+            gathered[0] = pending.pop(0)()
         if events is not None:
             events[0].record(stream)
         assert e.run_partial_chunk(STEADY_FROM, N, NTOT, B, sptr)
@@ -1059,7 +1104,7 @@ def main():
     for i in range(args.warmup):
         step(i)
     while pending:
-        gathered_rows[0] = pending.pop(0)().shape[0]
+        gathered[0] = pending.pop(0)()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1069,7 +1114,7 @@ def main():
     for i in range(args.steps):
         step(i, evs[i])
     while pending:
-        gathered_rows[0] = pending.pop(0)().shape[0]
+        gathered[0] = pending.pop(0)()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1078,14 +1123,17 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        assert gathered_rows[0] == total_batch, "the gather returned %d rows, expected %d" % (gathered_rows[0], total_batch)
+        assert gathered[0].shape[0] == total_batch, "the gather returned %d rows, expected %d" % (gathered[0].shape[0], total_batch)
     kern_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps
     ylast = ybuf[(args.steps - 1) % 2][:, STEADY_FROM:]
     hist = int(torch.unique(ylast).numel())
     status = e.chainStatus()
     clock_ghz = e.lastLaunchClockGHz()          # the clock the last timed launch ran at (the chip clocks to its power budget)
+    if args.dump_outputs and rank == 0:
+        note("dump outputs to %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, (gathered[0] if world > 1 else ylast).cpu().numpy())
     power = None
-    if rank == 0 and world == 1 and not args.no_power:
+    if args.full and rank == 0 and world == 1 and not args.no_power:
         note("socket power of the timed launch")
         power = power_reading(e, N, NTOT, B, sptr)
     e.close()
@@ -1103,111 +1151,115 @@ def main():
         bt = 4 if "BT=4" in kname else 3 if "BT=3" in kname else 2 if "BT=2" in kname else 1
         if not args.batch and args.config == "headline" and tiles > ncu:
             assert kname == HEADLINE_KERNELS[bt].replace("RAW=0", "RAW=3" if args.conditioning == "features" else "RAW=0"), kinfo     # the launches the parity tests pin
-        # workgroups (weight-stream passes) per sample
-        passes = (tiles + bt - 1) // bt
-        traffic, lds_counter, traffic_file, counters = None, None, None, None
-        # HBM and LDS bytes per launch from the PMC passes of the latest profiled round (profiles/traffic_rNN.json, written
-        # by scripts/make_profiles_r*.py from rocprofv3 counters); only valid for the launch shape it was measured on
-        # ... AND for the device code it was measured on: the file carries the kernel's name and the sha256 of its instruction stream
-        # (scripts/isa_stats.py sha); a kernel that has changed since drops the counters (the algorithmic bytes are reported, and why)
-        import glob
-        traffic_note = "no counter file for this launch shape (batch %d, %d samples): algorithmic bytes only" % (B, N)
-        sha_now = None
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "scripts"))
-            import isa_stats
-            sub = isa_stats.kernel_sub_of(kname)
-            sha_now = isa_stats.kernel_sha("inst_%d_%d_%d_p16.o" % (HEAD.R, HEAD.S, HEAD.A), sub) if sub else None
-        except Exception:
+        # ---- --full: the roofline of the timed launch (counter files of profiled rounds, the code objects' instruction streams,
+        #      socket power) ----
+        roofline = None
+        if args.full:
+            # workgroups (weight-stream passes) per sample
+            passes = (tiles + bt - 1) // bt
+            traffic, lds_counter, traffic_file, counters = None, None, None, None
+            # HBM and LDS bytes per launch from the PMC passes of the latest profiled round (profiles/traffic_rNN.json, written
+            # by scripts/make_profiles_r*.py from rocprofv3 counters); only valid for the launch shape it was measured on
+            # ... AND for the device code it was measured on: the file carries the kernel's name and the sha256 of its instruction stream
+            # (scripts/isa_stats.py sha); a kernel that has changed since drops the counters (the algorithmic bytes are reported, and why)
+            import glob
+            traffic_note = "no counter file for this launch shape (batch %d, %d samples): algorithmic bytes only" % (B, N)
             sha_now = None
-        for tf in sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r*.json")), reverse=True):
             try:
-                tj = json.load(open(tf))
-                if tj.get("batch") == B and tj.get("samples") == N:
-                    if tj.get("kernel") != kname or not sha_now or tj.get("kernel_sha256") != sha_now:
-                        traffic_note = ("%s was measured on %s, code %s; this run launches %s, code %s: counters dropped" %
-                                        (os.path.relpath(tf, ROOT), tj.get("kernel"), str(tj.get("kernel_sha256"))[:12], kname, str(sha_now)[:12]))
-                        break
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    lds_counter = tj.get("lds_bytes_per_launch")
-                    counters = tj
-                    traffic_file = os.path.relpath(tf, ROOT)
-                    traffic_note = "rocprofv3 counters of this launch shape and this device code (%s)" % traffic_file
-                    break
+                sys.path.insert(0, os.path.join(ROOT, "scripts"))
+                import isa_stats
+                sub = isa_stats.kernel_sub_of(kname)
+                sha_now = isa_stats.kernel_sha("inst_%d_%d_%d_p16.o" % (HEAD.R, HEAD.S, HEAD.A), sub) if sub else None
             except Exception:
-                pass
-        # compulsory HBM bytes per utterance and sample: the conditioning (2R x L fp16 values) or, computed in the kernel, the features
-        # it is computed from (feature fragments: 96 fp16 values), + selector + sample
-        hbm_alg = (2 * 96 + 8) if args.conditioning == "features" else HEAD.hbm_bytes
-        roofline = dict(bound="mfma", achieved=flops / (kern_ms * 1e-3) / 1e12, peak=MFMA_F16_PEAK_TFLOPS,
-                        unit="TFLOP/s", traffic=traffic, traffic_source=traffic_note, kernel=kname, kernel_sha256=sha_now, launch=kinfo,
-                        kernel_ms=kern_ms,
-                        hbm=dict(achieved=units * hbm_alg / (kern_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
-                                 bytes_per_utterance_sample=hbm_alg))
-        roofline["frac"] = roofline["achieved"] / roofline["peak"]
-        # measured inside the kernel (s_memtime ticks over s_memrealtime ticks of workgroup 0): under full load the chip
-        # runs this launch below its 2.4 GHz maximum -- power-limited, profiles/r04_clock_*.json -- and `frac` is against the
-        # peak at 2.4 GHz; frac_at_measured_clock prices the same work against the matrix peak at the clock actually granted
-        if clock_ghz > 0:
-            roofline["shader_clock_ghz"] = clock_ghz
-            roofline["shader_cycles_per_sample"] = kern_ms * 1e-3 / N * clock_ghz * 1e9
-            roofline["frac_at_measured_clock"] = roofline["frac"] * 2.4 / clock_ghz
-        # (round 6: the layers whose dilation is at most the `ring_in_lds=d<=N` of the launch keep their slots in LDS for the whole launch)
-        import re as _re
-        m_ring = _re.search(r"ring_in_lds=d<=(\d+)", kinfo)
-        ring_d = int(m_ring.group(1)) if m_ring else 0
-        d_, ring_layers = 1, 0
-        for _l in range(HEAD.L):
-            ring_layers += 1 if d_ > ring_d else 0
-            d_ = 1 if d_ * 2 > HEAD.maxD else d_ * 2
-        if power:
-            roofline["power"] = power
-            en = energy_roofline(power, kern_ms, B, N, bt, args.conditioning == "features", ring_layers_in_hbm=ring_layers)
-            if en:
-                roofline["energy"] = en
-                # ... and the same price list on what the launch ACTUALLY issued and moved (rocprofv3 counters of this kernel and launch shape,
-                # profiles/traffic_rNN.json): does the sum of the priced operations explain the energy the socket reports?
-                if counters and "prices_nj" in en and not chain_mode:
-                    try:
-                        pn = en["prices_nj"]
-                        mf = HEAD.macs / 8192.0
-                        act = {"mfma": mf * pn["mfma16"], "valu_and_transcendental": counters["valu_per_mfma"] * mf * pn["valu"],
-                               "lds": counters["lds_bytes_per_workgroup_sample"] / (16.0 * bt) / 1024.0 * pn["lds"],
-                               "l2_weight_stream": HEAD.weight_bytes / (16.0 * bt) / 1024.0 * pn["l2"],
-                               "hbm_read": counters["hbm_read_bytes_per_utterance_sample"] / 1024.0 * pn["hbm"],
-                               "hbm_write": counters["hbm_write_bytes_per_utterance_sample"] / 1024.0 * pn["hbmw"]}
-                        en["priced_counters_uj"] = sum(act.values()) * 1e-3
-                        en["priced_counters_parts_uj"] = {k: round(v * 1e-3, 4) for k, v in act.items()}
-                        en["priced_counters_over_achieved"] = en["priced_counters_uj"] / en["achieved_uj"]
-                        en["priced_counters_note"] = ("the price list applied to the instructions issued and bytes moved per utterance-sample (SQ_INSTS_VALU / SQ_INSTS_MFMA, "
-                                                      "SQ_INSTS_LDS_*_BANDWIDTH, FETCH_SIZE x2, WRITE_SIZE of %s): how much of the measured dynamic energy the priced operations explain" % traffic_file)
-                    except Exception:
-                        pass
-            # what binds: with every CU busy the socket sits at its power limit and gives the clock away -- the launch is
-            # bound by joules per utterance-sample, not by the matrix pipe nor by HBM
-            if power.get("limit_w") and power.get("socket_w", 0) >= 0.95 * power["limit_w"]:
-                roofline["bound"] = "power"
-                roofline["bound_evidence"] = ("socket %.0f W of %.0f W with the clock at %.2f GHz (2.4 GHz unconstrained); the MFMA figures below are "
-                                              "kept as the FLOP accounting the harness asks for" % (power["socket_w"], power["limit_w"], power.get("shader_clock_ghz") or 0.0))
-        roofline["hbm"]["frac"] = roofline["hbm"]["achieved"] / HBM_PEAK_GBS
-        # ... and with the dilation ring, which this design keeps in HBM (read x[t-d], write x[t]: 2 x 2R bytes per layer, utterance and
-        # sample): the bytes the kernel actually asks of the memory system (what `traffic` measures), and the roof it is nearest to
-        ring_bytes = 2 * 2 * HEAD.R * ring_layers
-        roofline["ring_layers_in_hbm"] = ring_layers
-        roofline["hbm_with_ring"] = dict(achieved=units * (hbm_alg + ring_bytes) / (kern_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
-                                         bytes_per_utterance_sample=hbm_alg + ring_bytes)
-        roofline["hbm_with_ring"]["frac"] = roofline["hbm_with_ring"]["achieved"] / HBM_PEAK_GBS
-        if not chain_mode:                                      # (the chain reads no weights after its prologue)
-            roofline["l2_weight_stream"] = dict(achieved=passes * N * HEAD.weight_bytes / (kern_ms * 1e-3) / 1e9,
-                                                peak=L2_PEAK_GBS, unit="GB/s")
-            roofline["l2_weight_stream"]["frac"] = roofline["l2_weight_stream"]["achieved"] / L2_PEAK_GBS
-            lds_alg = passes * N * lds_bytes_per_sample(bt)
-            # rocprof-reported when this launch shape was profiled: (SQ_INSTS_LDS_LOAD_BANDWIDTH + SQ_INSTS_LDS_STORE_BANDWIDTH) x 64 B
-            roofline["lds"] = dict(achieved=(lds_counter or lds_alg) / (kern_ms * 1e-3) / 1e9, peak=LDS_PEAK_GBS, unit="GB/s",
-                                   bytes_per_launch=lds_counter or lds_alg, algorithmic_bytes_per_launch=lds_alg,
-                                   source=("rocprofv3 counters of this launch shape (%s)" % traffic_file)
-                                   if lds_counter else "algorithmic bytes (exchange images, bias quads, logits): this launch shape was not profiled")
-            roofline["lds"]["frac"] = roofline["lds"]["achieved"] / LDS_PEAK_GBS
+                sha_now = None
+            for tf in sorted(glob.glob(os.path.join(ROOT, "profiles", "traffic_r*.json")), reverse=True):
+                try:
+                    tj = json.load(open(tf))
+                    if tj.get("batch") == B and tj.get("samples") == N:
+                        if tj.get("kernel") != kname or not sha_now or tj.get("kernel_sha256") != sha_now:
+                            traffic_note = ("%s was measured on %s, code %s; this run launches %s, code %s: counters dropped" %
+                                            (os.path.relpath(tf, ROOT), tj.get("kernel"), str(tj.get("kernel_sha256"))[:12], kname, str(sha_now)[:12]))
+                            break
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        lds_counter = tj.get("lds_bytes_per_launch")
+                        counters = tj
+                        traffic_file = os.path.relpath(tf, ROOT)
+                        traffic_note = "rocprofv3 counters of this launch shape and this device code (%s)" % traffic_file
+                        break
+                except Exception:
+                    pass
+            # compulsory HBM bytes per utterance and sample: the conditioning (2R x L fp16 values) or, computed in the kernel, the features
+            # it is computed from (feature fragments: 96 fp16 values), + selector + sample
+            hbm_alg = (2 * 96 + 8) if args.conditioning == "features" else HEAD.hbm_bytes
+            roofline = dict(bound="mfma", achieved=flops / (kern_ms * 1e-3) / 1e12, peak=MFMA_F16_PEAK_TFLOPS,
+                            unit="TFLOP/s", traffic=traffic, traffic_source=traffic_note, kernel=kname, kernel_sha256=sha_now, launch=kinfo,
+                            kernel_ms=kern_ms,
+                            hbm=dict(achieved=units * hbm_alg / (kern_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
+                                     bytes_per_utterance_sample=hbm_alg))
+            roofline["frac"] = roofline["achieved"] / roofline["peak"]
+            # measured inside the kernel (s_memtime ticks over s_memrealtime ticks of workgroup 0): under full load the chip
+            # runs this launch below its 2.4 GHz maximum -- power-limited, profiles/r04_clock_*.json -- and `frac` is against the
+            # peak at 2.4 GHz; frac_at_measured_clock prices the same work against the matrix peak at the clock actually granted
+            if clock_ghz > 0:
+                roofline["shader_clock_ghz"] = clock_ghz
+                roofline["shader_cycles_per_sample"] = kern_ms * 1e-3 / N * clock_ghz * 1e9
+                roofline["frac_at_measured_clock"] = roofline["frac"] * 2.4 / clock_ghz
+            # (round 6: the layers whose dilation is at most the `ring_in_lds=d<=N` of the launch keep their slots in LDS for the whole launch)
+            import re as _re
+            m_ring = _re.search(r"ring_in_lds=d<=(\d+)", kinfo)
+            ring_d = int(m_ring.group(1)) if m_ring else 0
+            d_, ring_layers = 1, 0
+            for _l in range(HEAD.L):
+                ring_layers += 1 if d_ > ring_d else 0
+                d_ = 1 if d_ * 2 > HEAD.maxD else d_ * 2
+            if power:
+                roofline["power"] = power
+                en = energy_roofline(power, kern_ms, B, N, bt, args.conditioning == "features", ring_layers_in_hbm=ring_layers)
+                if en:
+                    roofline["energy"] = en
+                    # ... and the same price list on what the launch ACTUALLY issued and moved (rocprofv3 counters of this kernel and launch shape,
+                    # profiles/traffic_rNN.json): does the sum of the priced operations explain the energy the socket reports?
+                    if counters and "prices_nj" in en and not chain_mode:
+                        try:
+                            pn = en["prices_nj"]
+                            mf = HEAD.macs / 8192.0
+                            act = {"mfma": mf * pn["mfma16"], "valu_and_transcendental": counters["valu_per_mfma"] * mf * pn["valu"],
+                                   "lds": counters["lds_bytes_per_workgroup_sample"] / (16.0 * bt) / 1024.0 * pn["lds"],
+                                   "l2_weight_stream": HEAD.weight_bytes / (16.0 * bt) / 1024.0 * pn["l2"],
+                                   "hbm_read": counters["hbm_read_bytes_per_utterance_sample"] / 1024.0 * pn["hbm"],
+                                   "hbm_write": counters["hbm_write_bytes_per_utterance_sample"] / 1024.0 * pn["hbmw"]}
+                            en["priced_counters_uj"] = sum(act.values()) * 1e-3
+                            en["priced_counters_parts_uj"] = {k: round(v * 1e-3, 4) for k, v in act.items()}
+                            en["priced_counters_over_achieved"] = en["priced_counters_uj"] / en["achieved_uj"]
+                            en["priced_counters_note"] = ("the price list applied to the instructions issued and bytes moved per utterance-sample (SQ_INSTS_VALU / SQ_INSTS_MFMA, "
+                                                          "SQ_INSTS_LDS_*_BANDWIDTH, FETCH_SIZE x2, WRITE_SIZE of %s): how much of the measured dynamic energy the priced operations explain" % traffic_file)
+                        except Exception:
+                            pass
+                # what binds: with every CU busy the socket sits at its power limit and gives the clock away -- the launch is
+                # bound by joules per utterance-sample, not by the matrix pipe nor by HBM
+                if power.get("limit_w") and power.get("socket_w", 0) >= 0.95 * power["limit_w"]:
+                    roofline["bound"] = "power"
+                    roofline["bound_evidence"] = ("socket %.0f W of %.0f W with the clock at %.2f GHz (2.4 GHz unconstrained); the MFMA figures below are "
+                                                  "kept as the FLOP accounting the harness asks for" % (power["socket_w"], power["limit_w"], power.get("shader_clock_ghz") or 0.0))
+            roofline["hbm"]["frac"] = roofline["hbm"]["achieved"] / HBM_PEAK_GBS
+            # ... and with the dilation ring, which this design keeps in HBM (read x[t-d], write x[t]: 2 x 2R bytes per layer, utterance and
+            # sample): the bytes the kernel actually asks of the memory system (what `traffic` measures), and the roof it is nearest to
+            ring_bytes = 2 * 2 * HEAD.R * ring_layers
+            roofline["ring_layers_in_hbm"] = ring_layers
+            roofline["hbm_with_ring"] = dict(achieved=units * (hbm_alg + ring_bytes) / (kern_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s",
+                                             bytes_per_utterance_sample=hbm_alg + ring_bytes)
+            roofline["hbm_with_ring"]["frac"] = roofline["hbm_with_ring"]["achieved"] / HBM_PEAK_GBS
+            if not chain_mode:                                      # (the chain reads no weights after its prologue)
+                roofline["l2_weight_stream"] = dict(achieved=passes * N * HEAD.weight_bytes / (kern_ms * 1e-3) / 1e9,
+                                                    peak=L2_PEAK_GBS, unit="GB/s")
+                roofline["l2_weight_stream"]["frac"] = roofline["l2_weight_stream"]["achieved"] / L2_PEAK_GBS
+                lds_alg = passes * N * lds_bytes_per_sample(bt)
+                # rocprof-reported when this launch shape was profiled: (SQ_INSTS_LDS_LOAD_BANDWIDTH + SQ_INSTS_LDS_STORE_BANDWIDTH) x 64 B
+                roofline["lds"] = dict(achieved=(lds_counter or lds_alg) / (kern_ms * 1e-3) / 1e9, peak=LDS_PEAK_GBS, unit="GB/s",
+                                       bytes_per_launch=lds_counter or lds_alg, algorithmic_bytes_per_launch=lds_alg,
+                                       source=("rocprofv3 counters of this launch shape (%s)" % traffic_file)
+                                       if lds_counter else "algorithmic bytes (exchange images, bias quads, logits): this launch shape was not profiled")
+                roofline["lds"]["frac"] = roofline["lds"]["achieved"] / LDS_PEAK_GBS
         out = {
             "metric": "samples/sec (all GPUs) in real time (every utterance >= 24 kHz) and max real-time batch @24kHz, R64/S256/A256 20L fp16",
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1223,29 +1275,32 @@ def main():
                        "parallelism": "batch-sharded x%d, final RCCL all_gather" % world},
             "samples_per_sec_per_gpu": value / world,
             "khz_per_utterance": khz,
-            "max_realtime_batch_per_gpu": (max_rt[0] if max_rt[0] and max_rt[0] > B else B) if khz >= REALTIME_KHZ else None,
-            "max_realtime_batch_khz_per_utterance": max_rt[1] if max_rt[0] and max_rt[0] > B else khz,
-            "timed_batch_note": (None if not max_rt[0] or max_rt[0] == B else
-                                 "the timed steps run the real-time batch with the highest aggregate rate (%d utterances, three tiles per workgroup on every CU); "
-                                 "the largest real-time batch is %d (four tiles per workgroup on %d CUs, %.2f kHz per utterance in its slowest probe = %.1f M samples/s)"
-                                 % (B, max_rt[0], (max_rt[0] // 16 + 3) // 4, max_rt[1], max_rt[0] * max_rt[1] / 1e3)),
-            "max_realtime_batch_definition": "(found by bisection in steps of 256 utterances, the chosen batch probed three more times) "
-                                             "largest batch whose samples 640..1151 (steady state: nv_wavenet_perf.cu:195-199 times "
-                                             "N=16384 at maxDilation 512) are generated at >= 24 kHz per utterance; conditioning pre-packed in HBM "
-                                             "(setInputs outside the timed region, like the reference's harness); see end_to_end for "
-                                             "conditioning streamed per chunk or read in place",
             "realtime_margin": khz / REALTIME_KHZ - 1.0,
-            "realtime_sweep_khz": {str(k): v for k, v in sorted(sweep.items(), key=lambda kv: str(kv[0]))},
-            "c3_b16": {"khz_per_utterance": c3_b16_khz, "samples_per_sec": None if c3_b16_khz is None else 16e3 * c3_b16_khz},
-            "reference_definition": refdef,
-            "end_to_end": e2e,
-            "dropin_fp32": dropin,
-            "oversubscribed": thr,
-            "extras_skipped_for_time": skipped,
             "distinct_samples_in_last_step": hist,
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                "max_realtime_batch_per_gpu": (max_rt[0] if max_rt[0] and max_rt[0] > B else B) if khz >= REALTIME_KHZ else None,
+                "max_realtime_batch_khz_per_utterance": max_rt[1] if max_rt[0] and max_rt[0] > B else khz,
+                "timed_batch_note": (None if not max_rt[0] or max_rt[0] == B else
+                                     "the timed steps run the real-time batch with the highest aggregate rate (%d utterances, three tiles per workgroup on every CU); "
+                                     "the largest real-time batch is %d (four tiles per workgroup on %d CUs, %.2f kHz per utterance in its slowest probe = %.1f M samples/s)"
+                                     % (B, max_rt[0], (max_rt[0] // 16 + 3) // 4, max_rt[1], max_rt[0] * max_rt[1] / 1e3)),
+                "max_realtime_batch_definition": "(found by bisection in steps of 256 utterances, the chosen batch probed three more times) "
+                                                 "largest batch whose samples 640..1151 (steady state: nv_wavenet_perf.cu:195-199 times "
+                                                 "N=16384 at maxDilation 512) are generated at >= 24 kHz per utterance; conditioning pre-packed in HBM "
+                                                 "(setInputs outside the timed region, like the reference's harness); see end_to_end for "
+                                                 "conditioning streamed per chunk or read in place",
+                "realtime_sweep_khz": {str(k): v for k, v in sorted(sweep.items(), key=lambda kv: str(kv[0]))},
+                "c3_b16": {"khz_per_utterance": c3_b16_khz, "samples_per_sec": None if c3_b16_khz is None else 16e3 * c3_b16_khz},
+                "reference_definition": refdef,
+                "end_to_end": e2e,
+                "dropin_fp32": dropin,
+                "oversubscribed": thr,
+                "extras_skipped_for_time": skipped,
+                "roofline": roofline,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             note("cpu_baseline")
             out["cpu_baseline"] = cpu_baseline(w)
         note("done")

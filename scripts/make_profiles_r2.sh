@@ -4,7 +4,7 @@
 set -e
 cd "$(dirname "$0")/.."
 P=profiles
-BENCH="python bench.py --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python bench.py --full --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 {
 echo "# round 2: $BENCH  under  rocprofv3 --kernel-trace --stats"
 echo "# (two tiles of 16 utterances per workgroup, 256 workgroups; bench.py's own line of this run:"
@@ -51,7 +51,7 @@ json.dump({"batch": 8192, "samples": 256, "fetch_size_kb": f, "write_size_kb": w
            "note": "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half of wide coalesced reads); "
                    "separate --pmc passes; wn::wavenet_wg, two tiles per workgroup"},
           open("profiles/traffic_r02.json", "w"), indent=1)
-hdr = ["# round 2, wn::wavenet_wg<fp16,64,256,256,BT=2,EMBLDS=1,DUMP=0> at batch 8192 x 256 samples (python bench.py --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras)",
+hdr = ["# round 2, wn::wavenet_wg<fp16,64,256,256,BT=2,EMBLDS=1,DUMP=0> at batch 8192 x 256 samples (python bench.py --full --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras)",
        "# separate runs: rocprofv3 --kernel-trace --pmc FETCH_SIZE | --pmc WRITE_SIZE | --pmc TCC_HIT_sum TCC_MISS_sum | --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_BUSY_CYCLES",
        "# FETCH_SIZE / WRITE_SIZE in KB per dispatch; gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE reports 1/2 of wide coalesced reads -> x2",
        "# HBM bytes per launch = (2*%.1f + %.1f) KB = %.2fe9 B  vs algorithmic 21.8e9 B (cond 10.7 + ring r/w 10.9 + sel/yOut 0.02): %.2fx" % (f, w, hbm / 1e9, hbm / 21.76e9),
@@ -63,7 +63,7 @@ open("profiles/r02_pmc_wg_b8192.txt", "w").write("\n".join(hdr + keep) + "\n")
 print("\n".join(hdr))
 PY
 # ---- three tiles per workgroup at 12288 utterances ----
-B3="python bench.py --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+B3="python bench.py --full --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 {
 echo "# round 2: $B3  under  rocprofv3 --kernel-trace --stats"
 echo "# (three tiles of 16 utterances per workgroup, 256 workgroups: the launch shape of 8193 .. 12288 utterances per GPU; bench.py's own line of this run:"
@@ -91,7 +91,7 @@ json.dump({"batch": 12288, "samples": 128, "fetch_size_kb": f, "write_size_kb": 
            "note": "FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half of wide coalesced reads); "
                    "separate --pmc passes; wn::wavenet_wg, three tiles per workgroup"},
           open("profiles/traffic_r02_b12288.json", "w"), indent=1)
-hdr = ["# round 2, wn::wavenet_wg<fp16,64,256,256,BT=3,EMBLDS=1,DUMP=0> at batch 12288 x 128 samples (python bench.py --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras)",
+hdr = ["# round 2, wn::wavenet_wg<fp16,64,256,256,BT=3,EMBLDS=1,DUMP=0> at batch 12288 x 128 samples (python bench.py --full --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras)",
        "# separate runs: rocprofv3 --kernel-trace --pmc FETCH_SIZE | --pmc WRITE_SIZE | --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_BUSY_CYCLES",
        "# HBM bytes per launch = (2*%.1f + %.1f) KB = %.2fe9 B  vs algorithmic %.2fe9 B: %.2fx" % (f, w, hbm / 1e9, alg / 1e9, hbm / alg),
        "# SQ counters are per shader engine (32 of them): VALU : MFMA = %.2f, LDS bank-conflict cycles / LDS active cycles = %.1f %%" %

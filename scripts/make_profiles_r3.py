@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.chdir(ROOT)
 G, P = "gpurun_out", "profiles"
 KERN = "wavenet_wg"
-CMD = "python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD = "python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 B, NSTEP, STEADY = 12288, 256, 640
 
 
@@ -105,7 +105,7 @@ json.dump(line, open(f"{P}/r03_bench_line_under_rocprof_b12288.json", "w"))
 l2 = json.load(open(f"{G}/prof3_bench_line_b8192.json"))
 d2 = sorted(dispatches(f"{G}/prof3_kt_b8192/p_results.db", KERN))[:-1]
 with open(f"{P}/r03_kernel_trace_stats_wg_b8192.txt", "w") as f:
-    f.write("# round 3: python bench.py --batch 8192 --steps 5 --warmup 1 --no-cpu-baseline --no-extras  under  rocprofv3 --kernel-trace --stats\n")
+    f.write("# round 3: python bench.py --full --batch 8192 --steps 5 --warmup 1 --no-cpu-baseline --no-extras  under  rocprofv3 --kernel-trace --stats\n")
     f.write("# wn::wavenet_wg<fp16,64,256,256,BT=2,...>, steady state, %d samples per launch; bench.py: kernel_ms %.3f, khz_per_utterance %.2f, roofline.frac %.4f\n" %
             (l2["config"]["samples_per_step"], l2["roofline"]["kernel_ms"], l2["khz_per_utterance"], l2["roofline"]["frac"]))
     f.write("# wavenet_wg launches of that size: n=%d avg %.3f ms min %.3f ms\n" % (len(d2), sum(d2) / len(d2) / 1e6, min(d2) / 1e6))

@@ -107,7 +107,7 @@ def issue_lines(c, f, waves_per_cu=4):
 
 # ---- the headline kernel at 12 288 utterances ------------------------------------------------------------------------------
 B = 12288
-CMD = f"python bench.py --batch {B} --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD = f"python bench.py --full --batch {B} --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 KERN = "wavenet_wgI"          # (this rocprofv3 stores mangled names)
 line, nl, avg, NSTEP = trace_file("prof4", KERN, B, CMD,
                            "wn::wavenet_wg<fp16,64,256,256,BT=3,EMBLDS=1,DUMP=0,RAW=0>: three tiles of 16 utterances per workgroup, 256 workgroups",
@@ -160,7 +160,7 @@ json.dump(line, open(f"{P}/r04_bench_line_under_rocprof_b12288.json", "w"))
 
 # ---- wavenet_bcast at 16 384 utterances ------------------------------------------------------------------------------------
 B2 = 16384
-CMD2 = f"python bench.py --batch {B2} --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD2 = f"python bench.py --full --batch {B2} --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 K2 = "wavenet_bcastI"
 line2, nl2, avg2, NS2 = trace_file("prof4_bc", K2, B2, CMD2,
                               "wn::wavenet_bcast<fp16,64,256,256,BTW=1,EMBLDS=1,DUMP=0>: every wave one tile (four per workgroup), 256 workgroups; "

@@ -90,7 +90,7 @@ def wg_launch(tag, label, raw, flop, alg_r, alg_w, alg_what, out_trace, out_pmc,
     dur = k["durations_ns"]
     timed = sorted(dur)[:-1]                 # the run also holds ONE launch of STEADY samples (the untimed run-in)
     avg = sum(timed) / len(timed) * 1e-9
-    cmd = "python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras" + (" --conditioning features" if raw == 3 else "")
+    cmd = "python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras" + (" --conditioning features" if raw == 3 else "")
     with open(out_trace, "w") as f:
         f.write(f"# round 5: {cmd}  under  rocprofv3 --kernel-trace --stats\n# {kname}: {label}\n")
         f.write(f"# every timed launch generates samples {STEADY}..{STEADY + NSTEP - 1} of {B} utterances (steady state: all dilated taps live);\n")

@@ -89,7 +89,7 @@ def wg_launch(tag, B, bt, label, alg_r, alg_w, alg_what, out_trace, out_pmc, out
     dur = k["durations_ns"]
     timed = sorted(dur)[:-1]                 # the run also holds ONE launch of STEADY samples (the untimed run-in)
     avg = sum(timed) / len(timed) * 1e-9
-    cmd = "python bench.py --batch %d --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-power" % B
+    cmd = "python bench.py --full --batch %d --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-power" % B
     wg_per_sample = (B // 16 + bt - 1) // bt
     with open(out_trace, "w") as f:
         f.write(f"# round 6: {cmd}  under  rocprofv3 --kernel-trace --stats\n# {kname}: {label}\n")

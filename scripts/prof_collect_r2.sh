@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd $R
 mkdir -p gpurun_out
-BENCH="python bench.py --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python bench.py --full --batch 8192 --samples 256 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run() { d=$1; shift; rm -rf gpurun_out/$d; timeout 600 rocprofv3 "$@" -d gpurun_out/$d -o p -- ${CMD} > gpurun_out/$d.log 2>&1; echo "$d rc=$?"; }
 CMD="$BENCH"
 run prof2_kt --kernel-trace --stats
@@ -15,7 +15,7 @@ run prof2_write --kernel-trace --pmc WRITE_SIZE
 run prof2_l2 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum
 run prof2_sq --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_BUSY_CYCLES
 # three tiles per workgroup (8193 .. 12288 utterances per GPU)
-CMD="python bench.py --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --batch 12288 --samples 128 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run prof2_kt_b12288 --kernel-trace --stats
 run prof2_fetch_b12288 --kernel-trace --pmc FETCH_SIZE
 run prof2_write_b12288 --kernel-trace --pmc WRITE_SIZE

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd $R
 mkdir -p gpurun_out
 run() { d=$1; shift; rm -rf gpurun_out/$d; timeout 900 rocprofv3 "$@" -d gpurun_out/$d -o p -- ${CMD} > gpurun_out/$d.log 2>&1; echo "$d rc=$?"; }
-CMD="python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run prof3_kt --kernel-trace --stats
 run prof3_fetch --kernel-trace --pmc FETCH_SIZE
 run prof3_write --kernel-trace --pmc WRITE_SIZE
@@ -18,7 +18,7 @@ run prof3_lds --kernel-trace --pmc SQ_INSTS_LDS SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_S
 run prof3_ldsbw --kernel-trace --pmc SQ_INSTS_LDS_LOAD_BANDWIDTH SQ_INSTS_LDS_STORE_BANDWIDTH SQ_INSTS_SALU SQ_INSTS_SMEM
 grep -h "^{" gpurun_out/prof3_kt.log | tail -1 > gpurun_out/prof3_bench_line.json
 # two tiles per workgroup (8192 utterances)
-CMD="python bench.py --batch 8192 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --batch 8192 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run prof3_kt_b8192 --kernel-trace --stats
 grep -h "^{" gpurun_out/prof3_kt_b8192.log | tail -1 > gpurun_out/prof3_bench_line_b8192.json
 # the multi-CU chain on C4 / C3 (reference definition: 16384 samples in chunks of 2048)

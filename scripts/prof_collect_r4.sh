@@ -12,7 +12,7 @@ cd $R
 mkdir -p gpurun_out
 run() { d=$1; shift; rm -rf gpurun_out/$d; timeout 900 rocprofv3 "$@" -d gpurun_out/$d -o p -- ${CMD} > gpurun_out/$d.log 2>&1; echo "$d rc=$?";
         python scripts/prof_extract.py gpurun_out/$d gpurun_out/$d.json; }
-CMD="python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run prof4_kt --kernel-trace --stats
 run prof4_fetch --kernel-trace --pmc FETCH_SIZE
 run prof4_write --kernel-trace --pmc WRITE_SIZE
@@ -21,7 +21,7 @@ run prof4_ldsbw --kernel-trace --pmc SQ_INSTS_LDS_LOAD_BANDWIDTH SQ_INSTS_LDS_ST
 run prof4_issue --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE
 run prof4_busy --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC GRBM_GUI_ACTIVE
 grep -h "^{" gpurun_out/prof4_kt.log | tail -1 > gpurun_out/prof4_bench_line.json
-CMD="python bench.py --batch 16384 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+CMD="python bench.py --full --batch 16384 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run prof4_bc_kt --kernel-trace --stats
 run prof4_bc_ldsbw --kernel-trace --pmc SQ_INSTS_LDS_LOAD_BANDWIDTH SQ_INSTS_LDS_STORE_BANDWIDTH SQ_INSTS_VALU SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 run prof4_bc_issue --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE

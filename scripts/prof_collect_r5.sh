@@ -17,8 +17,8 @@ run() { d=$1; shift; rm -rf gpurun_out/$d; timeout 900 rocprofv3 "$@" -d gpurun_
 for part in $WHAT; do
 case $part in
 A|B)
-  if [ $part = A ]; then T=prof5a; CMD="python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras";
-  else T=prof5b; CMD="python bench.py --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras --conditioning features"; fi
+  if [ $part = A ]; then T=prof5a; CMD="python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras";
+  else T=prof5b; CMD="python bench.py --full --batch 12288 --steps 5 --warmup 1 --no-cpu-baseline --no-extras --conditioning features"; fi
   run ${T}_kt --kernel-trace --stats
   run ${T}_fetch --kernel-trace --pmc FETCH_SIZE
   run ${T}_write --kernel-trace --pmc WRITE_SIZE

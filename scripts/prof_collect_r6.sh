@@ -24,7 +24,7 @@ for part in $WHAT; do
     continue
   fi
   if [ $part = A ]; then T=prof6a; BATCH=12288; else T=prof6b; BATCH=13824; fi
-  CMD="python bench.py --batch $BATCH --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-power"
+  CMD="python bench.py --full --batch $BATCH --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-power"
   run ${T}_kt --kernel-trace --stats
   run ${T}_fetch --kernel-trace --pmc FETCH_SIZE
   run ${T}_write --kernel-trace --pmc WRITE_SIZE

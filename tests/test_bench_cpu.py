@@ -94,3 +94,32 @@ def test_energy_roofline_prices_the_algorithms_counts(tmp_path, monkeypatch):
     p = e3["prices_nj"]
     assert p["hbm"] / 1024 > 50 * p["mfma16"] / 8192 and p["mfma32"] / 16384 > 0.9 * p["mfma16"] / 8192
     assert bench.energy_roofline(None, 9.5, B, N, 3) is None
+
+
+def test_bench_options_of_the_plain_and_the_full_run():
+    """`--full` (everything beside the headline) and `--dump-outputs DIR` exist; a run without timed steps is refused before any work."""
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout
+    r = _run(["--steps", "0", "--selftest-dist"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_float32_within_the_size_bound(tmp_path):
+    """--dump-outputs: the last step's samples as float32 (exact for sample indices); above the bound, the same seeded, sorted sample of
+    utterances on every call, with their indices beside them, and never more bytes than the bound."""
+    import numpy as np
+    import bench
+    y = np.random.default_rng(1).integers(0, 256, size=(96, 40), dtype=np.int32)
+    paths = bench.dump_outputs(str(tmp_path / "all"), y)
+    assert [os.path.basename(p) for p in paths] == ["samples.npy"]
+    got = np.load(paths[0])
+    assert got.dtype == np.float32 and np.array_equal(got, y.astype(np.float32))
+    bound = 10 * (40 * 4 + 8) + 512
+    a = bench.dump_outputs(str(tmp_path / "a"), y, max_bytes=bound)
+    b = bench.dump_outputs(str(tmp_path / "b"), y, max_bytes=bound)
+    assert [os.path.basename(p) for p in a] == ["samples_rows.npy", "samples.npy"]
+    rows, got = np.load(a[0]), np.load(a[1])
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and got.shape == (10, 40)
+    assert sum(os.path.getsize(p) for p in a) <= bound
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, y[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(b[0])) and np.array_equal(got, np.load(b[1]))

@@ -1187,6 +1187,30 @@ def test_bench_c5_path_runs_on_one_gpu():
     assert j["value"] > 0 and j["khz_per_utterance"] > 24.0 and j["distinct_samples_in_last_step"] > 8, j
 
 
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, reports ms_per_step and leaves the extras out; with --dump-outputs
+    it writes the last step's samples, and two runs with the same arguments write the same samples (seeded inputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "64", "--samples", "128",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0, j
+        assert j["config"]["batch_per_gpu"] == 64 and j["config"]["samples_per_step"] == 128
+        assert not {"roofline", "cpu_baseline", "reference_definition", "end_to_end"} & set(j), sorted(j)
+        y = np.load(os.path.join(d, "samples.npy"))
+        assert y.dtype == np.float32 and y.shape == (64, 128) and y.min() >= 0 and y.max() < 256 and len(np.unique(y)) > 8
+        got.append(y)
+    assert np.array_equal(got[0], got[1]), "two runs with the same arguments dumped different samples"
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_in_kernel_selectors_and_pcm_out(mode):
     """SURVEY.md 8f rank 2. With setSelectorSeed the engine draws its selectors in-kernel
