@@ -43,8 +43,8 @@ typedef void (*nvw_consume_fn)(int* yOut, int init_sample, int count, void* user
  * another revision should check this instead of finding a different kernel behind a number.  5 = round 5 (the
  * feature-conditioning entry points below); 6 = this header (round 6: nvw_get_features returns int; nvw_upsample_features,
  * nvw_generate_stream and nvw_get_features check their ranges and refuse with 0 instead of reaching the class's asserts;
- * organisation 10; nvw_set_ring_in_lds). */
-#define NVW_ABI_VERSION 6
+ * organisation 10; nvw_set_ring_in_lds); 7 = slot mode (nvw_slots_begin .. nvw_slots_end, below). */
+#define NVW_ABI_VERSION 7
 int nvw_abi_version(void);
 int nvw_supported(int R, int S, int A, int precision);
 /* writes up to `max` (R,S,A,precision) quadruples into out[4*i..], returns how many exist */
@@ -226,6 +226,33 @@ void nvw_get_zs(nvw_engine* e, float* dst);                    /* [maxBatch][A] 
 void nvw_get_za(nvw_engine* e, float* dst);                    /* [maxBatch][A] */
 void nvw_get_p(nvw_engine* e, float* dst);                     /* [maxBatch][A] */
 void nvw_get_y_out(nvw_engine* e, int* yOut, int offset, int size, void* stream);
+
+/* SLOT MODE: CONTINUOUS BATCHING (ABI 7).  Every column of the batch holds one utterance that starts and stops on its own while
+ * the others go on; the samples of an utterance depend on its upsampled features, its uid, the seed of nvw_set_selector_seed (0 if
+ * none was set) and the model only -- not on its column, the step it joined at, its neighbours or the chunk sizes.  Local sample k
+ * draws its selector from Philox4x32-10 with counter {k, uid, 0, 0}: an utterance with uid = b reproduces column b of a lockstep
+ * nvw_set_features + nvw_set_selector_seed run.  Needs nvw_set_conditioning_weights (the conditioning is computed in the kernel).
+ *   nvw_slots_begin  enters slot mode with a window of `window` samples, a positive multiple of the largest dilation of the schedule
+ *                    (state of the generation between steps, sized by the window and not by the engine's num_samples: an utterance
+ *                    may be of any length); every column idle; synchronises.  0 when refused (no conditioning weights, bad window).
+ *   nvw_slot_start   column `slot` takes a new utterance at the next step: features x[c*c_stride + k*t_stride] (device memory,
+ *                    `precision` = 16 | 32 bits, n_cond channels x `length` samples, kept alive and unchanged while the column
+ *                    runs), its uid; sample history 128 and dilation rings zero as for a new lockstep utterance.  0 when refused
+ *                    (not in slot mode, slot outside 0..batch-1, host memory, bad precision, non-positive strides or length).
+ *   nvw_slot_stop    column `slot` goes idle at the next step.  0 when refused (not in slot mode, slot out of range).
+ *   nvw_slots_step   `count` (1..window) samples of every column, asynchronously on `stream`: pending starts and stops, the window
+ *                    feed, the generation launches up to the highest active column's tile, the PCM when pcm != NULL, and the step's
+ *                    samples / PCM into yOut / pcm, [batch][count] int32 / int16, host or device, either may be NULL (synchronises
+ *                    the stream when one is host memory).  Idle columns and samples past an utterance's length hold unspecified
+ *                    values.  0 when refused (not in slot mode, count out of range; nothing changes) or a launch failed.  The steps
+ *                    of a session are issued on one stream.
+ *   nvw_slots_end    leaves slot mode and frees its buffers (synchronises); lockstep calls work as before afterwards. */
+int nvw_slots_begin(nvw_engine* e, int window);
+int nvw_slot_start(nvw_engine* e, int slot, const void* x, int precision, long long c_stride, long long t_stride, int length,
+                   unsigned uid);
+int nvw_slot_stop(nvw_engine* e, int slot);
+int nvw_slots_step(nvw_engine* e, int count, int* yOut, short* pcm, void* stream);
+void nvw_slots_end(nvw_engine* e);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

@@ -79,6 +79,11 @@ SIGNATURES = {
     "nvw_get_za": (None, [C.c_void_p, _fp]),
     "nvw_get_p": (None, [C.c_void_p, _fp]),
     "nvw_get_y_out": (None, [C.c_void_p, _fp, C.c_int, C.c_int, C.c_void_p]),
+    "nvw_slots_begin": (C.c_int, [C.c_void_p, C.c_int]),
+    "nvw_slot_start": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_uint]),
+    "nvw_slot_stop": (C.c_int, [C.c_void_p, C.c_int]),
+    "nvw_slots_step": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_void_p]),
+    "nvw_slots_end": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),
     "nvw_time_runs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "wavenet_infer": (None, [C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 7 +
@@ -88,7 +93,7 @@ SIGNATURES = {
     "get_A": (C.c_int, []),
 }
 
-ABI_VERSION = 6            # NVW_ABI_VERSION of include/nv_wavenet_c.h this package was written against
+ABI_VERSION = 7            # NVW_ABI_VERSION of include/nv_wavenet_c.h this package was written against
 # (checked before the other symbols are bound, so that an older library fails with the rebuild hint, not an AttributeError)
 _abi = getattr(lib, "nvw_abi_version", None)
 _have = None

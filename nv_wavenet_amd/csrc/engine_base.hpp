@@ -58,6 +58,11 @@ struct nvw_engine {
     virtual void getZa(float*) = 0;
     virtual void getP(float*) = 0;
     virtual void getYOut(int*, int, int, hipStream_t) = 0;
+    virtual bool slotsBegin(int) = 0;
+    virtual bool slotStart(int, const void*, int, long long, long long, int, unsigned) = 0;
+    virtual bool slotStop(int) = 0;
+    virtual bool slotsStep(int, int*, short*, hipStream_t) = 0;
+    virtual void slotsEnd() = 0;
 };
 
 template <typename Tw, typename Td, int R, int S, int A>
@@ -130,6 +135,13 @@ struct EngineImpl : nvw_engine {
     void getZa(float* d) override { eng.getZa(d); }
     void getP(float* d) override { eng.getP(d); }
     void getYOut(int* y, int off, int size, hipStream_t s) override { eng.getYOut(y, off, size, s); }
+    bool slotsBegin(int window) override { return eng.slotsBegin(window); }
+    bool slotStart(int slot, const void* x, int prec, long long cS, long long tS, int length, unsigned uid) override {
+        return eng.slotStart(slot, x, prec, cS, tS, length, uid);
+    }
+    bool slotStop(int slot) override { return eng.slotStop(slot); }
+    bool slotsStep(int count, int* y, short* pcm, hipStream_t s) override { return eng.slotsStep(count, y, pcm, s); }
+    void slotsEnd() override { eng.slotsEnd(); }
 };
 
 typedef nvw_engine* (*nvw_factory_fn)(int L, int maxD, int B, int N, int impl, int tanhEmbed, int organisation);

@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "slots.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
 
@@ -147,6 +148,22 @@ protected:
     size_t m_pcmUserElems;   // its size in int16 values when the caller said so (0: unknown)
     unsigned long long* m_clk;   // clock probe of the latest wavenet_wg launch (wn::Params::clk), when switched on
     bool m_clkOn;
+
+    // slot mode (slotsBegin .. slotsEnd; slots.hpp): one utterance per column, each started and stopped on its own
+    int m_slotW = 0;                        // window (samples); 0: not in slot mode
+    long long m_slotCounter = 0;            // samples generated since slotsBegin: window row of the next step = counter mod W
+    std::vector<wn::SlotDesc> m_slotHost;   // the columns' descriptors as the host has set them ...
+    std::vector<int> m_slotPending;         // ... and what the next step applies per column: 0 nothing, 1 start, 2 stop
+    std::vector<int> m_slotPendingList;
+    wn::SlotDesc* m_slotDesc = NULL;        // [maxBatch] on the device
+    elem* m_slotFeat = NULL;                // [W][tiles][KFC] feature fragments
+    float* m_slotSel = NULL;                // [W][maxBatch] selectors
+    int* m_slotY = NULL;                    // [maxBatch][W] samples
+    short* m_slotPcm = NULL;                // [maxBatch][W] int16 PCM
+    char* m_slotUpd = NULL;                 // device copy of a step's updates + restarted columns
+    char* m_slotStage[2] = {NULL, NULL};    // pinned host staging of them, used by alternate steps ...
+    hipEvent_t m_slotEv[2] = {NULL, NULL};  // ... each reused once the copy of the step before last has completed
+    int m_slotParity = 0;
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -601,6 +618,7 @@ public:
 
     virtual ~nvWavenetInfer() {
         gpuErrChk(hipDeviceSynchronize());
+        slotsEnd();
         for (hipEvent_t ev : m_poolEvents) gpuErrChk(hipEventDestroy(ev));
         gpuErrChk(hipFree(m_wblob));
         gpuErrChk(hipFree(m_bias));
@@ -1063,6 +1081,12 @@ public:
         if (pcmOut && !m_pcm) {
             gpuErrChk(hipMalloc(&m_pcm, (size_t)m_maxSamples * m_maxBatch * sizeof(short)));
             gpuErrChk(hipMemset(m_pcm, 0, (size_t)m_maxSamples * m_maxBatch * sizeof(short)));
+            ensureMulaw();
+        }
+    }
+    // the PCM value of every sample index, on the device (made once)
+    void ensureMulaw() {
+        if (!m_mulaw) {
             std::vector<short> table(A);
             const double mu = (double)A - 1.0;
             for (int y = 0; y < A; y++) {
@@ -1350,6 +1374,158 @@ public:
         m_ringDirtyTiles = 0;
     }
 
+    // ---- slot mode: continuous batching (slots.hpp; DESIGN.md "Slot mode") ------------------------------------------------------
+    // Every column holds one utterance that starts and stops on its own while the others go on.  An utterance's samples depend on
+    // its features, its uid, the seed and the model only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
+    // lockstep setFeatures + setSelectorSeed run --, its rings start at zero and its history at 128.  The state between steps lives
+    // in a window of W samples that wraps; the generation kernel is wavenet_wg<.., RAW=3> as the features path launches it, on
+    // window rows, reading the selectors from a table (useRng = 0).  Needs setConditioningWeights; the seed is the one of
+    // setSelectorSeed (0 if none was set).  Steps of a session are issued on one stream (they share the window and the rings).
+    int largestDilation() const {      // of the schedule: the window is a multiple of it, so that t mod W keeps t & (d - 1)
+        int d = 1, m = 1;
+        for (int l = 0; l < m_numLayers; l++) {
+            if (d > m) m = d;
+            d <<= 1;
+            if (d > m_maxDilation) d = 1;
+        }
+        return m;
+    }
+    // Enters slot mode with a window of `window` samples (ends a session in progress; every column idle).  false: no conditioning
+    // weights yet, or the window is not a positive multiple of largestDilation().  Synchronises.
+    bool slotsBegin(int window) {
+        if (!m_supported || m_nCond <= 0 || window <= 0 || window % largestDilation() != 0) return false;
+        slotsEnd();
+        m_slotW = window;
+        m_slotCounter = 0;
+        m_slotHost.assign(m_maxBatch, wn::SlotDesc{});
+        m_slotPending.assign(m_maxBatch, 0);
+        m_slotPendingList.clear();
+        const size_t cells = (size_t)window * m_maxBatch;
+        gpuErrChk(hipMalloc(&m_slotDesc, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
+        gpuErrChk(hipMemset(m_slotDesc, 0, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
+        gpuErrChk(hipMalloc(&m_slotFeat, featureElems(window) * sizeof(elem)));
+        gpuErrChk(hipMemset(m_slotFeat, 0, featureElems(window) * sizeof(elem)));
+        gpuErrChk(hipMalloc(&m_slotSel, cells * sizeof(float)));
+        gpuErrChk(hipMemset(m_slotSel, 0, cells * sizeof(float)));
+        gpuErrChk(hipMalloc(&m_slotY, cells * sizeof(int)));
+        gpuErrChk(hipMemset(m_slotY, 0, cells * sizeof(int)));
+        gpuErrChk(hipMalloc(&m_slotPcm, cells * sizeof(short)));
+        gpuErrChk(hipMemset(m_slotPcm, 0, cells * sizeof(short)));
+        gpuErrChk(hipMalloc(&m_slotUpd, slotUpdBytes()));
+        for (int i = 0; i < 2; i++) {
+            gpuErrChk(hipHostMalloc((void**)&m_slotStage[i], slotUpdBytes(), hipHostMallocDefault));
+            gpuErrChk(hipEventCreateWithFlags(&m_slotEv[i], hipEventDisableTiming));
+            gpuErrChk(hipEventRecord(m_slotEv[i], 0));
+        }
+        m_slotParity = 0;
+        ensureMulaw();
+        gpuErrChk(hipDeviceSynchronize());
+        return true;
+    }
+    int slotsWindow() const { return m_slotW; }
+    // Column `slot` takes a new utterance at the next step: its upsampled features x[c * cStride + k * tStride] (device memory,
+    // `precision`-bit floats, n_cond channels x `length` samples; kept alive and unchanged while the column runs), its uid.  Replaces
+    // whatever the column held.  false (nothing changes): not in slot mode, slot outside the batch, non-device x, bad precision,
+    // non-positive strides or length.
+    bool slotStart(int slot, const void* x, int precision, long long cStride, long long tStride, int length, unsigned uid) {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
+            tStride <= 0 || length <= 0 || !isDevicePtr(x))
+            return false;
+        wn::SlotDesc& d = m_slotHost[slot];
+        d.x = x;
+        d.cStride = cStride;
+        d.tStride = tStride;
+        d.start = 0;          // (the step that applies the start sets it)
+        d.length = length;
+        d.uid = uid;
+        d.precision = precision;
+        d.active = 1;
+        slotMarkPending(slot, 1);
+        return true;
+    }
+    // Column `slot` goes idle at the next step (its features are no longer read from then on).
+    bool slotStop(int slot) {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
+        m_slotHost[slot].active = 0;
+        slotMarkPending(slot, 2);
+        return true;
+    }
+    // One step of `count` <= W samples, asynchronously on `stream`: the pending starts and stops (one reset launch), the window feed
+    // (one launch), the generation -- two launches where the window rows wrap -- up to the tile of the highest active column, the PCM
+    // when pcm != NULL, and the copies of the step's samples / PCM into yOut / pcm ([maxBatch][count], host or device; NULL: none).
+    // Columns without an utterance hold unspecified values.  Synchronises the stream when an output is host memory.
+    bool slotsStep(int count, int* yOut, short* pcm, hipStream_t stream = 0) {
+        if (m_slotW <= 0 || count <= 0 || count > m_slotW) return false;
+        const int W = m_slotW;
+        bool ok = true;
+        if (!m_slotPendingList.empty()) ok = slotApplyPending(stream);
+        int cols = 0;
+        for (int b = m_maxBatch - 1; b >= 0; b--)
+            if (m_slotHost[b].active) {
+                cols = b + 1;
+                break;
+            }
+        const int T = (int)(m_slotCounter % W);
+        int piece[2][2], pieces = 0;      // (first window row, samples) of the launches
+        for (int done = 0; done < count; pieces++) {
+            const int t0 = (T + done) % W, c = count - done < W - t0 ? count - done : W - t0;
+            piece[pieces][0] = t0;
+            piece[pieces][1] = c;
+            done += c;
+        }
+        if (cols > 0) {
+            if (m_featDirty) buildFeatStream(stream);
+            ok = wn::slots_feed<F16>(stream, m_slotFeat, m_slotSel, m_slotDesc, cols, m_maxBatch, m_tiles, m_nCond, m_slotCounter, T, W, count,
+                                     m_rngSeed) && ok;
+            for (int i = 0; i < pieces; i++) ok = slotLaunch(piece[i][0], piece[i][1], cols, stream) && ok;
+            if (pcm != NULL) {
+                for (int i = 0; i < pieces; i++) {
+                    hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * piece[i][1])), dim3(256), 0, stream, m_slotY, m_slotPcm,
+                                       m_mulaw, cols, W, piece[i][0], piece[i][1]);
+                    ok = ok && hipGetLastError() == hipSuccess;
+                }
+            }
+        }
+        for (int i = 0, off = 0; i < pieces; off += piece[i][1], i++) {
+            if (yOut != NULL)
+                gpuErrChk(hipMemcpy2DAsync(yOut + off, (size_t)count * sizeof(int), m_slotY + piece[i][0], (size_t)W * sizeof(int),
+                                           (size_t)piece[i][1] * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
+            if (pcm != NULL)
+                gpuErrChk(hipMemcpy2DAsync(pcm + off, (size_t)count * sizeof(short), m_slotPcm + piece[i][0], (size_t)W * sizeof(short),
+                                           (size_t)piece[i][1] * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
+        }
+        m_slotCounter += count;
+        if ((yOut != NULL && !isDevicePtr(yOut)) || (pcm != NULL && !isDevicePtr(pcm))) gpuErrChk(hipStreamSynchronize(stream));
+        return ok;
+    }
+    // Leaves slot mode and frees its buffers (synchronises).  The rings it wrote are cleared by the next resetHistory, as after any run.
+    void slotsEnd() {
+        if (m_slotW <= 0) return;
+        gpuErrChk(hipDeviceSynchronize());
+        gpuErrChk(hipFree(m_slotDesc));
+        gpuErrChk(hipFree(m_slotFeat));
+        gpuErrChk(hipFree(m_slotSel));
+        gpuErrChk(hipFree(m_slotY));
+        gpuErrChk(hipFree(m_slotPcm));
+        gpuErrChk(hipFree(m_slotUpd));
+        for (int i = 0; i < 2; i++) {
+            gpuErrChk(hipHostFree(m_slotStage[i]));
+            gpuErrChk(hipEventDestroy(m_slotEv[i]));
+            m_slotStage[i] = NULL;
+            m_slotEv[i] = NULL;
+        }
+        m_slotDesc = NULL;
+        m_slotFeat = NULL;
+        m_slotSel = NULL;
+        m_slotY = NULL;
+        m_slotPcm = NULL;
+        m_slotUpd = NULL;
+        m_slotW = 0;
+        m_slotHost.clear();
+        m_slotPending.clear();
+        m_slotPendingList.clear();
+    }
+
     bool run(int num_samples, int batch_size, int* yOut = NULL, int batch_size_per_block = 1,
              bool dumpActivations = false, hipStream_t stream = 0) {
         m_num_samples_per_chunk = 0;
@@ -1407,6 +1583,94 @@ protected:
     int launchTiles(int tiles, bool dump, int raw) const {
         const int bt = wgTiles(tiles);
         return (bt == 4 && (dump || raw != 0)) ? 3 : bt;
+    }
+    // ---- slot mode internals ----
+    size_t slotUpdBytes() const { return (size_t)m_maxBatch * (sizeof(wn::SlotUpdate) + sizeof(int)); }
+    void slotMarkPending(int slot, int what) {
+        if (!m_slotPending[slot]) m_slotPendingList.push_back(slot);
+        m_slotPending[slot] = what;
+    }
+    // the pending starts and stops -> pinned staging -> device, then one slot_reset_kernel launch (ring + history of the started
+    // columns, every changed descriptor); the staging half is reused two steps later, once its copy has completed
+    bool slotApplyPending(hipStream_t stream) {
+        char* const stage = m_slotStage[m_slotParity];
+        gpuErrChk(hipEventSynchronize(m_slotEv[m_slotParity]));
+        wn::SlotUpdate* const upd = (wn::SlotUpdate*)stage;
+        const size_t colOff = (size_t)m_maxBatch * sizeof(wn::SlotUpdate);
+        int* const cols = (int*)(stage + colOff);
+        int nUpd = 0, nCols = 0;
+        for (int b : m_slotPendingList) {
+            wn::SlotUpdate u = {};
+            u.column = b;
+            u.reset = m_slotPending[b] == 1 ? 1 : 0;
+            if (u.reset) {
+                m_slotHost[b].start = m_slotCounter;      // local sample 0 is generated by this step
+                cols[nCols++] = b;
+            }
+            u.d = m_slotHost[b];
+            upd[nUpd++] = u;
+            m_slotPending[b] = 0;
+        }
+        m_slotPendingList.clear();
+        gpuErrChk(hipMemcpyAsync(m_slotUpd, upd, (size_t)nUpd * sizeof(wn::SlotUpdate), hipMemcpyHostToDevice, stream));
+        if (nCols) gpuErrChk(hipMemcpyAsync(m_slotUpd + colOff, cols, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, stream));
+        gpuErrChk(hipEventRecord(m_slotEv[m_slotParity], stream));
+        m_slotParity ^= 1;
+        return wn::slots_reset(stream, m_slotDesc, (const wn::SlotUpdate*)m_slotUpd, nUpd, (const int*)(m_slotUpd + colOff), nCols, m_ring,
+                               m_ringSlots, (int)(R * 16 * sizeof(elem) / 1024), m_yInPrev, m_yInCur);
+    }
+    // wavenet_wg<.., RAW=3> on window rows [t0, t0 + count) of the first `cols` columns (the launch of run_partial for features,
+    // with the window's buffers and the selector table)
+    bool slotLaunch(int t0, int count, int cols, hipStream_t stream) {
+        const int tiles = (cols + 15) / 16;
+        {
+            int bt = wgTiles(tiles);
+            if (bt >= 3 && wg4Fits()) bt = 12;      // (as run_partial: the rings of every tile a workgroup holds are written)
+            int touched = (tiles + bt - 1) / bt * bt;
+            if (touched > m_tiles) touched = m_tiles;
+            if (touched > m_ringDirtyTiles) m_ringDirtyTiles = touched;
+        }
+        wn::Params p;
+        p.wblob = m_wblobF;
+        p.bias = m_biasF;
+        p.embPrev = m_embedPrev;
+        p.embCur = m_embedCur;
+        p.cond = NULL;
+        p.condRaw = NULL;
+        p.condRawKind = 3;
+        p.feat = m_slotFeat;
+        p.gate = NULL;
+        p.sel = m_slotSel;
+        p.ring = m_ring;
+        p.maxDilation = m_maxDilation;
+        p.yInPrev = m_yInPrev;
+        p.yInCur = m_yInCur;
+        p.yOut = m_slotY;
+        p.xtOut = m_XtOut;
+        p.skipOut = m_skipOut;
+        p.zs = m_Zs;
+        p.za = m_Za;
+        p.p = m_p;
+        p.numLayers = m_numLayers;
+        p.batch = cols;
+        p.maxBatch = m_maxBatch;
+        p.numSamples = m_slotW;
+        p.condSamples = m_slotW;
+        p.initSample = t0;
+        p.count = count;
+        p.ringSlots = m_ringSlots;
+        p.ldsRingD = 0;
+        p.tiles = m_tiles;
+        p.tileBase = 0;
+        p.tanhEmbed = m_tanhEmbed ? 1 : 0;
+        p.dump = 0;
+        p.embLds = 0;
+        p.useRng = 0;
+        p.rngKey0 = (unsigned)m_rngSeed;
+        p.rngKey1 = (unsigned)(m_rngSeed >> 32);
+        p.clk = m_clkOn ? m_clk : NULL;
+        fillSchedule(p);
+        return launchWg(p, tiles, stream);
     }
     // wavenet_wg by batch size: one to four tiles per workgroup
     bool launchWg(wn::Params& p, int tiles, hipStream_t stream) {

@@ -269,6 +269,39 @@ void nvw_get_y_out(nvw_engine* e, int* yOut, int offset, int size, void* stream)
     e->getYOut(yOut, offset, size, (hipStream_t)stream);
 }
 
+// ---- slot mode: continuous batching (ABI 7) --------------------------------------------------------------------------------------
+int nvw_slots_begin(nvw_engine* e, int window) {
+    if (e->conditioningChannels() <= 0) {
+        fprintf(stderr, "nvw_slots_begin: call nvw_set_conditioning_weights first\n");
+        return 0;
+    }
+    if (!e->slotsBegin(window)) {
+        fprintf(stderr, "nvw_slots_begin: window %d is not a positive multiple of the largest dilation\n", window);
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_start(nvw_engine* e, int slot, const void* x, int precision, long long c_stride, long long t_stride, int length,
+                   unsigned uid) {
+    if (!e->slotStart(slot, x, precision, c_stride, t_stride, length, uid)) {
+        fprintf(stderr, "nvw_slot_start: refused (nvw_slots_begin first; slot %d of %d; device features of 16 or 32 bits; strides %lld, %lld "
+                "and length %d positive)\n", slot, e->maxBatch(), c_stride, t_stride, length);
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_stop(nvw_engine* e, int slot) {
+    if (!e->slotStop(slot)) {
+        fprintf(stderr, "nvw_slot_stop: refused (nvw_slots_begin first; slot %d of %d)\n", slot, e->maxBatch());
+        return 0;
+    }
+    return 1;
+}
+int nvw_slots_step(nvw_engine* e, int count, int* yOut, short* pcm, void* stream) {
+    return e->slotsStep(count, yOut, pcm, (hipStream_t)stream) ? 1 : 0;
+}
+void nvw_slots_end(nvw_engine* e) { e->slotsEnd(); }
+
 void nvw_device_synchronize(void) { gpuErrChk(hipDeviceSynchronize()); }
 
 float nvw_time_runs(nvw_engine* e, int reps, int num_samples, int batch_size, int bspb, void* stream) {

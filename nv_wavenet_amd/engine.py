@@ -333,6 +333,49 @@ class WavenetEngine:
             self._pcm_keep = None
             lib.nvw_set_audio_out(self._h, None)
 
+    # ---- slot mode: continuous batching (include/nv_wavenet_c.h, ABI 7; nv_wavenet_amd/slots.py schedules requests onto it) -----
+    def slotsBegin(self, window):
+        """Enters slot mode with a window of `window` samples (a multiple of the largest dilation); every column idle.  Needs
+        setConditioningWeights; the selectors are drawn from the seed of setSelectorSeed."""
+        if not lib.nvw_slots_begin(self._h, int(window)):
+            raise ValueError("nvw_slots_begin refused window %d (conditioning weights first; a multiple of the largest dilation)" % window)
+        self.slotWindow = int(window)
+        self._slot_keep = {}
+
+    def slotStart(self, slot, x, uid, length=None):
+        """Column `slot` takes a new utterance at the next step: x = its upsampled features, CUDA tensor [n_cond][T] (float32 or
+        float16, any strides), the first `length` (default T) samples; uid = the Philox counter word of its selectors."""
+        import torch
+        assert hasattr(x, "data_ptr") and x.is_cuda and x.dim() == 2, "features: a CUDA tensor [n_cond][samples]"
+        bits = {torch.float32: 32, torch.float16: 16}.get(x.dtype)
+        assert bits, "features must be float32 or float16"
+        n = x.size(1) if length is None else int(length)
+        assert x.size(0) == self.nCond and 0 < n <= x.size(1), "features [%d][>= %d] expected, got %s" % (self.nCond, n, tuple(x.shape))
+        if not lib.nvw_slot_start(self._h, int(slot), x.data_ptr(), bits, x.stride(0), x.stride(1), n, int(uid) & 0xFFFFFFFF):
+            raise ValueError("nvw_slot_start refused slot %d" % slot)
+        self._slot_keep[int(slot)] = x      # (read by the steps while the column runs; let go when the column starts again)
+
+    def slotStop(self, slot):
+        """Column `slot` goes idle at the next step."""
+        if not lib.nvw_slot_stop(self._h, int(slot)):
+            raise ValueError("nvw_slot_stop refused slot %d" % slot)
+
+    def slotsStep(self, count, yOut=None, pcm=None, stream=None):
+        """`count` samples of every column: yOut int32 / pcm int16 [maxBatch][count] (numpy or CUDA tensors; None: not copied)."""
+        for a, name in ((yOut, "yOut"), (pcm, "pcm")):
+            if a is not None:
+                n = a.numel() if hasattr(a, "numel") else a.size
+                assert n >= self.maxBatch * count, "%s must hold [maxBatch][count]" % name
+        if yOut is not None:
+            self._yout(yOut, count)
+        if pcm is not None and not hasattr(pcm, "data_ptr"):
+            assert pcm.dtype == np.int16 and pcm.flags["C_CONTIGUOUS"]
+        return bool(lib.nvw_slots_step(self._h, int(count), addr(yOut), addr(pcm), stream))
+
+    def slotsEnd(self):
+        lib.nvw_slots_end(self._h)
+        self._slot_keep = {}
+
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):
         if yOut is None:

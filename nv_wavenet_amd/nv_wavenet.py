@@ -369,7 +369,6 @@ class NVWaveNetEngine(NVWaveNet):
     MAX_ENGINES = 4
 
     def _engine(self, batch_size, sample_count, implementation):
-        from .engine import WavenetEngine
         capacity = -(-sample_count // self.BUCKET) * self.BUCKET
         key = (batch_size, capacity, int(implementation))
         e = self._engines.pop(key, None)
@@ -377,16 +376,32 @@ class NVWaveNetEngine(NVWaveNet):
             while len(self._engines) >= self.MAX_ENGINES:
                 old_key = next(iter(self._engines))
                 self._engines.pop(old_key).close()
-            e = WavenetEngine(self.R, self.S, self.A, self.num_layers, self.max_dilation, batch_size, capacity,
-                              impl=int(implementation), tanhEmbed=bool(self.use_embed_tanh), precision=self.precision)
-            f = lambda t: t.float().contiguous()
-            e.setEmbeddings(f(self.embedding_prev), f(self.embedding_curr))
-            for l in range(self.num_layers):
-                e.setLayerWeights(l, *[f(t) for t in self.layers[7 * l:7 * l + 7]])
-            zeros = torch.zeros(self.A, dtype=torch.float32, device=self.conv_out.device)
-            e.setOutWeights(f(self.conv_out), zeros, f(self.conv_end), zeros)   # wavenet_infer.cu:75-82
+            e = self._new_engine(batch_size, capacity, implementation)
         self._engines[key] = e          # (re-)inserted last: most recently used
         return e
+
+    def _new_engine(self, batch_size, capacity, implementation):
+        from .engine import WavenetEngine
+        e = WavenetEngine(self.R, self.S, self.A, self.num_layers, self.max_dilation, batch_size, capacity,
+                          impl=int(implementation), tanhEmbed=bool(self.use_embed_tanh), precision=self.precision)
+        f = lambda t: t.float().contiguous()
+        e.setEmbeddings(f(self.embedding_prev), f(self.embedding_curr))
+        for l in range(self.num_layers):
+            e.setLayerWeights(l, *[f(t) for t in self.layers[7 * l:7 * l + 7]])
+        zeros = torch.zeros(self.A, dtype=torch.float32, device=self.conv_out.device)
+        e.setOutWeights(f(self.conv_out), zeros, f(self.conv_end), zeros)   # wavenet_infer.cu:75-82
+        return e
+
+    def slot_stream(self, columns, window, cond_weight, cond_bias, seed=0, implementation=Impl.AUTO, pcm=True):
+        """Continuous batching (nv_wavenet_amd/slots.py): a SlotStream over an engine of its own with `columns` columns and a window of
+        `window` samples (a multiple of max_dilation), the conditioning convolution in the kernel as infer_features has it
+        (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
+        request; close() the stream to free the engine."""
+        from .slots import SlotStream
+        e = self._new_engine(columns, window, implementation)
+        e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
+        e.setSelectorSeed(seed)
+        return SlotStream(e, window, pcm=pcm, owns_engine=True)
 
     def close(self):
         for e in self._engines.values():

@@ -1,0 +1,113 @@
+"""Slot mode (continuous batching) against lockstep generation at the same batch: steady-state time per step.
+
+C3 shape (bench.py: R 64, S 256, A 256, 20 layers, maxDilation 512), fp16, 80 feature channels, in one process:
+  lockstep   per chunk: nvw_pack_features of the chunk's features + nvw_run_range (the features path of a batch that started
+             together)
+  slots      per chunk: nvw_slots_step with every column busy and the utterances staggered -- lengths of 8 192 to 16 384 samples
+             and random progress at the start, so that columns end and are restarted (ring reset) in every step -- samples copied
+             to device memory
+Both read their features from one shared fp16 tensor (every utterance a different window of it).  Prints one JSON line per chunk
+size with ms per step of each and their ratio (slots / lockstep rate).
+
+    python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=12288)
+    ap.add_argument("--chunks", default="256,2048")
+    ap.add_argument("--steps", type=int, default=6, help="timed steps per chunk size (after two warm-up steps)")
+    ap.add_argument("--window", type=int, default=4096)
+    args = ap.parse_args()
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+
+    B, W = args.batch, args.window
+    w = bench.make_weights()
+    Wc, bc = bench.make_cond_layers()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    T_SRC = 65536
+    LEN_MIN, LEN_MAX = 8192, 16384      # utterance lengths (0.4 to 0.7 s at 22 kHz): at chunk 256 a few hundred columns restart per step
+    src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()          # the shared features
+    rng = np.random.default_rng(3)
+    for chunk in [int(c) for c in args.chunks.split(",")]:
+        warm, steps = 2, max(2, args.steps * 256 // chunk)      # (the lockstep engine's feature buffer holds every step: 2.4 MiB per sample)
+        n = (warm + steps) * chunk
+        assert n <= T_SRC and chunk <= W
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+        # ---- lockstep: pack the chunk's features, generate it ----
+        e = bench.build_engine(w, B, n)
+        e.setConditioningWeights(Wc, bc)
+        e.setSelectorSeed(5)
+        s = torch.cuda.current_stream().cuda_stream
+        for k in range(warm + steps):
+            if k == warm:
+                torch.cuda.synchronize()
+                ev[0].record()
+            x = src[:, k * chunk:(k + 1) * chunk]
+            assert lib.nvw_pack_features(e._h, x.data_ptr(), 16, 0, x.stride(0), x.stride(1), k * chunk, chunk, s)   # (batch stride 0)
+            assert lib.nvw_run_range(e._h, k * chunk, chunk, n, B, s)
+        ev[1].record()
+        torch.cuda.synchronize()
+        lock_ms = ev[0].elapsed_time(ev[1]) / steps
+        info = e.kernelInfo(B, False)
+        e.close()
+        torch.cuda.empty_cache()
+
+        # ---- slots: every column busy, utterances staggered, restarted as they end ----
+        e = bench.build_engine(w, B, W)
+        e.setConditioningWeights(Wc, bc)
+        e.setSelectorSeed(5)
+        e.slotsBegin(W)
+        left = np.zeros(B, dtype=np.int64)
+        uid = 0
+        y = torch.empty(B, chunk, dtype=torch.int32, device="cuda")
+        restarts = 0
+        t_host = 0.0
+        for k in range(warm + steps):
+            if k == warm:
+                torch.cuda.synchronize()
+                ev[0].record()
+                restarts = 0
+            h0 = time.perf_counter()
+            for b in np.nonzero(left <= 0)[0]:
+                length = int(rng.integers(LEN_MIN, LEN_MAX))
+                off = int(rng.integers(0, T_SRC - length))
+                e.slotStart(int(b), src[:, off:off + length], uid)
+                uid += 1
+                left[b] = length
+                restarts += 1
+            if k == 0:      # staggered: the first utterances are already part-way through
+                left -= rng.integers(0, LEN_MIN, size=B)
+                left[left <= 0] = 1
+            assert e.slotsStep(chunk, y)
+            left -= chunk
+            t_host += time.perf_counter() - h0
+        ev[1].record()
+        torch.cuda.synchronize()
+        slot_ms = ev[0].elapsed_time(ev[1]) / steps
+        e.slotsEnd()
+        e.close()
+        torch.cuda.empty_cache()
+        print(json.dumps({"batch": B, "chunk": chunk, "window": W, "lockstep_ms_per_step": round(lock_ms, 3),
+                          "slots_ms_per_step": round(slot_ms, 3), "slots_rate_vs_lockstep": round(lock_ms / slot_ms, 4),
+                          "restarts_per_timed_step": round(restarts / steps, 1), "host_ms_per_step": round(1e3 * t_host / (warm + steps), 2),
+                          "kernel": info, "device": torch.cuda.get_device_name(0)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
