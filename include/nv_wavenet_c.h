@@ -209,7 +209,8 @@ void nvw_set_audio_out(nvw_engine* e, short* pcm_out);
 /* the same with the buffer's size in int16 values stated: every run call then checks batch * num_samples <= elems */
 void nvw_set_audio_out_n(nvw_engine* e, short* pcm_out, size_t elems);
 /* Introspection: the device code nvw_run(e, n, batch_size, ..., dump_activations, ...) launches, e.g.
- * "wn::wavenet_wg<fp16,64,256,256,BT=2,EMBLDS=1,DUMP=0> tiles/wg=2 wgs=256 lds=149120" */
+ * "wn::wavenet_wg<fp16,64,256,256,BT=2,EMBLDS=1,DUMP=0> tiles/wg=2 wgs=256 lds=149120"; in slot mode, what a step launches
+ * while the highest active column is batch_size - 1 (dump_activations 0) */
 void nvw_kernel_info(nvw_engine* e, int batch_size, int dump_activations, char* buf, int buf_size);
 
 int nvw_run(nvw_engine* e, int num_samples, int batch_size, int* yOut, int batch_size_per_block,

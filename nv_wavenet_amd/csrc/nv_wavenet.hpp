@@ -1112,8 +1112,9 @@ public:
     // template arguments, tiles per workgroup, workgroups, dynamic LDS bytes (for benchmarks / logs).
     void kernelInfo(int batch_size, bool dumpActivations, char* buf, int n) const {
         const int tiles = (batch_size + 15) / 16;
-        const bool chainLaunch = isChain() && !m_featPtr;
-        const bool dump = dumpActivations || (!F16 && !chainLaunch && (m_featPtr || m_condRaw));      // (see launch())
+        const bool feat = m_featPtr != NULL || m_slotW > 0;      // (a slot-mode step launches wavenet_wg<.., RAW=3> as the features path)
+        const bool chainLaunch = isChain() && !feat;
+        const bool dump = dumpActivations || (!F16 && !chainLaunch && (feat || m_condRaw));      // (see launch())
         if (chainLaunch) {
             const int perLaunch = m_numCUs / m_chainStages, chains = tiles < perLaunch ? tiles : perLaunch;
             const int tpcNow = chainTpc((m_maxBatch + 15) / 16);
@@ -1122,7 +1123,7 @@ public:
                      m_chainStages * chains, CC::ldsBytes());
             return;
         }
-        const int raw = m_featPtr ? 3 : m_condRaw ? m_condRawKind : 0;
+        const int raw = feat ? 3 : m_condRaw ? m_condRawKind : 0;
         const int bt = launchTiles(tiles, dump, raw);
         int nEmb = planEmb<1>(dump, raw);
         size_t lds = ldsNeed<1>(m_numLayers, nEmb, dump);

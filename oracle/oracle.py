@@ -239,6 +239,20 @@ def philox_selectors(seed, N, B):
     return sel
 
 
+def philox_selectors_at(seed, k, uid):
+    """Selectors of arbitrary (local sample, uid) pairs, any 32-bit uid: philox_selectors(seed, N, B)[k, uid] where uid < B.
+    k, uid: integer arrays of one shape (broadcast); returns float32 of that shape."""
+    k, uid = np.broadcast_arrays(np.asarray(k, dtype=np.int64), np.asarray(uid, dtype=np.int64))
+    assert k.size == 0 or (k.min() >= 0 and k.max() < 2 ** 32 and uid.min() >= 0 and uid.max() < 2 ** 32)
+    kk = np.ascontiguousarray(k, dtype=np.uint32).reshape(-1)
+    uu = np.ascontiguousarray(uid, dtype=np.uint32).reshape(-1)
+    sel = np.zeros(kk.size, dtype=np.float32)
+    lib = _lib("oracle")
+    lib.nvw_philox_selectors_at.argtypes = [C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, _fp]
+    lib.nvw_philox_selectors_at(int(seed), int(kk.size), kk.ctypes.data, uu.ctypes.data, _f(sel))
+    return sel.reshape(k.shape)
+
+
 def mulaw_pcm_table(A):
     """int16 PCM value of every sample index (pytorch/utils.py:62-70 + inference.py:58-60)."""
     t = np.zeros(A, dtype=np.int16)

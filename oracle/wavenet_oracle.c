@@ -444,6 +444,17 @@ void nvw_philox_selectors(uint64_t seed, int N, int B, float* sel) {
         }
 }
 
+/* the same selector for a list of (local sample k[i], uid[i]) pairs -- the counter {k, uid} of a slot-mode utterance, any uid of
+ * 32 bits (nvw_philox_selectors covers uid = column < B only): sel[i] = top 24 bits of word 0 of Philox({k, uid, 0, 0}, seed). */
+void nvw_philox_selectors_at(uint64_t seed, int n, const uint32_t* k, const uint32_t* uid, float* sel) {
+    uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    for (int i = 0; i < n; i++) {
+        uint32_t ctr[4] = {k[i], uid[i], 0u, 0u}, out[4];
+        nvw_philox4x32_10(ctr, key, out);
+        sel[i] = (float)(out[0] >> 8) * (1.0f / 16777216.0f);
+    }
+}
+
 /* pytorch/utils.py:62-70 (mu_law_decode_numpy) followed by pytorch/inference.py:58-60
  * (MAX_WAV_VALUE * audio, astype('int16')): float64 arithmetic, truncation toward zero, and the
  * top bin (signal = +1 -> 32768.0) wraps to -32768 exactly as numpy's cast does on x86.

@@ -8,11 +8,19 @@
 //                     it (buffer-resource ring: gemm_b / take_group / refill_group / skip_frags, the wrap behind the head)
 //   wnp_gate          the fp16 engine's gate on pre-scaled pre-activations (gate1<true> and the staged gate_stage)
 //   wnp_hog_*         a kernel that holds a number of CUs for a while (the chain's fault-tolerance test)
+//   wnp_slot_feed     wn::slots_feed<F16>: slot mode's window feed (features + selectors) from column descriptors
+//   wnp_slot_reset    wn::slots_reset: slot mode's column reset (ring lanes, descriptors, history)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
 #include "../../nv_wavenet_amd/csrc/wn_chain.hpp"
 #include "../../nv_wavenet_amd/csrc/wn_kernels.hpp"
+
+// The product's slot kernels and launchers, compiled into this library as they are.  Hidden: this copy of wn::slots_feed /
+// wn::slots_reset is neither exported nor bound to another library's copy (nor can it interpose on the engine library's).
+#pragma GCC visibility push(hidden)
+#include "../../nv_wavenet_amd/csrc/slots.hip"
+#pragma GCC visibility pop
 
 using namespace wn;
 
@@ -406,6 +414,32 @@ int wnp_gate(int n, int way, const float* a, const float* b, float* h) {
     CK(hipFree(dh));
     return 0;
 }
+
+// wn::slots_feed<precision == 16> on the null stream, then synchronises.  Every pointer is device memory: feat [W][tiles][KFC] of
+// the precision's fragments, sel [W][maxBatch] fp32, desc [>= cols] wn::SlotDesc.
+int wnp_slot_feed(int precision, void* feat, float* sel, const void* desc, int cols, int maxBatch, int tiles, int nCond,
+                  long long counter, int T, int W, int count, unsigned long long seed) {
+    const bool ok = precision == 16 ? slots_feed<true>(0, feat, sel, (const SlotDesc*)desc, cols, maxBatch, tiles, nCond, counter, T, W,
+                                                        count, seed)
+                                    : slots_feed<false>(0, feat, sel, (const SlotDesc*)desc, cols, maxBatch, tiles, nCond, counter, T,
+                                                        W, count, seed);
+    if (!ok) return -2;
+    CK(hipDeviceSynchronize());
+    return 0;
+}
+
+// wn::slots_reset on the null stream, then synchronises.  Device memory: desc [maxBatch] wn::SlotDesc, upd [nUpd] wn::SlotUpdate,
+// cols [nCols], ring [tiles][ringSlots][fragsPerSlot KiB], yInPrev / yInCur [maxBatch].
+int wnp_slot_reset(void* desc, const void* upd, int nUpd, const int* cols, int nCols, void* ring, int ringSlots, int fragsPerSlot,
+                   int* yInPrev, int* yInCur) {
+    if (!slots_reset(0, (SlotDesc*)desc, (const SlotUpdate*)upd, nUpd, cols, nCols, ring, ringSlots, fragsPerSlot, yInPrev, yInCur))
+        return -2;
+    CK(hipDeviceSynchronize());
+    return 0;
+}
+
+int wnp_slot_desc_bytes() { return (int)sizeof(SlotDesc); }
+int wnp_slot_update_bytes() { return (int)sizeof(SlotUpdate); }
 
 // asynchronously: `cus` workgroups of one wave and 100 KiB of LDS each spin for `ms` milliseconds on a stream of their own
 int wnp_hog_start(int cus, double ms) {

@@ -117,6 +117,23 @@ def test_philox_known_answers():
     assert abs(float(big.mean()) - 0.5) < 0.01 and len(np.unique(big)) > 16000
 
 
+def test_philox_selectors_at_any_uid_equal_the_selector_matrix():
+    """philox_selectors_at (the selectors of slot-mode utterances, any 32-bit uid) is philox_selectors where that one reaches,
+    uid < B, for a seed with a non-zero high word; beyond it, single draws of the generator (uids 2**31 and 2**32 - 1)."""
+    seed = 0x5EED0000000071
+    N, B = 300, 37
+    sel = O.philox_selectors(seed, N, B)
+    k, u = np.meshgrid(np.arange(N), np.arange(B), indexing="ij")
+    assert np.array_equal(O.philox_selectors_at(seed, k, u), sel)
+    ks = np.array([0, 1, 7, 2 ** 31 + 5, 2 ** 32 - 1])
+    for uid in (2 ** 31, 2 ** 32 - 1, 12345):
+        got = O.philox_selectors_at(seed, ks, uid)
+        want = [np.float32((O.philox4x32_10([int(kk), uid, 0, 0], [seed & 0xFFFFFFFF, seed >> 32])[0] >> 8) / 16777216.0)
+                for kk in ks]
+        assert np.array_equal(got, np.array(want, dtype=np.float32)), uid
+    assert O.philox_selectors_at(seed, [5], [1]).dtype == np.float32 and O.philox_selectors_at(seed, [], []).shape == (0,)
+
+
 def test_mulaw_pcm_table_matches_reference_python():
     """tests/golden/mulaw_pcm.npz was produced by the reference's utils.mu_law_decode_numpy +
     inference.py's int16 cast (tests/golden/make_mulaw_golden.py)."""

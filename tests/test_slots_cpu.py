@@ -151,3 +151,22 @@ def test_slot_kernels_are_in_the_shipped_code_object_and_use_no_scratch():
         _, vgpr, agpr, sgpr, scratch, spill = names[name]
         assert scratch == 0 and spill == 0, names[name]
         assert vgpr <= 64, names[name]          # (a memory-bound kernel: occupancy, not registers)
+
+
+def test_test_library_keeps_its_copy_of_the_slot_launchers_to_itself():
+    """tests/cpp/wn_primitives.hip compiles the product's slots.hip for the kernel-level tests (test_slot_kernels_gpu.py).  Its
+    copy of wn::slots_feed / wn::slots_reset must not be exported -- a process that loads both libraries would otherwise have two
+    definitions of one symbol -- while the test entries are."""
+    import shutil
+    import subprocess
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "libwn_primitives.so")
+    if not os.path.exists(path):
+        pytest.skip("build the test library first (__graft_entry__.build())")
+    nm = shutil.which("llvm-nm", path="/opt/rocm/llvm/bin") or shutil.which("nm")
+    assert nm, "no nm"
+    out = subprocess.check_output([nm, "-D", "--defined-only", path], text=True)
+    exported = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    for name in ("wnp_slot_feed", "wnp_slot_reset", "wnp_slot_desc_bytes", "wnp_slot_update_bytes"):
+        assert name in exported, name
+    leaked = [s for s in exported if "slots_feed" in s or "slots_reset" in s or "slot_feed_kernel" in s or "slot_reset_kernel" in s]
+    assert not leaked, leaked
