@@ -43,7 +43,8 @@ typedef void (*nvw_consume_fn)(int* yOut, int init_sample, int count, void* user
  * another revision should check this instead of finding a different kernel behind a number.  5 = round 5 (the
  * feature-conditioning entry points below); 6 = this header (round 6: nvw_get_features returns int; nvw_upsample_features,
  * nvw_generate_stream and nvw_get_features check their ranges and refuse with 0 instead of reaching the class's asserts;
- * organisation 10; nvw_set_ring_in_lds); 7 = slot mode (nvw_slots_begin .. nvw_slots_end, below). */
+ * organisation 10; nvw_set_ring_in_lds); 7 = slot mode (nvw_slots_begin .. nvw_slots_end, below), and since, additively within 7
+ * (every earlier entry unchanged), slot mode from mel frames (nvw_slot_start_mel .. nvw_slots_get_features). */
 #define NVW_ABI_VERSION 7
 int nvw_abi_version(void);
 int nvw_supported(int R, int S, int A, int precision);
@@ -254,6 +255,31 @@ int nvw_slot_start(nvw_engine* e, int slot, const void* x, int precision, long l
 int nvw_slot_stop(nvw_engine* e, int slot);
 int nvw_slots_step(nvw_engine* e, int count, int* yOut, short* pcm, void* stream);
 void nvw_slots_end(nvw_engine* e);
+
+/* SLOT MODE FROM MEL FRAMES (additive within ABI 7).  A column may hold a mel utterance instead of upsampled features: its frames
+ * before upsampling, upsampled by the engine (the table of nvw_set_upsampling) in the steps that generate them.  Its samples are bit
+ * for bit those of column uid of a lockstep nvw_set_mel + nvw_generate_stream run with the same seed, whatever the column, the join
+ * step, the step sizes, the neighbours, and however its frames were handed over.  Frames may arrive while the column runs (the
+ * upsampling is causal: sample k reads frames k / stride - j, j < window / stride): a step never goes past the frames available.
+ *   nvw_slot_start_mel     column `slot` takes a mel utterance at the next step: frames mel[c*c_stride + f*f_stride] (device memory,
+ *                          `precision` = 16 | 32 bits, n_cond channels, kept alive while the column runs), `frames` of them written
+ *                          so far, final != 0: no more will come (the utterance is frames x stride samples long), its uid.  0 when
+ *                          refused (not in slot mode, no nvw_set_upsampling, slot out of range, host memory, bad precision,
+ *                          non-positive strides, frames < 0, or 0 frames with final).
+ *   nvw_slot_mel_frames    `frames` frames of column `slot`'s utterance are now written in the same buffer, ordered before the next
+ *                          step on the step stream; final != 0: no more will come.  0 when refused (not a mel column, already final,
+ *                          fewer frames than before, 0 frames with final; nothing changes).
+ *   nvw_slots_headroom     the largest count the next nvw_slots_step accepts: the window, or the minimum over non-final mel columns
+ *                          of frames x stride minus their next local sample (may be 0).  nvw_slots_step refuses a larger count and
+ *                          changes nothing; only sessions with mel columns can meet this refusal.
+ *   nvw_slots_get_features debug getter: the window's feature fragments of engine samples [first_sample, first_sample + count), which
+ *                          must lie within the last window of samples generated, in the order of nvw_get_features (synchronises).
+ *                          0 when refused. */
+int nvw_slot_start_mel(nvw_engine* e, int slot, const void* mel, int precision, long long c_stride, long long f_stride, int frames,
+                       int final, unsigned uid);
+int nvw_slot_mel_frames(nvw_engine* e, int slot, int frames, int final);
+int nvw_slots_headroom(nvw_engine* e);
+int nvw_slots_get_features(nvw_engine* e, void* dst, long long first_sample, int count);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

@@ -84,6 +84,10 @@ SIGNATURES = {
     "nvw_slot_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "nvw_slots_step": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_void_p]),
     "nvw_slots_end": (None, [C.c_void_p]),
+    "nvw_slot_start_mel": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_uint]),
+    "nvw_slot_mel_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "nvw_slots_headroom": (C.c_int, [C.c_void_p]),
+    "nvw_slots_get_features": (C.c_int, [C.c_void_p, _fp, C.c_longlong, C.c_int]),
     "nvw_device_synchronize": (None, []),
     "nvw_time_runs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "wavenet_infer": (None, [C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 7 +

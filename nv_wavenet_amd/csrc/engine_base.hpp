@@ -63,6 +63,10 @@ struct nvw_engine {
     virtual bool slotStop(int) = 0;
     virtual bool slotsStep(int, int*, short*, hipStream_t) = 0;
     virtual void slotsEnd() = 0;
+    virtual bool slotStartMel(int, const void*, int, long long, long long, int, int, unsigned) = 0;
+    virtual bool slotMelFrames(int, int, int) = 0;
+    virtual int slotsHeadroom() = 0;
+    virtual bool slotsGetFeatures(void*, long long, int) = 0;
 };
 
 template <typename Tw, typename Td, int R, int S, int A>
@@ -142,6 +146,12 @@ struct EngineImpl : nvw_engine {
     bool slotStop(int slot) override { return eng.slotStop(slot); }
     bool slotsStep(int count, int* y, short* pcm, hipStream_t s) override { return eng.slotsStep(count, y, pcm, s); }
     void slotsEnd() override { eng.slotsEnd(); }
+    bool slotStartMel(int slot, const void* mel, int prec, long long cS, long long fS, int frames, int final, unsigned uid) override {
+        return eng.slotStartMel(slot, mel, prec, cS, fS, frames, final, uid);
+    }
+    bool slotMelFrames(int slot, int frames, int final) override { return eng.slotMelFrames(slot, frames, final); }
+    int slotsHeadroom() override { return eng.slotsHeadroom(); }
+    bool slotsGetFeatures(void* dst, long long first, int count) override { return eng.slotsGetFeatures(dst, first, count); }
 };
 
 typedef nvw_engine* (*nvw_factory_fn)(int L, int maxD, int B, int N, int impl, int tanhEmbed, int organisation);

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "slots.hpp"
+#include "slots_mel.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
 
@@ -164,6 +165,23 @@ protected:
     char* m_slotStage[2] = {NULL, NULL};    // pinned host staging of them, used by alternate steps ...
     hipEvent_t m_slotEv[2] = {NULL, NULL};  // ... each reused once the copy of the step before last has completed
     int m_slotParity = 0;
+    // ... and its mel columns (slots_mel.hpp): utterances handed over as frames, upsampled step by step
+    std::vector<wn::MelDesc> m_melHost;     // the columns' mel descriptors as the host has set them (state 0: not a mel column) ...
+    std::vector<char> m_melDirty;           // ... and the columns whose descriptor the next step writes
+    std::vector<int> m_melDirtyList;
+    int m_melColumns = 0;                   // columns with state != 0
+    bool m_melTilesDirty = false;           // the tile list changes at the next step
+    int m_melTiles = 0;                     // tiles in the device's list
+    bool m_melPrepared = false;             // slots_mel_prepare done for this engine
+    wn::MelDesc* m_melDesc = NULL;          // [maxBatch] on the device
+    char* m_melUpd = NULL;                  // device: a step's updates [maxBatch] + the list of tiles with mel columns [tiles]
+    char* m_melStageHost[2] = {NULL, NULL}; // pinned host staging of them, used by alternate steps as m_slotStage
+    hipEvent_t m_melEv[2] = {NULL, NULL};
+    int m_melParity = 0;
+    elem* m_melStage = NULL;                // the step's frames in fragment order, [stage frames][mel tiles][KFC], then at m_melRecOff
+    size_t m_melStageElems = 0;             // the step's upsampled samples per column, [mel tiles * 16][count] of KFC KiB / 16
+    size_t m_melRecOff = 0;
+    int* m_melColInfo = NULL;               // [tiles * 16] int2: per column, phase of its first sample and samples it stores
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -1401,6 +1419,12 @@ public:
         m_slotHost.assign(m_maxBatch, wn::SlotDesc{});
         m_slotPending.assign(m_maxBatch, 0);
         m_slotPendingList.clear();
+        m_melHost.assign(m_maxBatch, wn::MelDesc{});
+        m_melDirty.assign(m_maxBatch, 0);
+        m_melDirtyList.clear();
+        m_melColumns = 0;
+        m_melTiles = 0;
+        m_melTilesDirty = false;
         const size_t cells = (size_t)window * m_maxBatch;
         gpuErrChk(hipMalloc(&m_slotDesc, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
         gpuErrChk(hipMemset(m_slotDesc, 0, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
@@ -1432,6 +1456,7 @@ public:
         if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
             tStride <= 0 || length <= 0 || !isDevicePtr(x))
             return false;
+        slotDropMel(slot);
         wn::SlotDesc& d = m_slotHost[slot];
         d.x = x;
         d.cStride = cStride;
@@ -1447,22 +1472,94 @@ public:
     // Column `slot` goes idle at the next step (its features are no longer read from then on).
     bool slotStop(int slot) {
         if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
+        slotDropMel(slot);
         m_slotHost[slot].active = 0;
         slotMarkPending(slot, 2);
+        return true;
+    }
+    // Column `slot` takes a mel utterance at the next step: its frames mel[c * cStride + f * fStride] (device memory,
+    // `precision`-bit floats, n_cond channels; kept alive while the column runs), `frames` of them available so far, final != 0: no
+    // more will come (its length is frames x stride), its uid.  Upsampled with the table of setUpsampling in the steps that generate
+    // them.  Replaces whatever the column held.  false (nothing changes): not in slot mode, no upsampling, slot outside the batch,
+    // non-device mel, bad precision, non-positive strides, frames < 0, or 0 frames of a final utterance.
+    bool slotStartMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
+        if (m_slotW <= 0 || m_upStride <= 0 || slot < 0 || slot >= m_maxBatch || mel == NULL || (precision != 32 && precision != 16) ||
+            cStride <= 0 || fStride <= 0 || frames < 0 || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL ||
+            !isDevicePtr(mel))
+            return false;
+        if (!m_melDesc) melAllocate();
+        wn::MelDesc& d = m_melHost[slot];
+        if (!d.state) m_melColumns++;
+        d.mel = mel;
+        d.cStride = cStride;
+        d.fStride = fStride;
+        d.start = 0;          // (the step that applies the start sets it)
+        d.frames = frames;
+        d.uid = uid;
+        d.precision = precision;
+        d.state = final ? 2 : 1;
+        melMarkDirty(slot);
+        m_melTilesDirty = true;
+        m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
+        slotMarkPending(slot, 1);
+        return true;
+    }
+    // More frames of the mel utterance of column `slot` are available in the same buffer (written by the caller, ordered before the
+    // next step on the step stream); final != 0: no more will come.  false (nothing changes): not a mel column, already final, the
+    // count decreases, or 0 frames made final.
+    bool slotMelFrames(int slot, int frames, int final) {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
+        wn::MelDesc& d = m_melHost[slot];
+        if (d.state != 1 || frames < d.frames || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL) return false;
+        d.frames = frames;
+        if (final) d.state = 2;
+        melMarkDirty(slot);
+        return true;
+    }
+    // The largest count the next step accepts: W, or the fewest samples a non-final mel column has frames for beyond its next
+    // sample (0 when one has none).
+    int slotsHeadroom() const {
+        if (m_slotW <= 0) return 0;
+        long long h = m_slotW;
+        if (m_melColumns > 0)
+            for (int b = 0; b < m_maxBatch; b++) {
+                const wn::MelDesc& d = m_melHost[b];
+                if (d.state != 1) continue;
+                const long long next = m_slotPending[b] == 1 ? 0 : m_slotCounter - d.start;
+                const long long left = (long long)d.frames * m_upStride - next;
+                if (left < h) h = left;
+            }
+        return h < 0 ? 0 : (int)h;
+    }
+    // debug getter: the window's feature fragments of engine samples [first, first + count) -- within the last W generated -- in the
+    // order of getFeatures (synchronises).  false: outside that range.
+    bool slotsGetFeatures(void* dst, long long first, int count) {
+        if (m_slotW <= 0 || dst == NULL || count <= 0 || first < m_slotCounter - m_slotW || first < 0 || first + count > m_slotCounter)
+            return false;
+        gpuErrChk(hipDeviceSynchronize());
+        for (int done = 0; done < count;) {
+            const int row = (int)((first + done) % m_slotW), c = count - done < m_slotW - row ? count - done : m_slotW - row;
+            gpuErrChk(hipMemcpy((elem*)dst + featureElems(done), m_slotFeat + featureElems(row), featureElems(c) * sizeof(elem), hipMemcpyDefault));
+            done += c;
+        }
         return true;
     }
     // One step of `count` <= W samples, asynchronously on `stream`: the pending starts and stops (one reset launch), the window feed
     // (one launch), the generation -- two launches where the window rows wrap -- up to the tile of the highest active column, the PCM
     // when pcm != NULL, and the copies of the step's samples / PCM into yOut / pcm ([maxBatch][count], host or device; NULL: none).
-    // Columns without an utterance hold unspecified values.  Synchronises the stream when an output is host memory.
+    // Columns without an utterance hold unspecified values.  Synchronises the stream when an output is host memory.  With mel columns
+    // also their descriptor updates and their feed (slots_mel.hpp: three launches after the window feed); false (nothing changes)
+    // when count exceeds slotsHeadroom().
     bool slotsStep(int count, int* yOut, short* pcm, hipStream_t stream = 0) {
         if (m_slotW <= 0 || count <= 0 || count > m_slotW) return false;
+        if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return false;      // (mel columns short of frames)
         const int W = m_slotW;
         bool ok = true;
-        if (!m_slotPendingList.empty()) ok = slotApplyPending(stream);
+        if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream);      // (first: it reads the pending starts)
+        if (!m_slotPendingList.empty()) ok = slotApplyPending(stream) && ok;
         int cols = 0;
         for (int b = m_maxBatch - 1; b >= 0; b--)
-            if (m_slotHost[b].active) {
+            if (m_slotHost[b].active || (m_melColumns > 0 && m_melHost[b].state)) {
                 cols = b + 1;
                 break;
             }
@@ -1478,6 +1575,10 @@ public:
             if (m_featDirty) buildFeatStream(stream);
             ok = wn::slots_feed<F16>(stream, m_slotFeat, m_slotSel, m_slotDesc, cols, m_maxBatch, m_tiles, m_nCond, m_slotCounter, T, W, count,
                                      m_rngSeed) && ok;
+            if (m_melTiles > 0)
+                ok = wn::slots_mel_feed<F16>(stream, m_slotFeat, m_slotSel, melStage(count), m_melStage + m_melRecOff, m_melColInfo, m_melDesc,
+                                             (const int*)(m_melUpd + melTileOff()), m_melTiles, m_maxBatch, m_tiles, m_nCond, m_upTab, m_upBias,
+                                             m_upWindow / m_upStride, m_upStride, m_slotCounter, T, W, count, m_rngSeed) && ok;
             for (int i = 0; i < pieces; i++) ok = slotLaunch(piece[i][0], piece[i][1], cols, stream) && ok;
             if (pcm != NULL) {
                 for (int i = 0; i < pieces; i++) {
@@ -1525,6 +1626,28 @@ public:
         m_slotHost.clear();
         m_slotPending.clear();
         m_slotPendingList.clear();
+        if (m_melDesc) {
+            gpuErrChk(hipFree(m_melDesc));
+            gpuErrChk(hipFree(m_melUpd));
+            gpuErrChk(hipFree(m_melColInfo));
+            if (m_melStage) gpuErrChk(hipFree(m_melStage));
+            for (int i = 0; i < 2; i++) {
+                gpuErrChk(hipHostFree(m_melStageHost[i]));
+                gpuErrChk(hipEventDestroy(m_melEv[i]));
+                m_melStageHost[i] = NULL;
+                m_melEv[i] = NULL;
+            }
+            m_melDesc = NULL;
+            m_melUpd = NULL;
+            m_melColInfo = NULL;
+            m_melStage = NULL;
+            m_melStageElems = 0;
+        }
+        m_melHost.clear();
+        m_melDirty.clear();
+        m_melDirtyList.clear();
+        m_melColumns = 0;
+        m_melTiles = 0;
     }
 
     bool run(int num_samples, int batch_size, int* yOut = NULL, int batch_size_per_block = 1,
@@ -1619,6 +1742,86 @@ protected:
         m_slotParity ^= 1;
         return wn::slots_reset(stream, m_slotDesc, (const wn::SlotUpdate*)m_slotUpd, nUpd, (const int*)(m_slotUpd + colOff), nCols, m_ring,
                                m_ringSlots, (int)(R * 16 * sizeof(elem) / 1024), m_yInPrev, m_yInCur);
+    }
+    // ---- mel columns (slots_mel.hpp) ----
+    size_t melTileOff() const { return (size_t)m_maxBatch * sizeof(wn::MelUpdate); }
+    void melMarkDirty(int slot) {
+        if (!m_melDirty[slot]) m_melDirtyList.push_back(slot);
+        m_melDirty[slot] = 1;
+    }
+    // a column that is started or stopped stops being a mel column
+    void slotDropMel(int slot) {
+        if (m_melHost.empty() || !m_melHost[slot].state) return;
+        m_melHost[slot].state = 0;
+        m_melColumns--;
+        melMarkDirty(slot);
+        m_melTilesDirty = true;
+    }
+    void melAllocate() {
+        gpuErrChk(hipMalloc(&m_melDesc, (size_t)m_maxBatch * sizeof(wn::MelDesc)));
+        gpuErrChk(hipMemset(m_melDesc, 0, (size_t)m_maxBatch * sizeof(wn::MelDesc)));
+        const size_t bytes = melTileOff() + (size_t)m_tiles * sizeof(int);
+        gpuErrChk(hipMalloc(&m_melUpd, bytes));
+        gpuErrChk(hipMalloc(&m_melColInfo, (size_t)m_tiles * 16 * 2 * sizeof(int)));
+        for (int i = 0; i < 2; i++) {
+            gpuErrChk(hipHostMalloc((void**)&m_melStageHost[i], bytes, hipHostMallocDefault));
+            gpuErrChk(hipEventCreateWithFlags(&m_melEv[i], hipEventDisableTiming));
+            gpuErrChk(hipEventRecord(m_melEv[i], 0));
+        }
+        m_melParity = 0;
+        if (!m_melPrepared) m_melPrepared = wn::slots_mel_prepare<F16>();
+        gpuErrChk(hipDeviceSynchronize());
+    }
+    // the stage and records of a step of `count` samples (grown when a longer step needs more; the steps before it are waited for)
+    elem* melStage(int count) {
+        m_melRecOff = (size_t)wn::slots_mel_stage_frames(count, m_upStride, m_upWindow / m_upStride) * featureElems(1);
+        const size_t need = m_melRecOff + featureElems(count);
+        if (need > m_melStageElems) {
+            gpuErrChk(hipDeviceSynchronize());
+            if (m_melStage) gpuErrChk(hipFree(m_melStage));
+            gpuErrChk(hipMalloc(&m_melStage, need * sizeof(elem)));
+            m_melStageElems = need;
+        }
+        return m_melStage;
+    }
+    // the changed mel descriptors (a start takes the counter of this step) and, when it changed, the list of tiles holding mel
+    // columns -> pinned staging -> device, and one slot_mel_apply_kernel launch; the staging half is reused two steps later
+    bool melApplyPending(hipStream_t stream) {
+        char* const stage = m_melStageHost[m_melParity];
+        gpuErrChk(hipEventSynchronize(m_melEv[m_melParity]));
+        wn::MelUpdate* const upd = (wn::MelUpdate*)stage;
+        int* const tileList = (int*)(stage + melTileOff());
+        int nUpd = 0;
+        for (int b : m_melDirtyList) {
+            wn::MelDesc& d = m_melHost[b];
+            if (d.state && m_slotPending[b] == 1) d.start = m_slotCounter;      // local sample 0 is generated by this step
+            upd[nUpd].column = b;
+            upd[nUpd].pad = 0;
+            upd[nUpd].d = d;
+            nUpd++;
+            m_melDirty[b] = 0;
+        }
+        m_melDirtyList.clear();
+        bool ok = true;
+        if (nUpd) {
+            gpuErrChk(hipMemcpyAsync(m_melUpd, upd, (size_t)nUpd * sizeof(wn::MelUpdate), hipMemcpyHostToDevice, stream));
+            ok = wn::slots_mel_apply(stream, m_melDesc, (const wn::MelUpdate*)m_melUpd, nUpd);
+        }
+        if (m_melTilesDirty) {
+            int n = 0;
+            for (int tile = 0; tile * 16 < m_maxBatch; tile++)
+                for (int j = 0; j < 16 && tile * 16 + j < m_maxBatch; j++)
+                    if (m_melHost[tile * 16 + j].state) {
+                        tileList[n++] = tile;
+                        break;
+                    }
+            if (n) gpuErrChk(hipMemcpyAsync(m_melUpd + melTileOff(), tileList, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+            m_melTiles = n;
+            m_melTilesDirty = false;
+        }
+        gpuErrChk(hipEventRecord(m_melEv[m_melParity], stream));
+        m_melParity ^= 1;
+        return ok;
     }
     // wavenet_wg<.., RAW=3> on window rows [t0, t0 + count) of the first `cols` columns (the launch of run_partial for features,
     // with the window's buffers and the selector table)

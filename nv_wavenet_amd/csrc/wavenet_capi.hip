@@ -301,6 +301,33 @@ int nvw_slots_step(nvw_engine* e, int count, int* yOut, short* pcm, void* stream
     return e->slotsStep(count, yOut, pcm, (hipStream_t)stream) ? 1 : 0;
 }
 void nvw_slots_end(nvw_engine* e) { e->slotsEnd(); }
+// ---- slot mode from mel frames (additive within ABI 7) ---------------------------------------------------------------------------
+int nvw_slot_start_mel(nvw_engine* e, int slot, const void* mel, int precision, long long c_stride, long long f_stride, int frames,
+                       int final, unsigned uid) {
+    if (!e->slotStartMel(slot, mel, precision, c_stride, f_stride, frames, final, uid)) {
+        fprintf(stderr, "nvw_slot_start_mel: refused (nvw_slots_begin and nvw_set_upsampling first; slot %d of %d; device frames of 16 or 32 "
+                "bits; strides %lld, %lld positive; frames %d >= 0, > 0 when final)\n", slot, e->maxBatch(), c_stride, f_stride, frames);
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_mel_frames(nvw_engine* e, int slot, int frames, int final) {
+    if (!e->slotMelFrames(slot, frames, final)) {
+        fprintf(stderr, "nvw_slot_mel_frames: refused (slot %d of %d: not a running mel column, already final, or %d frames is fewer than "
+                "before)\n", slot, e->maxBatch(), frames);
+        return 0;
+    }
+    return 1;
+}
+int nvw_slots_headroom(nvw_engine* e) { return e->slotsHeadroom(); }
+int nvw_slots_get_features(nvw_engine* e, void* dst, long long first_sample, int count) {
+    if (!e->slotsGetFeatures(dst, first_sample, count)) {
+        fprintf(stderr, "nvw_slots_get_features: refused (samples [%lld, %lld) are not among the last window of samples generated)\n",
+                first_sample, first_sample + count);
+        return 0;
+    }
+    return 1;
+}
 
 void nvw_device_synchronize(void) { gpuErrChk(hipDeviceSynchronize()); }
 

@@ -372,6 +372,41 @@ class WavenetEngine:
             assert pcm.dtype == np.int16 and pcm.flags["C_CONTIGUOUS"]
         return bool(lib.nvw_slots_step(self._h, int(count), addr(yOut), addr(pcm), stream))
 
+    def slotStartMel(self, slot, mel, uid, frames=None, final=True):
+        """Column `slot` takes a mel utterance at the next step: mel = its frames before upsampling, CUDA tensor [n_cond][capacity]
+        (float32 or float16, any strides), of which the first `frames` (default: all) are written; final: no more will come (its
+        length is frames x stride).  More frames go into the same tensor, announced with slotMelFrames.  Needs setUpsampling."""
+        import torch
+        assert hasattr(mel, "data_ptr") and mel.is_cuda and mel.dim() == 2, "mel: a CUDA tensor [n_cond][frames]"
+        bits = {torch.float32: 32, torch.float16: 16}.get(mel.dtype)
+        assert bits, "mel must be float32 or float16"
+        n = mel.size(1) if frames is None else int(frames)
+        assert mel.size(0) == self.nCond and 0 <= n <= mel.size(1), "mel [%d][>= %d] expected, got %s" % (self.nCond, n, tuple(mel.shape))
+        if not lib.nvw_slot_start_mel(self._h, int(slot), mel.data_ptr(), bits, mel.stride(0), mel.stride(1), n, 1 if final else 0,
+                                      int(uid) & 0xFFFFFFFF):
+            raise ValueError("nvw_slot_start_mel refused slot %d" % slot)
+        self._slot_keep[int(slot)] = mel      # (read by the steps while the column runs; let go when the column starts again)
+
+    def slotMelFrames(self, slot, frames, final=False):
+        """The first `frames` frames of column `slot`'s mel tensor are written (ordered before the next step); final: no more."""
+        if not lib.nvw_slot_mel_frames(self._h, int(slot), int(frames), 1 if final else 0):
+            raise ValueError("nvw_slot_mel_frames refused slot %d, %d frames" % (slot, frames))
+
+    def slotsHeadroom(self):
+        """The largest count the next slotsStep accepts (the window unless a running mel column is short of frames)."""
+        return int(lib.nvw_slots_headroom(self._h))
+
+    def slotsGetFeatures(self, first, count):
+        """Debug getter: the window's feature fragments of engine samples [first, first + count) (within the last window generated)
+        as a CUDA tensor [count][condTiles()][featureFragments()][4][16][8 | 4], the layout of getFeatures."""
+        import torch
+        epl = 8 if self.precision == 16 else 4
+        out = torch.empty(count, self.condTiles(), self.featureFragments(), 4, 16, epl, device="cuda",
+                          dtype=torch.float16 if self.precision == 16 else torch.float32)
+        if not lib.nvw_slots_get_features(self._h, out.data_ptr(), int(first), int(count)):
+            raise ValueError("nvw_slots_get_features refused samples [%d, %d)" % (first, first + count))
+        return out
+
     def slotsEnd(self):
         lib.nvw_slots_end(self._h)
         self._slot_keep = {}

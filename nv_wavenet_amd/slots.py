@@ -12,6 +12,16 @@ the columns in use stay packed at the front of the batch and the launches cover 
             ...                                      # this step's samples of every running request
         for handle in stream.finished():
             ...                                      # each finished request once
+
+Requests may also be mel frames, upsampled by the engine (its setUpsampling table) as they are generated, and streamed: a front end
+that emits frames while it decodes submits what it has and extends the request as more are written into the same tensor.
+
+    h = stream.submit_mel(mel, frames=0, final=False)   # mel: CUDA tensor [n_cond][capacity]; frames written so far
+    stream.extend_mel(h, 12)                            # 12 frames written now (queued or running)
+    stream.extend_mel(h, 40, final=True)                # the last of them
+    stream.step(2048)                                   # min(2048, headroom) samples: a step never outruns the frames written
+
+A queued streamed request is admitted once it has frames for min(count, its length) samples, so admitting never shortens a step.
 """
 import heapq
 from collections import deque
@@ -37,8 +47,9 @@ class SlotStream:
         self._owns = owns_engine
         engine.slotsBegin(self.window)
         self._free = list(range(self.columns))         # a heap: lowest free column first
-        self._queue = deque()                          # (handle, features, uid) waiting for a column
-        self._running = {}                             # column -> [handle, samples still to come]
+        self._queue = deque()                          # (handle, features, uid, mel request or None) waiting for a column
+        self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
+        self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
         self._done = []
         self._next_handle = 0
         self._next_uid = 0
@@ -52,8 +63,36 @@ class SlotStream:
         if uid is None:
             uid = self._next_uid
         self._next_uid = max(self._next_uid, int(uid) + 1)
-        self._queue.append((handle, features, int(uid)))
+        self._queue.append((handle, features, int(uid), None))
         return handle
+
+    def submit_mel(self, mel, uid=None, frames=None, final=True):
+        """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
+        final: no more will come); returns its handle.  uid as for submit."""
+        assert mel.dim() == 2, "mel: [n_cond][frames]"
+        n = mel.size(1) if frames is None else int(frames)
+        assert 0 <= n <= mel.size(1) and (n > 0 or not final)
+        handle = self._next_handle
+        self._next_handle += 1
+        if uid is None:
+            uid = self._next_uid
+        self._next_uid = max(self._next_uid, int(uid) + 1)
+        req = [n, bool(final), None, 0]
+        self._mel[handle] = req
+        self._queue.append((handle, mel, int(uid), req))
+        return handle
+
+    def extend_mel(self, handle, frames, final=False):
+        """The first `frames` frames of mel request `handle` are written (queued or running); final: no more will come."""
+        req = self._mel[handle]
+        assert not req[1] and frames >= req[0], "a final request, or fewer frames than before"
+        if req[2] is not None:
+            self.engine.slotMelFrames(req[2], frames, final)
+        req[0], req[1] = int(frames), bool(final)
+
+    def _ready(self, item, count):
+        req = item[3]
+        return req is None or req[1] or req[0] * self.engine.upStride >= count      # (a final request: min(count, length) <= length)
 
     def busy(self):
         return bool(self._queue or self._running)
@@ -68,12 +107,24 @@ class SlotStream:
     def step(self, count):
         """Admits waiting requests into free columns, generates `count` samples of every column and returns {handle: (samples, pcm)}
         with this step's samples of every request that ran (numpy int32 / int16, at most `count`, fewer at its end; pcm None when
-        the stream was made with pcm=False)."""
-        while self._queue and self._free:
+        the stream was made with pcm=False).  With mel requests the step is min(count, headroom) samples; none (no engine call, {})
+        when a running mel request has no frames beyond what it has delivered."""
+        if self._mel:
+            count = min(count, self.engine.slotsHeadroom())
+            if count == 0:
+                return {}
+        while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
-            handle, x, uid = self._queue.popleft()
-            self.engine.slotStart(col, x, uid)
-            self._running[col] = [handle, x.size(1)]
+            handle, x, uid, req = self._queue.popleft()
+            if req is None:
+                self.engine.slotStart(col, x, uid)
+                self._running[col] = [handle, x.size(1)]
+            else:
+                self.engine.slotStartMel(col, x, uid, req[0], req[1])
+                req[2] = col
+                self._running[col] = [handle, None]
+        if self._mel and not self._running:
+            return {}
         y = np.empty((self.columns, count), dtype=np.int32)
         pcm = np.empty((self.columns, count), dtype=np.int16) if self.pcm else None
         if not self.engine.slotsStep(count, y, pcm):
@@ -81,10 +132,17 @@ class SlotStream:
         out = {}
         for col in sorted(self._running):
             rec = self._running[col]
-            n = min(count, rec[1])
+            req = self._mel.get(rec[0]) if rec[1] is None else None
+            left = rec[1] if req is None else (req[0] * self.engine.upStride - req[3] if req[1] else count)
+            n = min(count, left)
             out[rec[0]] = (y[col, :n].copy(), pcm[col, :n].copy() if pcm is not None else None)
-            rec[1] -= n
-            if rec[1] == 0:
+            if req is None:
+                rec[1] -= n
+            else:
+                req[3] += n
+            if (rec[1] == 0) if req is None else (req[1] and req[3] == req[0] * self.engine.upStride):
+                if req is not None:
+                    del self._mel[rec[0]]
                 del self._running[col]
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)

@@ -9,7 +9,14 @@ C3 shape (bench.py: R 64, S 256, A 256, 20 layers, maxDilation 512), fp16, 80 fe
 Both read their features from one shared fp16 tensor (every utterance a different window of it).  Prints one JSON line per chunk
 size with ms per step of each and their ratio (slots / lockstep rate).
 
-    python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6]
+--mel adds, on an engine with the upsampling of bench.py's synthetic model (window 1024, stride 256):
+  mel        per chunk: nvw_slots_step with every column a MEL column -- each with frames of its own (distinct fp16 [80][64] per
+             column, 126 MiB in all; its features upsampled in the step), the same lengths and restarts -- and
+             the columns' phases staggered: the 16 columns of a tile join 17 samples apart, so that no two of a tile share a
+             phase (the feed's stores are then as scattered as they get)
+and reports its rate against the feature-fed slot step (mel_rate_vs_slots).
+
+    python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
 """
 import argparse
 import json
@@ -29,6 +36,8 @@ def main():
     ap.add_argument("--chunks", default="256,2048")
     ap.add_argument("--steps", type=int, default=6, help="timed steps per chunk size (after two warm-up steps)")
     ap.add_argument("--window", type=int, default=4096)
+    ap.add_argument("--mel", action="store_true", help="also time slot steps fed with mel frames (distinct per column)")
+    ap.add_argument("--only-mel", action="store_true", help="time the mel-fed slot steps only (e.g. under a profiler)")
     args = ap.parse_args()
     import torch
     import bench
@@ -48,6 +57,10 @@ def main():
         n = (warm + steps) * chunk
         assert n <= T_SRC and chunk <= W
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        if args.only_mel:
+            mel_ms, mel_restarts = time_mel(args, w, Wc, bc, chunk, warm, steps, rng)
+            print(json.dumps({"batch": B, "chunk": chunk, "window": W, "mel_ms_per_step": round(mel_ms, 3)}), flush=True)
+            continue
 
         # ---- lockstep: pack the chunk's features, generate it ----
         e = bench.build_engine(w, B, n)
@@ -103,10 +116,73 @@ def main():
         e.slotsEnd()
         e.close()
         torch.cuda.empty_cache()
-        print(json.dumps({"batch": B, "chunk": chunk, "window": W, "lockstep_ms_per_step": round(lock_ms, 3),
-                          "slots_ms_per_step": round(slot_ms, 3), "slots_rate_vs_lockstep": round(lock_ms / slot_ms, 4),
-                          "restarts_per_timed_step": round(restarts / steps, 1), "host_ms_per_step": round(1e3 * t_host / (warm + steps), 2),
-                          "kernel": info, "device": torch.cuda.get_device_name(0)}), flush=True)
+        res = {"batch": B, "chunk": chunk, "window": W, "lockstep_ms_per_step": round(lock_ms, 3),
+               "slots_ms_per_step": round(slot_ms, 3), "slots_rate_vs_lockstep": round(lock_ms / slot_ms, 4),
+               "restarts_per_timed_step": round(restarts / steps, 1), "host_ms_per_step": round(1e3 * t_host / (warm + steps), 2),
+               "kernel": info, "device": torch.cuda.get_device_name(0)}
+        if args.mel:
+            mel_ms, mel_restarts = time_mel(args, w, Wc, bc, chunk, warm, steps, rng)
+            res.update({"mel_ms_per_step": round(mel_ms, 3), "mel_rate_vs_slots": round(slot_ms / mel_ms, 4),
+                        "mel_restarts_per_timed_step": round(mel_restarts / steps, 1)})
+        print(json.dumps(res), flush=True)
+
+
+def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
+    """ms per slot step with every column a mel column of its own frames (module docstring); restarts in the timed steps."""
+    import torch
+    import bench
+    B, W = args.batch, args.window
+    LEN_MIN, LEN_MAX = 8192, 16384
+    stride, frames_max = bench.UP_STRIDE, 16384 // bench.UP_STRIDE
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    r = np.random.default_rng(11)
+    up_w = ((r.random((bench.N_COND, bench.N_COND, bench.UP_WINDOW), dtype=np.float32) - 0.5) *
+            (np.sqrt(12.0) / np.sqrt(4 * bench.N_COND))).astype(np.float32)
+    e.setUpsampling(up_w, np.zeros(bench.N_COND, dtype=np.float32), stride)
+    e.setSelectorSeed(5)
+    e.slotsBegin(W)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(9)
+    mel = torch.randn(B, bench.N_COND, frames_max, device="cuda", generator=g).half()      # distinct frames for every column
+    y = torch.empty(B, chunk, dtype=torch.int32, device="cuda")
+    left = np.zeros(B, dtype=np.int64)
+    uid = 0
+
+    def start(b):
+        nonlocal uid
+        frames = int(rng.integers(LEN_MIN, LEN_MAX)) // stride
+        e.slotStartMel(int(b), mel[b], uid, frames=frames)
+        uid += 1
+        left[b] = frames * stride
+
+    # staggered phases: column j of every tile joins after j steps of 17 samples
+    for j in range(16):
+        for b in range(j, B, 16):
+            start(b)
+        assert e.slotsStep(17, y)
+        left[left > 0] -= 17
+    left -= rng.integers(0, LEN_MIN // 2, size=B)      # (and their ends spread: restarts in every step, as for the features)
+    left[left <= 0] = 1
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    restarts = 0
+    for k in range(warm + steps):
+        if k == warm:
+            torch.cuda.synchronize()
+            ev[0].record()
+            restarts = 0
+        for b in np.nonzero(left <= 0)[0]:
+            start(b)
+            restarts += 1
+        assert e.slotsStep(chunk, y)
+        left -= chunk
+    ev[1].record()
+    torch.cuda.synchronize()
+    e.slotsEnd()
+    e.close()
+    del mel
+    torch.cuda.empty_cache()
+    return ev[0].elapsed_time(ev[1]) / steps, restarts
 
 
 if __name__ == "__main__":
