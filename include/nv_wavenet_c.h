@@ -281,6 +281,43 @@ int nvw_slot_mel_frames(nvw_engine* e, int slot, int frames, int final);
 int nvw_slots_headroom(nvw_engine* e);
 int nvw_slots_get_features(nvw_engine* e, void* dst, long long first_sample, int count);
 
+/* SLOT MODE: A COLUMN'S STATE AS A VALUE (additive within ABI 7).  What an utterance owns on the device between steps -- its column's
+ * share of the dilation ring, two history words, its descriptor -- can be moved to another column, saved into a blob, and resumed
+ * from the blob in any column, at any step, in any engine with the same model and seed; the utterance's samples stay those of
+ * column uid of its lockstep run.  The blob is nvw_slot_state_bytes(e) bytes: a 64-byte header (magic, layout version, precision, R,
+ * layers, max_dilation, done = local samples generated, uid, the two history words) and the ring share in canonical order -- layer
+ * l's d_l slots rotated so that slot k mod d_l is the one local sample k uses, i.e. the ring of an utterance started at counter 0 --
+ * so it does not depend on the column, the join step, window wraps or the engine.  It holds neither the features / frames (handed
+ * over again on resume) nor the seed or the model.
+ *   nvw_slot_state_bytes  size of one column's blob for this engine's shape and precision.
+ *   nvw_slot_move         the utterance of column `from` goes on in column `to` (queued; the next nvw_slots_step applies its moves
+ *                         first -- one launch for all of them -- so `from` may take a new start in the same step).  0 when refused
+ *                         (not in slot mode; an index out of range or from == to; `from` holds no utterance or has a pending start
+ *                         or resume; `to` holds an utterance or has a pending start, resume or move; `from` is an endpoint of a
+ *                         pending move; nothing changes).  A pending stop on `to` is superseded.  Until the step has applied the move,
+ *                         nvw_slot_start / _start_mel / _resume / _resume_mel on `to` are refused (they would drop the utterance on
+ *                         its way in); nvw_slot_stop on `to` is not.
+ *   nvw_slot_save         the state of column `slot` after the steps issued so far into dst (device memory, 16-byte aligned),
+ *                         asynchronously on `stream` (the stream of the steps, or one ordered after them); the column goes on.
+ *                         Returns done >= 0, or -1 when refused (not in slot mode, no utterance, a pending start, resume or move on
+ *                         the column, bad dst; nothing is written).
+ *   nvw_slot_resume       nvw_slot_start, continuing from `state`: uid and done come from its header (read here with a small
+ *                         blocking copy on the null stream: it waits for a save issued on the null stream or on a stream that
+ *                         synchronises with it; a save on a non-blocking stream must have completed, or been ordered before this
+ *                         call by the caller); at the next step the column's
+ *                         ring and history are loaded from it and local sample `done` is generated.  x and length are the whole
+ *                         utterance's, as at its start.  `state` stays unchanged until the next step has been issued.  0 when
+ *                         refused (wrong magic or layout version, another shape or precision, done >= length, or what
+ *                         nvw_slot_start refuses; nothing changes).
+ *   nvw_slot_resume_mel   the same for a mel utterance (nvw_slot_start_mel); refused also when final and done >= frames x stride. */
+size_t nvw_slot_state_bytes(nvw_engine* e);
+int nvw_slot_move(nvw_engine* e, int from, int to);
+int nvw_slot_save(nvw_engine* e, int slot, void* dst, void* stream);
+int nvw_slot_resume(nvw_engine* e, int slot, const void* state, const void* x, int precision, long long c_stride, long long t_stride,
+                    int length);
+int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* mel, int precision, long long c_stride,
+                        long long f_stride, int frames, int final);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

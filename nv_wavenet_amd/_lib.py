@@ -88,6 +88,11 @@ SIGNATURES = {
     "nvw_slot_mel_frames": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "nvw_slots_headroom": (C.c_int, [C.c_void_p]),
     "nvw_slots_get_features": (C.c_int, [C.c_void_p, _fp, C.c_longlong, C.c_int]),
+    "nvw_slot_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "nvw_slot_move": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "nvw_slot_save": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_void_p]),
+    "nvw_slot_resume": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
+    "nvw_slot_resume_mel": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
     "nvw_device_synchronize": (None, []),
     "nvw_time_runs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "wavenet_infer": (None, [C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 7 +

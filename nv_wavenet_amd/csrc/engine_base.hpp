@@ -67,6 +67,11 @@ struct nvw_engine {
     virtual bool slotMelFrames(int, int, int) = 0;
     virtual int slotsHeadroom() = 0;
     virtual bool slotsGetFeatures(void*, long long, int) = 0;
+    virtual size_t slotStateBytes() = 0;
+    virtual bool slotMove(int, int) = 0;
+    virtual int slotSave(int, void*, hipStream_t) = 0;
+    virtual bool slotResume(int, const void*, const void*, int, long long, long long, int) = 0;
+    virtual bool slotResumeMel(int, const void*, const void*, int, long long, long long, int, int) = 0;
 };
 
 template <typename Tw, typename Td, int R, int S, int A>
@@ -152,6 +157,15 @@ struct EngineImpl : nvw_engine {
     bool slotMelFrames(int slot, int frames, int final) override { return eng.slotMelFrames(slot, frames, final); }
     int slotsHeadroom() override { return eng.slotsHeadroom(); }
     bool slotsGetFeatures(void* dst, long long first, int count) override { return eng.slotsGetFeatures(dst, first, count); }
+    size_t slotStateBytes() override { return eng.slotStateBytes(); }
+    bool slotMove(int from, int to) override { return eng.slotMove(from, to); }
+    int slotSave(int slot, void* dst, hipStream_t s) override { return eng.slotSave(slot, dst, s); }
+    bool slotResume(int slot, const void* state, const void* x, int prec, long long cS, long long tS, int length) override {
+        return eng.slotResume(slot, state, x, prec, cS, tS, length);
+    }
+    bool slotResumeMel(int slot, const void* state, const void* mel, int prec, long long cS, long long fS, int frames, int final) override {
+        return eng.slotResumeMel(slot, state, mel, prec, cS, fS, frames, final);
+    }
 };
 
 typedef nvw_engine* (*nvw_factory_fn)(int L, int maxD, int B, int N, int impl, int tanhEmbed, int organisation);

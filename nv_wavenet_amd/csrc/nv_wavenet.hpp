@@ -37,6 +37,7 @@
 
 #include "slots.hpp"
 #include "slots_mel.hpp"
+#include "slots_state.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
 
@@ -182,6 +183,12 @@ protected:
     size_t m_melStageElems = 0;             // the step's upsampled samples per column, [mel tiles * 16][count] of KFC KiB / 16
     size_t m_melRecOff = 0;
     int* m_melColInfo = NULL;               // [tiles * 16] int2: per column, phase of its first sample and samples it stores
+    // ... and columns' states as values (slots_state.hpp): moved, saved, resumed
+    std::vector<const void*> m_slotResume;  // per column: the blob its pending start resumes from (NULL: a new utterance) ...
+    std::vector<int> m_slotResumeDone;      // ... and the local samples that blob has behind it (0: a new utterance)
+    std::vector<char> m_slotMoveEnd;        // per column: 1 source, 2 destination of a pending move
+    std::vector<wn::SlotMove> m_slotMoves;  // the pending moves
+    wn::SlotLayer* m_slotLayers = NULL;     // the schedule per ring slot on the device (built by the first save or resume)
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -652,6 +659,7 @@ public:
         if (m_upTab) gpuErrChk(hipFree(m_upTab));
         if (m_upBias) gpuErrChk(hipFree(m_upBias));
         if (m_melFrag) gpuErrChk(hipFree(m_melFrag));
+        if (m_slotLayers) gpuErrChk(hipFree(m_slotLayers));
         gpuErrChk(hipFree(m_outputSelectors));
         gpuErrChk(hipFree(m_ring));
         gpuErrChk(hipFree(m_yInPrev));
@@ -1425,6 +1433,10 @@ public:
         m_melColumns = 0;
         m_melTiles = 0;
         m_melTilesDirty = false;
+        m_slotResume.assign(m_maxBatch, NULL);
+        m_slotResumeDone.assign(m_maxBatch, 0);
+        m_slotMoveEnd.assign(m_maxBatch, 0);
+        m_slotMoves.clear();
         const size_t cells = (size_t)window * m_maxBatch;
         gpuErrChk(hipMalloc(&m_slotDesc, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
         gpuErrChk(hipMemset(m_slotDesc, 0, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
@@ -1451,12 +1463,14 @@ public:
     // Column `slot` takes a new utterance at the next step: its upsampled features x[c * cStride + k * tStride] (device memory,
     // `precision`-bit floats, n_cond channels x `length` samples; kept alive and unchanged while the column runs), its uid.  Replaces
     // whatever the column held.  false (nothing changes): not in slot mode, slot outside the batch, non-device x, bad precision,
-    // non-positive strides or length.
+    // non-positive strides or length; or the column is the destination of a pending move (the start would silently drop the
+    // utterance on its way in: stop it, or step first).
     bool slotStart(int slot, const void* x, int precision, long long cStride, long long tStride, int length, unsigned uid) {
         if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
-            tStride <= 0 || length <= 0 || !isDevicePtr(x))
+            tStride <= 0 || length <= 0 || !isDevicePtr(x) || m_slotMoveEnd[slot] == 2)
             return false;
         slotDropMel(slot);
+        slotDropResume(slot);
         wn::SlotDesc& d = m_slotHost[slot];
         d.x = x;
         d.cStride = cStride;
@@ -1473,6 +1487,7 @@ public:
     bool slotStop(int slot) {
         if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
         slotDropMel(slot);
+        slotDropResume(slot);
         m_slotHost[slot].active = 0;
         slotMarkPending(slot, 2);
         return true;
@@ -1481,13 +1496,15 @@ public:
     // `precision`-bit floats, n_cond channels; kept alive while the column runs), `frames` of them available so far, final != 0: no
     // more will come (its length is frames x stride), its uid.  Upsampled with the table of setUpsampling in the steps that generate
     // them.  Replaces whatever the column held.  false (nothing changes): not in slot mode, no upsampling, slot outside the batch,
-    // non-device mel, bad precision, non-positive strides, frames < 0, or 0 frames of a final utterance.
+    // non-device mel, bad precision, non-positive strides, frames < 0, 0 frames of a final utterance, or the column is the destination
+    // of a pending move.
     bool slotStartMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
         if (m_slotW <= 0 || m_upStride <= 0 || slot < 0 || slot >= m_maxBatch || mel == NULL || (precision != 32 && precision != 16) ||
             cStride <= 0 || fStride <= 0 || frames < 0 || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL ||
-            !isDevicePtr(mel))
+            !isDevicePtr(mel) || m_slotMoveEnd[slot] == 2)
             return false;
         if (!m_melDesc) melAllocate();
+        slotDropResume(slot);
         wn::MelDesc& d = m_melHost[slot];
         if (!d.state) m_melColumns++;
         d.mel = mel;
@@ -1516,6 +1533,81 @@ public:
         melMarkDirty(slot);
         return true;
     }
+    // ---- a column's state as a value (slots_state.hpp) ----
+    // bytes of one column's state blob for this engine's shape and precision (header + its share of its tile's ring)
+    size_t slotStateBytes() const { return wn::slots_state_bytes(m_ringSlots, ringFragsPerSlot()); }
+    // The utterance of column `from` goes on in column `to` from the next step (queued; applied first in that step, so `from` may
+    // take a new start in the same step): ring share, history and descriptors move, start unchanged.  The host's view changes at
+    // once.  false (nothing changes): not in slot mode; an index outside the batch or from == to; `from` holds no utterance or has a
+    // pending start or resume; `to` holds an utterance or has a pending start, resume or move; `from` is an endpoint of a pending
+    // move.  A pending stop on `to` is superseded.
+    bool slotMove(int from, int to) {
+        if (m_slotW <= 0 || from < 0 || from >= m_maxBatch || to < 0 || to >= m_maxBatch || from == to) return false;
+        if (!slotHolds(from) || m_slotPending[from] == 1 || m_slotMoveEnd[from]) return false;
+        if (slotHolds(to) || m_slotPending[to] == 1 || m_slotMoveEnd[to]) return false;
+        m_slotHost[to] = m_slotHost[from];
+        m_slotHost[from].active = 0;
+        if (m_melHost[from].state) {
+            m_melHost[to] = m_melHost[from];
+            m_melHost[from].state = 0;
+            if (m_melDirty[from]) melMarkDirty(to);      // (frames announced since the last step: the update path writes them after the move)
+            m_melTilesDirty = true;
+        }
+        m_slotMoveEnd[from] = 1;
+        m_slotMoveEnd[to] = 2;
+        m_slotMoves.push_back(wn::SlotMove{from, to});
+        return true;
+    }
+    // The state of column `slot` after the steps issued so far into dst (device memory, 16-byte aligned, slotStateBytes() bytes),
+    // asynchronously on `stream` -- the stream of the session's steps, or one ordered after them.  The column goes on running.
+    // Returns done, the local samples it has generated; -1 (nothing written): not in slot mode, slot outside the batch, no
+    // utterance, a pending start, resume or move on the column, or a bad dst.
+    int slotSave(int slot, void* dst, hipStream_t stream = 0) {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot) || m_slotPending[slot] == 1 || m_slotMoveEnd[slot] ||
+            dst == NULL || ((size_t)dst & 15) != 0 || !isDevicePtr(dst))
+            return -1;
+        const bool mel = m_melHost[slot].state != 0;
+        const long long start = mel ? m_melHost[slot].start : m_slotHost[slot].start, done = m_slotCounter - start;
+        if (done < 0 || done > 0x7fffffffLL) return -1;
+        wn::SlotStateHeader h = {};
+        h.magic = wn::kSlotStateMagic;
+        h.version = wn::kSlotStateVersion;
+        h.precision = F16 ? 16 : 32;
+        h.R = R;
+        h.numLayers = m_numLayers;
+        h.maxDilation = m_maxDilation;
+        h.done = (int)done;
+        h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
+        if (!wn::slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur))
+            return -1;
+        return (int)done;
+    }
+    // slotStart / slotStartMel, but the column continues from the blob `state` (of slotSave, device memory): at the next step its
+    // ring share and history are loaded from it in place of the zeroing, and start = that step's counter - done; uid and done come
+    // from the blob's header, which is read here with a small blocking copy on the null stream: the call waits for a save issued
+    // on the null stream or on a stream that synchronises with it; a save on a non-blocking stream must have completed (or have
+    // been ordered before this call by the caller) first.  The features / frames are those of the saved utterance, handed over again by the caller; `state` stays unchanged until
+    // the next step has been issued (it reads it in stream order).  false (nothing changes): wrong magic or layout version, a shape
+    // or precision that is not this engine's, done >= length (final mel: done >= frames x stride), or what slotStart / slotStartMel
+    // refuse.
+    bool slotResume(int slot, const void* state, const void* x, int precision, long long cStride, long long tStride, int length) {
+        wn::SlotStateHeader h;
+        if (m_slotW <= 0 || !slotStateHeader(state, h) || h.done >= length) return false;
+        if (!slotStart(slot, x, precision, cStride, tStride, length, h.uid)) return false;
+        slotLayers();
+        m_slotResume[slot] = state;
+        m_slotResumeDone[slot] = h.done;
+        return true;
+    }
+    bool slotResumeMel(int slot, const void* state, const void* mel, int precision, long long cStride, long long fStride, int frames, int final) {
+        wn::SlotStateHeader h;
+        if (m_slotW <= 0 || m_upStride <= 0 || !slotStateHeader(state, h) || (final && h.done >= (long long)frames * m_upStride)) return false;
+        if (!slotStartMel(slot, mel, precision, cStride, fStride, frames, final, h.uid)) return false;
+        slotLayers();
+        m_slotResume[slot] = state;
+        m_slotResumeDone[slot] = h.done;
+        return true;
+    }
     // The largest count the next step accepts: W, or the fewest samples a non-final mel column has frames for beyond its next
     // sample (0 when one has none).
     int slotsHeadroom() const {
@@ -1525,7 +1617,7 @@ public:
             for (int b = 0; b < m_maxBatch; b++) {
                 const wn::MelDesc& d = m_melHost[b];
                 if (d.state != 1) continue;
-                const long long next = m_slotPending[b] == 1 ? 0 : m_slotCounter - d.start;
+                const long long next = m_slotPending[b] == 1 ? m_slotResumeDone[b] : m_slotCounter - d.start;      // (a resumed column goes on from done)
                 const long long left = (long long)d.frames * m_upStride - next;
                 if (left < h) h = left;
             }
@@ -1544,6 +1636,9 @@ public:
         }
         return true;
     }
+    // Order within a step (fixed): the pending moves (one launch); then the descriptor updates with the resets of started columns
+    // (one launch) and the loads of resumed ones (one launch); then the feed.  A column that is the source of a move may therefore
+    // take a new start in the same step.  A session that never moves or resumes launches what it launched before these existed.
     // One step of `count` <= W samples, asynchronously on `stream`: the pending starts and stops (one reset launch), the window feed
     // (one launch), the generation -- two launches where the window rows wrap -- up to the tile of the highest active column, the PCM
     // when pcm != NULL, and the copies of the step's samples / PCM into yOut / pcm ([maxBatch][count], host or device; NULL: none).
@@ -1555,7 +1650,8 @@ public:
         if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return false;      // (mel columns short of frames)
         const int W = m_slotW;
         bool ok = true;
-        if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream);      // (first: it reads the pending starts)
+        if (!m_slotMoves.empty()) ok = slotApplyMoves(stream);
+        if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream) && ok;      // (before the starts: it reads the pending ones)
         if (!m_slotPendingList.empty()) ok = slotApplyPending(stream) && ok;
         int cols = 0;
         for (int b = m_maxBatch - 1; b >= 0; b--)
@@ -1626,6 +1722,10 @@ public:
         m_slotHost.clear();
         m_slotPending.clear();
         m_slotPendingList.clear();
+        m_slotResume.clear();
+        m_slotResumeDone.clear();
+        m_slotMoveEnd.clear();
+        m_slotMoves.clear();
         if (m_melDesc) {
             gpuErrChk(hipFree(m_melDesc));
             gpuErrChk(hipFree(m_melUpd));
@@ -1709,7 +1809,68 @@ protected:
         return (bt == 4 && (dump || raw != 0)) ? 3 : bt;
     }
     // ---- slot mode internals ----
-    size_t slotUpdBytes() const { return (size_t)m_maxBatch * (sizeof(wn::SlotUpdate) + sizeof(int)); }
+    // a step's staging: the descriptor updates, the loads of resumed columns, the moves, the restarted columns -- [maxBatch] each
+    size_t slotLoadOff() const { return (size_t)m_maxBatch * sizeof(wn::SlotUpdate); }
+    size_t slotMoveOff() const { return slotLoadOff() + (size_t)m_maxBatch * sizeof(wn::SlotLoad); }
+    size_t slotColOff() const { return slotMoveOff() + (size_t)m_maxBatch * sizeof(wn::SlotMove); }
+    size_t slotUpdBytes() const { return slotColOff() + (size_t)m_maxBatch * sizeof(int); }
+    int ringFragsPerSlot() const { return (int)(R * 16 * sizeof(elem) / 1024); }
+    bool slotHolds(int slot) const { return m_slotHost[slot].active || m_melHost[slot].state; }
+    void slotDropResume(int slot) {
+        m_slotResume[slot] = NULL;
+        m_slotResumeDone[slot] = 0;
+    }
+    // start mod the largest dilation (every dilation divides it), non-negative: the rotation of a column's ring against its blob
+    int slotRotation(long long start) const {
+        const long long D = largestDilation();
+        return (int)(((start % D) + D) % D);
+    }
+    void slotTouchTile(int slot) {
+        if ((slot >> 4) + 1 > m_ringDirtyTiles) m_ringDirtyTiles = (slot >> 4) + 1;
+    }
+    // {first slot, dilation} of its layer for every ring slot, on the device
+    const wn::SlotLayer* slotLayers() {
+        if (!m_slotLayers) {
+            std::vector<wn::SlotLayer> tab;
+            int d = 1;
+            for (int l = 0, off = 0; l < m_numLayers; l++) {
+                for (int i = 0; i < d; i++) tab.push_back(make_int2(off, d));
+                off += d;
+                d <<= 1;
+                if (d > m_maxDilation) d = 1;
+            }
+            assert((int)tab.size() == m_ringSlots);
+            gpuErrChk(hipMalloc(&m_slotLayers, tab.size() * sizeof(wn::SlotLayer)));
+            gpuErrChk(hipMemcpy(m_slotLayers, tab.data(), tab.size() * sizeof(wn::SlotLayer), hipMemcpyHostToDevice));
+        }
+        return m_slotLayers;
+    }
+    // the header of a blob, read back (blocking) and checked against this engine
+    bool slotStateHeader(const void* state, wn::SlotStateHeader& h) const {
+        if (state == NULL || ((size_t)state & 15) != 0 || !isDevicePtr(state)) return false;
+        gpuErrChk(hipMemcpy(&h, state, sizeof(h), hipMemcpyDeviceToHost));
+        return h.magic == wn::kSlotStateMagic && h.version == wn::kSlotStateVersion && h.precision == (F16 ? 16 : 32) && h.R == R &&
+               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0;
+    }
+    // the pending moves -> pinned staging -> device, then one slot_move_kernel launch (staging halves as slotApplyPending)
+    bool slotApplyMoves(hipStream_t stream) {
+        char* const stage = m_slotStage[m_slotParity];
+        gpuErrChk(hipEventSynchronize(m_slotEv[m_slotParity]));
+        wn::SlotMove* const mv = (wn::SlotMove*)(stage + slotMoveOff());
+        const int n = (int)m_slotMoves.size();
+        for (int i = 0; i < n; i++) {
+            mv[i] = m_slotMoves[i];
+            m_slotMoveEnd[mv[i].from] = 0;
+            m_slotMoveEnd[mv[i].to] = 0;
+            slotTouchTile(mv[i].to);
+        }
+        m_slotMoves.clear();
+        gpuErrChk(hipMemcpyAsync(m_slotUpd + slotMoveOff(), mv, (size_t)n * sizeof(wn::SlotMove), hipMemcpyHostToDevice, stream));
+        gpuErrChk(hipEventRecord(m_slotEv[m_slotParity], stream));
+        m_slotParity ^= 1;
+        return wn::slots_move(stream, (const wn::SlotMove*)(m_slotUpd + slotMoveOff()), n, m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev,
+                              m_yInCur, m_slotDesc, m_melDesc);
+    }
     void slotMarkPending(int slot, int what) {
         if (!m_slotPending[slot]) m_slotPendingList.push_back(slot);
         m_slotPending[slot] = what;
@@ -1720,14 +1881,21 @@ protected:
         char* const stage = m_slotStage[m_slotParity];
         gpuErrChk(hipEventSynchronize(m_slotEv[m_slotParity]));
         wn::SlotUpdate* const upd = (wn::SlotUpdate*)stage;
-        const size_t colOff = (size_t)m_maxBatch * sizeof(wn::SlotUpdate);
+        const size_t colOff = slotColOff();
         int* const cols = (int*)(stage + colOff);
-        int nUpd = 0, nCols = 0;
+        wn::SlotLoad* const loads = (wn::SlotLoad*)(stage + slotLoadOff());
+        int nUpd = 0, nCols = 0, nLoads = 0;
         for (int b : m_slotPendingList) {
             wn::SlotUpdate u = {};
             u.column = b;
             u.reset = m_slotPending[b] == 1 ? 1 : 0;
-            if (u.reset) {
+            if (u.reset && m_slotResume[b] != NULL) {      // a resume: ring and history from the blob, local sample `done` by this step
+                m_slotHost[b].start = m_slotCounter - m_slotResumeDone[b];
+                loads[nLoads++] = wn::SlotLoad{m_slotResume[b], b, slotRotation(m_slotHost[b].start)};
+                slotTouchTile(b);
+                slotDropResume(b);
+                u.reset = 0;
+            } else if (u.reset) {
                 m_slotHost[b].start = m_slotCounter;      // local sample 0 is generated by this step
                 cols[nCols++] = b;
             }
@@ -1738,10 +1906,15 @@ protected:
         m_slotPendingList.clear();
         gpuErrChk(hipMemcpyAsync(m_slotUpd, upd, (size_t)nUpd * sizeof(wn::SlotUpdate), hipMemcpyHostToDevice, stream));
         if (nCols) gpuErrChk(hipMemcpyAsync(m_slotUpd + colOff, cols, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (nLoads) gpuErrChk(hipMemcpyAsync(m_slotUpd + slotLoadOff(), loads, (size_t)nLoads * sizeof(wn::SlotLoad), hipMemcpyHostToDevice, stream));
         gpuErrChk(hipEventRecord(m_slotEv[m_slotParity], stream));
         m_slotParity ^= 1;
-        return wn::slots_reset(stream, m_slotDesc, (const wn::SlotUpdate*)m_slotUpd, nUpd, (const int*)(m_slotUpd + colOff), nCols, m_ring,
-                               m_ringSlots, (int)(R * 16 * sizeof(elem) / 1024), m_yInPrev, m_yInCur);
+        bool ok = wn::slots_reset(stream, m_slotDesc, (const wn::SlotUpdate*)m_slotUpd, nUpd, (const int*)(m_slotUpd + colOff), nCols, m_ring,
+                                  m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur);
+        if (nLoads)
+            ok = wn::slots_load(stream, (const wn::SlotLoad*)(m_slotUpd + slotLoadOff()), nLoads, slotLayers(), m_ring, m_ringSlots,
+                                ringFragsPerSlot(), m_yInPrev, m_yInCur) && ok;
+        return ok;
     }
     // ---- mel columns (slots_mel.hpp) ----
     size_t melTileOff() const { return (size_t)m_maxBatch * sizeof(wn::MelUpdate); }
@@ -1794,7 +1967,7 @@ protected:
         int nUpd = 0;
         for (int b : m_melDirtyList) {
             wn::MelDesc& d = m_melHost[b];
-            if (d.state && m_slotPending[b] == 1) d.start = m_slotCounter;      // local sample 0 is generated by this step
+            if (d.state && m_slotPending[b] == 1) d.start = m_slotCounter - m_slotResumeDone[b];      // local sample 0 (resumed: done) is generated by this step
             upd[nUpd].column = b;
             upd[nUpd].pad = 0;
             upd[nUpd].d = d;

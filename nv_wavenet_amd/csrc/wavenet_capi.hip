@@ -328,6 +328,41 @@ int nvw_slots_get_features(nvw_engine* e, void* dst, long long first_sample, int
     }
     return 1;
 }
+// ---- slot mode: a column's state as a value (additive within ABI 7) --------------------------------------------------------------
+size_t nvw_slot_state_bytes(nvw_engine* e) { return e->slotStateBytes(); }
+int nvw_slot_move(nvw_engine* e, int from, int to) {
+    if (!e->slotMove(from, to)) {
+        fprintf(stderr, "nvw_slot_move: refused (nvw_slots_begin first; %d -> %d of %d columns: a running column without a pending start, "
+                "resume or move into an idle one without them)\n", from, to, e->maxBatch());
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_save(nvw_engine* e, int slot, void* dst, void* stream) {
+    const int done = e->slotSave(slot, dst, (hipStream_t)stream);
+    if (done < 0)
+        fprintf(stderr, "nvw_slot_save: refused (nvw_slots_begin first; slot %d of %d: a running column without a pending start, resume or "
+                "move; dst 16-byte aligned device memory)\n", slot, e->maxBatch());
+    return done;
+}
+int nvw_slot_resume(nvw_engine* e, int slot, const void* state, const void* x, int precision, long long c_stride, long long t_stride,
+                    int length) {
+    if (!e->slotResume(slot, state, x, precision, c_stride, t_stride, length)) {
+        fprintf(stderr, "nvw_slot_resume: refused (a state of nvw_slot_save for this shape and precision with fewer than %d samples done, "
+                "device memory; otherwise as nvw_slot_start: slot %d of %d)\n", length, slot, e->maxBatch());
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* mel, int precision, long long c_stride,
+                        long long f_stride, int frames, int final) {
+    if (!e->slotResumeMel(slot, state, mel, precision, c_stride, f_stride, frames, final)) {
+        fprintf(stderr, "nvw_slot_resume_mel: refused (a state of nvw_slot_save for this shape and precision, device memory, with fewer "
+                "samples done than %d final frames hold; otherwise as nvw_slot_start_mel: slot %d of %d)\n", frames, slot, e->maxBatch());
+        return 0;
+    }
+    return 1;
+}
 
 void nvw_device_synchronize(void) { gpuErrChk(hipDeviceSynchronize()); }
 

@@ -407,6 +407,58 @@ class WavenetEngine:
             raise ValueError("nvw_slots_get_features refused samples [%d, %d)" % (first, first + count))
         return out
 
+    # ---- ... a column's state as a value: moved, saved, resumed ----
+    def slotStateBytes(self):
+        """Bytes of one column's state blob for this engine's shape and precision."""
+        return int(lib.nvw_slot_state_bytes(self._h))
+
+    def slotMove(self, src, dst):
+        """The utterance of column `src` goes on in the idle column `dst` from the next step (which applies its moves first)."""
+        if not lib.nvw_slot_move(self._h, int(src), int(dst)):
+            raise ValueError("nvw_slot_move refused %d -> %d" % (src, dst))
+        self._slot_keep[int(dst)] = self._slot_keep.pop(int(src), None)      # (the steps now read the tensor for column dst)
+
+    def slotSave(self, slot, stream=None):
+        """The state of column `slot` after the steps issued so far: (CUDA uint8 tensor of slotStateBytes(), done = its local samples
+        generated).  Asynchronous on `stream` (the stream of the steps); the column goes on running."""
+        import torch
+        blob = torch.empty(self.slotStateBytes(), dtype=torch.uint8, device="cuda")
+        done = lib.nvw_slot_save(self._h, int(slot), blob.data_ptr(), stream)
+        if done < 0:
+            raise ValueError("nvw_slot_save refused slot %d" % slot)
+        return blob, int(done)
+
+    def slotResume(self, slot, state, x, length=None):
+        """slotStart, continuing from `state` (a blob of slotSave of an engine with the same model and seed): x = the whole
+        utterance's features as at its start; uid and done come from the blob.  Reads the blob's header on the null stream (a save
+        on a non-blocking stream must have been ordered before this call); the blob
+        is kept until the column starts again."""
+        import torch
+        assert hasattr(x, "data_ptr") and x.is_cuda and x.dim() == 2, "features: a CUDA tensor [n_cond][samples]"
+        assert state.is_cuda and state.dtype == torch.uint8 and state.is_contiguous(), "state: a CUDA uint8 tensor of slotSave"
+        bits = {torch.float32: 32, torch.float16: 16}.get(x.dtype)
+        assert bits, "features must be float32 or float16"
+        n = x.size(1) if length is None else int(length)
+        assert x.size(0) == self.nCond and 0 < n <= x.size(1), "features [%d][>= %d] expected, got %s" % (self.nCond, n, tuple(x.shape))
+        if state.numel() != self.slotStateBytes() or not lib.nvw_slot_resume(self._h, int(slot), state.data_ptr(), x.data_ptr(), bits,
+                                                                             x.stride(0), x.stride(1), n):
+            raise ValueError("nvw_slot_resume refused slot %d" % slot)
+        self._slot_keep[int(slot)] = (x, state)
+
+    def slotResumeMel(self, slot, state, mel, frames=None, final=True):
+        """slotStartMel, continuing from `state` (see slotResume); mel, frames, final as for slotStartMel."""
+        import torch
+        assert hasattr(mel, "data_ptr") and mel.is_cuda and mel.dim() == 2, "mel: a CUDA tensor [n_cond][frames]"
+        assert state.is_cuda and state.dtype == torch.uint8 and state.is_contiguous(), "state: a CUDA uint8 tensor of slotSave"
+        bits = {torch.float32: 32, torch.float16: 16}.get(mel.dtype)
+        assert bits, "mel must be float32 or float16"
+        n = mel.size(1) if frames is None else int(frames)
+        assert mel.size(0) == self.nCond and 0 <= n <= mel.size(1), "mel [%d][>= %d] expected, got %s" % (self.nCond, n, tuple(mel.shape))
+        if state.numel() != self.slotStateBytes() or not lib.nvw_slot_resume_mel(self._h, int(slot), state.data_ptr(), mel.data_ptr(), bits,
+                                                                                 mel.stride(0), mel.stride(1), n, 1 if final else 0):
+            raise ValueError("nvw_slot_resume_mel refused slot %d" % slot)
+        self._slot_keep[int(slot)] = (mel, state)
+
     def slotsEnd(self):
         lib.nvw_slots_end(self._h)
         self._slot_keep = {}

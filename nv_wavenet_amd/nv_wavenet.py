@@ -393,12 +393,13 @@ class NVWaveNetEngine(NVWaveNet):
         return e
 
     def slot_stream(self, columns, window, cond_weight, cond_bias, seed=0, implementation=Impl.AUTO, pcm=True, upsample_weight=None,
-                    upsample_bias=None, upsample_stride=None):
+                    upsample_bias=None, upsample_stride=None, compact=False):
         """Continuous batching (nv_wavenet_amd/slots.py): a SlotStream over an engine of its own with `columns` columns and a window of
         `window` samples (a multiple of max_dilation), the conditioning convolution in the kernel as infer_features has it
         (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
         request; with the model's `upsample` ConvTranspose1d (upsample_weight [n_cond][n_cond][window], upsample_bias, its stride)
-        mel frames [n_cond][frames] as well (submit_mel).  close() the stream to free the engine."""
+        mel frames [n_cond][frames] as well (submit_mel).  compact: every step first packs the running requests into the front of the
+        batch (SlotStream.compact).  close() the stream to free the engine."""
         from .slots import SlotStream
         e = self._new_engine(columns, window, implementation)
         e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
@@ -406,7 +407,7 @@ class NVWaveNetEngine(NVWaveNet):
             assert upsample_bias is not None and upsample_stride is not None, "upsampling needs its weight, bias and stride"
             e.setUpsampling(upsample_weight.float().contiguous(), upsample_bias.float().contiguous(), int(upsample_stride))
         e.setSelectorSeed(seed)
-        return SlotStream(e, window, pcm=pcm, owns_engine=True)
+        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact)
 
     def close(self):
         for e in self._engines.values():

@@ -22,6 +22,17 @@ that emits frames while it decodes submits what it has and extends the request a
     stream.step(2048)                                   # min(2048, headroom) samples: a step never outruns the frames written
 
 A queued streamed request is admitted once it has frames for min(count, its length) samples, so admitting never shortens a step.
+
+A running request's state is a value (nvw_slot_move / nvw_slot_save / nvw_slot_resume), which the stream uses twice.
+When load falls the survivors of a burst are scattered over the batch and every step still launches up to the highest of them:
+compact() moves the requests beyond the first 16 * ceil(running / 16) columns into the free columns below, and
+SlotStream(..., compact=True) does so in every step, after finished requests have retired and before queued ones are admitted.
+suspend() takes a request out -- its column is free for something more urgent, or its engine can be drained -- and resume() puts it
+back at the front of the queue of this or any other stream whose engine has the same model and seed; what was delivered before the
+suspend is not delivered again.
+
+    state = stream.suspend(h)                           # a SlotState: the blob, the source tensor, uid, samples done
+    h2 = other_stream.resume(state)                     # goes on at sample state.done
 """
 import heapq
 from collections import deque
@@ -38,18 +49,30 @@ def window_pieces(counter, count, window):
     return [(t, first)] if first == count else [(t, first), (0, count - first)]
 
 
+class SlotState:
+    """A suspended request (SlotStream.suspend): blob = the column's state, a CUDA uint8 tensor of WavenetEngine.slotSave (None: the
+    request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
+    frames, final = of a mel request (frames written so far, no more to come)."""
+
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None):
+        self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
+
+
 class SlotStream:
-    def __init__(self, engine, window, pcm=True, owns_engine=False):
+    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False):
         self.engine = engine
         self.columns = engine.maxBatch
         self.window = int(window)
         self.pcm = pcm
         self._owns = owns_engine
+        self._compact = bool(compact)
         engine.slotsBegin(self.window)
         self._free = list(range(self.columns))         # a heap: lowest free column first
-        self._queue = deque()                          # (handle, features, uid, mel request or None) waiting for a column
+        self._queue = deque()                          # (handle, features, uid, mel request or None[, SlotState]) waiting for a column
+        self._src = {}                                 # handle -> (source tensor, uid) of the running requests
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
+        self._inflight = set()                         # columns that are endpoints of moves the next step has yet to apply
         self._done = []
         self._next_handle = 0
         self._next_uid = 0
@@ -92,7 +115,7 @@ class SlotStream:
 
     def _ready(self, item, count):
         req = item[3]
-        return req is None or req[1] or req[0] * self.engine.upStride >= count      # (a final request: min(count, length) <= length)
+        return req is None or req[1] or req[0] * self.engine.upStride - req[3] >= count      # (a final request: min(count, length) <= length)
 
     def busy(self):
         return bool(self._queue or self._running)
@@ -104,6 +127,74 @@ class SlotStream:
         """{handle: column} of the requests in the batch."""
         return {rec[0]: col for col, rec in self._running.items()}
 
+    def compact(self):
+        """Packs the running requests into the front of the batch: with n of them, every one in a column at or beyond
+        16 * ceil(n / 16) moves into the lowest free column below that bound, the highest source first.  Returns the number of
+        moves (0: no engine call); the next step applies them before anything else.  While moves of an earlier call are still
+        waiting for that step it does nothing (their columns can be neither source nor destination again): call it again after."""
+        if self._inflight:
+            return 0
+        n = len(self._running)
+        bound = 16 * ((n + 15) // 16)
+        sources = sorted((c for c in self._running if c >= bound), reverse=True)
+        if not sources:
+            return 0
+        targets = sorted(c for c in self._free if c < bound)
+        for src, dst in zip(sources, targets):
+            self.engine.slotMove(src, dst)
+            rec = self._running[dst] = self._running.pop(src)
+            if rec[1] is None:
+                self._mel[rec[0]][2] = dst
+            self._free.remove(dst)
+            self._free.append(src)
+            self._inflight.update((src, dst))
+        heapq.heapify(self._free)
+        return len(sources)
+
+    def suspend(self, handle):
+        """Takes request `handle` out of the stream and returns its SlotState; a running request's column is saved and freed, a
+        queued one is simply dequeued (an empty state unless it was itself resumed).  The handle is gone; resume() gives a new one.
+        A request that compact() has just moved cannot be saved before the next step has applied the move: RuntimeError, and
+        nothing has changed."""
+        for i, item in enumerate(self._queue):
+            if item[0] == handle:
+                del self._queue[i]
+                req = item[3]
+                if req is not None:
+                    del self._mel[handle]
+                if len(item) > 4:
+                    if req is not None:
+                        item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
+                    return item[4]
+                return SlotState(None, item[1], item[2], 0, "features") if req is None else SlotState(None, item[1], item[2], 0, "mel", req[0], req[1])
+        col = self.running()[handle]
+        if col in self._inflight:
+            raise RuntimeError("request %d is being moved to column %d: step once before suspending it" % (handle, col))
+        blob, done = self.engine.slotSave(col)      # (first: a refusal leaves the stream as it was)
+        self.engine.slotStop(col)
+        rec = self._running.pop(col)
+        x, uid = self._src.pop(handle)
+        heapq.heappush(self._free, col)
+        if rec[1] is not None:
+            assert done == x.size(1) - rec[1], (done, x.size(1), rec[1])
+            return SlotState(blob, x, uid, done, "features")
+        req = self._mel.pop(handle)
+        assert done == req[3], (done, req[3])
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1])
+
+    def resume(self, state):
+        """Queues a suspended request at the FRONT (of this stream, or of another whose engine has the same model and seed); returns
+        its handle here.  It goes on at sample state.done: nothing delivered before the suspend comes again.  A streamed mel
+        request can be extended as before (extend_mel with the new handle)."""
+        handle = self._next_handle
+        self._next_handle += 1
+        self._next_uid = max(self._next_uid, int(state.uid) + 1)
+        req = None
+        if state.kind == "mel":
+            req = self._mel[handle] = [int(state.frames), bool(state.final), None, int(state.done)]
+        self._queue.appendleft((handle, state.source, int(state.uid), req, state))
+        return handle
+
     def step(self, count):
         """Admits waiting requests into free columns, generates `count` samples of every column and returns {handle: (samples, pcm)}
         with this step's samples of every request that ran (numpy int32 / int16, at most `count`, fewer at its end; pcm None when
@@ -113,14 +204,26 @@ class SlotStream:
             count = min(count, self.engine.slotsHeadroom())
             if count == 0:
                 return {}
+        if self._compact:
+            self.compact()
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
-            handle, x, uid, req = self._queue.popleft()
+            item = self._queue.popleft()
+            handle, x, uid, req = item[:4]
+            state = item[4] if len(item) > 4 else None
+            blob = state.blob if state is not None else None
+            self._src[handle] = (x, uid)
             if req is None:
-                self.engine.slotStart(col, x, uid)
-                self._running[col] = [handle, x.size(1)]
+                if blob is None:
+                    self.engine.slotStart(col, x, uid)
+                else:
+                    self.engine.slotResume(col, blob, x)
+                self._running[col] = [handle, x.size(1) - (state.done if blob is not None else 0)]
             else:
-                self.engine.slotStartMel(col, x, uid, req[0], req[1])
+                if blob is None:
+                    self.engine.slotStartMel(col, x, uid, req[0], req[1])
+                else:
+                    self.engine.slotResumeMel(col, blob, x, req[0], req[1])
                 req[2] = col
                 self._running[col] = [handle, None]
         if self._mel and not self._running:
@@ -129,6 +232,7 @@ class SlotStream:
         pcm = np.empty((self.columns, count), dtype=np.int16) if self.pcm else None
         if not self.engine.slotsStep(count, y, pcm):
             raise RuntimeError("slot step of %d samples failed" % count)
+        self._inflight.clear()
         out = {}
         for col in sorted(self._running):
             rec = self._running[col]
@@ -144,6 +248,7 @@ class SlotStream:
                 if req is not None:
                     del self._mel[rec[0]]
                 del self._running[col]
+                del self._src[rec[0]]
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
                 self._done.append(rec[0])

@@ -16,7 +16,17 @@ size with ms per step of each and their ratio (slots / lockstep rate).
              phase (the feed's stores are then as scattered as they get)
 and reports its rate against the feature-fed slot step (mel_rate_vs_slots).
 
+--compact times, instead, what moving columns buys a fragmented batch, in one process, back to back:
+  every column starts, then all but one column of every tile (column 5 of each: 1/16 of the batch, scattered over all tiles)
+  stop -- the survivors of a burst.  Per round: steps of 2048 and 256 samples as they lie (the launch covers every tile), the
+  survivors moved into the front columns (nvw_slot_move, one launch), the same steps compacted, and the survivors moved back.
+  The move launch, and the loads of resumed columns, are isolated as the difference between a step of ONE sample that carries them
+  and plain steps of one sample around it; saves are timed directly (events around nvw_slot_save calls).  Prints one JSON line
+  with the medians, the run-to-run spread over the rounds (min .. max), the tiles launched, and save / load GB/s against the
+  bytes of the blobs (read + written) and against the 128-byte lines the ring side touches (one per 16-byte piece).
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
 """
 import argparse
 import json
@@ -38,6 +48,8 @@ def main():
     ap.add_argument("--window", type=int, default=4096)
     ap.add_argument("--mel", action="store_true", help="also time slot steps fed with mel frames (distinct per column)")
     ap.add_argument("--only-mel", action="store_true", help="time the mel-fed slot steps only (e.g. under a profiler)")
+    ap.add_argument("--compact", action="store_true", help="time a fragmented batch with and without compaction, moves, saves and loads")
+    ap.add_argument("--rounds", type=int, default=5, help="--compact: rounds of (scattered, compacted) measurements")
     args = ap.parse_args()
     import torch
     import bench
@@ -46,6 +58,9 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.compact:
+        print(json.dumps(time_compact(args, w, Wc, bc)), flush=True)
+        return
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
     T_SRC = 65536
@@ -183,6 +198,139 @@ def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
     del mel
     torch.cuda.empty_cache()
     return ev[0].elapsed_time(ev[1]) / steps, restarts
+
+
+def time_compact(args, w, Wc, bc):
+    """The --compact measurement (module docstring)."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    B, W = args.batch, args.window
+    T_SRC = 262144      # (longer than everything the rounds generate: a resume needs done < length)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    e.setSelectorSeed(5)
+    e.slotsBegin(W)
+    surv = [b for b in range(B) if b % 16 == 5]
+    n = len(surv)
+    bound = 16 * ((n + 15) // 16)
+    for b in range(B):
+        e.slotStart(b, src, b)
+    y = torch.empty(B, 2048, dtype=torch.int32, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def timed(count, steps, before=None):
+        """ms per step of `steps` steps of `count` samples; before(): host calls that the first step applies (inside the timing)."""
+        torch.cuda.synchronize()
+        if before:
+            before()
+        ev[0].record()
+        for _ in range(steps):
+            assert e.slotsStep(count, y)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / steps
+
+    timed(256, 1)
+    for b in range(B):
+        if b % 16 != 5:
+            e.slotStop(b)
+    timed(256, 1)
+    # SlotStream.compact()'s rule: the survivors at or beyond the bound, highest first, into the free columns below it, lowest first
+    sources = sorted((b for b in surv if b >= bound), reverse=True)
+    targets = [b for b in range(bound) if b % 16 != 5][:len(sources)]
+    pairs = list(zip(sources, targets))
+
+    def info(top):
+        s = e.kernelInfo(top + 1)
+        return {"tiles": (top + 16) // 16, "workgroups": int(s.split("wgs=")[1].split()[0]), "tiles_per_wg": int(s.split("tiles/wg=")[1].split()[0])}
+
+    res = {"batch": B, "window": W, "running": n, "moves": len(pairs), "rounds": args.rounds, "device": torch.cuda.get_device_name(0),
+           "launch_scattered": info(max(surv)), "launch_compacted": info(bound - 1)}
+    keys = ("scattered_2048", "scattered_256", "compacted_2048", "compacted_256", "plain_1_scattered", "plain_1_compacted",
+            "move_step_1", "move_back_step_1")
+    t = {k: [] for k in keys}
+    for _ in range(args.rounds):
+        timed(2048, 1)
+        t["scattered_2048"].append(timed(2048, 2))
+        t["scattered_256"].append(timed(256, 4))
+        t["plain_1_scattered"].append(timed(1, 8))
+        t["move_step_1"].append(timed(1, 1, lambda: [e.slotMove(a, b) for a, b in pairs]))
+        t["plain_1_compacted"].append(timed(1, 8))
+        timed(2048, 1)
+        t["compacted_2048"].append(timed(2048, 2))
+        t["compacted_256"].append(timed(256, 4))
+        t["move_back_step_1"].append(timed(1, 1, lambda: [e.slotMove(b, a) for a, b in pairs]))
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4), "max": round(float(max(v)), 4)}
+
+    res["ms_per_step"] = {k: stats(v) for k, v in t.items()}
+    # the move launch alone: a one-sample step that carries the moves minus the plain one-sample steps of the launch it runs with
+    mv = [a - b for a, b in zip(t["move_step_1"], t["plain_1_compacted"])] + [a - b for a, b in zip(t["move_back_step_1"], t["plain_1_scattered"])]
+    res["move_launch_ms"] = stats(mv)
+    res["move_launch_vs_compacted_256_step"] = round(float(np.median(mv)) / float(np.median(t["compacted_256"])), 4)
+    res["speedup_2048"] = round(float(np.median(t["scattered_2048"])) / float(np.median(t["compacted_2048"])), 3)
+    res["speedup_256"] = round(float(np.median(t["scattered_256"])) / float(np.median(t["compacted_256"])), 3)
+    # ---- saves and loads (compacted: the survivors are in columns 0 .. bound - 1) ----
+    for a, b in pairs:
+        e.slotMove(a, b)
+    timed(1, 1)
+    cols = sorted(set(surv) - set(sources)) + targets
+    nbytes = e.slotStateBytes()
+    payload = nbytes - 64
+    blobs = torch.empty(len(cols), nbytes, dtype=torch.uint8, device="cuda")
+    s0 = torch.cuda.current_stream().cuda_stream
+
+    def save(which):
+        torch.cuda.synchronize()
+        ev[0].record()
+        for i in which:
+            assert lib.nvw_slot_save(e._h, cols[i], blobs[i].data_ptr(), s0) >= 0
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1])
+
+    save(range(len(cols)))
+    one = [save([i]) for i in range(args.rounds)]
+    bulk = [save(range(len(cols))) for _ in range(args.rounds)]
+    plain = [timed(1, 8) for _ in range(args.rounds)]
+
+    def resume(which):
+        for i in which:
+            e.slotResume(cols[i], blobs[i], src)
+
+    load_one, load_bulk = [], []
+    for r in range(args.rounds):
+        save(range(len(cols)))
+        e.slotStop(cols[r])
+        timed(1, 1)
+        load_one.append(timed(1, 1, lambda: resume([r])) - float(np.median(plain)))
+        save(range(len(cols)))
+        for c in cols:
+            e.slotStop(c)
+        timed(1, 1)
+        load_bulk.append(timed(1, 1, lambda: resume(range(len(cols)))) - float(np.median(plain)))
+
+    def gbs(ms, columns, lines=False):
+        per = payload * (1 + (8 if lines else 1))
+        return round(columns * per / (ms * 1e-3) / 1e9, 1) if ms > 0 else None
+
+    res["state_bytes"] = nbytes
+    res["save_ms"] = {"one_column": stats(one), "bulk_%d_columns" % len(cols): stats(bulk),
+                      "bulk_GBps_blob_bytes": gbs(float(np.median(bulk)), len(cols)), "bulk_GBps_lines_touched": gbs(float(np.median(bulk)), len(cols), True),
+                      "one_GBps_blob_bytes": gbs(float(np.median(one)), 1)}
+    res["load_ms"] = {"one_column_step_difference": stats(load_one), "bulk_%d_columns_step_difference" % len(cols): stats(load_bulk),
+                      "bulk_GBps_blob_bytes": gbs(float(np.median(load_bulk)), len(cols)),
+                      "bulk_GBps_lines_touched": gbs(float(np.median(load_bulk)), len(cols), True),
+                      "note": "differences of two one-sample steps: the one-column figure lies within their spread"}
+    res["plain_1_step_ms_for_loads"] = stats(plain)
+    e.slotsEnd()
+    e.close()
+    return res
 
 
 if __name__ == "__main__":
