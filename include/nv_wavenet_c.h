@@ -318,6 +318,50 @@ int nvw_slot_resume(nvw_engine* e, int slot, const void* state, const void* x, i
 int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* mel, int precision, long long c_stride,
                         long long f_stride, int frames, int final);
 
+/* SLOT MODE: RAGGED DELIVERY, STEPS THAT NEVER BLOCK (additive within ABI 7).  nvw_slots_step copies [batch][count] rows, idle columns
+ * and the samples past an utterance's end included, and synchronises when an output is host memory.  A ragged step delivers pieces:
+ * one per column that holds an utterance with at least one sample in this step, in ascending column order; a piece's n samples lie
+ * contiguously at element `offset` of `samples` (int32) and their PCM at the same offset of `pcm` (int16).  Every offset is a
+ * multiple of 8 elements; the 0 to 7 elements between a piece's end and the next piece's start are not written.
+ *   nvw_slots_step_ragged  the launches of nvw_slots_step up to and including the generation, one delivery launch, an event record;
+ *                          never synchronises.  samples / pcm: device memory or pinned host memory (hipHostMalloc, a registered
+ *                          range, nvw_pinned_alloc, torch pin_memory), `capacity` elements each; either may be NULL.  pieces[0 ..
+ *                          *n_pieces) (host memory, room for max_pieces) is filled before the call returns, from what the host
+ *                          knows: first = local index of the piece's first sample; n = min(count, length - first) for a feature
+ *                          column and a final mel column, count for a non-final mel column; finished != 0: the piece ends the
+ *                          utterance (the column is NOT stopped: nvw_slot_stop stays the caller's call); uid of the utterance.
+ *                          *ticket (1, 2, ...) names the step.  Returns the ragged size in elements (the end of the last piece; 0
+ *                          when no column delivers); -2 when a launch failed (the step was issued and has its ticket, its outputs
+ *                          are not to be read: nvw_slots_step returns 0 there); or -1 with nothing changed: not in slot mode, count outside 1..window or above
+ *                          nvw_slots_headroom, both outputs NULL, an output in pageable host memory, capacity or max_pieces too
+ *                          small (batch x (count rounded up to 8) elements and batch pieces always suffice).  Ragged and plain
+ *                          steps may be mixed.  The outputs of a step are complete once its ticket is.
+ *   nvw_slots_wait         blocks until the outputs of the step with that ticket are complete; 1, or 0 for a ticket never given.
+ *                          The engine keeps the events of the last 4 tickets: an older one is complete (a fifth step in flight
+ *                          waits for the first) and the call returns at once.
+ *   nvw_slots_done         the same question without blocking: 1 complete, 0 not yet (or never given).
+ *   nvw_pinned_alloc/free  pinned host memory for hosts without a HIP binding (NULL when it cannot be had).
+ *   nvw_slots_time_outputs measurement only (as nvw_time_runs): `reps` output passes over the last `count` samples generated, timed
+ *                          with events on `stream`, milliseconds for all of them.  ragged = 0: what nvw_slots_step issues after the
+ *                          generation (PCM launches + 2-D copies into samples / pcm [batch][count]); ragged != 0: the delivery
+ *                          launch for every column holding an utterance.  Both outputs given, device or pinned, `capacity` elements.
+ *                          Synchronises the device, changes nothing of the session; < 0 when refused. */
+typedef struct {
+    int slot;
+    unsigned uid;
+    long long first;
+    int n;
+    int finished;
+    long long offset;
+} nvw_slot_piece;
+long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
+                                int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream);
+int nvw_slots_wait(nvw_engine* e, unsigned long long ticket);
+float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream);
+int nvw_slots_done(nvw_engine* e, unsigned long long ticket);
+void* nvw_pinned_alloc(size_t bytes);
+void nvw_pinned_free(void* p);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

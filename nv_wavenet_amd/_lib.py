@@ -93,6 +93,13 @@ SIGNATURES = {
     "nvw_slot_save": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_void_p]),
     "nvw_slot_resume": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "nvw_slot_resume_mel": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "nvw_slots_step_ragged": (C.c_longlong, [C.c_void_p, C.c_int, _fp, _fp, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_ulonglong), C.c_void_p]),
+    "nvw_slots_time_outputs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),
+    "nvw_slots_wait": (C.c_int, [C.c_void_p, C.c_ulonglong]),
+    "nvw_slots_done": (C.c_int, [C.c_void_p, C.c_ulonglong]),
+    "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),
+    "nvw_pinned_free": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),
     "nvw_time_runs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "wavenet_infer": (None, [C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int] + [C.POINTER(C.c_void_p)] * 7 +

@@ -72,7 +72,16 @@ struct nvw_engine {
     virtual int slotSave(int, void*, hipStream_t) = 0;
     virtual bool slotResume(int, const void*, const void*, int, long long, long long, int) = 0;
     virtual bool slotResumeMel(int, const void*, const void*, int, long long, long long, int, int) = 0;
+    virtual long long slotsStepRagged(int, int*, short*, long long, nvw_slot_piece*, int, int*, unsigned long long*, hipStream_t) = 0;
+    virtual bool slotsWait(unsigned long long) = 0;
+    virtual int slotsDone(unsigned long long) = 0;
+    virtual float slotsTimeOutputs(bool, int, int*, short*, long long, int, hipStream_t) = 0;
 };
+static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
+              offsetof(nvw_slot_piece, uid) == offsetof(wn::SlotPiece, uid) && offsetof(nvw_slot_piece, finished) == offsetof(wn::SlotPiece, finished) &&
+              offsetof(nvw_slot_piece, first) == offsetof(wn::SlotPiece, first) &&
+              offsetof(nvw_slot_piece, n) == offsetof(wn::SlotPiece, n) && offsetof(nvw_slot_piece, offset) == offsetof(wn::SlotPiece, offset),
+              "nvw_slot_piece is wn::SlotPiece");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -165,6 +174,15 @@ struct EngineImpl : nvw_engine {
     }
     bool slotResumeMel(int slot, const void* state, const void* mel, int prec, long long cS, long long fS, int frames, int final) override {
         return eng.slotResumeMel(slot, state, mel, prec, cS, fS, frames, final);
+    }
+    long long slotsStepRagged(int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces, int maxPieces, int* nPieces,
+                              unsigned long long* ticket, hipStream_t s) override {
+        return eng.slotsStepRagged(count, samples, pcm, capacity, (wn::SlotPiece*)pieces, maxPieces, nPieces, ticket, s);
+    }
+    bool slotsWait(unsigned long long ticket) override { return eng.slotsWait(ticket); }
+    int slotsDone(unsigned long long ticket) override { return eng.slotsDone(ticket); }
+    float slotsTimeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t s) override {
+        return eng.slotsTimeOutputs(ragged, count, samples, pcm, capacity, reps, s);
     }
 };
 

@@ -38,6 +38,7 @@
 #include "slots.hpp"
 #include "slots_mel.hpp"
 #include "slots_state.hpp"
+#include "slots_deliver.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
 
@@ -189,6 +190,12 @@ protected:
     std::vector<char> m_slotMoveEnd;        // per column: 1 source, 2 destination of a pending move
     std::vector<wn::SlotMove> m_slotMoves;  // the pending moves
     wn::SlotLayer* m_slotLayers = NULL;     // the schedule per ring slot on the device (built by the first save or resume)
+    // ... and ragged delivery (slots_deliver.hpp): a step's valid samples piece by piece, completion by ticket
+    static constexpr int kSlotTickets = 4;  // events kept: a ticket older than that is complete (the stream is ordered)
+    wn::DeliverPiece* m_dlvDev = NULL;      // [maxBatch] on the device: the pieces of the step being delivered
+    wn::DeliverPiece* m_dlvStage[kSlotTickets] = {};      // pinned host staging of them, one per ticket in flight ...
+    hipEvent_t m_dlvEv[kSlotTickets] = {};  // ... and the event recorded after that ticket's delivery
+    unsigned long long m_dlvTicket = 0;     // the last ticket given out (they count from 1)
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -1455,6 +1462,12 @@ public:
             gpuErrChk(hipEventRecord(m_slotEv[i], 0));
         }
         m_slotParity = 0;
+        gpuErrChk(hipMalloc(&m_dlvDev, (size_t)m_maxBatch * sizeof(wn::DeliverPiece)));
+        for (int i = 0; i < kSlotTickets; i++) {
+            gpuErrChk(hipHostMalloc((void**)&m_dlvStage[i], (size_t)m_maxBatch * sizeof(wn::DeliverPiece), hipHostMallocDefault));
+            gpuErrChk(hipEventCreateWithFlags(&m_dlvEv[i], hipEventDisableTiming));
+        }
+        m_dlvTicket = 0;
         ensureMulaw();
         gpuErrChk(hipDeviceSynchronize());
         return true;
@@ -1649,18 +1662,43 @@ public:
         if (m_slotW <= 0 || count <= 0 || count > m_slotW) return false;
         if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return false;      // (mel columns short of frames)
         const int W = m_slotW;
+        int piece[2][2], pieces = 0, cols = 0;
+        bool ok = slotsGenerate(count, piece, pieces, cols, stream);
+        if (cols > 0 && pcm != NULL) {
+            for (int i = 0; i < pieces; i++) {
+                hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * piece[i][1])), dim3(256), 0, stream, m_slotY, m_slotPcm,
+                                   m_mulaw, cols, W, piece[i][0], piece[i][1]);
+                ok = ok && hipGetLastError() == hipSuccess;
+            }
+        }
+        for (int i = 0, off = 0; i < pieces; off += piece[i][1], i++) {
+            if (yOut != NULL)
+                gpuErrChk(hipMemcpy2DAsync(yOut + off, (size_t)count * sizeof(int), m_slotY + piece[i][0], (size_t)W * sizeof(int),
+                                           (size_t)piece[i][1] * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
+            if (pcm != NULL)
+                gpuErrChk(hipMemcpy2DAsync(pcm + off, (size_t)count * sizeof(short), m_slotPcm + piece[i][0], (size_t)W * sizeof(short),
+                                           (size_t)piece[i][1] * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
+        }
+        m_slotCounter += count;
+        if ((yOut != NULL && !isDevicePtr(yOut)) || (pcm != NULL && !isDevicePtr(pcm))) gpuErrChk(hipStreamSynchronize(stream));
+        return ok;
+    }
+    // The launches of a step up to and including the generation (the order above), shared by slotsStep and slotsStepRagged: the
+    // window rows of the launches -> piece[0 .. pieces), the columns they cover -> cols.  The counter is the caller's to advance.
+    bool slotsGenerate(int count, int piece[2][2], int& pieces, int& cols, hipStream_t stream) {
+        const int W = m_slotW;
         bool ok = true;
         if (!m_slotMoves.empty()) ok = slotApplyMoves(stream);
         if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream) && ok;      // (before the starts: it reads the pending ones)
         if (!m_slotPendingList.empty()) ok = slotApplyPending(stream) && ok;
-        int cols = 0;
+        cols = 0;
         for (int b = m_maxBatch - 1; b >= 0; b--)
             if (m_slotHost[b].active || (m_melColumns > 0 && m_melHost[b].state)) {
                 cols = b + 1;
                 break;
             }
         const int T = (int)(m_slotCounter % W);
-        int piece[2][2], pieces = 0;      // (first window row, samples) of the launches
+        pieces = 0;      // (first window row, samples) of the launches
         for (int done = 0; done < count; pieces++) {
             const int t0 = (T + done) % W, c = count - done < W - t0 ? count - done : W - t0;
             piece[pieces][0] = t0;
@@ -1676,25 +1714,179 @@ public:
                                              (const int*)(m_melUpd + melTileOff()), m_melTiles, m_maxBatch, m_tiles, m_nCond, m_upTab, m_upBias,
                                              m_upWindow / m_upStride, m_upStride, m_slotCounter, T, W, count, m_rngSeed) && ok;
             for (int i = 0; i < pieces; i++) ok = slotLaunch(piece[i][0], piece[i][1], cols, stream) && ok;
-            if (pcm != NULL) {
-                for (int i = 0; i < pieces; i++) {
-                    hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * piece[i][1])), dim3(256), 0, stream, m_slotY, m_slotPcm,
-                                       m_mulaw, cols, W, piece[i][0], piece[i][1]);
-                    ok = ok && hipGetLastError() == hipSuccess;
-                }
+        }
+        return ok;
+    }
+    // ---- ragged delivery (slots_deliver.hpp) ----
+    // The address the device stores through for an output of slotsStepRagged: the pointer itself for device memory, the mapped
+    // address for pinned host memory (hipHostMalloc, hipHostRegister); NULL for anything else (pageable host memory).
+    static void* deliverTarget(void* p) {
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+            (void)hipGetLastError();
+            return NULL;
+        }
+        if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return p;
+        if (attr.type != hipMemoryTypeHost) return NULL;
+        void* d = NULL;
+        if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return NULL;
+        }
+        return d;
+    }
+    // The pieces a step of `count` samples delivers, from what the host knows (the descriptors with the pending starts, resumes and
+    // moves already in them, the counter): one per column holding an utterance with a sample in this step, ascending.  first = the
+    // local index of its first sample; n = min(count, length - first) for a feature column and a final mel column, count for a
+    // non-final mel column (the headroom rule); offsets packed, each rounded up to kDeliverAlign elements.  out may be NULL (count
+    // only).  Returns the number of pieces; total = the end of the last one.
+    int slotPieces(int count, wn::SlotPiece* out, int maxOut, long long& total) const {
+        int n = 0;
+        long long off = 0;
+        total = 0;
+        for (int b = 0; b < m_maxBatch; b++) {
+            const bool mel = m_melColumns > 0 && m_melHost[b].state != 0;
+            if (!mel && !m_slotHost[b].active) continue;
+            const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
+            const long long first = m_slotPending[b] == 1 ? m_slotResumeDone[b] : m_slotCounter - start;
+            long long len = count, left = count;
+            bool bounded = true;
+            if (!mel) len = m_slotHost[b].length;
+            else if (m_melHost[b].state == 2) len = (long long)m_melHost[b].frames * m_upStride;
+            else bounded = false;
+            if (bounded) left = len - first;
+            if (left <= 0) continue;      // (ended in an earlier step and not stopped since)
+            const int k = left < count ? (int)left : count;
+            if (out != NULL && n < maxOut) {
+                wn::SlotPiece& p = out[n];
+                p.slot = b;
+                p.uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
+                p.first = first;
+                p.n = k;
+                p.finished = bounded && first + k == len ? 1 : 0;
+                p.offset = off;
+            }
+            n++;
+            total = off + k;
+            off = (total + wn::kDeliverAlign - 1) / wn::kDeliverAlign * wn::kDeliverAlign;
+        }
+        return n;
+    }
+    // slotsStep, delivering pieces in place of rows, and never synchronising: the launches of slotsStep up to and including the
+    // generation, then ONE slot_deliver_kernel launch that writes each piece's n samples at its offset of `samples` (int32) and / or
+    // their PCM at the same offset of `pcm` (int16) -- device memory or pinned host memory, `capacity` elements each, NULL: not
+    // wanted --, then an event record.  pieces[0 .. *nPieces) (host) is filled before anything is launched.  *ticket names the step
+    // for slotsWait / slotsDone.  Returns the ragged size (end of the last piece; 0 when no column delivers); -2 when a launch
+    // failed (the step was issued and has its ticket, but its outputs are not to be read: slotsStep returns false there); or -1 with
+    // nothing changed: not in slot mode, count out of range or above the headroom, both outputs NULL, an output that is neither device
+    // nor pinned memory, capacity or maxPieces too small.  Mixes freely with slotsStep.  (A step that reuses a ticket slot waits for
+    // the step kSlotTickets before it: with at most that many steps in flight it waits for nothing.)
+    long long slotsStepRagged(int count, int* samples, short* pcm, long long capacity, wn::SlotPiece* pieces, int maxPieces, int* nPieces,
+                              unsigned long long* ticket, hipStream_t stream = 0) {
+        if (m_slotW <= 0 || count <= 0 || count > m_slotW || (samples == NULL && pcm == NULL) || pieces == NULL || nPieces == NULL ||
+            ticket == NULL)
+            return -1;
+        if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return -1;
+        int* const dSamples = samples ? (int*)deliverTarget(samples) : NULL;
+        short* const dPcm = pcm ? (short*)deliverTarget(pcm) : NULL;
+        if ((samples && !dSamples) || (pcm && !dPcm)) return -1;
+        long long total = 0;
+        const int n = slotPieces(count, NULL, 0, total);
+        if (n > maxPieces || total > capacity) return -1;
+        slotPieces(count, pieces, maxPieces, total);
+        *nPieces = n;
+        const int T = (int)(m_slotCounter % m_slotW);
+        const int at = (int)(m_dlvTicket % kSlotTickets);
+        if (m_dlvTicket >= (unsigned long long)kSlotTickets) gpuErrChk(hipEventSynchronize(m_dlvEv[at]));
+        int piece[2][2], launches = 0, cols = 0;
+        bool ok = slotsGenerate(count, piece, launches, cols, stream);
+        if (n > 0) {
+            wn::DeliverPiece* const stage = m_dlvStage[at];
+            for (int i = 0; i < n; i++) stage[i] = wn::DeliverPiece{pieces[i].slot, pieces[i].n, pieces[i].offset};
+            gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(wn::DeliverPiece), hipMemcpyHostToDevice, stream));
+            ok = wn::slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, dPcm) && ok;
+        }
+        gpuErrChk(hipEventRecord(m_dlvEv[at], stream));
+        m_slotCounter += count;
+        *ticket = ++m_dlvTicket;
+        return ok ? total : -2;
+    }
+    // Measurement only (scripts/slots_perf.py --serve): `reps` back-to-back output passes over the last `count` samples generated,
+    // timed with events on `stream`; returns milliseconds for all of them, < 0 when refused.  ragged = false: what slotsStep
+    // issues after the generation -- the PCM launches and the 2-D copies into samples / pcm [maxBatch][count]; ragged = true: the
+    // delivery launch for every column holding an utterance (n = min(count, its samples so far)) into samples / pcm of `capacity`
+    // elements.  Device or pinned outputs, both given.  Synchronises the device; changes nothing of the session.
+    float slotsTimeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t stream = 0) {
+        if (m_slotW <= 0 || count <= 0 || count > m_slotW || count > m_slotCounter || samples == NULL || pcm == NULL || reps <= 0) return -1.f;
+        int* const dSamples = (int*)deliverTarget(samples);
+        short* const dPcm = (short*)deliverTarget(pcm);
+        if (!dSamples || !dPcm) return -1.f;
+        const int W = m_slotW, T = (int)((m_slotCounter - count) % W);
+        gpuErrChk(hipDeviceSynchronize());
+        int n = 0, cols = 0;
+        long long off = 0, total = 0;
+        for (int b = 0; b < m_maxBatch; b++) {
+            const bool mel = m_melColumns > 0 && m_melHost[b].state != 0;
+            if ((!mel && !m_slotHost[b].active) || m_slotPending[b] == 1) continue;
+            cols = b + 1;
+            const long long done = m_slotCounter - (mel ? m_melHost[b].start : m_slotHost[b].start);
+            if (done <= 0) continue;
+            const int k = done < count ? (int)done : count;
+            m_dlvStage[0][n++] = wn::DeliverPiece{b, k, off};
+            total = off + k;
+            off = (total + wn::kDeliverAlign - 1) / wn::kDeliverAlign * wn::kDeliverAlign;
+        }
+        if (n == 0 || (ragged ? total : (long long)m_maxBatch * count) > capacity) return -1.f;
+        gpuErrChk(hipMemcpyAsync(m_dlvDev, m_dlvStage[0], (size_t)n * sizeof(wn::DeliverPiece), hipMemcpyHostToDevice, stream));
+        hipEvent_t t0, t1;
+        gpuErrChk(hipEventCreate(&t0));
+        gpuErrChk(hipEventCreate(&t1));
+        bool ok = true;
+        gpuErrChk(hipEventRecord(t0, stream));
+        for (int r = 0; r < reps; r++) {
+            if (ragged) {
+                ok = wn::slots_deliver(stream, m_slotY, m_mulaw, T, W, count, m_dlvDev, n, dSamples, dPcm) && ok;
+                continue;
+            }
+            for (int done = 0; done < count;) {
+                const int t = (T + done) % W, c = count - done < W - t ? count - done : W - t;
+                hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * c)), dim3(256), 0, stream, m_slotY, m_slotPcm, m_mulaw, cols,
+                                   W, t, c);
+                ok = ok && hipGetLastError() == hipSuccess;
+                gpuErrChk(hipMemcpy2DAsync(samples + done, (size_t)count * sizeof(int), m_slotY + t, (size_t)W * sizeof(int),
+                                           (size_t)c * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
+                gpuErrChk(hipMemcpy2DAsync(pcm + done, (size_t)count * sizeof(short), m_slotPcm + t, (size_t)W * sizeof(short),
+                                           (size_t)c * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
+                done += c;
             }
         }
-        for (int i = 0, off = 0; i < pieces; off += piece[i][1], i++) {
-            if (yOut != NULL)
-                gpuErrChk(hipMemcpy2DAsync(yOut + off, (size_t)count * sizeof(int), m_slotY + piece[i][0], (size_t)W * sizeof(int),
-                                           (size_t)piece[i][1] * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
-            if (pcm != NULL)
-                gpuErrChk(hipMemcpy2DAsync(pcm + off, (size_t)count * sizeof(short), m_slotPcm + piece[i][0], (size_t)W * sizeof(short),
-                                           (size_t)piece[i][1] * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
+        gpuErrChk(hipEventRecord(t1, stream));
+        gpuErrChk(hipEventSynchronize(t1));
+        float ms = 0.f;
+        gpuErrChk(hipEventElapsedTime(&ms, t0, t1));
+        gpuErrChk(hipEventDestroy(t0));
+        gpuErrChk(hipEventDestroy(t1));
+        return ok ? ms : -1.f;
+    }
+    // Blocks until the outputs of the step with that ticket are complete (true), at once for a ticket older than the events kept;
+    // false: no such ticket.
+    bool slotsWait(unsigned long long ticket) {
+        if (m_slotW <= 0 || ticket == 0 || ticket > m_dlvTicket) return false;
+        if (m_dlvTicket - ticket >= (unsigned long long)kSlotTickets) return true;
+        gpuErrChk(hipEventSynchronize(m_dlvEv[(ticket - 1) % kSlotTickets]));
+        return true;
+    }
+    // 1: complete, 0: not yet, -1: no such ticket.  Never blocks.
+    int slotsDone(unsigned long long ticket) {
+        if (m_slotW <= 0 || ticket == 0 || ticket > m_dlvTicket) return -1;
+        if (m_dlvTicket - ticket >= (unsigned long long)kSlotTickets) return 1;
+        const hipError_t e = hipEventQuery(m_dlvEv[(ticket - 1) % kSlotTickets]);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();
+            return 0;
         }
-        m_slotCounter += count;
-        if ((yOut != NULL && !isDevicePtr(yOut)) || (pcm != NULL && !isDevicePtr(pcm))) gpuErrChk(hipStreamSynchronize(stream));
-        return ok;
+        gpuErrChk(e);
+        return 1;
     }
     // Leaves slot mode and frees its buffers (synchronises).  The rings it wrote are cleared by the next resetHistory, as after any run.
     void slotsEnd() {
@@ -1711,6 +1903,14 @@ public:
             gpuErrChk(hipEventDestroy(m_slotEv[i]));
             m_slotStage[i] = NULL;
             m_slotEv[i] = NULL;
+        }
+        gpuErrChk(hipFree(m_dlvDev));
+        m_dlvDev = NULL;
+        for (int i = 0; i < kSlotTickets; i++) {
+            gpuErrChk(hipHostFree(m_dlvStage[i]));
+            gpuErrChk(hipEventDestroy(m_dlvEv[i]));
+            m_dlvStage[i] = NULL;
+            m_dlvEv[i] = NULL;
         }
         m_slotDesc = NULL;
         m_slotFeat = NULL;

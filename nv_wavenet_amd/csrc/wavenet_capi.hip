@@ -363,6 +363,27 @@ int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* 
     }
     return 1;
 }
+// ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
+long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
+                                int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {
+    return e->slotsStepRagged(count, samples, pcm, capacity, pieces, max_pieces, n_pieces, ticket, (hipStream_t)stream);
+}
+float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream) {
+    return e->slotsTimeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);
+}
+int nvw_slots_wait(nvw_engine* e, unsigned long long ticket) { return e->slotsWait(ticket) ? 1 : 0; }
+int nvw_slots_done(nvw_engine* e, unsigned long long ticket) { return e->slotsDone(ticket) > 0 ? 1 : 0; }
+void* nvw_pinned_alloc(size_t bytes) {
+    void* p = NULL;
+    if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return NULL;
+    }
+    return p;
+}
+void nvw_pinned_free(void* p) {
+    if (p) gpuErrChk(hipHostFree(p));
+}
 
 void nvw_device_synchronize(void) { gpuErrChk(hipDeviceSynchronize()); }
 

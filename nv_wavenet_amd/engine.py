@@ -10,6 +10,10 @@ import numpy as np
 
 from ._lib import lib, addr, CONSUME_FN
 
+# nvw_slot_piece of include/nv_wavenet_c.h: one delivered piece of a ragged slot step
+SLOT_PIECE = np.dtype([("slot", "<i4"), ("uid", "<u4"), ("first", "<i8"), ("n", "<i4"), ("finished", "<i4"), ("offset", "<i8")])
+assert SLOT_PIECE.itemsize == 32
+
 
 class Impl:
     """nvWavenetInfer::Implementation (nv_wavenet.cuh:223-229). The reference's Python enum
@@ -371,6 +375,44 @@ class WavenetEngine:
         if pcm is not None and not hasattr(pcm, "data_ptr"):
             assert pcm.dtype == np.int16 and pcm.flags["C_CONTIGUOUS"]
         return bool(lib.nvw_slots_step(self._h, int(count), addr(yOut), addr(pcm), stream))
+
+    def slotsStepRagged(self, count, samples=None, pcm=None, stream=None):
+        """`count` samples of every column, delivered piece by piece, without ever waiting (nvw_slots_step_ragged): samples int32 /
+        pcm int16, 1-D CUDA or pinned tensors (slotsPinned; either may be None), take each running utterance's valid samples
+        contiguously at an offset that is a multiple of 8.  Returns (total, pieces, ticket): the ragged size in elements, a numpy
+        structured array (SLOT_PIECE: slot, uid, first, n, finished, offset) with one record per delivering column in ascending
+        column order -- known at once, from the host's bookkeeping --, and the ticket for slotsWait / slotsDone, after which the
+        outputs hold the step.  ValueError when refused (nothing changed)."""
+        cap = None
+        for a, dt, name in ((samples, "int32", "samples"), (pcm, "int16", "pcm")):
+            if a is not None:
+                assert hasattr(a, "data_ptr") and (a.is_cuda or a.is_pinned()) and a.is_contiguous() and str(a.dtype) == "torch." + dt, \
+                    "%s: a contiguous CUDA or pinned %s tensor" % (name, dt)
+                cap = a.numel() if cap is None else min(cap, a.numel())
+        pieces = np.empty(self.maxBatch, dtype=SLOT_PIECE)
+        n, ticket = C.c_int(0), C.c_ulonglong(0)
+        total = lib.nvw_slots_step_ragged(self._h, int(count), addr(samples), addr(pcm), cap or 0, pieces.ctypes.data, self.maxBatch,
+                                          C.byref(n), C.byref(ticket), stream)
+        if total == -2:
+            raise RuntimeError("nvw_slots_step_ragged: a launch of the step of %d samples failed" % count)
+        if total < 0:
+            raise ValueError("nvw_slots_step_ragged refused a step of %d samples into %s elements" % (count, cap))
+        return int(total), pieces[:n.value], int(ticket.value)
+
+    def slotsWait(self, ticket):
+        """Blocks until the outputs of the ragged step with that ticket are complete."""
+        if not lib.nvw_slots_wait(self._h, int(ticket)):
+            raise ValueError("nvw_slots_wait: no ticket %d" % ticket)
+
+    def slotsDone(self, ticket):
+        """Whether the outputs of the ragged step with that ticket are complete (never blocks)."""
+        return bool(lib.nvw_slots_done(self._h, int(ticket)))
+
+    def slotsPinned(self, elems, pcm=True):
+        """(samples, pcm) pinned host tensors of `elems` int32 / int16 for slotsStepRagged (pcm None when not wanted)."""
+        import torch
+        return (torch.empty(int(elems), dtype=torch.int32, pin_memory=True),
+                torch.empty(int(elems), dtype=torch.int16, pin_memory=True) if pcm else None)
 
     def slotStartMel(self, slot, mel, uid, frames=None, final=True):
         """Column `slot` takes a mel utterance at the next step: mel = its frames before upsampling, CUDA tensor [n_cond][capacity]

@@ -399,7 +399,9 @@ class NVWaveNetEngine(NVWaveNet):
         (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
         request; with the model's `upsample` ConvTranspose1d (upsample_weight [n_cond][n_cond][window], upsample_bias, its stride)
         mel frames [n_cond][frames] as well (submit_mel).  compact: every step first packs the running requests into the front of the
-        batch (SlotStream.compact).  close() the stream to free the engine."""
+        batch (SlotStream.compact).  stream.step(n) waits for its samples; stream.step_async(n) issues the step and returns a
+        PendingStep, two of which may be in flight (the pipelined service loop of INTEGRATION.md §2g).  close() the stream to free
+        the engine."""
         from .slots import SlotStream
         e = self._new_engine(columns, window, implementation)
         e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())

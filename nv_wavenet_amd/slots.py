@@ -33,6 +33,23 @@ suspend is not delivered again.
 
     state = stream.suspend(h)                           # a SlotState: the blob, the source tensor, uid, samples done
     h2 = other_stream.resume(state)                     # goes on at sample state.done
+
+step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
+(DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
+owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
+a step is a few numpy operations over the pieces, whatever the number of columns, and a Python loop only over the requests that
+start or end in it.  Two steps may be pending: the GPU generates step k + 1 while the host consumes step k.
+
+    pending = None
+    while serving or stream.busy() or pending is not None:
+        nxt = stream.step_async(2048) if stream.busy() else None      # step k + 1: issued before step k is waited for
+        if pending is not None:
+            out = pending.result()                                     # a StepOutput: waits for step k only
+            for handle, (samples, pcm) in out.items():                 # views of a pinned buffer: valid until two more steps
+                ...                                                    # have been issued (.copy() to keep them)
+            for handle in stream.finished():
+                ...
+        pending = nxt                                                  # (None while the stream is idle)
 """
 import heapq
 from collections import deque
@@ -58,6 +75,73 @@ class SlotState:
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
 
 
+class StepOutput:
+    """What one step delivered (PendingStep.result): per delivering request, in ascending column order, handles[i], offsets[i] and
+    lengths[i] (numpy) -- its samples are samples[offsets[i] : offsets[i] + lengths[i]], its PCM the same range of pcm (None when the
+    stream was made with pcm=False) --, and finished, the handles whose last sample is in this step.  samples and pcm are views of a
+    pinned buffer of the stream, valid until the second step after this one is issued (the stream's two buffers take turns).  out[handle] and out.items() slice lazily."""
+
+    def __init__(self, handles, offsets, lengths, samples, pcm, finished):
+        self.handles, self.offsets, self.lengths, self.samples, self.pcm, self.finished = handles, offsets, lengths, samples, pcm, finished
+        self._index = None
+
+    def __len__(self):
+        return len(self.handles)
+
+    def __contains__(self, handle):
+        return self._at(handle) is not None
+
+    def _at(self, handle):
+        if self._index is None:
+            self._index = {int(h): i for i, h in enumerate(self.handles)}
+        return self._index.get(int(handle))
+
+    def _slice(self, i):
+        a, b = int(self.offsets[i]), int(self.offsets[i]) + int(self.lengths[i])
+        return self.samples[a:b], (self.pcm[a:b] if self.pcm is not None else None)
+
+    def __getitem__(self, handle):
+        i = self._at(handle)
+        if i is None:
+            raise KeyError(handle)
+        return self._slice(i)
+
+    def items(self):
+        for i, h in enumerate(self.handles):
+            yield int(h), self._slice(i)
+
+
+class PendingStep:
+    """A step that has been issued (SlotStream.step_async).  result() waits for its samples -- for nothing else -- and returns its
+    StepOutput (the same one every time; a pending step issued before it is collected first); done() asks without waiting."""
+
+    def __init__(self, stream, ticket, buf, total, handles, offsets, lengths, finished):
+        self._stream, self._ticket, self._buf, self._total = stream, ticket, buf, total
+        self._handles, self._offsets, self._lengths, self._finished = handles, offsets, lengths, finished
+        self._out = None
+
+    def done(self):
+        return self._out is not None or self._ticket is None or self._stream.engine.slotsDone(self._ticket)
+
+    def result(self):
+        if self._out is None:
+            st = self._stream
+            if self._ticket is not None:
+                for earlier in list(st._pending):      # (in the order of issue: the steps before this one are collected first)
+                    if earlier is self:
+                        break
+                    earlier.result()
+                st.engine.slotsWait(self._ticket)
+                y, pcm = st._bufs[self._buf]
+                self._out = StepOutput(self._handles, self._offsets, self._lengths, y[:self._total], pcm[:self._total] if pcm is not None else None,
+                                       self._finished)
+                st._pending.remove(self)
+                st._done.extend(self._finished)
+            else:      # (a step that generated nothing: step() returns {} there)
+                self._out = StepOutput(self._handles, self._offsets, self._lengths, np.empty(0, np.int32), np.empty(0, np.int16) if st.pcm else None, [])
+        return self._out
+
+
 class SlotStream:
     def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False):
         self.engine = engine
@@ -72,6 +156,16 @@ class SlotStream:
         self._src = {}                                 # handle -> (source tensor, uid) of the running requests
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
+        # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
+        # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
+        self._arrays = False
+        self._ch = np.full(self.columns, -1, dtype=np.int64)        # per column: the handle it runs (-1: none) ...
+        self._left = np.zeros(self.columns, dtype=np.int64)         # ... a feature request's samples still to come ...
+        self._deliv = np.zeros(self.columns, dtype=np.int64)        # ... a mel request's samples delivered
+        self._pending = []                             # the steps issued by step_async and not yet collected (at most two)
+        self._bufs = [None, None]                      # their pinned outputs: (samples, pcm) numpy views, grown on demand
+        self._bufs_keep = [None, None]
+        self._last_buf = 1                             # the buffer of the step issued last: the next step takes the other
         self._inflight = set()                         # columns that are endpoints of moves the next step has yet to apply
         self._done = []
         self._next_handle = 0
@@ -143,6 +237,8 @@ class SlotStream:
         for src, dst in zip(sources, targets):
             self.engine.slotMove(src, dst)
             rec = self._running[dst] = self._running.pop(src)
+            self._ch[dst], self._left[dst], self._deliv[dst] = self._ch[src], self._left[src], self._deliv[src]
+            self._ch[src] = -1
             if rec[1] is None:
                 self._mel[rec[0]][2] = dst
             self._free.remove(dst)
@@ -175,11 +271,14 @@ class SlotStream:
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
         heapq.heappush(self._free, col)
+        self._ch[col] = -1
         if rec[1] is not None:
-            assert done == x.size(1) - rec[1], (done, x.size(1), rec[1])
+            left = int(self._left[col]) if self._arrays else rec[1]
+            assert done == x.size(1) - left, (done, x.size(1), left)
             return SlotState(blob, x, uid, done, "features")
         req = self._mel.pop(handle)
-        assert done == req[3], (done, req[3])
+        delivered = int(self._deliv[col]) if self._arrays else req[3]
+        assert done == delivered, (done, delivered)
         return SlotState(blob, x, uid, done, "mel", req[0], req[1])
 
     def resume(self, state):
@@ -195,17 +294,25 @@ class SlotStream:
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
         return handle
 
-    def step(self, count):
-        """Admits waiting requests into free columns, generates `count` samples of every column and returns {handle: (samples, pcm)}
-        with this step's samples of every request that ran (numpy int32 / int16, at most `count`, fewer at its end; pcm None when
-        the stream was made with pcm=False).  With mel requests the step is min(count, headroom) samples; none (no engine call, {})
-        when a running mel request has no frames beyond what it has delivered."""
-        if self._mel:
-            count = min(count, self.engine.slotsHeadroom())
-            if count == 0:
-                return {}
-        if self._compact:
-            self.compact()
+    def _use_arrays(self, on):
+        """Brings the form of the per-column counts that the caller now uses up to date (a loop over the running columns, made
+        when the caller changes between step() and step_async(), not per step)."""
+        if on == self._arrays:
+            return
+        for col, rec in self._running.items():
+            req = self._mel[rec[0]] if rec[1] is None else None
+            if on:
+                self._ch[col] = rec[0]
+                self._left[col] = rec[1] if req is None else 0
+                self._deliv[col] = req[3] if req is not None else 0
+            elif req is None:
+                rec[1] = int(self._left[col])
+            else:
+                req[3] = int(self._deliv[col])
+        self._arrays = on
+
+    def _admit(self, count):
+        """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
             item = self._queue.popleft()
@@ -226,6 +333,26 @@ class SlotStream:
                     self.engine.slotResumeMel(col, blob, x, req[0], req[1])
                 req[2] = col
                 self._running[col] = [handle, None]
+            if self._arrays:
+                self._ch[col] = handle
+                self._left[col] = self._running[col][1] if req is None else 0
+                self._deliv[col] = req[3] if req is not None else 0
+
+    def step(self, count):
+        """Admits waiting requests into free columns, generates `count` samples of every column and returns {handle: (samples, pcm)}
+        with this step's samples of every request that ran (numpy int32 / int16, at most `count`, fewer at its end; pcm None when
+        the stream was made with pcm=False).  With mel requests the step is min(count, headroom) samples; none (no engine call, {})
+        when a running mel request has no frames beyond what it has delivered.  Not while steps of step_async are pending."""
+        if self._pending:
+            raise RuntimeError("%d pending steps: collect them (PendingStep.result) before a synchronous step" % len(self._pending))
+        self._use_arrays(False)
+        if self._mel:
+            count = min(count, self.engine.slotsHeadroom())
+            if count == 0:
+                return {}
+        if self._compact:
+            self.compact()
+        self._admit(count)
         if self._mel and not self._running:
             return {}
         y = np.empty((self.columns, count), dtype=np.int32)
@@ -254,12 +381,65 @@ class SlotStream:
                 self._done.append(rec[0])
         return out
 
+    def _retire(self, col):
+        """The request of column `col` has had its last sample issued: the column stops at the next step and is free."""
+        handle = self._running.pop(col)[0]
+        self._mel.pop(handle, None)
+        del self._src[handle]
+        self._ch[col] = -1
+        self.engine.slotStop(col)
+        heapq.heappush(self._free, col)
+        return handle
+
+    def step_async(self, count):
+        """step(), without waiting for the samples: compacts, admits, issues the step, retires what it finishes and returns a
+        PendingStep whose result() is the step's StepOutput.  At most two steps may be pending; a third raises RuntimeError before
+        anything has changed.  Steps take the stream's two pinned buffers by turns, so a StepOutput's views stay valid until the
+        second step after its own has been issued, whether or not steps are pending in between.  suspend, resume, compact and
+        extend_mel work with steps pending (they are ordered on the engine's stream, and what a request has done is the host's
+        knowledge); with mel requests the step is min(count, headroom) samples, the headroom counted from the frames announced and
+        the samples issued, not from what has arrived.  finished() reports a request once the step carrying its last sample has
+        been collected."""
+        if len(self._pending) >= 2:
+            raise RuntimeError("two steps are pending: collect one (PendingStep.result) before issuing a third")
+        self._use_arrays(True)
+        empty = np.empty(0, dtype=np.int64)
+        if self._mel:
+            count = min(count, self.engine.slotsHeadroom())
+            if count == 0:
+                return PendingStep(self, None, None, 0, empty, empty, empty, [])
+        if self._compact:
+            self.compact()
+        self._admit(count)
+        if self._mel and not self._running:
+            return PendingStep(self, None, None, 0, empty, empty, empty, [])
+        buf = self._last_buf ^ 1      # (never the buffer of a pending step: at most one is pending here, and it was issued last)
+        need = len(self._running) * ((count + 7) & ~7)
+        if self._bufs[buf] is None or self._bufs[buf][0].size < need:
+            keep = self.engine.slotsPinned(max(need, 8), self.pcm)
+            self._bufs_keep[buf] = keep
+            self._bufs[buf] = tuple(a.numpy() if hasattr(a, "numpy") and not isinstance(a, np.ndarray) else a for a in keep)
+        y, pcm = self._bufs_keep[buf]
+        total, pieces, ticket = self.engine.slotsStepRagged(count, y, pcm)
+        self._last_buf = buf
+        self._inflight.clear()
+        slots = pieces["slot"]
+        handles = self._ch[slots]
+        self._left[slots] -= pieces["n"]
+        self._deliv[slots] += pieces["n"]
+        finished = [self._retire(int(col)) for col in slots[pieces["finished"] != 0]]
+        step = PendingStep(self, ticket, buf, total, handles, pieces["offset"].copy(), pieces["n"].astype(np.int64), finished)
+        self._pending.append(step)
+        return step
+
     def finished(self):
         """Handles that have delivered their last sample since the previous call (each exactly once)."""
         done, self._done = self._done, []
         return done
 
     def close(self):
+        for step in list(self._pending):
+            step.result()
         self.engine.slotsEnd()
         if self._owns:
             self.engine.close()

@@ -25,8 +25,19 @@ and reports its rate against the feature-fed slot step (mel_rate_vs_slots).
   with the medians, the run-to-run spread over the rounds (min .. max), the tiles launched, and save / load GB/s against the
   bytes of the blobs (read + written) and against the 128-byte lines the ring side touches (one per 16-byte piece).
 
+--serve times the door a caller uses, at full load and at 1/16 load, per chunk size, cases back to back in one
+process, `--rounds` rounds each (min / median / max of the per-step means):
+  engine      (i)   nvw_slots_step into device buffers, columns restarted as they end: device time per step (events)
+  step        (ii)  SlotStream.step(): wall time per step, requests resubmitted as they finish -- the baseline
+  step_async  (iii) SlotStream.step_async() two deep, the same service: wall time per step
+  delivery    (iv)  the output paths alone over a step's samples (nvw_slots_time_outputs: events around the launches): the PCM
+                    launch + 2-D copies of plain rows to device and to pinned memory, the delivery launch to device and to pinned
+                    memory (direct stores), and the delivery to device + one contiguous copy to pinned memory (staging)
+Prints one JSON line per (load, chunk).
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
+    python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
 """
 import argparse
 import json
@@ -49,7 +60,8 @@ def main():
     ap.add_argument("--mel", action="store_true", help="also time slot steps fed with mel frames (distinct per column)")
     ap.add_argument("--only-mel", action="store_true", help="time the mel-fed slot steps only (e.g. under a profiler)")
     ap.add_argument("--compact", action="store_true", help="time a fragmented batch with and without compaction, moves, saves and loads")
-    ap.add_argument("--rounds", type=int, default=5, help="--compact: rounds of (scattered, compacted) measurements")
+    ap.add_argument("--rounds", type=int, default=5, help="--compact, --serve: rounds of measurements")
+    ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
     args = ap.parse_args()
     import torch
     import bench
@@ -60,6 +72,11 @@ def main():
     Wc, bc = bench.make_cond_layers()
     if args.compact:
         print(json.dumps(time_compact(args, w, Wc, bc)), flush=True)
+        return
+    if args.serve:
+        for load in (B, max(16, B // 16)):
+            for chunk in [int(c) for c in args.chunks.split(",")]:
+                print(json.dumps(time_serve(args, w, Wc, bc, load, chunk)), flush=True)
         return
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
@@ -198,6 +215,162 @@ def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
     del mel
     torch.cuda.empty_cache()
     return ev[0].elapsed_time(ev[1]) / steps, restarts
+
+
+def _stats(v):
+    return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4), "max": round(float(max(v)), 4)}
+
+
+def time_serve(args, w, Wc, bc, load, chunk):
+    """The --serve measurement (module docstring) with `load` utterances in flight on args.batch columns."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.slots import SlotStream
+    B, W = args.batch, args.window
+    T_SRC, LEN_MIN, LEN_MAX = 65536, 8192, 16384
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
+    steps = max(2, 3 * 2048 // chunk // (1 if chunk >= 1024 else 2))      # per round: 3 of 2048, 12 of 256
+    warm = 2
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    res = {"batch": B, "load": load, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
+           "realtime_budget_ms": round(1e3 * chunk / 24000.0, 2), "device": torch.cuda.get_device_name(0)}
+
+    def engine():
+        e = bench.build_engine(w, B, W)
+        e.setConditioningWeights(Wc, bc)
+        e.setSelectorSeed(5)
+        return e
+
+    def window_of(rng, first):
+        length = int(rng.integers(256 if first else LEN_MIN, LEN_MAX))      # (the first wave ends staggered)
+        off = int(rng.integers(0, T_SRC - length))
+        return src[:, off:off + length], length
+
+    # ---- (i) engine level, and (iv) the delivery paths on the same session ----
+    rng = np.random.default_rng(3)
+    e = engine()
+    e.slotsBegin(W)
+    left = np.zeros(B, dtype=np.int64)
+    left[load:] = 1 << 60
+    uid = [0]
+    y = torch.empty(B, chunk, dtype=torch.int32, device="cuda")
+    pcm = torch.empty(B, chunk, dtype=torch.int16, device="cuda")
+    cap = B * ((chunk + 7) & ~7)
+    dev = (torch.empty(cap, dtype=torch.int32, device="cuda"), torch.empty(cap, dtype=torch.int16, device="cuda"))
+    pin = e.slotsPinned(cap)
+    first = [True]
+
+    def restart():
+        for b in np.nonzero(left <= 0)[0]:
+            x, length = window_of(rng, first[0])
+            e.slotStart(int(b), x, uid[0])
+            uid[0] += 1
+            left[b] = length
+        first[0] = False
+
+    def timed(n):
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(n):
+            restart()
+            assert e.slotsStep(chunk, y)
+            left[:load] -= chunk
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / n
+
+    def outputs(is_ragged, ys, ps, reps=3):
+        """ms per pass of the output path alone over the last step's samples (nvw_slots_time_outputs: events around the launches)"""
+        ms = lib.nvw_slots_time_outputs(e._h, 1 if is_ragged else 0, chunk, ys.data_ptr(), ps.data_ptr(), ys.numel(), reps, None)
+        assert ms >= 0
+        return ms / reps
+
+    def staging_copy(total, reps=3):
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(reps):
+            pin[0][:total].copy_(dev[0][:total], non_blocking=True)
+            pin[1][:total].copy_(dev[1][:total], non_blocking=True)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / reps
+
+    timed(warm)
+    rows_pin = (torch.empty(B * chunk, dtype=torch.int32, pin_memory=True), torch.empty(B * chunk, dtype=torch.int16, pin_memory=True))
+    keys = ("plain_rows_to_device", "plain_rows_to_pinned", "ragged_to_device", "ragged_to_pinned_direct", "staging_copy_alone")
+    t = {k: [] for k in keys}
+    t_engine = []
+    total = 0
+    for _ in range(args.rounds):
+        t_engine.append(timed(steps))
+        restart()
+        total, pieces, ticket = e.slotsStepRagged(chunk, *dev)      # (the ragged size of this load, and a step whose rows the passes read)
+        left[:load] -= chunk
+        t["plain_rows_to_device"].append(outputs(False, y.view(-1), pcm.view(-1)))
+        t["plain_rows_to_pinned"].append(outputs(False, *rows_pin))
+        t["ragged_to_device"].append(outputs(True, *dev))
+        t["ragged_to_pinned_direct"].append(outputs(True, *pin))
+        t["staging_copy_alone"].append(staging_copy(total))
+    res["engine_ms_per_step"] = _stats(t_engine)
+    res["output_path_ms"] = {k: _stats(v) for k, v in t.items()}
+    res["output_path_ms"]["ragged_to_device_then_copy_to_pinned"] = _stats([a + b for a, b in zip(t["ragged_to_device"], t["staging_copy_alone"])])
+    res["delivered_bytes_per_step"] = {"plain": B * chunk * 6, "ragged": int(total) * 6}
+    del rows_pin
+    torch.cuda.synchronize()
+    e.slotsEnd()
+    e.close()
+    del y, pcm, dev, pin
+    torch.cuda.empty_cache()
+
+    # ---- (ii) SlotStream.step and (iii) SlotStream.step_async two deep: the same service ----
+    for name in ("step", "step_async"):
+        rng = np.random.default_rng(3)
+        st = SlotStream(engine(), W, pcm=True, owns_engine=True)
+        for _ in range(load):
+            st.submit(window_of(rng, True)[0])
+
+        def resubmit():
+            for _ in st.finished():
+                st.submit(window_of(rng, False)[0])
+
+        rounds = []
+        if name == "step":
+            for r in range(args.rounds + 1):
+                n = warm if r == 0 else steps
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    out = st.step(chunk)
+                    resubmit()
+                torch.cuda.synchronize()
+                if r:
+                    rounds.append(1e3 * (time.perf_counter() - t0) / n)
+        else:
+            pending = st.step_async(chunk)
+            for r in range(args.rounds + 1):
+                n = warm if r == 0 else steps
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    nxt = st.step_async(chunk)
+                    out = pending.result()
+                    int(out.samples[:1].sum())      # (the consumer touches what arrived)
+                    resubmit()
+                    pending = nxt
+                if r:
+                    rounds.append(1e3 * (time.perf_counter() - t0) / n)
+            pending.result()
+        res[name + "_wall_ms_per_step"] = _stats(rounds)
+        st.close()
+        torch.cuda.empty_cache()
+    eng_ms = res["engine_ms_per_step"]["median"]
+    res["step_vs_engine"] = round(res["step_wall_ms_per_step"]["median"] / eng_ms, 4)
+    res["step_async_vs_engine"] = round(res["step_async_wall_ms_per_step"]["median"] / eng_ms, 4)
+    res["step_async_kHz_per_utterance"] = round(chunk / res["step_async_wall_ms_per_step"]["median"], 2)
+    res["engine_kHz_per_utterance"] = round(chunk / eng_ms, 2)
+    return res
 
 
 def time_compact(args, w, Wc, bc):
