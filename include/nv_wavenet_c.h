@@ -318,6 +318,48 @@ int nvw_slot_resume(nvw_engine* e, int slot, const void* state, const void* x, i
 int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* mel, int precision, long long c_stride,
                         long long f_stride, int frames, int final);
 
+/* SLOT MODE: LISTS OF COLUMNS SAVED AND RESUMED, BLOBS IN PINNED MEMORY (additive within ABI 7).  Draining an engine, rebalancing
+ * between engines and checkpointing take many columns at once: one call saves a list of them with one launch, one call resumes a
+ * list after reading every header at once.  The blobs are those of nvw_slot_save, byte for byte, rows of one buffer: blob i at
+ * base + i * stride, base 16-byte aligned, stride a multiple of 16 and at least nvw_slot_state_bytes(e).  The buffer is device
+ * memory or pinned host memory (hipHostMalloc, a registered range, nvw_pinned_alloc, torch pin_memory), which the device writes and
+ * reads in place -- a drained engine's state leaves the GPU without a further copy.  (nvw_slot_save, nvw_slot_resume and
+ * nvw_slot_resume_mel keep refusing host memory.)
+ *   nvw_slots_save_list    the states of the n columns slots[0 .. n) after the steps issued so far, asynchronously on `stream`: one
+ *                          small staging copy of the entries and one launch; never synchronises the stream and waits for nothing
+ *                          queued on it (only a third list save in a row waits, for the first to have completed; the first of a
+ *                          session allocates two small staging buffers on either side, once).  saved[i] = {slot, uid, done, mel != 0 for a mel column}
+ *                          is filled before the call returns, from host state.  The columns go on running.  Returns n; -1 with
+ *                          nothing written and nothing launched when not in slot mode, n outside 1..batch, a slot out of range or
+ *                          listed twice, a slot without an utterance or with a pending start, resume or move, dst NULL, misaligned
+ *                          or pageable host memory, a bad stride.
+ *   nvw_slots_resume_list  n resumes, all or nothing: reqs[i] names the column, the kind (mel != 0: nvw_slot_resume_mel, length =
+ *                          frames, final as there; mel == 0: nvw_slot_resume, length = samples, final ignored), the features / frames
+ *                          (src, precision, c_stride, t_stride) and continues from the blob states + i * stride.  The n headers are
+ *                          read at once: device memory with one blocking 2-D copy on the null stream (the ordering rule of
+ *                          nvw_slot_resume); pinned memory in place, so the save must have completed.  Each request is refused for
+ *                          what nvw_slot_resume / nvw_slot_resume_mel refuse, and also when its column holds an utterance or has a
+ *                          pending start or resume (a list never replaces one) or is named twice.  Any refusal: 0, and the session
+ *                          is exactly as before.  Otherwise n: the next step loads all of them in its one load launch and generates
+ *                          each column's local sample `done`.  The blobs stay unchanged until that step has been issued. */
+typedef struct {
+    int slot;
+    unsigned uid;
+    int done;
+    int mel;
+} nvw_slot_saved;
+int nvw_slots_save_list(nvw_engine* e, const int* slots, int n, void* dst, long long stride, nvw_slot_saved* saved, void* stream);
+typedef struct {
+    int slot;
+    int mel;
+    const void* src;
+    int precision;
+    long long c_stride, t_stride;
+    int length; /* feature columns: samples; mel columns: frames */
+    int final;
+} nvw_slot_resume_req;
+int nvw_slots_resume_list(nvw_engine* e, const nvw_slot_resume_req* reqs, int n, const void* states, long long stride);
+
 /* SLOT MODE: RAGGED DELIVERY, STEPS THAT NEVER BLOCK (additive within ABI 7).  nvw_slots_step copies [batch][count] rows, idle columns
  * and the samples past an utterance's end included, and synchronises when an output is host memory.  A ragged step delivers pieces:
  * one per column that holds an utterance with at least one sample in this step, in ascending column order; a piece's n samples lie

@@ -93,6 +93,8 @@ SIGNATURES = {
     "nvw_slot_save": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_void_p]),
     "nvw_slot_resume": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "nvw_slot_resume_mel": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "nvw_slots_save_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "nvw_slots_resume_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong]),
     "nvw_slots_step_ragged": (C.c_longlong, [C.c_void_p, C.c_int, _fp, _fp, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                              C.POINTER(C.c_ulonglong), C.c_void_p]),
     "nvw_slots_time_outputs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),

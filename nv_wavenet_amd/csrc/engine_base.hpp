@@ -72,6 +72,8 @@ struct nvw_engine {
     virtual int slotSave(int, void*, hipStream_t) = 0;
     virtual bool slotResume(int, const void*, const void*, int, long long, long long, int) = 0;
     virtual bool slotResumeMel(int, const void*, const void*, int, long long, long long, int, int) = 0;
+    virtual int slotsSaveList(const int*, int, void*, long long, nvw_slot_saved*, hipStream_t) = 0;
+    virtual int slotsResumeList(const nvw_slot_resume_req*, int, const void*, long long) = 0;
     virtual long long slotsStepRagged(int, int*, short*, long long, nvw_slot_piece*, int, int*, unsigned long long*, hipStream_t) = 0;
     virtual bool slotsWait(unsigned long long) = 0;
     virtual int slotsDone(unsigned long long) = 0;
@@ -82,6 +84,19 @@ static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_sl
               offsetof(nvw_slot_piece, first) == offsetof(wn::SlotPiece, first) &&
               offsetof(nvw_slot_piece, n) == offsetof(wn::SlotPiece, n) && offsetof(nvw_slot_piece, offset) == offsetof(wn::SlotPiece, offset),
               "nvw_slot_piece is wn::SlotPiece");
+
+static_assert(sizeof(nvw_slot_saved) == sizeof(wn::SlotSaved) && offsetof(nvw_slot_saved, slot) == offsetof(wn::SlotSaved, slot) &&
+              offsetof(nvw_slot_saved, uid) == offsetof(wn::SlotSaved, uid) && offsetof(nvw_slot_saved, done) == offsetof(wn::SlotSaved, done) &&
+              offsetof(nvw_slot_saved, mel) == offsetof(wn::SlotSaved, mel),
+              "nvw_slot_saved is wn::SlotSaved");
+static_assert(sizeof(nvw_slot_resume_req) == sizeof(wn::SlotResumeReq) && offsetof(nvw_slot_resume_req, slot) == offsetof(wn::SlotResumeReq, slot) &&
+              offsetof(nvw_slot_resume_req, mel) == offsetof(wn::SlotResumeReq, mel) && offsetof(nvw_slot_resume_req, src) == offsetof(wn::SlotResumeReq, src) &&
+              offsetof(nvw_slot_resume_req, precision) == offsetof(wn::SlotResumeReq, precision) &&
+              offsetof(nvw_slot_resume_req, c_stride) == offsetof(wn::SlotResumeReq, cStride) &&
+              offsetof(nvw_slot_resume_req, t_stride) == offsetof(wn::SlotResumeReq, tStride) &&
+              offsetof(nvw_slot_resume_req, length) == offsetof(wn::SlotResumeReq, length) &&
+              offsetof(nvw_slot_resume_req, final) == offsetof(wn::SlotResumeReq, final),
+              "nvw_slot_resume_req is wn::SlotResumeReq");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -174,6 +189,12 @@ struct EngineImpl : nvw_engine {
     }
     bool slotResumeMel(int slot, const void* state, const void* mel, int prec, long long cS, long long fS, int frames, int final) override {
         return eng.slotResumeMel(slot, state, mel, prec, cS, fS, frames, final);
+    }
+    int slotsSaveList(const int* slots, int n, void* dst, long long stride, nvw_slot_saved* saved, hipStream_t s) override {
+        return eng.slotsSaveList(slots, n, dst, stride, (wn::SlotSaved*)saved, s);
+    }
+    int slotsResumeList(const nvw_slot_resume_req* reqs, int n, const void* states, long long stride) override {
+        return eng.slotsResumeList((const wn::SlotResumeReq*)reqs, n, states, stride);
     }
     long long slotsStepRagged(int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces, int maxPieces, int* nPieces,
                               unsigned long long* ticket, hipStream_t s) override {

@@ -190,6 +190,13 @@ protected:
     std::vector<char> m_slotMoveEnd;        // per column: 1 source, 2 destination of a pending move
     std::vector<wn::SlotMove> m_slotMoves;  // the pending moves
     wn::SlotLayer* m_slotLayers = NULL;     // the schedule per ring slot on the device (built by the first save or resume)
+    // ... and lists of columns saved in one launch: the entries' staging, made by the first list save
+    wn::SlotSave* m_saveDev[2] = {NULL, NULL};      // [maxBatch] on the device, used by alternate list saves ...
+    wn::SlotSave* m_saveStage[2] = {NULL, NULL};    // ... their pinned host staging ...
+    hipEvent_t m_saveEv[2] = {NULL, NULL};          // ... each reused once the save before last has completed
+    bool m_saveUsed[2] = {false, false};            // (a half that has carried no save yet has nothing to wait for)
+    int m_saveParity = 0;
+    std::vector<int> m_listMark;                    // scratch of the list calls: per column, the index + 1 of the entry that names it
     // ... and ragged delivery (slots_deliver.hpp): a step's valid samples piece by piece, completion by ticket
     static constexpr int kSlotTickets = 4;  // events kept: a ticket older than that is complete (the stream is ordered)
     wn::DeliverPiece* m_dlvDev = NULL;      // [maxBatch] on the device: the pieces of the step being delivered
@@ -1479,9 +1486,7 @@ public:
     // non-positive strides or length; or the column is the destination of a pending move (the start would silently drop the
     // utterance on its way in: stop it, or step first).
     bool slotStart(int slot, const void* x, int precision, long long cStride, long long tStride, int length, unsigned uid) {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
-            tStride <= 0 || length <= 0 || !isDevicePtr(x) || m_slotMoveEnd[slot] == 2)
-            return false;
+        if (!slotStartOk(slot, x, precision, cStride, tStride, length)) return false;
         slotDropMel(slot);
         slotDropResume(slot);
         wn::SlotDesc& d = m_slotHost[slot];
@@ -1512,10 +1517,7 @@ public:
     // non-device mel, bad precision, non-positive strides, frames < 0, 0 frames of a final utterance, or the column is the destination
     // of a pending move.
     bool slotStartMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
-        if (m_slotW <= 0 || m_upStride <= 0 || slot < 0 || slot >= m_maxBatch || mel == NULL || (precision != 32 && precision != 16) ||
-            cStride <= 0 || fStride <= 0 || frames < 0 || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL ||
-            !isDevicePtr(mel) || m_slotMoveEnd[slot] == 2)
-            return false;
+        if (!slotStartMelOk(slot, mel, precision, cStride, fStride, frames, final)) return false;
         if (!m_melDesc) melAllocate();
         slotDropResume(slot);
         wn::MelDesc& d = m_melHost[slot];
@@ -1582,13 +1584,7 @@ public:
         const bool mel = m_melHost[slot].state != 0;
         const long long start = mel ? m_melHost[slot].start : m_slotHost[slot].start, done = m_slotCounter - start;
         if (done < 0 || done > 0x7fffffffLL) return -1;
-        wn::SlotStateHeader h = {};
-        h.magic = wn::kSlotStateMagic;
-        h.version = wn::kSlotStateVersion;
-        h.precision = F16 ? 16 : 32;
-        h.R = R;
-        h.numLayers = m_numLayers;
-        h.maxDilation = m_maxDilation;
+        wn::SlotStateHeader h = slotHeaderCommon();
         h.done = (int)done;
         h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
         if (!wn::slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur))
@@ -1620,6 +1616,98 @@ public:
         m_slotResume[slot] = state;
         m_slotResumeDone[slot] = h.done;
         return true;
+    }
+    // ---- lists of columns ----
+    // slotSave for the n columns slots[0 .. n): blob i at dst + i * stride, ONE launch after one small staging copy, asynchronously on
+    // `stream`; never synchronises the stream and waits for nothing already queued on it: the entries go through two staging
+    // halves, each released by an event recorded behind its launch, so only a third list save in a row waits -- for the first to
+    // have completed.  The first list save of a session allocates the halves (two small device and two pinned host buffers, once).  dst: 16-byte aligned device memory or pinned host memory (mapped as the outputs of slotsStepRagged);
+    // stride: a multiple of 16, at least slotStateBytes().  saved[i] is filled before the call returns, from host state.  The columns
+    // go on running.  Returns n; -1 with nothing written and nothing launched: not in slot mode, n outside 1..maxBatch, a slot out of
+    // range or listed twice, a slot without an utterance or with a pending start, resume or move, a bad dst or stride.
+    int slotsSaveList(const int* slots, int n, void* dst, long long stride, wn::SlotSaved* saved, hipStream_t stream = 0) {
+        if (m_slotW <= 0 || slots == NULL || saved == NULL || n < 1 || n > m_maxBatch) return -1;
+        bool pinned = false;
+        char* const out = (char*)slotBlobRange(dst, n, stride, &pinned);
+        if (out == NULL) return -1;
+        m_listMark.assign(m_maxBatch, 0);
+        for (int i = 0; i < n; i++) {
+            const int b = slots[i];
+            if (b < 0 || b >= m_maxBatch || m_listMark[b] || !slotHolds(b) || m_slotPending[b] == 1 || m_slotMoveEnd[b]) return -1;
+            m_listMark[b] = i + 1;
+            const bool mel = m_melHost[b].state != 0;
+            const long long done = m_slotCounter - (mel ? m_melHost[b].start : m_slotHost[b].start);
+            if (done < 0 || done > 0x7fffffffLL) return -1;
+        }
+        if (!m_saveDev[0])
+            for (int i = 0; i < 2; i++) {
+                gpuErrChk(hipMalloc((void**)&m_saveDev[i], (size_t)m_maxBatch * sizeof(wn::SlotSave)));
+                gpuErrChk(hipHostMalloc((void**)&m_saveStage[i], (size_t)m_maxBatch * sizeof(wn::SlotSave), hipHostMallocDefault));
+                gpuErrChk(hipEventCreateWithFlags(&m_saveEv[i], hipEventDisableTiming));
+                m_saveUsed[i] = false;
+            }
+        const wn::SlotLayer* const layers = slotLayers();
+        const int at = m_saveParity;
+        if (m_saveUsed[at]) gpuErrChk(hipEventSynchronize(m_saveEv[at]));
+        m_saveUsed[at] = true;
+        wn::SlotSave* const stage = m_saveStage[at];
+        for (int i = 0; i < n; i++) {
+            const int b = slots[i];
+            const bool mel = m_melHost[b].state != 0;
+            const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
+            const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
+            const int done = (int)(m_slotCounter - start);
+            stage[i] = wn::SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid};
+            saved[i] = wn::SlotSaved{b, uid, done, mel ? 1 : 0};
+        }
+        gpuErrChk(hipMemcpyAsync(m_saveDev[at], stage, (size_t)n * sizeof(wn::SlotSave), hipMemcpyHostToDevice, stream));
+        const bool ok = wn::slots_save_list(stream, m_saveDev[at], n, slotHeaderCommon(), layers, m_ring, m_ringSlots, ringFragsPerSlot(),
+                                            m_yInPrev, m_yInCur);
+        gpuErrChk(hipEventRecord(m_saveEv[at], stream));
+        m_saveParity ^= 1;
+        return ok ? n : -1;
+    }
+    // slotResume / slotResumeMel for n requests at once, all or nothing: the blob of reqs[i] is states + i * stride (memory and stride
+    // as for slotsSaveList).  The n headers are read at once -- device memory: one blocking 2-D copy on the null stream (the ordering
+    // rule of slotResume); pinned memory: in place, so the save must have completed -- and checked as slotResume checks them; each
+    // request is then refused for what slotResume / slotResumeMel refuse, and also when its column holds an utterance or has a
+    // pending start or resume (a list never replaces one), or is named twice.  Any refusal: 0, and the session is exactly as before.
+    // Otherwise n: every column has its pending resume, loaded by the next step in its one slot_load_kernel launch.  The blobs stay
+    // unchanged until that step has been issued.
+    int slotsResumeList(const wn::SlotResumeReq* reqs, int n, const void* states, long long stride) {
+        if (m_slotW <= 0 || reqs == NULL || n < 1 || n > m_maxBatch) return 0;
+        bool pinned = false;
+        const char* const dev = (const char*)slotBlobRange(states, n, stride, &pinned);
+        if (dev == NULL) return 0;
+        std::vector<wn::SlotStateHeader> hdr(n);
+        if (pinned)
+            for (int i = 0; i < n; i++) memcpy(&hdr[i], (const char*)states + (size_t)i * (size_t)stride, sizeof(wn::SlotStateHeader));
+        else
+            gpuErrChk(hipMemcpy2D(hdr.data(), sizeof(wn::SlotStateHeader), states, (size_t)stride, sizeof(wn::SlotStateHeader), n,
+                                  hipMemcpyDeviceToHost));
+        m_listMark.assign(m_maxBatch, 0);
+        for (int i = 0; i < n; i++) {
+            const wn::SlotResumeReq& q = reqs[i];
+            const wn::SlotStateHeader& h = hdr[i];
+            if (!slotHeaderOk(h)) return 0;
+            if (q.mel ? !slotStartMelOk(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, q.final)
+                      : !slotStartOk(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length))
+                return 0;
+            if (q.mel ? (q.final && h.done >= (long long)q.length * m_upStride) : h.done >= q.length) return 0;
+            if (m_listMark[q.slot] || slotHolds(q.slot) || m_slotPending[q.slot] == 1) return 0;
+            m_listMark[q.slot] = i + 1;
+        }
+        slotLayers();
+        for (int i = 0; i < n; i++) {
+            const wn::SlotResumeReq& q = reqs[i];
+            const bool ok = q.mel ? slotStartMel(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, q.final, hdr[i].uid)
+                                  : slotStart(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, hdr[i].uid);
+            assert(ok);
+            (void)ok;
+            m_slotResume[q.slot] = dev + (size_t)i * (size_t)stride;
+            m_slotResumeDone[q.slot] = hdr[i].done;
+        }
+        return n;
     }
     // The largest count the next step accepts: W, or the fewest samples a non-final mel column has frames for beyond its next
     // sample (0 when one has none).
@@ -1720,12 +1808,13 @@ public:
     // ---- ragged delivery (slots_deliver.hpp) ----
     // The address the device stores through for an output of slotsStepRagged: the pointer itself for device memory, the mapped
     // address for pinned host memory (hipHostMalloc, hipHostRegister); NULL for anything else (pageable host memory).
-    static void* deliverTarget(void* p) {
+    static void* deliverTarget(void* p, bool* pinned = NULL) {
         hipPointerAttribute_t attr;
         if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
             (void)hipGetLastError();
             return NULL;
         }
+        if (pinned) *pinned = attr.type == hipMemoryTypeHost;
         if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return p;
         if (attr.type != hipMemoryTypeHost) return NULL;
         void* d = NULL;
@@ -1906,6 +1995,16 @@ public:
         }
         gpuErrChk(hipFree(m_dlvDev));
         m_dlvDev = NULL;
+        for (int i = 0; i < 2 && m_saveDev[i]; i++) {
+            gpuErrChk(hipFree(m_saveDev[i]));
+            gpuErrChk(hipHostFree(m_saveStage[i]));
+            gpuErrChk(hipEventDestroy(m_saveEv[i]));
+            m_saveDev[i] = NULL;
+            m_saveStage[i] = NULL;
+            m_saveEv[i] = NULL;
+            m_saveUsed[i] = false;
+        }
+        m_saveParity = 0;
         for (int i = 0; i < kSlotTickets; i++) {
             gpuErrChk(hipHostFree(m_dlvStage[i]));
             gpuErrChk(hipEventDestroy(m_dlvEv[i]));
@@ -2016,6 +2115,40 @@ protected:
     size_t slotUpdBytes() const { return slotColOff() + (size_t)m_maxBatch * sizeof(int); }
     int ringFragsPerSlot() const { return (int)(R * 16 * sizeof(elem) / 1024); }
     bool slotHolds(int slot) const { return m_slotHost[slot].active || m_melHost[slot].state; }
+    // what slotStart / slotStartMel refuse (shared with slotsResumeList, which checks every request before it changes anything)
+    bool slotStartOk(int slot, const void* x, int precision, long long cStride, long long tStride, int length) const {
+        return !(m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
+                 tStride <= 0 || length <= 0 || !isDevicePtr(x) || m_slotMoveEnd[slot] == 2);
+    }
+    bool slotStartMelOk(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final) const {
+        return !(m_slotW <= 0 || m_upStride <= 0 || slot < 0 || slot >= m_maxBatch || mel == NULL || (precision != 32 && precision != 16) ||
+                 cStride <= 0 || fStride <= 0 || frames < 0 || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL ||
+                 !isDevicePtr(mel) || m_slotMoveEnd[slot] == 2);
+    }
+    bool slotHeaderOk(const wn::SlotStateHeader& h) const {
+        return h.magic == wn::kSlotStateMagic && h.version == wn::kSlotStateVersion && h.precision == (F16 ? 16 : 32) && h.R == R &&
+               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0;
+    }
+    // the fields of a blob's header that every blob of this engine shares
+    wn::SlotStateHeader slotHeaderCommon() const {
+        wn::SlotStateHeader h = {};
+        h.magic = wn::kSlotStateMagic;
+        h.version = wn::kSlotStateVersion;
+        h.precision = F16 ? 16 : 32;
+        h.R = R;
+        h.numLayers = m_numLayers;
+        h.maxDilation = m_maxDilation;
+        return h;
+    }
+    // n blobs of `stride` bytes from `base`: 16-byte aligned device memory (-> base) or mapped pinned host memory (-> its device-side
+    // address; *pinned set), the last blob in the same range as the first; NULL for anything else or a bad stride
+    void* slotBlobRange(const void* base, int n, long long stride, bool* pinned) const {
+        if (base == NULL || ((size_t)base & 15) != 0 || (stride & 15) != 0 || stride < (long long)slotStateBytes()) return NULL;
+        char* const first = (char*)deliverTarget((void*)base, pinned);
+        const size_t span = (size_t)(n - 1) * (size_t)stride;
+        if (first == NULL || (char*)deliverTarget((char*)base + span + slotStateBytes() - 16) != first + span + slotStateBytes() - 16) return NULL;
+        return first;
+    }
     void slotDropResume(int slot) {
         m_slotResume[slot] = NULL;
         m_slotResumeDone[slot] = 0;
@@ -2049,8 +2182,7 @@ protected:
     bool slotStateHeader(const void* state, wn::SlotStateHeader& h) const {
         if (state == NULL || ((size_t)state & 15) != 0 || !isDevicePtr(state)) return false;
         gpuErrChk(hipMemcpy(&h, state, sizeof(h), hipMemcpyDeviceToHost));
-        return h.magic == wn::kSlotStateMagic && h.version == wn::kSlotStateVersion && h.precision == (F16 ? 16 : 32) && h.R == R &&
-               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0;
+        return slotHeaderOk(h);
     }
     // the pending moves -> pinned staging -> device, then one slot_move_kernel launch (staging halves as slotApplyPending)
     bool slotApplyMoves(hipStream_t stream) {

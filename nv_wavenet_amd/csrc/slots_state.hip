@@ -1,5 +1,5 @@
-// slots_state.hip -- the kernels that take a column's state out of a column and put it into another (slots_state.hpp): move, save,
-// load.  Compiled once, both precisions.  Bandwidth kernels over the pieces slot_reset_kernel zeroes: piece r of a column is lanes
+// slots_state.hip -- the kernels that take a column's state out of a column and put it into another (slots_state.hpp): move, save
+// (one column, a list), load.  Compiled once, both precisions.  Bandwidth kernels over the pieces slot_reset_kernel zeroes: piece r of a column is lanes
 // 16g + j (g = r & 3) of fragment r >> 2 of its tile's ring, 16 bytes in a 128-byte line of its own (8 columns share a line, the
 // four pieces of a fragment are 256 bytes apart) -- the ring side of every copy is strided whatever the thread order, so the
 // threads walk the pieces in blob order and the blob side is one contiguous run of 16-byte vector accesses per wave.
@@ -72,6 +72,34 @@ __global__ __launch_bounds__(256) void slot_save_kernel(uintx4* __restrict__ blo
     }
 }
 
+// Column save for a list: slot_save_kernel per entry, blockIdx.y striding over the entries (the grid of slot_load_kernel).  The common
+// header fields are one argument, done and uid come from the entry; every destination is device memory or the device-side address
+// of mapped pinned host memory -- the blob side stays contiguous 16-byte stores either way.
+__global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __restrict__ saves, int nSaves, SlotStateHeader hdr,
+                                                             const SlotLayer* __restrict__ layers, const uintx4* __restrict__ ring,
+                                                             int ringSlots, int pshift, const int* __restrict__ yInPrev,
+                                                             const int* __restrict__ yInCur) {
+    const int per = ringSlots << pshift;
+    for (int c = blockIdx.y; c < nSaves; c += gridDim.y) {
+        const SlotSave sv = saves[c];
+        const uintx4* const src = ring + (size_t)(sv.column >> 4) * ((size_t)per * 16) + (sv.column & 15);
+        uintx4* const out = (uintx4*)sv.dst + sizeof(SlotStateHeader) / 16;
+        for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < per; r += gridDim.x * blockDim.x) {
+            const int s = r >> pshift, q = r & ((1 << pshift) - 1);
+            const SlotLayer l = layers[s];
+            out[r] = src[ring_piece(l.x + ((s - l.x + sv.rot) & (l.y - 1)), q, pshift)];
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            SlotStateHeader h = hdr;
+            h.done = sv.done;
+            h.uid = sv.uid;
+            h.yInPrev = yInPrev[sv.column];
+            h.yInCur = yInCur[sv.column];
+            *(SlotStateHeader*)sv.dst = h;
+        }
+    }
+}
+
 // Column load: blockIdx.y walks the resumed columns; the inverse of the save -- blob piece (s, q) -> ring slot
 // off + ((s - off + rot') & (d - 1)) -- and the history from the header.  Every piece of the column is written.
 __global__ __launch_bounds__(256) void slot_load_kernel(const SlotLoad* __restrict__ loads, int nLoads, const SlotLayer* __restrict__ layers,
@@ -121,6 +149,16 @@ bool slots_save(hipStream_t stream, void* dst, SlotStateHeader hdr, int column, 
     if (pshift < 0) return false;
     hipLaunchKernelGGL(slot_save_kernel, dim3(gridOf(ringSlots << pshift, 64)), dim3(256), 0, stream, (uintx4*)dst, hdr, column, rot, layers,
                        (const uintx4*)ring, ringSlots, pshift, yInPrev, yInCur);
+    return hipGetLastError() == hipSuccess;
+}
+
+bool slots_save_list(hipStream_t stream, const SlotSave* saves, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
+                     int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur) {
+    const int pshift = pieceShift(fragsPerSlot);
+    if (pshift < 0) return false;
+    if (nSaves <= 0) return true;
+    hipLaunchKernelGGL(slot_save_list_kernel, dim3(gridOf(ringSlots << pshift, 64), nSaves > 1024 ? 1024 : nSaves), dim3(256), 0, stream, saves,
+                       nSaves, hdr, layers, (const uintx4*)ring, ringSlots, pshift, yInPrev, yInCur);
     return hipGetLastError() == hipSuccess;
 }
 

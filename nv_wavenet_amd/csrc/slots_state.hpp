@@ -50,6 +50,34 @@ struct SlotLoad {
     int rot;
 };
 static_assert(sizeof(SlotLoad) == 16, "SlotLoad layout");
+// one saved column of a list: where its blob goes (device memory, or the device-side address of mapped pinned host memory), the
+// rotation start mod (largest dilation), and the two header fields that differ per column
+struct SlotSave {
+    void* dst;
+    int column;
+    int rot;
+    int done;
+    unsigned uid;
+};
+static_assert(sizeof(SlotSave) == 24, "SlotSave layout");
+
+// what the host reports per column of a list save, and one request of a list resume (nvw_slot_saved, nvw_slot_resume_req)
+struct SlotSaved {
+    int slot;
+    unsigned uid;
+    int done;
+    int mel;
+};
+struct SlotResumeReq {
+    int slot;
+    int mel;                 // 0: features (slotResume), != 0: mel frames (slotResumeMel)
+    const void* src;
+    int precision;
+    long long cStride, tStride;
+    int length;              // feature columns: samples; mel columns: frames
+    int final;               // mel columns only
+};
+static_assert(sizeof(SlotResumeReq) == 48, "SlotResumeReq layout");
 
 // nMoves (from, to) pairs -- sources pairwise distinct, destinations pairwise distinct, no destination a source --: ring share,
 // history and descriptors (mel: NULL when the session has no mel columns) of `from` into `to`; `from` goes idle.  Asynchronous.
@@ -59,6 +87,10 @@ bool slots_move(hipStream_t stream, const SlotMove* moves, int nMoves, void* rin
 // with its header (hdr: everything but the history, which the kernel reads).  Asynchronous.
 bool slots_save(hipStream_t stream, void* dst, SlotStateHeader hdr, int column, int rot, const SlotLayer* layers, const void* ring,
                 int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur);
+// slots_save for nSaves columns in one launch: entry i's column into entry i's dst, hdr = the fields every blob shares (done, uid and
+// the history are filled per entry).  The destinations are pairwise disjoint.  Asynchronous.
+bool slots_save_list(hipStream_t stream, const SlotSave* saves, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
+                     int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur);
 // The nLoads blobs into their columns with the inverse rotation; the history from their headers.  Asynchronous.
 bool slots_load(hipStream_t stream, const SlotLoad* loads, int nLoads, const SlotLayer* layers, void* ring, int ringSlots,
                 int fragsPerSlot, int* yInPrev, int* yInCur);

@@ -363,6 +363,24 @@ int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* 
     }
     return 1;
 }
+// ---- slot mode: lists of columns saved and resumed (additive within ABI 7) --------------------------------------------------------
+int nvw_slots_save_list(nvw_engine* e, const int* slots, int n, void* dst, long long stride, nvw_slot_saved* saved, void* stream) {
+    const int got = e->slotsSaveList(slots, n, dst, stride, saved, (hipStream_t)stream);
+    if (got < 0)
+        fprintf(stderr, "nvw_slots_save_list: refused (nvw_slots_begin first; %d slots of %d, each once: running columns without a pending "
+                "start, resume or move; dst 16-byte aligned device or pinned memory; stride %lld a multiple of 16, at least %zu)\n", n,
+                e->maxBatch(), stride, e->slotStateBytes());
+    return got;
+}
+int nvw_slots_resume_list(nvw_engine* e, const nvw_slot_resume_req* reqs, int n, const void* states, long long stride) {
+    const int got = e->slotsResumeList(reqs, n, states, stride);
+    if (got != n || n < 1)
+        fprintf(stderr, "nvw_slots_resume_list: refused, nothing changed (%d requests of %d columns, each column once, idle and without a "
+                "pending start; states of nvw_slot_save / nvw_slots_save_list for this shape and precision in device or pinned memory, "
+                "stride %lld a multiple of 16, at least %zu; otherwise as nvw_slot_resume / nvw_slot_resume_mel)\n", n, e->maxBatch(),
+                stride, e->slotStateBytes());
+    return got;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

@@ -13,6 +13,12 @@ from ._lib import lib, addr, CONSUME_FN
 # nvw_slot_piece of include/nv_wavenet_c.h: one delivered piece of a ragged slot step
 SLOT_PIECE = np.dtype([("slot", "<i4"), ("uid", "<u4"), ("first", "<i8"), ("n", "<i4"), ("finished", "<i4"), ("offset", "<i8")])
 assert SLOT_PIECE.itemsize == 32
+# ... nvw_slot_saved and nvw_slot_resume_req of nvw_slots_save_list / nvw_slots_resume_list
+SLOT_SAVED = np.dtype([("slot", "<i4"), ("uid", "<u4"), ("done", "<i4"), ("mel", "<i4")])
+SLOT_RESUME_REQ = np.dtype({"names": ["slot", "mel", "src", "precision", "c_stride", "t_stride", "length", "final"],
+                            "formats": ["<i4", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<i4"],
+                            "offsets": [0, 4, 8, 16, 24, 32, 40, 44], "itemsize": 48})
+assert SLOT_SAVED.itemsize == 16
 
 
 class Impl:
@@ -500,6 +506,58 @@ class WavenetEngine:
                                                                                  mel.stride(0), mel.stride(1), n, 1 if final else 0):
             raise ValueError("nvw_slot_resume_mel refused slot %d" % slot)
         self._slot_keep[int(slot)] = (mel, state)
+
+    # ---- ... lists of columns saved and resumed at once, blobs on the GPU or in pinned memory ----
+    def slotsSaveList(self, slots, pinned=False, stream=None, out=None):
+        """The states of the columns `slots` after the steps issued so far, with one launch: (blobs, saved).  blobs = a uint8 tensor
+        [n][stride] on the GPU, or in pinned host memory (pinned=True: the device writes it in place), row i the blob of slots[i]
+        (stride = slotStateBytes(), which is a multiple of 16); out = a buffer of that kind the caller keeps -- a drain buffer
+        allocated once, a registered range -- to write into instead of a new one ([>= n][stride >= slotStateBytes()], stride a
+        multiple of 16).  saved = a numpy structured array (SLOT_SAVED: slot, uid, done, mel), known at once.  Asynchronous on `stream` (the
+        stream of the steps): the blobs hold the states once the stream has got there -- torch.cuda.synchronize(), or any later
+        blocking call, before the host reads a pinned buffer.  The columns go on running.  ValueError when refused (nothing
+        written): see nvw_slots_save_list."""
+        import torch
+        idx = np.ascontiguousarray(np.asarray(list(slots), dtype=np.int32))
+        n = int(idx.size)
+        if out is None:
+            out = torch.empty((max(n, 1), self.slotStateBytes()), dtype=torch.uint8, device=None if pinned else "cuda", pin_memory=bool(pinned))
+        assert out.dtype == torch.uint8 and out.dim() == 2 and out.stride(1) == 1 and out.size(0) >= n and (out.is_cuda or out.is_pinned()), \
+            "out: a uint8 CUDA or pinned tensor [>= n][stride]"
+        saved = np.zeros(max(n, 1), dtype=SLOT_SAVED)
+        got = lib.nvw_slots_save_list(self._h, idx.ctypes.data, n, out.data_ptr(), out.stride(0), saved.ctypes.data, stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_slots_save_list refused %d slots" % n)
+        return out[:n], saved[:n]
+
+    def slotsResumeList(self, slots, blobs, sources, lengths_or_frames=None, finals=None):
+        """slotResume / slotResumeMel for many columns at once, all or nothing: column slots[i] continues from row i of `blobs` (a
+        uint8 tensor [n][stride] of slotsSaveList, on the GPU or pinned; a pinned one is read in place and its save must have
+        completed) with sources[i], its whole features [n_cond][T] -- or its mel frames, where finals[i] is True or False (None: a
+        feature column); lengths_or_frames[i] = samples / frames written (None: all of the tensor).  ValueError when any request is
+        refused (the session is as before): see nvw_slots_resume_list.  `blobs` and the sources are kept until the columns start
+        again."""
+        import torch
+        slots = [int(c) for c in slots]
+        n = len(slots)
+        assert blobs.dtype == torch.uint8 and blobs.dim() == 2 and blobs.stride(1) == 1 and blobs.size(0) >= n and \
+            (blobs.is_cuda or blobs.is_pinned()), "blobs: a uint8 CUDA or pinned tensor [n][stride]"
+        assert len(sources) == n and blobs.size(1) >= self.slotStateBytes()
+        reqs = np.zeros(max(n, 1), dtype=SLOT_RESUME_REQ)
+        for i, (col, x) in enumerate(zip(slots, sources)):
+            assert hasattr(x, "data_ptr") and x.is_cuda and x.dim() == 2 and x.size(0) == self.nCond, "sources: CUDA tensors [n_cond][...]"
+            bits = {torch.float32: 32, torch.float16: 16}.get(x.dtype)
+            assert bits, "sources must be float32 or float16"
+            final = finals[i] if finals is not None else None
+            count = lengths_or_frames[i] if lengths_or_frames is not None else None
+            count = x.size(1) if count is None else int(count)
+            assert 0 <= count <= x.size(1)
+            reqs[i] = (col, 0 if final is None else 1, x.data_ptr(), bits, x.stride(0), x.stride(1), count, 1 if final else 0)
+        got = lib.nvw_slots_resume_list(self._h, reqs.ctypes.data, n, blobs.data_ptr(), blobs.stride(0))
+        if got != n or n == 0:
+            raise ValueError("nvw_slots_resume_list refused %d requests" % n)
+        for col, x in zip(slots, sources):
+            self._slot_keep[col] = (x, blobs)
 
     def slotsEnd(self):
         lib.nvw_slots_end(self._h)

@@ -34,6 +34,17 @@ suspend is not delivered again.
     state = stream.suspend(h)                           # a SlotState: the blob, the source tensor, uid, samples done
     h2 = other_stream.resume(state)                     # goes on at sample state.done
 
+Draining an engine, rebalancing and checkpointing take many requests at once (nvw_slots_save_list /
+nvw_slots_resume_list): suspend_many() saves all the running ones among its handles with one launch into the rows of one buffer --
+on the GPU, or in pinned host memory, which the device writes in place --, drain() does so for everything the stream holds, and
+resume_many() puts a list of states back, which the admitting step hands to the engine in one call per buffer.  A state can leave the
+process: to_bytes() is a small record and the blob, from_bytes() the way back (the source tensor is the caller's to hand over again).
+
+    states = stream.drain(pinned=True)                  # every request, running ones first; the stream is empty afterwards
+    data = [st.to_bytes() for st in states]             # ... to a file, to another process
+    back = [SlotState.from_bytes(d, src, pinned=True) for d, src in zip(data, sources)]
+    handles = other_stream.resume_many(back)            # at the front of the queue, in this order
+
 step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
 (DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
 owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
@@ -52,6 +63,7 @@ start or end in it.  Two steps may be pending: the GPU generates step k + 1 whil
         pending = nxt                                                  # (None while the stream is idle)
 """
 import heapq
+import struct
 from collections import deque
 
 import numpy as np
@@ -71,8 +83,59 @@ class SlotState:
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
     frames, final = of a mel request (frames written so far, no more to come)."""
 
-    def __init__(self, blob, source, uid, done, kind, frames=None, final=None):
+    # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
+    RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
+    RECORD_BYTES = RECORD.size
+    RECORD_MAGIC, RECORD_VERSION = b"NWSS", 1
+    BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid
+
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0):
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
+        # the blob as a row of a buffer that SlotStream hands to slotsResumeList (suspend_many, drain, from_bytes(pinned=True));
+        # None: a blob of its own -- a CUDA tensor of suspend(), resumed by slotResume, or a CPU tensor of from_bytes(), uploaded
+        self.buffer, self.row = buffer, row
+
+    def to_bytes(self):
+        """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
+        tensor is not included.  A blob on the GPU is copied to the host here -- a synchronising copy --, and for a pinned blob
+        the call waits for the device to have written it."""
+        blob = b""
+        if self.blob is not None:
+            if getattr(self.blob, "is_cuda", False):
+                blob = self.blob.cpu().numpy().tobytes()
+            else:
+                if self.blob.is_pinned():
+                    import torch
+                    torch.cuda.synchronize()
+                blob = self.blob.numpy().tobytes()
+        mel = self.kind == "mel"
+        return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
+                                1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob
+
+    @classmethod
+    def from_bytes(cls, data, source, pinned=False):
+        """The state of to_bytes(), with its source tensor (features or mel frames) handed over again.  pinned=True: the blob in
+        pinned host memory, which the engine reads in place when the request is admitted (a buffer of its own: one engine call
+        per such state); False: a CPU tensor, which the stream uploads then, together with the others of the step (one call).  ValueError for data that is truncated or not a state."""
+        import torch
+        data = bytes(data)
+        if len(data) < cls.RECORD_BYTES:
+            raise ValueError("a SlotState record is %d bytes, got %d" % (cls.RECORD_BYTES, len(data)))
+        magic, version, kind, frames, final, uid, done, nblob = cls.RECORD.unpack_from(data)
+        if magic != cls.RECORD_MAGIC or version != cls.RECORD_VERSION or kind not in (0, 1):
+            raise ValueError("not a SlotState record (magic %r, version %d, kind %d)" % (magic, version, kind))
+        if len(data) != cls.RECORD_BYTES + nblob or (nblob and (nblob < 64 or nblob % 16)):
+            raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
+        blob = buffer = None
+        if nblob:
+            words = np.frombuffer(data, dtype="<u4", count=16, offset=cls.RECORD_BYTES)
+            if int(words[0]) != cls.BLOB_MAGIC or int(words[6]) != done or int(words[7]) != uid:
+                raise ValueError("the blob's header does not belong to the record (magic %#x, done %d, uid %d)" % tuple(words[[0, 6, 7]]))
+            host = torch.empty((1, nblob), dtype=torch.uint8, pin_memory=bool(pinned))
+            host[0].numpy()[:] = np.frombuffer(data, dtype=np.uint8, count=nblob, offset=cls.RECORD_BYTES)
+            blob, buffer = host[0], host if pinned else None
+        mel = kind == 1
+        return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0)
 
 
 class StepOutput:
@@ -255,18 +318,26 @@ class SlotStream:
         for i, item in enumerate(self._queue):
             if item[0] == handle:
                 del self._queue[i]
-                req = item[3]
-                if req is not None:
-                    del self._mel[handle]
-                if len(item) > 4:
-                    if req is not None:
-                        item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
-                    return item[4]
-                return SlotState(None, item[1], item[2], 0, "features") if req is None else SlotState(None, item[1], item[2], 0, "mel", req[0], req[1])
+                return self._dequeued(item)
         col = self.running()[handle]
         if col in self._inflight:
             raise RuntimeError("request %d is being moved to column %d: step once before suspending it" % (handle, col))
         blob, done = self.engine.slotSave(col)      # (first: a refusal leaves the stream as it was)
+        return self._stopped(handle, col, blob, done)
+
+    def _dequeued(self, item):
+        """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
+        handle, req = item[0], item[3]
+        if req is not None:
+            del self._mel[handle]
+        if len(item) > 4:
+            if req is not None:
+                item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
+            return item[4]
+        return SlotState(None, item[1], item[2], 0, "features") if req is None else SlotState(None, item[1], item[2], 0, "mel", req[0], req[1])
+
+    def _stopped(self, handle, col, blob, done, buffer=None, row=0):
+        """Stops the saved request of column `col` and frees the column; its state."""
         self.engine.slotStop(col)
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
@@ -275,16 +346,73 @@ class SlotStream:
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features")
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row)
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1])
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row)
+
+    def suspend_many(self, handles=None, pinned=False):
+        """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
+        save for the running ones among them: their blobs are the rows of one buffer -- on the GPU, or with pinned=True in pinned
+        host memory, written in place by the device (complete once the stream has got there: to_bytes() waits for it).  Queued
+        requests are dequeued as suspend() does.  Returns the SlotStates in the order of `handles`.  KeyError for a handle the
+        stream does not hold, ValueError for one named twice, RuntimeError if one is being moved by a compact() whose step has not
+        been issued -- all before anything has changed.  Works with steps pending, as suspend() does."""
+        running = self.running()
+        queued = {item[0]: item for item in self._queue}
+        if handles is None:
+            handles = sorted(running) + sorted(queued)
+        handles = [int(h) for h in handles]
+        if len(set(handles)) != len(handles):
+            raise ValueError("a handle is named twice")
+        for h in handles:
+            if h not in running and h not in queued:
+                raise KeyError(h)
+            if h in running and running[h] in self._inflight:
+                raise RuntimeError("request %d is being moved to column %d: step once before suspending it" % (h, running[h]))
+        saving = [h for h in handles if h in running]
+        states = {}
+        if saving:
+            cols = [running[h] for h in saving]
+            blobs, saved = self.engine.slotsSaveList(cols, pinned=pinned)      # (first: a refusal leaves the stream as it was)
+            for i, (h, col) in enumerate(zip(saving, cols)):
+                states[h] = self._stopped(h, col, blobs[i], int(saved["done"][i]), blobs, i)
+        if len(saving) < len(handles):
+            self._queue = deque(item for item in self._queue if item[0] not in set(handles))
+            for h in handles:
+                if h in queued:
+                    states[h] = self._dequeued(queued[h])
+        return [states[h] for h in handles]
+
+    def drain(self, pinned=False):
+        """Suspends everything the stream holds (suspend_many(None)): the running requests in handle order, then the queued ones in
+        handle order.  Afterwards busy() is false and every column is free (the stops are applied by the next step, or dropped by
+        close())."""
+        return self.suspend_many(None, pinned=pinned)
+
+    def resume_many(self, states):
+        """resume() for a list: the states go to the FRONT of the queue in the order given; returns their handles in that order.
+        Every blob's size is checked before any state is queued (ValueError, nothing changed).  States whose blobs are rows of
+        one buffer (suspend_many, drain) and that a step admits together reach the engine in ONE call, and so do the CPU blobs of
+        from_bytes(pinned=False), uploaded together; a from_bytes(pinned=True) state is a pinned buffer of its own, read in
+        place, and costs an engine call each -- after a trip through bytes, pinned=False is the path that batches."""
+        states = list(states)
+        for state in states:
+            if hasattr(state.blob, "numel") and state.blob.numel() != self.engine.slotStateBytes():
+                raise ValueError("a state of %d bytes, this engine's are %d: another shape or precision" % (state.blob.numel(), self.engine.slotStateBytes()))
+        return [self.resume(state) for state in reversed(states)][::-1]
 
     def resume(self, state):
         """Queues a suspended request at the FRONT (of this stream, or of another whose engine has the same model and seed); returns
         its handle here.  It goes on at sample state.done: nothing delivered before the suspend comes again.  A streamed mel
-        request can be extended as before (extend_mel with the new handle)."""
+        request can be extended as before (extend_mel with the new handle).  ValueError, with nothing queued, for a blob whose
+        size is not this engine's.  What only the engine can see -- a blob of another model of the same size, a corrupted
+        header, a source shorter than `done` -- is refused by the step that admits the request: that step raises ValueError after
+        the stream has already booked its admissions, and the stream is to be closed (the engine itself is unchanged by a refused
+        list and can be drained)."""
+        if hasattr(state.blob, "numel") and state.blob.numel() != self.engine.slotStateBytes():
+            raise ValueError("a state of %d bytes, this engine's are %d: another shape or precision" % (state.blob.numel(), self.engine.slotStateBytes()))
         handle = self._next_handle
         self._next_handle += 1
         self._next_uid = max(self._next_uid, int(state.uid) + 1)
@@ -313,22 +441,29 @@ class SlotStream:
 
     def _admit(self, count):
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
+        listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
             item = self._queue.popleft()
             handle, x, uid, req = item[:4]
             state = item[4] if len(item) > 4 else None
             blob = state.blob if state is not None else None
+            # a row of a shared buffer, or a CPU tensor still to be uploaded: by list; a CUDA blob of its own (suspend()): singly
+            by_list = blob is not None and (state.buffer is not None or not getattr(blob, "is_cuda", True))
             self._src[handle] = (x, uid)
             if req is None:
                 if blob is None:
                     self.engine.slotStart(col, x, uid)
+                elif by_list:
+                    listed.append((col, state, x, x.size(1), None))
                 else:
                     self.engine.slotResume(col, blob, x)
                 self._running[col] = [handle, x.size(1) - (state.done if blob is not None else 0)]
             else:
                 if blob is None:
                     self.engine.slotStartMel(col, x, uid, req[0], req[1])
+                elif by_list:
+                    listed.append((col, state, x, req[0], bool(req[1])))
                 else:
                     self.engine.slotResumeMel(col, blob, x, req[0], req[1])
                 req[2] = col
@@ -337,6 +472,26 @@ class SlotStream:
                 self._ch[col] = handle
                 self._left[col] = self._running[col][1] if req is None else 0
                 self._deliv[col] = req[3] if req is not None else 0
+        if listed:
+            self._resume_listed(listed)
+
+    def _resume_listed(self, listed):
+        """One slotsResumeList call per run of consecutive rows of a shared buffer, in the order admitted (after drain() and
+        resume_many(): one call per buffer); the CPU blobs of from_bytes() are uploaded together first, as the rows of one buffer."""
+        host = [it for it in listed if it[1].buffer is None]
+        if host:
+            import torch
+            up = torch.stack([it[1].blob for it in host]).cuda()
+            for i, it in enumerate(host):
+                it[1].blob, it[1].buffer, it[1].row = up[i], up, i
+        run = []
+        for it in listed + [None]:
+            if run and (it is None or it[1].buffer is not run[-1][1].buffer or it[1].row != run[-1][1].row + 1):
+                first = run[0][1]
+                self.engine.slotsResumeList([r[0] for r in run], first.buffer[first.row:first.row + len(run)], [r[2] for r in run],
+                                            [r[3] for r in run], [r[4] for r in run])
+                run = []
+            run.append(it)
 
     def step(self, count):
         """Admits waiting requests into free columns, generates `count` samples of every column and returns {handle: (samples, pcm)}

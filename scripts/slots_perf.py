@@ -35,9 +35,20 @@ process, `--rounds` rounds each (min / median / max of the per-step means):
                     memory (direct stores), and the delivery to device + one contiguous copy to pinned memory (staging)
 Prints one JSON line per (load, chunk).
 
+--drain times saving and resuming many columns at once on the setup of --compact -- every column starts, all but
+column 5 of every tile stop, the survivors are compacted to the front --, in one process, `--rounds` rounds back to back.  Per round:
+  save    the survivors with ONE nvw_slots_save_list into device memory; the same into pinned host memory; and with one
+          nvw_slot_save per column (the comparand: what a drain cost before) -- events around the calls, and the host's wall time
+  resume  from each of the three: the columns stopped, then a one-sample step that carries the loads minus the plain one-sample
+          steps around it (the device side: the load launch reading device or pinned blobs), and the wall time of the host calls
+          that queue the resumes (one nvw_slots_resume_list against one nvw_slot_resume, i.e. one blocking header copy, per column)
+Prints one JSON line with medians, min .. max over the rounds, GB/s of blob bytes (read + written), and the verdict on the claim
+that the list save into device memory beats the single saves by more than the run-to-run spread.
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
+    python scripts/slots_perf.py --drain [--batch 12288] [--rounds 5]
 """
 import argparse
 import json
@@ -60,7 +71,8 @@ def main():
     ap.add_argument("--mel", action="store_true", help="also time slot steps fed with mel frames (distinct per column)")
     ap.add_argument("--only-mel", action="store_true", help="time the mel-fed slot steps only (e.g. under a profiler)")
     ap.add_argument("--compact", action="store_true", help="time a fragmented batch with and without compaction, moves, saves and loads")
-    ap.add_argument("--rounds", type=int, default=5, help="--compact, --serve: rounds of measurements")
+    ap.add_argument("--rounds", type=int, default=5, help="--compact, --serve, --drain: rounds of measurements")
+    ap.add_argument("--drain", action="store_true", help="time list saves (device, pinned) and list resumes against one call per column")
     ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
     args = ap.parse_args()
     import torch
@@ -72,6 +84,9 @@ def main():
     Wc, bc = bench.make_cond_layers()
     if args.compact:
         print(json.dumps(time_compact(args, w, Wc, bc)), flush=True)
+        return
+    if args.drain:
+        print(json.dumps(time_drain(args, w, Wc, bc)), flush=True)
         return
     if args.serve:
         for load in (B, max(16, B // 16)):
@@ -501,6 +516,128 @@ def time_compact(args, w, Wc, bc):
                       "bulk_GBps_lines_touched": gbs(float(np.median(load_bulk)), len(cols), True),
                       "note": "differences of two one-sample steps: the one-column figure lies within their spread"}
     res["plain_1_step_ms_for_loads"] = stats(plain)
+    e.slotsEnd()
+    e.close()
+    return res
+
+
+def time_drain(args, w, Wc, bc):
+    """The --drain measurement (module docstring)."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    B, W = args.batch, args.window
+    T_SRC = 65536
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    e.setSelectorSeed(5)
+    e.slotsBegin(W)
+    for b in range(B):
+        e.slotStart(b, src, b)
+    y = torch.empty(B, 256, dtype=torch.int32, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def timed(count, steps, before=None):
+        """(ms per step of `steps` steps of `count` samples, host ms of before()); before(): host calls the first step applies."""
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        if before:
+            before()
+        host = 1e3 * (time.perf_counter() - h0)
+        ev[0].record()
+        for _ in range(steps):
+            assert e.slotsStep(count, y)
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / steps, host
+
+    timed(256, 1)
+    surv = [b for b in range(B) if b % 16 == 5]
+    for b in range(B):
+        if b % 16 != 5:
+            e.slotStop(b)
+    timed(256, 1)
+    n = len(surv)
+    bound = 16 * ((n + 15) // 16)
+    sources = sorted((b for b in surv if b >= bound), reverse=True)
+    targets = [b for b in range(bound) if b % 16 != 5][:len(sources)]
+    for a, b in zip(sources, targets):
+        e.slotMove(a, b)
+    timed(1, 1)
+    cols = sorted(set(surv) - set(sources)) + targets
+    nbytes = e.slotStateBytes()
+    dev = torch.empty(n, nbytes, dtype=torch.uint8, device="cuda")
+    pin = torch.empty(n, nbytes, dtype=torch.uint8, pin_memory=True)
+    one = torch.empty(n, nbytes, dtype=torch.uint8, device="cuda")
+    s0 = torch.cuda.current_stream().cuda_stream
+
+    def save(how):
+        """(device ms, host ms) of saving all the columns one way."""
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        ev[0].record()
+        if how == "single":
+            for i in range(n):
+                assert lib.nvw_slot_save(e._h, cols[i], one[i].data_ptr(), s0) >= 0
+        else:
+            e.slotsSaveList(cols, stream=s0, out=dev if how == "list_device" else pin)
+        ev[1].record()
+        host = 1e3 * (time.perf_counter() - h0)
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]), host
+
+    def resume(how):
+        if how == "single":
+            for i in range(n):
+                e.slotResume(cols[i], one[i], src)
+        else:
+            e.slotsResumeList(cols, dev if how == "list_device" else pin, [src] * n)
+
+    ways = ("list_device", "list_pinned", "single")
+    for how in ways:
+        save(how)      # (warm-up: the first launch of a kernel, the staging buffers)
+    assert torch.equal(dev, one) and torch.equal(pin.cuda(), one), "the three ways must write the same bytes"
+    sv = {how: [] for how in ways}
+    sv_host = {how: [] for how in ways}
+    ld = {how: [] for how in ways}
+    ld_host = {how: [] for how in ways}
+    plain = []
+    for _ in range(args.rounds):
+        for how in ways:
+            ms, host = save(how)
+            sv[how].append(ms)
+            sv_host[how].append(host)
+        plain.append(timed(1, 8)[0])
+        for how in ways:
+            save(how)
+            for c in cols:
+                e.slotStop(c)
+            timed(1, 1)
+            ms, host = timed(1, 1, lambda: resume(how))
+            ld[how].append(ms - plain[-1])
+            ld_host[how].append(host)
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4), "max": round(float(max(v)), 4)}
+
+    def gbs(ms):
+        return round(n * 2 * (nbytes - 64) / (ms * 1e-3) / 1e9, 1) if ms > 0 else None
+
+    res = {"batch": B, "window": W, "columns": n, "rounds": args.rounds, "state_bytes": nbytes, "device": torch.cuda.get_device_name(0),
+           "save_ms": {how: stats(sv[how]) for how in ways}, "save_host_ms": {how: stats(sv_host[how]) for how in ways},
+           "save_GBps_blob_bytes": {how: gbs(float(np.median(sv[how]))) for how in ways},
+           "load_step_difference_ms": {how: stats(ld[how]) for how in ways},
+           "load_GBps_blob_bytes": {how: gbs(float(np.median(ld[how]))) for how in ways},
+           "resume_calls_host_ms": {how: stats(ld_host[how]) for how in ways}, "plain_1_step_ms": stats(plain)}
+    a, b = sv["single"], sv["list_device"]
+    gain = float(np.median(a)) - float(np.median(b))
+    spread = max(max(a) - min(a), max(b) - min(b))
+    res["claim_list_save_faster_than_single_saves_beyond_spread"] = {
+        "median_gain_ms": round(gain, 4), "largest_min_max_spread_ms": round(spread, 4), "speedup": round(float(np.median(a)) / float(np.median(b)), 2),
+        "holds": bool(gain > spread and max(b) < min(a))}
     e.slotsEnd()
     e.close()
     return res
