@@ -289,13 +289,15 @@ protected:
         p.dil[m_numLayers + 1] = p.dil[1];
     }
     // The ring slots of the short dilations in LDS (round 6): the largest dilation D (a power of two) whose layers' slots -- sum of d
-    // over the layers with d <= D, BT x R/32 KiB each -- fit beside everything else; 0: none.  Sets p.ldsRingD and the LDS slot numbers
-    // of the schedule table; returns the bytes to add to the launch's dynamic LDS.
+    // over the layers with d <= D, BT x R/32 KiB each -- fit beside everything else; 0: none.  The first Cfg::RING_INPLACE slots take the space
+    // the exchange images left when they moved onto the head's image (Cfg::OVERLAY): `need` counts it already; the others follow them
+    // (Cfg::ringSlotOffset).  Sets p.ldsRingD and the LDS slot numbers of the schedule table; returns the bytes to add to the launch's
+    // dynamic LDS (0 when the in-place slots are enough: p.ldsRingD says whether there are any).
     template <int BT> size_t placeLdsRing(wn::Params& p, size_t need) const {
         using CB = wn::Cfg<F16, R, S, A, BT>;
         int D = 0;
         for (int d = 1; d <= m_maxDilation && d <= WN_LDS_RING_MAXD; d <<= 1)
-            if (need + (size_t)CB::ldsRingSlots(m_numLayers, m_maxDilation, d) * CB::RING_SLOT <= kLdsMax) D = d;
+            if (need + (size_t)CB::ringTailSlots(CB::ldsRingSlots(m_numLayers, m_maxDilation, d)) * CB::RING_SLOT <= kLdsMax) D = d;
         p.ldsRingD = D;
         int slot = 0;
         for (int l = 0; l < m_numLayers; l++) {
@@ -304,12 +306,13 @@ protected:
         }
         p.dil[m_numLayers] = p.dil[0];
         p.dil[m_numLayers + 1] = p.dil[1];
-        return (size_t)slot * CB::RING_SLOT;
+        return (size_t)CB::ringTailSlots(slot) * CB::RING_SLOT;
     }
     // ... and whether a launch uses them (the LR instantiations of wavenet_wg: the dump-free kernels).
-    // m_ringLdsMode >= 0 (default): as many of the short dilations as fit; -1: never.  Measured at C3 (LABNOTES round 6, us per sample
-    // with / without): one tile per workgroup, d <= 4 on chip, 21.1 / 21.7; two tiles, d <= 2 in the place of the older tap's
-    // embedding table, 28.4 / 29.2; three tiles, d <= 1, 37.3 / 37.4; four tiles, d <= 1, 43.6 / 44.2.
+    // m_ringLdsMode >= 0 (default): as many of the short dilations as fit; -1: never.  Measured at C3 (us per sample with / without):
+    // one tile per workgroup, d <= 4 on chip, 21.1 / 21.7; two tiles, d <= 2 in the place of the older tap's embedding table,
+    // 28.4 / 29.2; four tiles, d <= 1, 43.6 / 44.2 (LABNOTES round 6, separate calls); three tiles, one call with the arms alternating
+    // (LABNOTES, "Exchange images on the head's image"): d <= 2 with the in-place slots 36.7 / 37.6, d <= 1 as before them 37.2.
     static constexpr bool lrBuilt(bool dump, int raw) { return !dump && (raw == 0 || F16); }      // (fp32 engines: dump-free code exists for the packed conditioning only)
     template <int BT> size_t ringPlan(wn::Params& p, size_t need, bool dump, int raw) const {
         p.ldsRingD = 0;
@@ -330,7 +333,7 @@ protected:
         const size_t need = ldsNeed<BT>(m_numLayers, nEmb, DUMP);
         if constexpr (lrBuilt(DUMP, RAW)) {
             const size_t ringBytes = ringPlan<BT>(p, need, DUMP, RAW);
-            if (ringBytes > 0) {
+            if (p.ldsRingD > 0) {
                 hipLaunchKernelGGL((wn::wavenet_wg<F16, R, S, A, BT, EMB, DUMP, RAW, true>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
                 return hipGetLastError() == hipSuccess;
             }
@@ -340,7 +343,10 @@ protected:
         return hipGetLastError() == hipSuccess;
     }
     // embedding tables of a launch in LDS: as many as fit; a launch whose two tables leave no room for a single ring slot gives up the
-    // OLDER tap's table for ring slots (its gather is one sample early, off the dependent chain; C3 at two tiles: 28.4 against 29.2 us)
+    // OLDER tap's table for ring slots (its gather is one sample early, off the dependent chain; C3 at two tiles: 28.4 against 29.2 us).
+    // With the in-place slots (Cfg::RING_INPLACE) the two layers of dilation 1 always fit: the older table likewise goes where it stands
+    // between them and a longer dilation (d <= 1 alone is two layers of twenty at C3: 37.3 against 37.4 us at three tiles), and stays
+    // where the same dilations fit beside it.
     template <int BT> int planEmb(bool dump, int raw) const {
         int nEmb = embTables<BT>(dump);
 #ifdef WN_EXP_TWO_WG
@@ -349,7 +355,10 @@ protected:
         if (nEmb == 2 && m_ringLdsMode >= 0 && lrBuilt(dump, raw)) {
             wn::Params q;
             fillSchedule(q);
-            if (placeLdsRing<BT>(q, ldsNeed<BT>(m_numLayers, 2, dump)) == 0) nEmb = 1;
+            placeLdsRing<BT>(q, ldsNeed<BT>(m_numLayers, 2, dump));
+            const int D2 = q.ldsRingD;
+            placeLdsRing<BT>(q, ldsNeed<BT>(m_numLayers, 1, dump));
+            if (D2 == 0 || (D2 < 2 && q.ldsRingD > D2)) nEmb = 1;
         }
         return nEmb;
     }

@@ -206,22 +206,51 @@ struct Cfg {
     // (also with three tiles per workgroup: the 24 KiB it frees let the current tap's embedding table into LDS)
     static constexpr bool ALIAS_LG = ZSBUF + LGBUF > 100 * 1024 || BT >= 3;
     static constexpr bool ZA_B_FROM_LDS = KF_A * BT * 4 > WN_ZA_B_REGS;
-    static constexpr int OFF_X = 0, OFF_H = OFF_X + XBUF, OFF_SK = OFF_H + HBUF, OFF_ZS = OFF_SK + SKBUF;
+    // The three exchange images of the layers (x, h, dilated tap) are live during the layers only, the head's zs / logits image
+    // during the head only: where they fit, the exchange images lie ON the logits image (OVERLAY).  The space they leave, one
+    // RING_SLOT each, moves behind the tables: the bias table then starts at OFF_BIAS = LDS_FIXED - 3 * RING_SLOT, and the
+    // last RING_INPLACE slots' worth of what LDS_FIXED counts holds the first ring slots (ringSlotOffset), contiguous with those
+    // a launch asks for beyond ldsBytes().  LDS_FIXED and ldsBytes() keep their values: a launch without ring slots asks for
+    // what it always did.
+    // Why no image is overwritten while it is live, barrier by barrier of wavenet_wg (every variant runs the same barriers):
+    //  * prologue: publish_xp writes the tap image, __syncthreads, every wave reads it; the first sample's x stores go to another
+    //    image of the overlay; nothing of the head is live before the first head.
+    //  * layers: x, h and tap image keep their order among themselves (the x / h barriers of each layer, as before).  The last
+    //    layer's residual x and, in kernels that do not hold the first layer's slot in LDS, the tap of the next sample's layer 0
+    //    (published at the end of the last layer) are read into registers behind the last x barrier, and h behind the last h
+    //    barrier: all in front of the barrier that follows the skbuf stores (wg_barrier drains the wave's LDS reads first).
+    //  * head: the first store into the zs / logits area (zs; where ALIAS_LG is off the logits: later still) comes behind that
+    //    barrier.  The A x S GEMM that reads its B operands from LDS (gemm_ldsb_b) reads skbuf, the A x A one (ZA_B_FROM_LDS)
+    //    the zs image itself; softmax passes of fewer than BT tiles (LGT < BT) write and read the logits image between barriers
+    //    of their own.  Every logits read is in front of the sample's closing barrier, the next sample's first x store behind it.
+    //  * dumps (DUMP) go to global memory; in-place and feature conditioning (RAW 1, 2, 3) never pass through LDS.
+    //  * ring slots, bias and embedding tables are nobody else's place at any time.
+    static constexpr int HEADIMG = ALIAS_LG ? (ZSBUF > LGBUF ? ZSBUF : LGBUF) : ZSBUF + LGBUF;      // zs and logits
+    static constexpr bool OVERLAY = XBUF + HBUF + XPBUF <= (ALIAS_LG ? HEADIMG : LGBUF);
+    static constexpr int OFF_SK = OVERLAY ? 0 : XBUF + HBUF, OFF_ZS = OFF_SK + SKBUF;
     static constexpr int OFF_LG = ALIAS_LG ? OFF_ZS : OFF_ZS + ZSBUF;
-    static constexpr int OFF_Y = ALIAS_LG ? OFF_ZS + (ZSBUF > LGBUF ? ZSBUF : LGBUF) : OFF_LG + LGBUF;
-    static constexpr int OFF_XP = OFF_Y + YBUF;
-    static constexpr int LDS_FIXED = OFF_XP + XPBUF;
+    static constexpr int OFF_Y = OFF_ZS + HEADIMG;
+    static constexpr int OFF_X = OVERLAY ? OFF_LG : 0, OFF_H = OFF_X + XBUF, OFF_XP = OVERLAY ? OFF_H + HBUF : OFF_Y + YBUF;
+    static constexpr int OFF_BIAS = OVERLAY ? OFF_Y + YBUF : OFF_XP + XPBUF;
+    static constexpr int LDS_FIXED = XBUF + HBUF + SKBUF + HEADIMG + YBUF + XPBUF;
     // + optionally both embedding tables (T_data) behind the bias table
     // Bias table in LDS.  Kernels that can dump hold the model's table as it is, [L][Bh | Bres | Bskip] + the head's, the skip rows turned
     // into running sums (the per-layer skipOut dump needs every one of them).  Dump-free kernels (round 6) only ever add the LAST running
     // sum -- at the head --, so they hold [L][Bh | Bres], ONE row of S skip-bias sums, then the head's: S * (L - 1) floats less (C3: 19 KiB).
     static constexpr int BIAS_LN = 3 * R;                  // per-layer stride of the dump-free table
     __host__ __device__ static constexpr int biasFloats(int L, bool dump) { return (dump ? L * BIAS_L : L * BIAS_LN + S) + 2 * A; }
-    static size_t ldsBytes(int L, int embTables, bool dump = true) {      // embTables: 0, 1 (current tap only) or 2
+    __host__ __device__ static constexpr size_t ldsBytes(int L, int embTables, bool dump = true) {      // embTables: 0, 1 (current tap only) or 2
         return (size_t)LDS_FIXED + (size_t)biasFloats(L, dump) * sizeof(float) + (size_t)embTables * A * R * sizeof(typename P::elem);
     }
     // one ring slot of a workgroup in LDS: x of one (layer, sample) as B fragments, all BT tiles (the layout of the tap image XPBUF)
     static constexpr int RING_SLOT = BT * KF_R * 1024;
+    // Slot number -> byte offset in the launch's LDS; tailBase = ldsBytes(): where the LDS a launch asks for beyond its tables
+    // starts.  The first RING_INPLACE slots lie in front of it, in the space the overlaid exchange images left (see OVERLAY).
+    static constexpr int RING_INPLACE = OVERLAY ? 3 : 0;
+    static_assert(XBUF == RING_SLOT && HBUF == RING_SLOT && XPBUF == RING_SLOT, "a vacated exchange image is one ring slot");
+    static_assert(OFF_BIAS + RING_INPLACE * RING_SLOT == LDS_FIXED, "the in-place slots are what LDS_FIXED counts behind the tables");
+    __host__ __device__ static constexpr int ringSlotOffset(int slot, int tailBase) { return tailBase + (slot - RING_INPLACE) * RING_SLOT; }
+    __host__ __device__ static constexpr int ringTailSlots(int slots) { return slots > RING_INPLACE ? slots - RING_INPLACE : 0; }
     // slots of the layers with dilation <= D (the schedule of nv_wavenet.cuh:99,110-111)
     __host__ __device__ static constexpr int ldsRingSlots(int L, int maxDilation, int D) {
         int n = 0, d = 1;
@@ -884,8 +913,9 @@ template <bool F16> WN_DEV void cond_add(floatx4* a, typename Prec<F16>::frag c,
 // wave's stream (Cfg<.., KFC>), their B operands -- KFC fragments per tile, 160 B per utterance instead of 2R * L values --
 // loaded once per sample.  Summation order of the gate pre-activation: (Bh + bcond), Wcond c, dilated tap, current tap.
 // LR: the launch keeps the ring slots of the short dilations in LDS (Params::ldsRingD; see ring_lds_copy).  A separate instantiation:
-// the uniform branches it puts into every layer cost 3-5 % of a sample's cycles (measured, LABNOTES round 6), which pays when most of
-// the ring traffic goes (a model whose whole ring fits) and not for two layers of twenty (C3 at three tiles per workgroup).
+// its uniform branches are in every layer, whether the layer's slots are in LDS or not.  Measured on one box, arms alternating, C3 at
+// three tiles per workgroup and 12 288 utterances (LABNOTES, "Exchange images on the head's image"): ring in HBM 37.6 us per sample,
+// d <= 1 in LDS (two layers of twenty) 37.2, d <= 2 (four layers, with the in-place slots of Cfg::OVERLAY) 36.7.
 template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP = true, int RAW = 0, bool LR = false>
 // (WN_EXP_TWO_WG, experiment build of round 6: the one-tile kernel with a register budget that lets TWO workgroups share a CU -- two waves per
 //  SIMD, each with its own tile and its own weight stream; the A/B the round-5 review asked for at 8 192 utterances.  LABNOTES round 6.)
@@ -913,7 +943,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
     float* const lgbuf = (float*)(lds + C::OFF_LG);
     int* const ybuf = (int*)(lds + C::OFF_Y);
     char* const xpbuf = lds + C::OFF_XP;
-    float* const biasLds = (float*)(lds + C::LDS_FIXED);
+    float* const biasLds = (float*)(lds + C::OFF_BIAS);
 
     static_assert(RAW == 0 || RAW == 1 || (RAW == 2 && F16) || RAW == 3, "RAW: 0 packed, 1 fp32 in place, 2 fp16 in place (fp16 engine), 3 features");
     if (p.gate != nullptr && __builtin_nontemporal_load(p.gate) == 0u) return;   // (a fallback launch that is not needed)
@@ -1064,7 +1094,8 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
     const unsigned ringTileB = (unsigned)ringTile;
     // the part of the ring that is in LDS for the length of the launch (see ring_lds_copy below): layers with dilation <= ldsD
     const int ldsD = LR ? p.ldsRingD : 0;
-    char* const ringLds = (char*)(biasLds + C::biasFloats(L, DUMP)) + (size_t)(EMBLDS ? p.embLds : 0) * A * R * sizeof(elem);
+    // (slot -> place: Cfg::ringSlotOffset, whose first slot follows the tables)
+    char* const ringLds = lds + C::ringSlotOffset(0, (int)C::ldsBytes(L, EMBLDS ? p.embLds : 0, DUMP));
     const char* condNext = condMine + (size_t)p.initSample * L * condStride;
     // in-place conditioning: one row = [maxBatch][2R] source elements; per-lane part of the address (utterance, channel quad)
     constexpr unsigned RAWE = RAW == 2 ? 2u : 4u;                                   // bytes per source element

@@ -3,7 +3,8 @@
 
   isa_stats.py regs  [inst]                 registers / scratch / LDS of every kernel of an instantiation object
   isa_stats.py mix   [inst] <kernel-substr> instruction mix of the kernel whose demangled name contains the substring,
-                                            whole kernel and its largest loop body (the per-sample loop of wavenet_wg)
+                                            whole kernel and its largest loop body (the per-sample loop of wavenet_wg); the scalar
+                                            side of the layer-pair loop and of the rest of the sample loop by opcode
   isa_stats.py sha   [inst] <kernel-substr> sha256 of that kernel's disassembly (addresses stripped): the identity of the device code
                                             a measurement belongs to (profiles/traffic_rNN.json; bench.py drops a measurement taken on
                                             other code)
@@ -110,13 +111,17 @@ def mix(inst, sub):
                 loops.append((addr_to_idx[base + off], i))
         print("== %s" % short(dm[s]))
 
-        def report(title, lo, hi, excl=()):
+        def report(title, lo, hi, excl=(), scalar=False):
             idx = [i for i in range(lo, hi + 1) if not any(a <= i <= b for a, b in excl)]
             cnt = collections.Counter(classify(lines[i][1]) for i in idx)
             tot = sum(cnt.values())
             valu = sum(v for k, v in cnt.items() if k in ("v_pk_f32", "v_pk_other", "trans", "accvgpr", "cndmask", "v_cvt", "dpp/perm", "valu_other"))
             print("  %s: %d instructions, VALU %d, MFMA %d, VALU:MFMA %.2f" % (title, tot, valu, cnt["mfma"], valu / max(1, cnt["mfma"])))
             print("   " + "  ".join("%s %d" % (k, cnt[k]) for k, _ in CLASSES if cnt[k]))
+            if scalar:          # the scalar side by opcode (waits, s_nop and barriers are classes of their own above)
+                ops = collections.Counter(lines[i][1] for i in idx if lines[i][1].startswith("s_") and lines[i][1] not in ("s_waitcnt", "s_nop", "s_barrier"))
+                br = sum(v for k, v in ops.items() if "branch" in k)
+                print("   scalar: SALU/SMEM %d, branches %d:  %s" % (sum(ops.values()) - br, br, "  ".join("%s %d" % kv for kv in sorted(ops.items(), key=lambda kv: -kv[1]))))
         report("whole kernel", 0, len(lines) - 1)
         big = sorted(loops, key=lambda l: l[0] - l[1])[:3]
         if big:
@@ -124,9 +129,11 @@ def mix(inst, sub):
             inner = [l for l in big[1:] if outer[0] <= l[0] and l[1] <= outer[1] and l[1] - l[0] > 200]
             report("per-sample loop (lines %d-%d)" % outer, outer[0], outer[1])
             for l in inner:
-                report("  inner loop (lines %d-%d: layer pair)" % l, l[0], l[1])
+                report("  inner loop (lines %d-%d: layer pair)" % l, l[0], l[1], scalar=True)
             if inner:
                 report("  per-sample loop outside the inner loop(s) (first layer, odd tail, head, softmax)", outer[0], outer[1], inner)
+                small = sorted(inner, key=lambda l: l[1] - l[0])[:1]
+                report("  per-sample loop outside the layer-pair loop lines %d-%d" % small[0], outer[0], outer[1], small, scalar=True)
 
 
 def kernel_sha(inst, sub):
