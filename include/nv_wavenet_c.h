@@ -231,7 +231,8 @@ void nvw_get_y_out(nvw_engine* e, int* yOut, int offset, int size, void* stream)
 
 /* SLOT MODE: CONTINUOUS BATCHING (ABI 7).  Every column of the batch holds one utterance that starts and stops on its own while
  * the others go on; the samples of an utterance depend on its upsampled features, its uid, the seed of nvw_set_selector_seed (0 if
- * none was set) and the model only -- not on its column, the step it joined at, its neighbours or the chunk sizes.  Local sample k
+ * none was set), the model and the sampling temperature in force at each local sample (1 unless nvw_slot_set_temperature says
+ * otherwise; see SAMPLING TEMPERATURE below) only -- not on its column, the step it joined at, its neighbours or the chunk sizes.  Local sample k
  * draws its selector from Philox4x32-10 with counter {k, uid, 0, 0}: an utterance with uid = b reproduces column b of a lockstep
  * nvw_set_features + nvw_set_selector_seed run.  Needs nvw_set_conditioning_weights (the conditioning is computed in the kernel).
  *   nvw_slots_begin  enters slot mode with a window of `window` samples, a positive multiple of the largest dilation of the schedule
@@ -403,6 +404,38 @@ float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples,
 int nvw_slots_done(nvw_engine* e, unsigned long long ticket);
 void* nvw_pinned_alloc(size_t bytes);
 void nvw_pinned_free(void* p);
+
+/* SAMPLING TEMPERATURE PER UTTERANCE, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  The last step of the network draws from
+ * softmax(logits / T): T = 1 is the model as trained, a smaller T sharpens the distribution (less noise, towards muffled), a larger
+ * one flattens it.  The softmax computes exp2(x c - m c) with c = log2(e) / T per column in place of the constant log2(e): the
+ * instructions per sample are the same, T = 1 is bit-identical to a run without these calls, and for T a power of two the samples
+ * and probabilities are bit for bit those of the same model with Wza / T and Bza / T handed to nvw_set_out_weights.  T is finite
+ * and in [2^-10, 2^10].  Greedy (argmax) decoding is not offered: T = 2^-10 approaches it, but still draws between logits that tie
+ * at the maximum.  Only the launches that compute the conditioning in the kernel read the temperatures (nvw_set_features,
+ * nvw_pack_features, nvw_set_conditioning_features, nvw_set_mel + nvw_generate_stream, slot mode); the probability dump
+ * (nvw_get_p) reports the tempered probabilities, nvw_get_za the raw logits.
+ * This extends the contract of slot mode: an utterance's samples depend on its features (or frames), its uid, the seed, the model
+ * AND THE TEMPERATURE IN FORCE AT EACH LOCAL SAMPLE -- and on nothing else.  With uid = b and the same temperatures at the same
+ * local samples it reproduces column b of a lockstep run, bit for bit, in both precisions.
+ *   nvw_set_temperatures      lockstep: column b < n samples at T[b] (host array, 1 <= n <= batch) in the runs that follow; columns
+ *                             past n, and every column with T == NULL, at 1.  The values stay in force across nvw_set_features,
+ *                             nvw_set_mel, nvw_reset_history and between nvw_run_partial / nvw_run_range chunks until the next call;
+ *                             a call between two chunks takes effect at the next chunk and leaves the history alone.  While any
+ *                             column's T is not 1, a run on packed or in-place conditioning or on a multi-CU (chain) engine
+ *                             prints one line and returns 0: nothing is generated, nothing is silently ignored.  Synchronises.
+ *                             0 when refused (in slot mode, n out of range, a bad value); nothing changes.
+ *   nvw_slot_set_temperature  slot mode: the utterance of column `slot` samples at T from the next step on, from that step's first
+ *                             sample.  nvw_slot_start / _start_mel put the column back to 1, so the order is start, then set;
+ *                             nvw_slots_begin and nvw_slots_end put every column back to 1.  nvw_slot_move, the saves and the
+ *                             resumes carry the value: a blob holds it in word 10 of its header as the bits of the float, all-zero
+ *                             bits for T = 1, so blobs of utterances at T = 1 are byte for byte what they were; a resume refuses a
+ *                             header whose word is neither zero nor a valid temperature.  A step with changed columns issues one
+ *                             small launch ahead of its generation launch.  0 when refused (not in slot mode, slot out of range,
+ *                             a column without an utterance or a pending start or resume, a bad value); nothing changes.
+ *   nvw_slot_temperature      the value in force for column `slot` (host state); 0 when the column holds no utterance. */
+int nvw_set_temperatures(nvw_engine* e, const float* T, int n);
+int nvw_slot_set_temperature(nvw_engine* e, int slot, float T);
+float nvw_slot_temperature(nvw_engine* e, int slot);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

@@ -100,6 +100,9 @@ SIGNATURES = {
     "nvw_slots_time_outputs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),
     "nvw_slots_wait": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "nvw_slots_done": (C.c_int, [C.c_void_p, C.c_ulonglong]),
+    "nvw_set_temperatures": (C.c_int, [C.c_void_p, _fp, C.c_int]),
+    "nvw_slot_set_temperature": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "nvw_slot_temperature": (C.c_float, [C.c_void_p, C.c_int]),
     "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),
     "nvw_pinned_free": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),

@@ -78,6 +78,9 @@ struct nvw_engine {
     virtual bool slotsWait(unsigned long long) = 0;
     virtual int slotsDone(unsigned long long) = 0;
     virtual float slotsTimeOutputs(bool, int, int*, short*, long long, int, hipStream_t) = 0;
+    virtual bool setTemperatures(const float*, int) = 0;
+    virtual bool slotSetTemperature(int, float) = 0;
+    virtual float slotTemperature(int) = 0;
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
               offsetof(nvw_slot_piece, uid) == offsetof(wn::SlotPiece, uid) && offsetof(nvw_slot_piece, finished) == offsetof(wn::SlotPiece, finished) &&
@@ -205,6 +208,9 @@ struct EngineImpl : nvw_engine {
     float slotsTimeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t s) override {
         return eng.slotsTimeOutputs(ragged, count, samples, pcm, capacity, reps, s);
     }
+    bool setTemperatures(const float* T, int n) override { return eng.setTemperatures(T, n); }
+    bool slotSetTemperature(int slot, float T) override { return eng.slotSetTemperature(slot, T); }
+    float slotTemperature(int slot) override { return eng.slotTemperature(slot); }
 };
 
 typedef nvw_engine* (*nvw_factory_fn)(int L, int maxD, int B, int N, int impl, int tanhEmbed, int organisation);

@@ -39,6 +39,7 @@
 #include "slots_mel.hpp"
 #include "slots_state.hpp"
 #include "slots_deliver.hpp"
+#include "slots_sampler.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
 
@@ -87,6 +88,7 @@ protected:
     static constexpr int KFC = wn::feat_kfc<F16>();                    // feature fragments per tile and sample
     static constexpr int KC = KFC * 16 * wn::Prec<F16>::TPF;           // channels the features are padded to
     using CF = wn::Cfg<F16, R, S, A, 1, KFC>;
+    static_assert(wn::kSoftScaleUnit == wn::kLog2e, "T = 1 is the kernel's default scale");
 
     Implementation m_implementation;
     int m_numLayers, m_maxBatch, m_maxSamples, m_maxDilation, m_tiles, m_numCUs;
@@ -203,6 +205,19 @@ protected:
     wn::DeliverPiece* m_dlvStage[kSlotTickets] = {};      // pinned host staging of them, one per ticket in flight ...
     hipEvent_t m_dlvEv[kSlotTickets] = {};  // ... and the event recorded after that ticket's delivery
     unsigned long long m_dlvTicket = 0;     // the last ticket given out (they count from 1)
+
+    // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode: the host's values are the
+    // authority, the device table follows them.  Nothing is allocated, and Params::softScale stays NULL, until a temperature other
+    // than 1 has been set: an engine that never uses the feature launches what it launched before.
+    std::vector<float> m_temp;              // [maxBatch] T per column (empty: 1 everywhere)
+    int m_tempNonUnit = 0;                  // columns with T != 1
+    float* m_softScale = NULL;              // [maxBatch] log2(e) / T on the device, made at the first use and filled with log2(e)
+    std::vector<char> m_tempDirty;          // slot mode: the columns whose table entry the next step writes
+    std::vector<int> m_tempDirtyList;
+    wn::SlotScale* m_scaleDev = NULL;       // [maxBatch] on the device: a step's changed entries ...
+    wn::SlotScale* m_scaleStage[2] = {NULL, NULL};      // ... their pinned host staging, used by alternate steps as m_slotStage
+    hipEvent_t m_scaleEv[2] = {NULL, NULL};
+    int m_scaleParity = 0;
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -683,6 +698,14 @@ public:
         if (m_upBias) gpuErrChk(hipFree(m_upBias));
         if (m_melFrag) gpuErrChk(hipFree(m_melFrag));
         if (m_slotLayers) gpuErrChk(hipFree(m_slotLayers));
+        if (m_softScale) gpuErrChk(hipFree(m_softScale));
+        if (m_scaleDev) {
+            gpuErrChk(hipFree(m_scaleDev));
+            for (int i = 0; i < 2; i++) {
+                gpuErrChk(hipHostFree(m_scaleStage[i]));
+                gpuErrChk(hipEventDestroy(m_scaleEv[i]));
+            }
+        }
         gpuErrChk(hipFree(m_outputSelectors));
         gpuErrChk(hipFree(m_ring));
         gpuErrChk(hipFree(m_yInPrev));
@@ -1236,6 +1259,38 @@ public:
                                    (size_t)m_maxBatch, hipMemcpyDefault, stream));
     }
 
+    // ---- sampling temperature (beyond the reference; slots_sampler.hpp) ------------------------------------------
+    // Column b of the runs that follow samples from softmax(logits / T[b]), b < n; the columns past n, and all of them with
+    // T == NULL, from softmax(logits) as before.  T: a host array, 1 <= n <= maxBatch, every value finite and in [2^-10, 2^10].
+    // The values stay in force across setFeatures / setMel / resetHistory and between run_partial chunks until the next call; a
+    // call between two chunks takes effect at the next chunk and leaves the history alone.  They reach every launch of the
+    // features path (the conditioning computed in the kernel); while any column's T is not 1 a run on packed or in-place
+    // conditioning, or on a multi-CU engine, prints one line and returns false.  T = 1 is bit-identical to never having called
+    // this; for T a power of two the samples are those of the model with Wza / T and Bza / T.  Greedy (argmax) decoding is not
+    // offered: T = 2^-10 approaches it, but still draws between logits that tie at the maximum.  Synchronises.
+    // false (nothing changes): in slot mode (slotSetTemperature is the call there), n outside the batch with a non-NULL T, or a
+    // bad value.
+    bool setTemperatures(const float* T, int n) {
+        if (m_slotW > 0) return false;
+        if (T != NULL) {
+            if (n < 1 || n > m_maxBatch) return false;
+            for (int b = 0; b < n; b++)
+                if (!wn::temperature_ok(T[b])) return false;
+        }
+        gpuErrChk(hipDeviceSynchronize());
+        resetTemperatures();
+        if (T == NULL) return true;
+        for (int b = 0; b < n; b++) tempSet(b, T[b]);
+        if (m_softScale) {
+            std::vector<float> c(m_maxBatch);
+            for (int b = 0; b < m_maxBatch; b++) c[b] = wn::temperature_scale(temperature(b));      // (m_temp is empty when every value is 1)
+            gpuErrChk(hipMemcpy(m_softScale, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        return true;
+    }
+    // the temperature in force for column b (1 when none was ever set)
+    float temperature(int b) const { return (b >= 0 && b < (int)m_temp.size()) ? m_temp[b] : 1.0f; }
+
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to
     // consume(yOut, firstSample, count) on the calling thread (role of nv_wavenet.cuh:445-497).  Two
@@ -1314,6 +1369,13 @@ public:
         assert(m_pcmUser == NULL || m_pcmUserElems == 0 || m_pcmUserElems >= (size_t)batch_size * num_samples);
         if (m_implementation == SINGLE_BLOCK) assert(S <= 4 * R);
         if (!m_supported) return false;
+        if (m_tempNonUnit > 0 && !m_featPtr) {
+            // only the kernels that compute the conditioning from the features read the temperatures: nothing is generated rather than
+            // generated at T = 1
+            fprintf(stderr, "nvWavenetInfer: %d columns have a sampling temperature other than 1, which packed or in-place conditioning "
+                    "and multi-CU launches cannot honour: use the features path, or setTemperatures(NULL, 0)\n", m_tempNonUnit);
+            return false;
+        }
 
         // a new utterance: the dilation rings read as zero until written (wavenet_wg takes x[t-d] = 0 for t < d from the ring
         // itself).  resetHistory() -- every way of handing over a new utterance's conditioning calls it -- has normally done this
@@ -1379,6 +1441,7 @@ public:
         p.rngKey0 = (unsigned)m_rngSeed;
         p.rngKey1 = (unsigned)(m_rngSeed >> 32);
         p.clk = m_clkOn ? m_clk : NULL;
+        p.softScale = m_featPtr ? m_softScale : NULL;
         fillSchedule(p);
         m_lastStride = num_samples;
         if (p.count <= 0) return true;
@@ -1426,7 +1489,8 @@ public:
 
     // ---- slot mode: continuous batching (slots.hpp; DESIGN.md "Slot mode") ------------------------------------------------------
     // Every column holds one utterance that starts and stops on its own while the others go on.  An utterance's samples depend on
-    // its features, its uid, the seed and the model only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
+    // its features, its uid, the seed, the model and the temperature in force at each local sample (slotSetTemperature; 1 by default)
+    // only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
     // lockstep setFeatures + setSelectorSeed run --, its rings start at zero and its history at 128.  The state between steps lives
     // in a window of W samples that wraps; the generation kernel is wavenet_wg<.., RAW=3> as the features path launches it, on
     // window rows, reading the selectors from a table (useRng = 0).  Needs setConditioningWeights; the seed is the one of
@@ -1460,6 +1524,7 @@ public:
         m_slotResumeDone.assign(m_maxBatch, 0);
         m_slotMoveEnd.assign(m_maxBatch, 0);
         m_slotMoves.clear();
+        resetTemperatures();      // (every column at T = 1, a lockstep run's values included)
         const size_t cells = (size_t)window * m_maxBatch;
         gpuErrChk(hipMalloc(&m_slotDesc, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
         gpuErrChk(hipMemset(m_slotDesc, 0, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
@@ -1508,6 +1573,7 @@ public:
         d.precision = precision;
         d.active = 1;
         slotMarkPending(slot, 1);
+        slotTempSet(slot, 1.0f);
         return true;
     }
     // Column `slot` goes idle at the next step (its features are no longer read from then on).
@@ -1543,6 +1609,7 @@ public:
         m_melTilesDirty = true;
         m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
         slotMarkPending(slot, 1);
+        slotTempSet(slot, 1.0f);
         return true;
     }
     // More frames of the mel utterance of column `slot` are available in the same buffer (written by the caller, ordered before the
@@ -1556,6 +1623,22 @@ public:
         if (final) d.state = 2;
         melMarkDirty(slot);
         return true;
+    }
+    // The utterance of column `slot` samples from softmax(logits / T) from the next step on, from that step's first sample (the
+    // local sample the column has reached then); T as for setTemperatures.  slotStart / slotStartMel put the column back to 1, so
+    // the order is start, then set; slotsBegin and slotsEnd put every column back to 1.  Moves, saves and resumes carry the value
+    // (a blob holds it in SlotStateHeader::pad[0]).  A step with changed columns issues one small launch (slots_set_scales) ahead
+    // of its generation launch.  false (nothing changes): not in slot mode, slot outside the batch, a column that holds no
+    // utterance and has no pending start or resume, or a bad value.
+    bool slotSetTemperature(int slot, float T) {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot) || !wn::temperature_ok(T)) return false;
+        slotTempSet(slot, T);
+        return true;
+    }
+    // the host's value for column `slot`; 0 when it holds no utterance (or outside slot mode, or outside the batch)
+    float slotTemperature(int slot) const {
+        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot)) return 0.f;
+        return m_temp.empty() ? 1.0f : m_temp[slot];
     }
     // ---- a column's state as a value (slots_state.hpp) ----
     // bytes of one column's state blob for this engine's shape and precision (header + its share of its tile's ring)
@@ -1580,6 +1663,7 @@ public:
         m_slotMoveEnd[from] = 1;
         m_slotMoveEnd[to] = 2;
         m_slotMoves.push_back(wn::SlotMove{from, to});
+        slotTempSet(to, temperature(from));
         return true;
     }
     // The state of column `slot` after the steps issued so far into dst (device memory, 16-byte aligned, slotStateBytes() bytes),
@@ -1596,6 +1680,7 @@ public:
         wn::SlotStateHeader h = slotHeaderCommon();
         h.done = (int)done;
         h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
+        h.pad[0] = wn::temperature_word(temperature(slot));
         if (!wn::slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur))
             return -1;
         return (int)done;
@@ -1615,6 +1700,7 @@ public:
         slotLayers();
         m_slotResume[slot] = state;
         m_slotResumeDone[slot] = h.done;
+        slotTempFromHeader(slot, h);
         return true;
     }
     bool slotResumeMel(int slot, const void* state, const void* mel, int precision, long long cStride, long long fStride, int frames, int final) {
@@ -1624,6 +1710,7 @@ public:
         slotLayers();
         m_slotResume[slot] = state;
         m_slotResumeDone[slot] = h.done;
+        slotTempFromHeader(slot, h);
         return true;
     }
     // ---- lists of columns ----
@@ -1666,7 +1753,7 @@ public:
             const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
             const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
             const int done = (int)(m_slotCounter - start);
-            stage[i] = wn::SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid};
+            stage[i] = wn::SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, wn::temperature_word(temperature(b)), 0};
             saved[i] = wn::SlotSaved{b, uid, done, mel ? 1 : 0};
         }
         gpuErrChk(hipMemcpyAsync(m_saveDev[at], stage, (size_t)n * sizeof(wn::SlotSave), hipMemcpyHostToDevice, stream));
@@ -1715,6 +1802,7 @@ public:
             (void)ok;
             m_slotResume[q.slot] = dev + (size_t)i * (size_t)stride;
             m_slotResumeDone[q.slot] = hdr[i].done;
+            slotTempFromHeader(q.slot, hdr[i]);
         }
         return n;
     }
@@ -1788,6 +1876,7 @@ public:
         if (!m_slotMoves.empty()) ok = slotApplyMoves(stream);
         if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream) && ok;      // (before the starts: it reads the pending ones)
         if (!m_slotPendingList.empty()) ok = slotApplyPending(stream) && ok;
+        if (!m_tempDirtyList.empty()) ok = slotApplyTemperatures(stream) && ok;      // (the host's values: whatever moved or started above)
         cols = 0;
         for (int b = m_maxBatch - 1; b >= 0; b--)
             if (m_slotHost[b].active || (m_melColumns > 0 && m_melHost[b].state)) {
@@ -2034,6 +2123,7 @@ public:
         m_slotResumeDone.clear();
         m_slotMoveEnd.clear();
         m_slotMoves.clear();
+        resetTemperatures();
         if (m_melDesc) {
             gpuErrChk(hipFree(m_melDesc));
             gpuErrChk(hipFree(m_melUpd));
@@ -2135,8 +2225,9 @@ protected:
                  !isDevicePtr(mel) || m_slotMoveEnd[slot] == 2);
     }
     bool slotHeaderOk(const wn::SlotStateHeader& h) const {
+        float T;      // (word 10: zero, or the bits of a valid temperature)
         return h.magic == wn::kSlotStateMagic && h.version == wn::kSlotStateVersion && h.precision == (F16 ? 16 : 32) && h.R == R &&
-               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0;
+               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0 && wn::temperature_of_word(h.pad[0], T);
     }
     // the fields of a blob's header that every blob of this engine shares
     wn::SlotStateHeader slotHeaderCommon() const {
@@ -2256,6 +2347,77 @@ protected:
             ok = wn::slots_load(stream, (const wn::SlotLoad*)(m_slotUpd + slotLoadOff()), nLoads, slotLayers(), m_ring, m_ringSlots,
                                 ringFragsPerSlot(), m_yInPrev, m_yInCur) && ok;
         return ok;
+    }
+    // ---- sampling temperature (slots_sampler.hpp) ----
+    // the host's value of column b; the first value other than 1 makes the device table (filled with log2(e); synchronises)
+    void tempSet(int b, float T) {
+        if (m_temp.empty()) {
+            if (T == 1.0f) return;
+            m_temp.assign(m_maxBatch, 1.0f);
+        }
+        if (T != 1.0f && !m_softScale) {
+            std::vector<float> unit(m_maxBatch, wn::kSoftScaleUnit);
+            gpuErrChk(hipMalloc(&m_softScale, unit.size() * sizeof(float)));
+            gpuErrChk(hipMemcpy(m_softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        m_tempNonUnit += (T != 1.0f) - (m_temp[b] != 1.0f);
+        m_temp[b] = T;
+    }
+    // every column back to T = 1, on the host and in the table (synchronises when the table has to be rewritten)
+    void resetTemperatures() {
+        if (m_softScale && (m_tempNonUnit > 0 || !m_tempDirtyList.empty())) {
+            std::vector<float> unit(m_maxBatch, wn::kSoftScaleUnit);
+            gpuErrChk(hipDeviceSynchronize());
+            gpuErrChk(hipMemcpy(m_softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        m_temp.clear();
+        m_tempNonUnit = 0;
+        m_tempDirty.clear();
+        m_tempDirtyList.clear();
+    }
+    // slot mode: ... and the next step writes the column's table entry when the value changes
+    void slotTempSet(int slot, float T) {
+        if (temperature(slot) == T) return;
+        tempSet(slot, T);
+        if (m_tempDirty.empty()) m_tempDirty.assign(m_maxBatch, 0);
+        if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
+        m_tempDirty[slot] = 1;
+    }
+    void slotTempFromHeader(int slot, const wn::SlotStateHeader& h) {
+        float T = 1.0f;
+        const bool ok = wn::temperature_of_word(h.pad[0], T);      // (slotHeaderOk has checked it)
+        assert(ok);
+        (void)ok;
+        slotTempSet(slot, T);
+    }
+    // the changed columns -> pinned staging -> device, then one slot_scale_kernel launch (staging halves as slotApplyPending, made
+    // by the first step that needs them)
+    bool slotApplyTemperatures(hipStream_t stream) {
+        if (!m_softScale) {      // (only columns that went back to 1 before anything else was set: the table does not exist)
+            for (int b : m_tempDirtyList) m_tempDirty[b] = 0;
+            m_tempDirtyList.clear();
+            return true;
+        }
+        if (!m_scaleDev) {
+            gpuErrChk(hipMalloc((void**)&m_scaleDev, (size_t)m_maxBatch * sizeof(wn::SlotScale)));
+            for (int i = 0; i < 2; i++) {
+                gpuErrChk(hipHostMalloc((void**)&m_scaleStage[i], (size_t)m_maxBatch * sizeof(wn::SlotScale), hipHostMallocDefault));
+                gpuErrChk(hipEventCreateWithFlags(&m_scaleEv[i], hipEventDisableTiming));
+                gpuErrChk(hipEventRecord(m_scaleEv[i], stream));
+            }
+        }
+        wn::SlotScale* const stage = m_scaleStage[m_scaleParity];
+        gpuErrChk(hipEventSynchronize(m_scaleEv[m_scaleParity]));
+        int n = 0;
+        for (int b : m_tempDirtyList) {
+            stage[n++] = wn::SlotScale{b, wn::temperature_scale(m_temp[b])};
+            m_tempDirty[b] = 0;
+        }
+        m_tempDirtyList.clear();
+        gpuErrChk(hipMemcpyAsync(m_scaleDev, stage, (size_t)n * sizeof(wn::SlotScale), hipMemcpyHostToDevice, stream));
+        gpuErrChk(hipEventRecord(m_scaleEv[m_scaleParity], stream));
+        m_scaleParity ^= 1;
+        return wn::slots_set_scales(stream, m_softScale, m_maxBatch, m_scaleDev, n);
     }
     // ---- mel columns (slots_mel.hpp) ----
     size_t melTileOff() const { return (size_t)m_maxBatch * sizeof(wn::MelUpdate); }
@@ -2387,6 +2549,7 @@ protected:
         p.rngKey0 = (unsigned)m_rngSeed;
         p.rngKey1 = (unsigned)(m_rngSeed >> 32);
         p.clk = m_clkOn ? m_clk : NULL;
+        p.softScale = m_softScale;
         fillSchedule(p);
         return launchWg(p, tiles, stream);
     }

@@ -1,0 +1,23 @@
+// slots_sampler.hip -- the kernel that writes the changed columns' softmax scales into the engine's table (slots_sampler.hpp).
+// Compiled once, both precisions.  At most maxBatch entries of 8 bytes per step: one thread per entry.
+#include "slots_sampler.hpp"
+
+namespace wn {
+
+__global__ __launch_bounds__(256) void slot_scale_kernel(float* __restrict__ table, int columns, const SlotScale* __restrict__ upd, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const SlotScale u = upd[i];
+        if (u.column >= 0 && u.column < columns) table[u.column] = u.scale;
+    }
+}
+
+bool slots_set_scales(hipStream_t stream, float* table, int columns, const SlotScale* upd, int n) {
+    if (n <= 0) return true;
+    if (table == NULL || upd == NULL || columns <= 0) return false;
+    int grid = (n + 255) / 256;
+    if (grid > 64) grid = 64;
+    hipLaunchKernelGGL(slot_scale_kernel, dim3(grid), dim3(256), 0, stream, table, columns, upd, n);
+    return hipGetLastError() == hipSuccess;
+}
+
+}  // namespace wn

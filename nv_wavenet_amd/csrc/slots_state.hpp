@@ -29,7 +29,8 @@ struct SlotStateHeader {
     int done;                // local samples generated so far
     unsigned uid;
     int yInPrev, yInCur;     // the column's sample history
-    int pad[6];
+    int pad[6];              // pad[0]: the sampling temperature as the bits of the float, all-zero bits for T = 1 (slots_sampler.hpp:
+                             // blobs of utterances at T = 1 are what they were before temperatures existed); the rest zero
 };
 static_assert(sizeof(SlotStateHeader) == 64, "SlotStateHeader layout");
 
@@ -51,15 +52,17 @@ struct SlotLoad {
 };
 static_assert(sizeof(SlotLoad) == 16, "SlotLoad layout");
 // one saved column of a list: where its blob goes (device memory, or the device-side address of mapped pinned host memory), the
-// rotation start mod (largest dilation), and the two header fields that differ per column
+// rotation start mod (largest dilation), and the header fields that differ per column
 struct SlotSave {
     void* dst;
     int column;
     int rot;
     int done;
     unsigned uid;
+    int temp;                // header word 10 (pad[0]): the bits of the column's sampling temperature, 0 for T = 1 (slots_sampler.hpp)
+    int pad;
 };
-static_assert(sizeof(SlotSave) == 24, "SlotSave layout");
+static_assert(sizeof(SlotSave) == 32, "SlotSave layout");
 
 // what the host reports per column of a list save, and one request of a list resume (nvw_slot_saved, nvw_slot_resume_req)
 struct SlotSaved {

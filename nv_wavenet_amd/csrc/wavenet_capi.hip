@@ -381,6 +381,24 @@ int nvw_slots_resume_list(nvw_engine* e, const nvw_slot_resume_req* reqs, int n,
                 stride, e->slotStateBytes());
     return got;
 }
+// ---- sampling temperature per utterance, lockstep and in slot mode (additive within ABI 7) ---------------------------------------
+int nvw_set_temperatures(nvw_engine* e, const float* T, int n) {
+    if (!e->setTemperatures(T, n)) {
+        fprintf(stderr, "nvw_set_temperatures: refused, nothing changed (not in slot mode; %d values for %d columns; every value finite and in "
+                "[2^-10, 2^10])\n", n, e->maxBatch());
+        return 0;
+    }
+    return 1;
+}
+int nvw_slot_set_temperature(nvw_engine* e, int slot, float T) {
+    if (!e->slotSetTemperature(slot, T)) {
+        fprintf(stderr, "nvw_slot_set_temperature: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
+                "a pending start or resume; T = %g finite and in [2^-10, 2^10])\n", slot, e->maxBatch(), (double)T);
+        return 0;
+    }
+    return 1;
+}
+float nvw_slot_temperature(nvw_engine* e, int slot) { return e->slotTemperature(slot); }
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

@@ -332,6 +332,8 @@ struct Params {
                              // (4 words): ticks of s_memtime over ticks of the constant-rate s_memrealtime = the clock the launch
                              // actually ran at (the chip clocks to its power budget: MI355X_MICROARCH.md, DVFS)
     Dil dil[kMaxLayers + 2]; // schedule of layer l; entries L and L+1 repeat layers 0 and 1 (of the next sample)
+    const float* softScale;  // RAW = 3 only: [maxBatch] floats, log2(e) / T of every column's sampling temperature T; NULL: T = 1 everywhere.
+                             // Behind everything else: no other argument's offset depends on it.
 };
 
 // ------------------------------------------------------------------------------------------
@@ -759,8 +761,10 @@ template <int LPU> WN_DEV int group_min_i(int v) {
     return v;
 }
 
+// `scale`: log2(e) / T of the utterance's sampling temperature T (Params::softScale); the default is T = 1.
+constexpr float kLog2e = 1.44269504088896340736f;
 template <int A, int LPU, int RPL>
-WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total) {
+WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total, float scale = kLog2e) {
     (void)lane;
 #pragma unroll
     for (int i = 0; i < RPL / 4; i++) {
@@ -774,12 +778,11 @@ WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&
     m = group_reduce_f<LPU>(m, [](float a, float b) { return __builtin_fmaxf(a, b); });
     float lsum = 0.f;
     {
-        // exp(x - m) = 2^(x log2 e - m log2 e): one fma in front of the v_exp_f32 instead of a subtraction and a multiplication
-        constexpr float kLog2e = 1.44269504088896340736f;
-        const float mneg = -m * kLog2e;
+        // exp((x - m) / T) = 2^(x c - m c), c = log2 e / T: one fma in front of the v_exp_f32 instead of a subtraction and a multiplication
+        const float mneg = -m * scale;
 #pragma unroll
         for (int i = 0; i < RPL; i++) {
-            e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], kLog2e, mneg));
+            e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], scale, mneg));
             lsum += e[i];
         }
     }
@@ -1262,6 +1265,16 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                 for (int k = 0; k < C::COND_FR; k++) cond_add<F16>(&acc[bt][k * P::TPF], cond_frag<F16, RAW>(cdA[bt], k), selA);
         }
         gemm_direct<F16, BT, 2 * HTW, KF_R>(wbase + C::streamPos(0, C::O_PREV, L) * 1024, laneOff, acc, xp);
+    }
+    // FEAT: log2(e) / T of the utterance this lane serves in the softmax (Params::softScale), constant over the launch
+    float sscale[FEAT ? BT : 1];
+    if constexpr (FEAT) {
+#pragma unroll
+        for (int bt = 0; bt < BT; bt++) {
+            int sb = (tile0 + bt) * 16 + su;
+            sb = sb < p.batch ? sb : p.batch - 1;
+            sscale[bt] = p.softScale != nullptr ? p.softScale[sb] : kLog2e;
+        }
     }
     const int tEnd = p.initSample + p.count;
     for (int t = p.initSample; t < tEnd; t++) {
@@ -1771,7 +1784,9 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                 float e[C::RPL];
                 float total;
                 const float* lrow = lgbuf + (bl * 16 + su) * C::LROW + sq * C::RPL;
-                const int pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total);
+                int pick;
+                if constexpr (FEAT) pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
+                else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total);
                 const int sb = (tile0 + bt) * 16 + su;
                 if (sq == 0) {
                     ybuf[bt * 16 + su] = pick;

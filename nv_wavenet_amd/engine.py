@@ -563,6 +563,31 @@ class WavenetEngine:
         lib.nvw_slots_end(self._h)
         self._slot_keep = {}
 
+    # ---- sampling temperature per utterance (include/nv_wavenet_c.h, "SAMPLING TEMPERATURE") ----
+    def setTemperatures(self, T=None):
+        """Lockstep: column b of the features-path runs that follow samples from softmax(logits / T[b]).  T: None (every column at
+        1), a float (every column), or a sequence of 1..maxBatch floats (the columns past it at 1), each finite and in
+        [2^-10, 2^10].  In force until the next call; a call between two chunks takes effect at the next chunk.  While any
+        column's T is not 1, runs on packed or in-place conditioning and on chain engines return False.  ValueError when refused
+        (nothing changes)."""
+        if T is None:
+            ok = lib.nvw_set_temperatures(self._h, None, 0)
+        else:
+            t = np.ascontiguousarray(np.full(self.maxBatch, T, dtype=np.float32) if np.isscalar(T) else np.asarray(T, dtype=np.float32).reshape(-1))
+            ok = lib.nvw_set_temperatures(self._h, t.ctypes.data, int(t.size))
+        if not ok:
+            raise ValueError("nvw_set_temperatures refused %r" % (T,))
+
+    def slotSetTemperature(self, slot, T):
+        """Slot mode: the utterance of column `slot` samples at temperature T from the next step on (after slotStart / slotResume,
+        which put the column back to 1 / to the blob's value).  ValueError when refused (nothing changes)."""
+        if not lib.nvw_slot_set_temperature(self._h, int(slot), float(T)):
+            raise ValueError("nvw_slot_set_temperature refused slot %d, T = %r" % (slot, T))
+
+    def slotTemperature(self, slot):
+        """The temperature in force for column `slot` (host state); 0.0 when the column holds no utterance."""
+        return float(lib.nvw_slot_temperature(self._h, int(slot)))
+
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):
         if yOut is None:

@@ -421,14 +421,19 @@ class NVWaveNetEngine(NVWaveNet):
         return self._engine(batch_size, sample_count, implementation).condTiles()
 
     def infer(self, cond_input, implementation=Impl.AUTO, seed=None, return_audio=False, layout="CBLN",
-              generator=None, batch_size=None):
+              generator=None, batch_size=None, temperature=None):
         """cond_input: 2R x batch x layers x samples (layout "CBLN", the reference's: converted to the engine's fragment order
         by the one permuting copy any layout change needs), [samples][layers][batch][2R] contiguous (layout "NLBC", read in
         place), or the engine's own fragment order
         (layout "packed": get_cond_input(..., layout="packed") / pack_cond_input; batch_size must be given; the generation
         kernels run their packed path on it, no copy and no conversion).
         seed: int -> selectors drawn in-kernel by Philox4x32-10; None -> torch.rand on the device.
-        Returns int32 [batch][samples] (and int16 audio [batch][samples] when return_audio)."""
+        Returns int32 [batch][samples] (and int16 audio [batch][samples] when return_audio).
+        temperature: not here -- only the kernels that compute the conditioning from the features sample at a temperature
+        (infer_features); anything but None raises ValueError."""
+        if temperature is not None:
+            raise ValueError("infer() runs on a conditioning tensor, whose kernels sample at temperature 1 only: use "
+                             "infer_features(x, cond_weight, cond_bias, temperature=...)")
         if layout == "packed":
             assert batch_size is not None and cond_input.is_cuda and cond_input.is_contiguous()
             return self._infer_packed(cond_input, batch_size, implementation, seed, return_audio, generator)
@@ -461,12 +466,19 @@ class NVWaveNetEngine(NVWaveNet):
         e.setConditioningDirect(cond_input, sample_count)
         return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
 
-    def infer_features(self, x, cond_weight, cond_bias, implementation=Impl.AUTO, seed=None, return_audio=False, generator=None):
+    def infer_features(self, x, cond_weight, cond_bias, implementation=Impl.AUTO, seed=None, return_audio=False, generator=None,
+                       temperature=None):
         """Generation with the conditioning convolution INSIDE the kernel (round 5): x = the upsampled features [batch][n_cond][samples]
         on the GPU (upsample_features(...) / the model's self.upsample output, trimmed), cond_weight / cond_bias = the model's
         cond_layers.weight / .bias.  Equivalent to infer(model.get_cond_input(features)) without ever building the
-        2R x batch x layers x samples tensor."""
+        2R x batch x layers x samples tensor.
+        temperature: None (1), a float, or a sequence of `batch` floats -- utterance b is drawn from softmax(logits / T_b); each
+        finite and in [2^-10, 2^10] (ValueError otherwise)."""
         batch_size, sample_count = x.size(0), x.size(2)
+        if temperature is not None and not isinstance(temperature, (int, float)):
+            temperature = [float(t) for t in temperature]
+            if len(temperature) != batch_size:
+                raise ValueError("%d temperatures for a batch of %d" % (len(temperature), batch_size))
         e = self._engine(batch_size, sample_count, implementation)
         dev = x.device
         key = (cond_weight.data_ptr(), cond_weight._version, cond_bias.data_ptr(), cond_bias._version)
@@ -476,7 +488,12 @@ class NVWaveNetEngine(NVWaveNet):
         stream = torch.cuda.current_stream(dev)
         stream.synchronize()
         e.setFeatures(x, sample_count)
-        return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
+        e.setTemperatures(temperature)
+        try:
+            return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
+        finally:
+            if temperature is not None:
+                e.setTemperatures(None)      # (the engine is shared with infer(), whose kernels refuse to run at another temperature)
 
     def _infer_packed(self, frags, batch_size, implementation, seed, return_audio, generator):
         sample_count = frags.size(0) - 1

@@ -45,6 +45,13 @@ process: to_bytes() is a small record and the blob, from_bytes() the way back (t
     back = [SlotState.from_bytes(d, src, pinned=True) for d, src in zip(data, sources)]
     handles = other_stream.resume_many(back)            # at the front of the queue, in this order
 
+A request may carry a sampling temperature (nvw_slot_set_temperature): the last step of the network draws from
+softmax(logits / T).  It is set when the request is submitted or at any time after -- from the next step on --, and suspend, drain,
+resume, compact and to_bytes / from_bytes keep it (a blob holds it in word 10 of its header).
+
+    h = stream.submit(features, temperature=0.8)
+    stream.set_temperature(h, 1.1)                      # waiting or running: the samples of the steps that follow
+
 step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
 (DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
 owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
@@ -69,6 +76,17 @@ from collections import deque
 import numpy as np
 
 
+def check_temperature(T):
+    """T as the engine takes it (a float32 value, finite, in [2^-10, 2^10]); ValueError otherwise."""
+    try:
+        t = float(np.float32(T))
+    except (TypeError, ValueError):
+        raise ValueError("temperature %r is not a number" % (T,))
+    if not (2.0 ** -10 <= t <= 2.0 ** 10):      # (a NaN fails both comparisons)
+        raise ValueError("temperature %r: finite and in [2^-10, 2^10]" % (T,))
+    return t
+
+
 def window_pieces(counter, count, window):
     """The generation launches of a step: (first window row, samples) for samples [counter, counter + count) of a window of
     `window` rows -- one piece, or two where the rows wrap (the split nvWavenetInfer::slotsStep makes)."""
@@ -81,16 +99,20 @@ def window_pieces(counter, count, window):
 class SlotState:
     """A suspended request (SlotStream.suspend): blob = the column's state, a CUDA uint8 tensor of WavenetEngine.slotSave (None: the
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
-    frames, final = of a mel request (frames written so far, no more to come)."""
+    frames, final = of a mel request (frames written so far, no more to come); temperature = its sampling temperature (the one in
+    the blob's header, word 10; a resume goes on at this attribute's value)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
     RECORD_BYTES = RECORD.size
     RECORD_MAGIC, RECORD_VERSION = b"NWSS", 1
-    BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid
+    BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid,
+    TEMPERATURE_WORD = 10                    # word 10 the temperature as the bits of the float (zero: 1.0)
 
-    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0):
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0):
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
+        self.temperature = check_temperature(temperature)
+        self._blob_temperature = self.temperature if blob is not None else 1.0      # (what the engine reads from the header on resume)
         # the blob as a row of a buffer that SlotStream hands to slotsResumeList (suspend_many, drain, from_bytes(pinned=True));
         # None: a blob of its own -- a CUDA tensor of suspend(), resumed by slotResume, or a CPU tensor of from_bytes(), uploaded
         self.buffer, self.row = buffer, row
@@ -98,8 +120,14 @@ class SlotState:
     def to_bytes(self):
         """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
         tensor is not included.  A blob on the GPU is copied to the host here -- a synchronising copy --, and for a pinned blob
-        the call waits for the device to have written it."""
+        the call waits for the device to have written it.  A request that had not started has no blob; with a temperature other
+        than 1 it carries the 64 bytes of a header alone (magic, uid, done = 0 and word 10), so that the value survives."""
         blob = b""
+        if self.blob is None and self.temperature != 1.0:
+            hdr = np.zeros(16, dtype="<u4")
+            hdr[0], hdr[1], hdr[7] = self.BLOB_MAGIC, 1, int(self.uid) & 0xFFFFFFFF
+            hdr[self.TEMPERATURE_WORD] = np.array([self.temperature], dtype="<f4").view("<u4")[0]
+            blob = hdr.tobytes()
         if self.blob is not None:
             if getattr(self.blob, "is_cuda", False):
                 blob = self.blob.cpu().numpy().tobytes()
@@ -127,15 +155,20 @@ class SlotState:
         if len(data) != cls.RECORD_BYTES + nblob or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
+        temperature = 1.0
         if nblob:
             words = np.frombuffer(data, dtype="<u4", count=16, offset=cls.RECORD_BYTES)
             if int(words[0]) != cls.BLOB_MAGIC or int(words[6]) != done or int(words[7]) != uid:
                 raise ValueError("the blob's header does not belong to the record (magic %#x, done %d, uid %d)" % tuple(words[[0, 6, 7]]))
+            if int(words[cls.TEMPERATURE_WORD]):
+                temperature = check_temperature(words[cls.TEMPERATURE_WORD:cls.TEMPERATURE_WORD + 1].view("<f4")[0])
+        if nblob > 64 or (nblob and done):      # (64 bytes with done = 0: the header alone of a request that had not started)
             host = torch.empty((1, nblob), dtype=torch.uint8, pin_memory=bool(pinned))
             host[0].numpy()[:] = np.frombuffer(data, dtype=np.uint8, count=nblob, offset=cls.RECORD_BYTES)
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
-        return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0)
+        return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
+                   temperature)
 
 
 class StepOutput:
@@ -219,6 +252,7 @@ class SlotStream:
         self._src = {}                                 # handle -> (source tensor, uid) of the running requests
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
+        self._temp = {}                                # handle -> sampling temperature of the requests (queued or running) whose T is not 1
         # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
         # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
         self._arrays = False
@@ -234,24 +268,29 @@ class SlotStream:
         self._next_handle = 0
         self._next_uid = 0
 
-    def submit(self, features, uid=None):
+    def submit(self, features, uid=None, temperature=1.0):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
-        (default: 0, 1, 2, ... in submission order) -- the same features and uid give the same samples whenever they run."""
+        (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
+        run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
+        [2^-10, 2^10])."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
+        temperature = check_temperature(temperature)
         handle = self._next_handle
         self._next_handle += 1
         if uid is None:
             uid = self._next_uid
         self._next_uid = max(self._next_uid, int(uid) + 1)
         self._queue.append((handle, features, int(uid), None))
+        self._note_temperature(handle, temperature)
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
-        final: no more will come); returns its handle.  uid as for submit."""
+        final: no more will come); returns its handle.  uid and temperature as for submit."""
         assert mel.dim() == 2, "mel: [n_cond][frames]"
         n = mel.size(1) if frames is None else int(frames)
         assert 0 <= n <= mel.size(1) and (n > 0 or not final)
+        temperature = check_temperature(temperature)
         handle = self._next_handle
         self._next_handle += 1
         if uid is None:
@@ -260,7 +299,33 @@ class SlotStream:
         req = [n, bool(final), None, 0]
         self._mel[handle] = req
         self._queue.append((handle, mel, int(uid), req))
+        self._note_temperature(handle, temperature)
         return handle
+
+    def _note_temperature(self, handle, T):
+        if T != 1.0:
+            self._temp[handle] = T
+        else:
+            self._temp.pop(handle, None)
+
+    def set_temperature(self, handle, temperature):
+        """Request `handle` samples at `temperature` from the next step on: a running one through the engine at once (its column's
+        value changes with that step's first sample), a waiting one when it is admitted.  KeyError for a handle the stream does
+        not hold, ValueError for a bad value -- nothing changes."""
+        T = check_temperature(temperature)
+        col = self.running().get(handle)
+        if col is None:
+            if not any(item[0] == handle for item in self._queue):
+                raise KeyError(handle)
+        else:
+            self.engine.slotSetTemperature(col, T)
+        self._note_temperature(handle, T)
+
+    def temperature(self, handle):
+        """The temperature request `handle` (queued or running) samples at."""
+        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        return self._temp.get(handle, 1.0)
 
     def extend_mel(self, handle, frames, final=False):
         """The first `frames` frames of mel request `handle` are written (queued or running); final: no more will come."""
@@ -328,29 +393,34 @@ class SlotStream:
     def _dequeued(self, item):
         """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
         handle, req = item[0], item[3]
+        T = self._temp.pop(handle, 1.0)
         if req is not None:
             del self._mel[handle]
         if len(item) > 4:
             if req is not None:
                 item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
+            item[4].temperature = T                                 # (... or given another temperature)
             return item[4]
-        return SlotState(None, item[1], item[2], 0, "features") if req is None else SlotState(None, item[1], item[2], 0, "mel", req[0], req[1])
+        if req is None:
+            return SlotState(None, item[1], item[2], 0, "features", temperature=T)
+        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T)
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
         self.engine.slotStop(col)
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
+        T = self._temp.pop(handle, 1.0)      # (the engine has written the same value into the blob's header)
         heapq.heappush(self._free, col)
         self._ch[col] = -1
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row)
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T)
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row)
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T)
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -420,6 +490,7 @@ class SlotStream:
         if state.kind == "mel":
             req = self._mel[handle] = [int(state.frames), bool(state.final), None, int(state.done)]
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
+        self._note_temperature(handle, check_temperature(state.temperature))
         return handle
 
     def _use_arrays(self, on):
@@ -442,6 +513,7 @@ class SlotStream:
     def _admit(self, count):
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
+        tempered = []    # (column, temperature) of the admitted requests whose temperature is not what their start leaves the column at
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
             item = self._queue.popleft()
@@ -451,6 +523,9 @@ class SlotStream:
             # a row of a shared buffer, or a CPU tensor still to be uploaded: by list; a CUDA blob of its own (suspend()): singly
             by_list = blob is not None and (state.buffer is not None or not getattr(blob, "is_cuda", True))
             self._src[handle] = (x, uid)
+            T = self._temp.get(handle, 1.0)
+            if T != (state._blob_temperature if blob is not None else 1.0):      # (a start leaves 1, a resume the header's value)
+                tempered.append((col, T))
             if req is None:
                 if blob is None:
                     self.engine.slotStart(col, x, uid)
@@ -474,6 +549,8 @@ class SlotStream:
                 self._deliv[col] = req[3] if req is not None else 0
         if listed:
             self._resume_listed(listed)
+        for col, T in tempered:      # (start, then set: the engine applies both at the step that follows)
+            self.engine.slotSetTemperature(col, T)
 
     def _resume_listed(self, listed):
         """One slotsResumeList call per run of consecutive rows of a shared buffer, in the order admitted (after drain() and
@@ -531,6 +608,7 @@ class SlotStream:
                     del self._mel[rec[0]]
                 del self._running[col]
                 del self._src[rec[0]]
+                self._temp.pop(rec[0], None)
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
                 self._done.append(rec[0])
@@ -540,6 +618,7 @@ class SlotStream:
         """The request of column `col` has had its last sample issued: the column stops at the next step and is free."""
         handle = self._running.pop(col)[0]
         self._mel.pop(handle, None)
+        self._temp.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1
         self.engine.slotStop(col)

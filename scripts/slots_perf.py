@@ -45,7 +45,16 @@ column 5 of every tile stop, the survivors are compacted to the front --, in one
 Prints one JSON line with medians, min .. max over the rounds, GB/s of blob bytes (read + written), and the verdict on the claim
 that the list save into device memory beats the single saves by more than the run-to-run spread.
 
+--temperature times what the per-column sampling temperature costs a slot step, three cases back to back in one
+process, `--rounds` rounds, the cases alternating within a round: the PARENT commit's step (a libwavenet_infer.so built from it,
+--parent-lib; loaded beside this commit's and driven through the same ctypes calls), this commit with every T = 1 (no table, the
+kernel argument NULL) and this commit with mixed T (0.7, 0.85, 1, 1.2 cycling over the columns: the table and its scatter launch).
+Every column runs one long utterance (no restarts: the same work in every case and round).  Prints one JSON line per chunk size
+with the per-round ms per step of each case, the medians, the parent's run-to-run spread (max - min over median) and the verdict:
+neither case of this commit slower than the parent by more than twice that spread.
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --drain [--batch 12288] [--rounds 5]
@@ -74,6 +83,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="--compact, --serve, --drain: rounds of measurements")
     ap.add_argument("--drain", action="store_true", help="time list saves (device, pinned) and list resumes against one call per column")
     ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
+    ap.add_argument("--temperature", action="store_true", help="time the slot step of the parent commit, of this one at T = 1 and at mixed T")
+    ap.add_argument("--parent-lib", default=None, help="--temperature: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
     import torch
     import bench
@@ -82,6 +93,10 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.temperature:
+        for chunk in [int(c) for c in args.chunks.split(",")]:
+            print(json.dumps(time_temperature(args, w, Wc, bc, chunk)), flush=True)
+        return
     if args.compact:
         print(json.dumps(time_compact(args, w, Wc, bc)), flush=True)
         return
@@ -172,6 +187,96 @@ def main():
             res.update({"mel_ms_per_step": round(mel_ms, 3), "mel_rate_vs_slots": round(slot_ms / mel_ms, 4),
                         "mel_restarts_per_timed_step": round(mel_restarts / steps, 1)})
         print(json.dumps(res), flush=True)
+
+
+def time_temperature(args, w, Wc, bc, chunk):
+    """The --temperature measurement (module docstring) for steps of `chunk` samples."""
+    import ctypes as C
+    import torch
+    import bench
+    from nv_wavenet_amd import _lib
+    B, W = args.batch, args.window
+    sh = bench.HEAD
+    vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
+    sigs = {"nvw_create_ex": (vp, [ci] * 11), "nvw_destroy": (None, [vp]), "nvw_set_embeddings": (None, [vp, vp, vp]),
+            "nvw_set_layer_weights": (None, [vp, ci] + [vp] * 7), "nvw_set_out_weights": (None, [vp] * 5),
+            "nvw_set_conditioning_weights": (ci, [vp, vp, vp, ci]), "nvw_set_selector_seed": (None, [vp, C.c_ulonglong]),
+            "nvw_slots_begin": (ci, [vp, ci]), "nvw_slot_start": (ci, [vp, ci, vp, ci, ll, ll, ci, C.c_uint]),
+            "nvw_slots_step": (ci, [vp, ci, vp, vp, vp]), "nvw_slots_end": (None, [vp]), "nvw_kernel_info": (None, [vp, ci, ci, C.c_char_p, ci])}
+
+    def load(path):
+        h = C.CDLL(path)
+        for name, (res, argt) in sigs.items():
+            getattr(h, name).restype, getattr(h, name).argtypes = res, argt
+        return h
+
+    here = load(_lib.LIB_PATH)
+    here.nvw_slot_set_temperature.restype, here.nvw_slot_set_temperature.argtypes = ci, [vp, ci, C.c_float]
+    libs = {"unit": here, "mixed": here}
+    if args.parent_lib:
+        libs = dict({"parent": load(args.parent_lib)}, **libs)
+        assert not hasattr(libs["parent"], "nvw_slot_set_temperature"), "--parent-lib has the temperature entries: not the parent commit's"
+    g = torch.Generator(device="cuda")
+    g.manual_seed(7)
+    warm, steps = 2, max(2, args.steps * 256 // chunk)
+    need = (warm + args.rounds * steps) * chunk
+    T_SRC = need + 4096
+    src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
+    rng = np.random.default_rng(3)
+    offs = rng.integers(0, 4096, size=B)
+    mixed = (0.7, 0.85, 1.0, 1.2)
+    a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
+    engines, info = {}, {}
+    for case, h in libs.items():
+        e = h.nvw_create_ex(sh.R, sh.S, sh.A, 16, sh.L, sh.maxD, B, W, 0, 1, 0)
+        assert e, case
+        h.nvw_set_embeddings(e, a(w["embP"]), a(w["embC"]))
+        for l in range(sh.L):
+            h.nvw_set_layer_weights(e, l, *[a(w[k][l]) for k in ("Wprev", "Wcur", "Bh", "Wres", "Bres", "Wskip", "Bskip")])
+        h.nvw_set_out_weights(e, a(w["Wzs"]), a(w["Bzs"]), a(w["Wza"]), a(w["Bza"]))
+        assert h.nvw_set_conditioning_weights(e, a(Wc), a(bc), bench.N_COND)
+        h.nvw_set_selector_seed(e, 5)
+        assert h.nvw_slots_begin(e, W)
+        for b in range(B):
+            x = src[:, int(offs[b]):int(offs[b]) + need]
+            assert h.nvw_slot_start(e, b, x.data_ptr(), 16, x.stride(0), x.stride(1), need, b)
+            if case == "mixed":
+                assert h.nvw_slot_set_temperature(e, b, mixed[b % len(mixed)])
+        buf = C.create_string_buffer(256)
+        h.nvw_kernel_info(e, B, 0, buf, 256)
+        engines[case], info[case] = e, buf.value.decode()
+    y = torch.empty(B, chunk, dtype=torch.int32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for case, h in libs.items():
+        for _ in range(warm):
+            assert h.nvw_slots_step(engines[case], chunk, y.data_ptr(), None, s)
+    torch.cuda.synchronize()
+    ms = {case: [] for case in libs}
+    for _ in range(args.rounds):
+        for case, h in libs.items():
+            ev[0].record()
+            for _ in range(steps):
+                assert h.nvw_slots_step(engines[case], chunk, y.data_ptr(), None, s)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms[case].append(ev[0].elapsed_time(ev[1]) / steps)
+    for case, h in libs.items():
+        h.nvw_slots_end(engines[case])
+        h.nvw_destroy(engines[case])
+    torch.cuda.empty_cache()
+    med = {case: float(np.median(v)) for case, v in ms.items()}
+    res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps, "mixed_temperatures": mixed,
+           "ms_per_step": {case: [round(v, 3) for v in vs] for case, vs in ms.items()}, "median_ms_per_step": {k: round(v, 3) for k, v in med.items()},
+           "kernel": info["unit"], "device": torch.cuda.get_device_name(0)}
+    if "parent" in ms:
+        spread = (max(ms["parent"]) - min(ms["parent"])) / med["parent"]
+        res.update({"parent_spread": round(spread, 4), "unit_vs_parent": round(med["unit"] / med["parent"], 4),
+                    "mixed_vs_parent": round(med["mixed"] / med["parent"], 4), "parent_kernel": info["parent"],
+                    "within_twice_the_parent_spread": bool(max(med["unit"], med["mixed"]) <= med["parent"] * (1.0 + 2.0 * spread))})
+    else:
+        res["parent"] = "not measured (no --parent-lib)"
+    return res
 
 
 def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
