@@ -58,29 +58,8 @@ struct nvw_engine {
     virtual void getZa(float*) = 0;
     virtual void getP(float*) = 0;
     virtual void getYOut(int*, int, int, hipStream_t) = 0;
-    virtual bool slotsBegin(int) = 0;
-    virtual bool slotStart(int, const void*, int, long long, long long, int, unsigned) = 0;
-    virtual bool slotStop(int) = 0;
-    virtual bool slotsStep(int, int*, short*, hipStream_t) = 0;
-    virtual void slotsEnd() = 0;
-    virtual bool slotStartMel(int, const void*, int, long long, long long, int, int, unsigned) = 0;
-    virtual bool slotMelFrames(int, int, int) = 0;
-    virtual int slotsHeadroom() = 0;
-    virtual bool slotsGetFeatures(void*, long long, int) = 0;
-    virtual size_t slotStateBytes() = 0;
-    virtual bool slotMove(int, int) = 0;
-    virtual int slotSave(int, void*, hipStream_t) = 0;
-    virtual bool slotResume(int, const void*, const void*, int, long long, long long, int) = 0;
-    virtual bool slotResumeMel(int, const void*, const void*, int, long long, long long, int, int) = 0;
-    virtual int slotsSaveList(const int*, int, void*, long long, nvw_slot_saved*, hipStream_t) = 0;
-    virtual int slotsResumeList(const nvw_slot_resume_req*, int, const void*, long long) = 0;
-    virtual long long slotsStepRagged(int, int*, short*, long long, nvw_slot_piece*, int, int*, unsigned long long*, hipStream_t) = 0;
-    virtual bool slotsWait(unsigned long long) = 0;
-    virtual int slotsDone(unsigned long long) = 0;
-    virtual float slotsTimeOutputs(bool, int, int*, short*, long long, int, hipStream_t) = 0;
     virtual bool setTemperatures(const float*, int) = 0;
-    virtual bool slotSetTemperature(int, float) = 0;
-    virtual float slotTemperature(int) = 0;
+    virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
               offsetof(nvw_slot_piece, uid) == offsetof(wn::SlotPiece, uid) && offsetof(nvw_slot_piece, finished) == offsetof(wn::SlotPiece, finished) &&
@@ -171,46 +150,8 @@ struct EngineImpl : nvw_engine {
     void getZa(float* d) override { eng.getZa(d); }
     void getP(float* d) override { eng.getP(d); }
     void getYOut(int* y, int off, int size, hipStream_t s) override { eng.getYOut(y, off, size, s); }
-    bool slotsBegin(int window) override { return eng.slotsBegin(window); }
-    bool slotStart(int slot, const void* x, int prec, long long cS, long long tS, int length, unsigned uid) override {
-        return eng.slotStart(slot, x, prec, cS, tS, length, uid);
-    }
-    bool slotStop(int slot) override { return eng.slotStop(slot); }
-    bool slotsStep(int count, int* y, short* pcm, hipStream_t s) override { return eng.slotsStep(count, y, pcm, s); }
-    void slotsEnd() override { eng.slotsEnd(); }
-    bool slotStartMel(int slot, const void* mel, int prec, long long cS, long long fS, int frames, int final, unsigned uid) override {
-        return eng.slotStartMel(slot, mel, prec, cS, fS, frames, final, uid);
-    }
-    bool slotMelFrames(int slot, int frames, int final) override { return eng.slotMelFrames(slot, frames, final); }
-    int slotsHeadroom() override { return eng.slotsHeadroom(); }
-    bool slotsGetFeatures(void* dst, long long first, int count) override { return eng.slotsGetFeatures(dst, first, count); }
-    size_t slotStateBytes() override { return eng.slotStateBytes(); }
-    bool slotMove(int from, int to) override { return eng.slotMove(from, to); }
-    int slotSave(int slot, void* dst, hipStream_t s) override { return eng.slotSave(slot, dst, s); }
-    bool slotResume(int slot, const void* state, const void* x, int prec, long long cS, long long tS, int length) override {
-        return eng.slotResume(slot, state, x, prec, cS, tS, length);
-    }
-    bool slotResumeMel(int slot, const void* state, const void* mel, int prec, long long cS, long long fS, int frames, int final) override {
-        return eng.slotResumeMel(slot, state, mel, prec, cS, fS, frames, final);
-    }
-    int slotsSaveList(const int* slots, int n, void* dst, long long stride, nvw_slot_saved* saved, hipStream_t s) override {
-        return eng.slotsSaveList(slots, n, dst, stride, (wn::SlotSaved*)saved, s);
-    }
-    int slotsResumeList(const nvw_slot_resume_req* reqs, int n, const void* states, long long stride) override {
-        return eng.slotsResumeList((const wn::SlotResumeReq*)reqs, n, states, stride);
-    }
-    long long slotsStepRagged(int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces, int maxPieces, int* nPieces,
-                              unsigned long long* ticket, hipStream_t s) override {
-        return eng.slotsStepRagged(count, samples, pcm, capacity, (wn::SlotPiece*)pieces, maxPieces, nPieces, ticket, s);
-    }
-    bool slotsWait(unsigned long long ticket) override { return eng.slotsWait(ticket); }
-    int slotsDone(unsigned long long ticket) override { return eng.slotsDone(ticket); }
-    float slotsTimeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t s) override {
-        return eng.slotsTimeOutputs(ragged, count, samples, pcm, capacity, reps, s);
-    }
     bool setTemperatures(const float* T, int n) override { return eng.setTemperatures(T, n); }
-    bool slotSetTemperature(int slot, float T) override { return eng.slotSetTemperature(slot, T); }
-    float slotTemperature(int slot) override { return eng.slotTemperature(slot); }
+    wn::SlotSession& slots() override { return eng.slots(); }
 };
 
 typedef nvw_engine* (*nvw_factory_fn)(int L, int maxD, int B, int N, int impl, int tanhEmbed, int organisation);

@@ -32,26 +32,14 @@
 #include <string.h>
 
 #include <cmath>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
-#include "slots.hpp"
-#include "slots_mel.hpp"
-#include "slots_state.hpp"
-#include "slots_deliver.hpp"
-#include "slots_sampler.hpp"
+#include "gpu_check.hpp"
+#include "slots_session.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
-
-#ifndef gpuErrChk
-#define gpuErrChk(ans) { wnGpuAssert((ans), __FILE__, __LINE__); }
-inline void wnGpuAssert(hipError_t code, const char* file, int line, bool abort = true) {
-    if (code != hipSuccess) {
-        fprintf(stderr, "GPUassert: %s %s %d\n", hipGetErrorString(code), file, line);
-        if (abort) exit(code);
-    }
-}
-#endif
 
 // kernel organisations (beyond the reference: its Implementation enum maps onto these, see above)
 enum nvwOrganisation {
@@ -70,7 +58,7 @@ enum nvwOrganisation {
 };
 
 template <typename T_weight, typename T_data, int R = 64, int S = 128, int A = 256>
-class nvWavenetInfer {
+class nvWavenetInfer : protected wn::SlotHost {
 public:
     enum Implementation { AUTO = 0, SINGLE_BLOCK, DUAL_BLOCK, PERSISTENT, MANYBLOCK_NONPERSISTENT };
 
@@ -154,70 +142,10 @@ protected:
     unsigned long long* m_clk;   // clock probe of the latest wavenet_wg launch (wn::Params::clk), when switched on
     bool m_clkOn;
 
-    // slot mode (slotsBegin .. slotsEnd; slots.hpp): one utterance per column, each started and stopped on its own
-    int m_slotW = 0;                        // window (samples); 0: not in slot mode
-    long long m_slotCounter = 0;            // samples generated since slotsBegin: window row of the next step = counter mod W
-    std::vector<wn::SlotDesc> m_slotHost;   // the columns' descriptors as the host has set them ...
-    std::vector<int> m_slotPending;         // ... and what the next step applies per column: 0 nothing, 1 start, 2 stop
-    std::vector<int> m_slotPendingList;
-    wn::SlotDesc* m_slotDesc = NULL;        // [maxBatch] on the device
-    elem* m_slotFeat = NULL;                // [W][tiles][KFC] feature fragments
-    float* m_slotSel = NULL;                // [W][maxBatch] selectors
-    int* m_slotY = NULL;                    // [maxBatch][W] samples
-    short* m_slotPcm = NULL;                // [maxBatch][W] int16 PCM
-    char* m_slotUpd = NULL;                 // device copy of a step's updates + restarted columns
-    char* m_slotStage[2] = {NULL, NULL};    // pinned host staging of them, used by alternate steps ...
-    hipEvent_t m_slotEv[2] = {NULL, NULL};  // ... each reused once the copy of the step before last has completed
-    int m_slotParity = 0;
-    // ... and its mel columns (slots_mel.hpp): utterances handed over as frames, upsampled step by step
-    std::vector<wn::MelDesc> m_melHost;     // the columns' mel descriptors as the host has set them (state 0: not a mel column) ...
-    std::vector<char> m_melDirty;           // ... and the columns whose descriptor the next step writes
-    std::vector<int> m_melDirtyList;
-    int m_melColumns = 0;                   // columns with state != 0
-    bool m_melTilesDirty = false;           // the tile list changes at the next step
-    int m_melTiles = 0;                     // tiles in the device's list
-    bool m_melPrepared = false;             // slots_mel_prepare done for this engine
-    wn::MelDesc* m_melDesc = NULL;          // [maxBatch] on the device
-    char* m_melUpd = NULL;                  // device: a step's updates [maxBatch] + the list of tiles with mel columns [tiles]
-    char* m_melStageHost[2] = {NULL, NULL}; // pinned host staging of them, used by alternate steps as m_slotStage
-    hipEvent_t m_melEv[2] = {NULL, NULL};
-    int m_melParity = 0;
-    elem* m_melStage = NULL;                // the step's frames in fragment order, [stage frames][mel tiles][KFC], then at m_melRecOff
-    size_t m_melStageElems = 0;             // the step's upsampled samples per column, [mel tiles * 16][count] of KFC KiB / 16
-    size_t m_melRecOff = 0;
-    int* m_melColInfo = NULL;               // [tiles * 16] int2: per column, phase of its first sample and samples it stores
-    // ... and columns' states as values (slots_state.hpp): moved, saved, resumed
-    std::vector<const void*> m_slotResume;  // per column: the blob its pending start resumes from (NULL: a new utterance) ...
-    std::vector<int> m_slotResumeDone;      // ... and the local samples that blob has behind it (0: a new utterance)
-    std::vector<char> m_slotMoveEnd;        // per column: 1 source, 2 destination of a pending move
-    std::vector<wn::SlotMove> m_slotMoves;  // the pending moves
-    wn::SlotLayer* m_slotLayers = NULL;     // the schedule per ring slot on the device (built by the first save or resume)
-    // ... and lists of columns saved in one launch: the entries' staging, made by the first list save
-    wn::SlotSave* m_saveDev[2] = {NULL, NULL};      // [maxBatch] on the device, used by alternate list saves ...
-    wn::SlotSave* m_saveStage[2] = {NULL, NULL};    // ... their pinned host staging ...
-    hipEvent_t m_saveEv[2] = {NULL, NULL};          // ... each reused once the save before last has completed
-    bool m_saveUsed[2] = {false, false};            // (a half that has carried no save yet has nothing to wait for)
-    int m_saveParity = 0;
-    std::vector<int> m_listMark;                    // scratch of the list calls: per column, the index + 1 of the entry that names it
-    // ... and ragged delivery (slots_deliver.hpp): a step's valid samples piece by piece, completion by ticket
-    static constexpr int kSlotTickets = 4;  // events kept: a ticket older than that is complete (the stream is ordered)
-    wn::DeliverPiece* m_dlvDev = NULL;      // [maxBatch] on the device: the pieces of the step being delivered
-    wn::DeliverPiece* m_dlvStage[kSlotTickets] = {};      // pinned host staging of them, one per ticket in flight ...
-    hipEvent_t m_dlvEv[kSlotTickets] = {};  // ... and the event recorded after that ticket's delivery
-    unsigned long long m_dlvTicket = 0;     // the last ticket given out (they count from 1)
-
-    // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode: the host's values are the
-    // authority, the device table follows them.  Nothing is allocated, and Params::softScale stays NULL, until a temperature other
-    // than 1 has been set: an engine that never uses the feature launches what it launched before.
-    std::vector<float> m_temp;              // [maxBatch] T per column (empty: 1 everywhere)
-    int m_tempNonUnit = 0;                  // columns with T != 1
-    float* m_softScale = NULL;              // [maxBatch] log2(e) / T on the device, made at the first use and filled with log2(e)
-    std::vector<char> m_tempDirty;          // slot mode: the columns whose table entry the next step writes
-    std::vector<int> m_tempDirtyList;
-    wn::SlotScale* m_scaleDev = NULL;       // [maxBatch] on the device: a step's changed entries ...
-    wn::SlotScale* m_scaleStage[2] = {NULL, NULL};      // ... their pinned host staging, used by alternate steps as m_slotStage
-    hipEvent_t m_scaleEv[2] = {NULL, NULL};
-    int m_scaleParity = 0;
+    // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode
+    wn::TemperatureTable m_temps;
+    // slot mode (slots_session.hpp): made at the end of the constructor, when the facts it is given are known
+    std::unique_ptr<wn::SlotSession> m_slots;
 
     // events of run_chunks / run_stream, made on first use and kept
     std::vector<hipEvent_t> m_poolEvents;
@@ -229,15 +157,7 @@ protected:
         }
         return m_poolEvents[i];
     }
-    static bool isDevicePtr(const void* ptr) {
-        hipPointerAttribute_t attr;
-        hipError_t e = hipPointerGetAttributes(&attr, ptr);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-    }
+    static bool isDevicePtr(const void* ptr) { return wn::is_device_ptr(ptr); }
     // ---- staging of fp32 host sources: every array of ONE upload call gets its own place in the
     //      staging buffer, so the pack kernels of that call can all be in flight; the public set* calls
     //      end with one stream synchronisation (the caller may free or reuse its buffers afterwards)
@@ -559,7 +479,7 @@ public:
           m_feat(NULL), m_featPtr(NULL), m_featSamples(0),
           m_mail(NULL), m_chainStatus(NULL), m_mailBytes(0), m_ringShadow(NULL), m_histShadow(NULL),
           m_chainTimeoutTicks(wn::kChainTimeoutTicks), m_stage(NULL), m_stageElems(0), m_useRng(false), m_rngSeed(0), m_pcm(NULL),
-          m_mulaw(NULL), m_pcmUser(NULL), m_pcmUserElems(0), m_clk(NULL), m_clkOn(false), m_stageUsed(0) {
+          m_mulaw(NULL), m_pcmUser(NULL), m_pcmUserElems(0), m_clk(NULL), m_clkOn(false), m_temps(batchSize), m_stageUsed(0) {
         assert(numLayers >= 2 && batchSize > 0 && numSamples > 0 && maxDilation > 0);
         m_ringDirtyTiles = 0;
         m_ringLdsMode = 0;
@@ -677,11 +597,14 @@ public:
             }
         }
         gpuErrChk(hipDeviceSynchronize());
+        m_slots.reset(new wn::SlotSession(wn::SlotFacts{m_maxBatch, m_tiles, m_numLayers, m_maxDilation, m_ringSlots, (int)(R * 16 * sizeof(elem) / 1024), R,
+                                                        F16, featureElems(1), m_supported, m_ring, m_yInPrev, m_yInCur},
+                                          *this, m_temps));
     }
 
     virtual ~nvWavenetInfer() {
         gpuErrChk(hipDeviceSynchronize());
-        slotsEnd();
+        m_slots.reset();
         for (hipEvent_t ev : m_poolEvents) gpuErrChk(hipEventDestroy(ev));
         gpuErrChk(hipFree(m_wblob));
         gpuErrChk(hipFree(m_bias));
@@ -697,15 +620,6 @@ public:
         if (m_upTab) gpuErrChk(hipFree(m_upTab));
         if (m_upBias) gpuErrChk(hipFree(m_upBias));
         if (m_melFrag) gpuErrChk(hipFree(m_melFrag));
-        if (m_slotLayers) gpuErrChk(hipFree(m_slotLayers));
-        if (m_softScale) gpuErrChk(hipFree(m_softScale));
-        if (m_scaleDev) {
-            gpuErrChk(hipFree(m_scaleDev));
-            for (int i = 0; i < 2; i++) {
-                gpuErrChk(hipHostFree(m_scaleStage[i]));
-                gpuErrChk(hipEventDestroy(m_scaleEv[i]));
-            }
-        }
         gpuErrChk(hipFree(m_outputSelectors));
         gpuErrChk(hipFree(m_ring));
         gpuErrChk(hipFree(m_yInPrev));
@@ -1184,7 +1098,7 @@ public:
     // template arguments, tiles per workgroup, workgroups, dynamic LDS bytes (for benchmarks / logs).
     void kernelInfo(int batch_size, bool dumpActivations, char* buf, int n) const {
         const int tiles = (batch_size + 15) / 16;
-        const bool feat = m_featPtr != NULL || m_slotW > 0;      // (a slot-mode step launches wavenet_wg<.., RAW=3> as the features path)
+        const bool feat = m_featPtr != NULL || m_slots->active();      // (a slot-mode step launches wavenet_wg<.., RAW=3> as the features path)
         const bool chainLaunch = isChain() && !feat;
         const bool dump = dumpActivations || (!F16 && !chainLaunch && (feat || m_condRaw));      // (see launch())
         if (chainLaunch) {
@@ -1271,25 +1185,21 @@ public:
     // false (nothing changes): in slot mode (slotSetTemperature is the call there), n outside the batch with a non-NULL T, or a
     // bad value.
     bool setTemperatures(const float* T, int n) {
-        if (m_slotW > 0) return false;
+        if (m_slots->active()) return false;
         if (T != NULL) {
             if (n < 1 || n > m_maxBatch) return false;
             for (int b = 0; b < n; b++)
                 if (!wn::temperature_ok(T[b])) return false;
         }
         gpuErrChk(hipDeviceSynchronize());
-        resetTemperatures();
+        m_temps.reset(false);
         if (T == NULL) return true;
-        for (int b = 0; b < n; b++) tempSet(b, T[b]);
-        if (m_softScale) {
-            std::vector<float> c(m_maxBatch);
-            for (int b = 0; b < m_maxBatch; b++) c[b] = wn::temperature_scale(temperature(b));      // (m_temp is empty when every value is 1)
-            gpuErrChk(hipMemcpy(m_softScale, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+        for (int b = 0; b < n; b++) m_temps.set(b, T[b]);
+        m_temps.upload();
         return true;
     }
     // the temperature in force for column b (1 when none was ever set)
-    float temperature(int b) const { return (b >= 0 && b < (int)m_temp.size()) ? m_temp[b] : 1.0f; }
+    float temperature(int b) const { return m_temps.get(b); }
 
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to
@@ -1369,11 +1279,11 @@ public:
         assert(m_pcmUser == NULL || m_pcmUserElems == 0 || m_pcmUserElems >= (size_t)batch_size * num_samples);
         if (m_implementation == SINGLE_BLOCK) assert(S <= 4 * R);
         if (!m_supported) return false;
-        if (m_tempNonUnit > 0 && !m_featPtr) {
+        if (m_temps.nonUnit > 0 && !m_featPtr) {
             // only the kernels that compute the conditioning from the features read the temperatures: nothing is generated rather than
             // generated at T = 1
             fprintf(stderr, "nvWavenetInfer: %d columns have a sampling temperature other than 1, which packed or in-place conditioning "
-                    "and multi-CU launches cannot honour: use the features path, or setTemperatures(NULL, 0)\n", m_tempNonUnit);
+                    "and multi-CU launches cannot honour: use the features path, or setTemperatures(NULL, 0)\n", m_temps.nonUnit);
             return false;
         }
 
@@ -1381,23 +1291,10 @@ public:
         // itself).  resetHistory() -- every way of handing over a new utterance's conditioning calls it -- has normally done this
         // already, outside the generation's critical path; this covers run() after run() on the same inputs.
         if (init_sample == 0) clearRings(stream);
-        {
-            // the tiles whose rings this launch writes: a wavenet_wg workgroup of BT tiles stores into the rings of ALL its tiles, the
-            // padding tiles beyond the batch included (a later, larger batch must find those slots zero as well)
-            int touched = (batch_size + 15) / 16;
-            if (!(isChain() && !m_featPtr)) {
-                int bt = wgTiles(touched);
-                if (bt >= 3 && wg4Fits()) bt = 12;      // (three or four tiles per workgroup by launch: both roundings)
-                touched = (touched + bt - 1) / bt * bt;
-            }
-            if (touched > m_tiles) touched = m_tiles;
-            if (touched > m_ringDirtyTiles) m_ringDirtyTiles = touched;
-        }
-        wn::Params p;
-        p.wblob = m_wblob;
-        p.bias = m_bias;
-        p.embPrev = m_embedPrev;
-        p.embCur = m_embedCur;
+        const int tiles = (batch_size + 15) / 16;
+        if (isChain() && !m_featPtr) slotRingsDirty(tiles);      // (a chain launch writes the rings of the batch's tiles only)
+        else wgRingsDirty(tiles);
+        wn::Params p = baseParams();
         p.cond = m_condUser ? m_condUser : m_cond;
         p.condRaw = m_condRaw;
         p.condRawKind = m_condRaw ? m_condRawKind : 0;
@@ -1410,43 +1307,20 @@ public:
             p.feat = m_featPtr;
             p.condRawKind = 3;
         }
-        p.gate = NULL;
         p.sel = m_outputSelectors;
-        p.ring = m_ring;
-        p.maxDilation = m_maxDilation;
-        p.yInPrev = m_yInPrev;
-        p.yInCur = m_yInCur;
         p.yOut = m_yOut;
-        p.xtOut = m_XtOut;
-        p.skipOut = m_skipOut;
-        p.zs = m_Zs;
-        p.za = m_Za;
-        p.p = m_p;
-        p.numLayers = m_numLayers;
         p.batch = batch_size;
-        p.maxBatch = m_maxBatch;
         p.numSamples = num_samples;
         p.condSamples = m_featPtr ? m_featSamples : m_condRaw ? m_condRawSamples : m_maxSamples;
         p.initSample = init_sample;
         p.count = m_num_samples_per_chunk ? m_num_samples_per_chunk : num_samples;
         if (p.initSample + p.count > num_samples) p.count = num_samples - p.initSample;
-        p.ringSlots = m_ringSlots;
-        p.ldsRingD = 0;                 // (the wavenet_wg launchers place ring slots in the LDS their tables leave free: placeLdsRing)
-        p.tiles = m_tiles;
-        p.tileBase = 0;
-        p.tanhEmbed = m_tanhEmbed ? 1 : 0;
         p.dump = dumpActivations ? 1 : 0;
-        p.embLds = 0;
         p.useRng = m_useRng ? 1 : 0;
-        p.rngKey0 = (unsigned)m_rngSeed;
-        p.rngKey1 = (unsigned)(m_rngSeed >> 32);
-        p.clk = m_clkOn ? m_clk : NULL;
-        p.softScale = m_featPtr ? m_softScale : NULL;
-        fillSchedule(p);
+        p.softScale = m_featPtr ? m_temps.softScale : NULL;
         m_lastStride = num_samples;
         if (p.count <= 0) return true;
 
-        const int tiles = (batch_size + 15) / 16;
         // (computing the conditioning from the features is wavenet_wg's: a chain engine runs it for such a launch)
         bool result = (isChain() && !m_featPtr) ? launchChain(p, tiles, stream) : launchWg(p, tiles, stream);
         if (m_pcmUser != NULL) {
@@ -1487,666 +1361,9 @@ public:
         m_ringDirtyTiles = 0;
     }
 
-    // ---- slot mode: continuous batching (slots.hpp; DESIGN.md "Slot mode") ------------------------------------------------------
-    // Every column holds one utterance that starts and stops on its own while the others go on.  An utterance's samples depend on
-    // its features, its uid, the seed, the model and the temperature in force at each local sample (slotSetTemperature; 1 by default)
-    // only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
-    // lockstep setFeatures + setSelectorSeed run --, its rings start at zero and its history at 128.  The state between steps lives
-    // in a window of W samples that wraps; the generation kernel is wavenet_wg<.., RAW=3> as the features path launches it, on
-    // window rows, reading the selectors from a table (useRng = 0).  Needs setConditioningWeights; the seed is the one of
-    // setSelectorSeed (0 if none was set).  Steps of a session are issued on one stream (they share the window and the rings).
-    int largestDilation() const {      // of the schedule: the window is a multiple of it, so that t mod W keeps t & (d - 1)
-        int d = 1, m = 1;
-        for (int l = 0; l < m_numLayers; l++) {
-            if (d > m) m = d;
-            d <<= 1;
-            if (d > m_maxDilation) d = 1;
-        }
-        return m;
-    }
-    // Enters slot mode with a window of `window` samples (ends a session in progress; every column idle).  false: no conditioning
-    // weights yet, or the window is not a positive multiple of largestDilation().  Synchronises.
-    bool slotsBegin(int window) {
-        if (!m_supported || m_nCond <= 0 || window <= 0 || window % largestDilation() != 0) return false;
-        slotsEnd();
-        m_slotW = window;
-        m_slotCounter = 0;
-        m_slotHost.assign(m_maxBatch, wn::SlotDesc{});
-        m_slotPending.assign(m_maxBatch, 0);
-        m_slotPendingList.clear();
-        m_melHost.assign(m_maxBatch, wn::MelDesc{});
-        m_melDirty.assign(m_maxBatch, 0);
-        m_melDirtyList.clear();
-        m_melColumns = 0;
-        m_melTiles = 0;
-        m_melTilesDirty = false;
-        m_slotResume.assign(m_maxBatch, NULL);
-        m_slotResumeDone.assign(m_maxBatch, 0);
-        m_slotMoveEnd.assign(m_maxBatch, 0);
-        m_slotMoves.clear();
-        resetTemperatures();      // (every column at T = 1, a lockstep run's values included)
-        const size_t cells = (size_t)window * m_maxBatch;
-        gpuErrChk(hipMalloc(&m_slotDesc, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
-        gpuErrChk(hipMemset(m_slotDesc, 0, (size_t)m_maxBatch * sizeof(wn::SlotDesc)));
-        gpuErrChk(hipMalloc(&m_slotFeat, featureElems(window) * sizeof(elem)));
-        gpuErrChk(hipMemset(m_slotFeat, 0, featureElems(window) * sizeof(elem)));
-        gpuErrChk(hipMalloc(&m_slotSel, cells * sizeof(float)));
-        gpuErrChk(hipMemset(m_slotSel, 0, cells * sizeof(float)));
-        gpuErrChk(hipMalloc(&m_slotY, cells * sizeof(int)));
-        gpuErrChk(hipMemset(m_slotY, 0, cells * sizeof(int)));
-        gpuErrChk(hipMalloc(&m_slotPcm, cells * sizeof(short)));
-        gpuErrChk(hipMemset(m_slotPcm, 0, cells * sizeof(short)));
-        gpuErrChk(hipMalloc(&m_slotUpd, slotUpdBytes()));
-        for (int i = 0; i < 2; i++) {
-            gpuErrChk(hipHostMalloc((void**)&m_slotStage[i], slotUpdBytes(), hipHostMallocDefault));
-            gpuErrChk(hipEventCreateWithFlags(&m_slotEv[i], hipEventDisableTiming));
-            gpuErrChk(hipEventRecord(m_slotEv[i], 0));
-        }
-        m_slotParity = 0;
-        gpuErrChk(hipMalloc(&m_dlvDev, (size_t)m_maxBatch * sizeof(wn::DeliverPiece)));
-        for (int i = 0; i < kSlotTickets; i++) {
-            gpuErrChk(hipHostMalloc((void**)&m_dlvStage[i], (size_t)m_maxBatch * sizeof(wn::DeliverPiece), hipHostMallocDefault));
-            gpuErrChk(hipEventCreateWithFlags(&m_dlvEv[i], hipEventDisableTiming));
-        }
-        m_dlvTicket = 0;
-        ensureMulaw();
-        gpuErrChk(hipDeviceSynchronize());
-        return true;
-    }
-    int slotsWindow() const { return m_slotW; }
-    // Column `slot` takes a new utterance at the next step: its upsampled features x[c * cStride + k * tStride] (device memory,
-    // `precision`-bit floats, n_cond channels x `length` samples; kept alive and unchanged while the column runs), its uid.  Replaces
-    // whatever the column held.  false (nothing changes): not in slot mode, slot outside the batch, non-device x, bad precision,
-    // non-positive strides or length; or the column is the destination of a pending move (the start would silently drop the
-    // utterance on its way in: stop it, or step first).
-    bool slotStart(int slot, const void* x, int precision, long long cStride, long long tStride, int length, unsigned uid) {
-        if (!slotStartOk(slot, x, precision, cStride, tStride, length)) return false;
-        slotDropMel(slot);
-        slotDropResume(slot);
-        wn::SlotDesc& d = m_slotHost[slot];
-        d.x = x;
-        d.cStride = cStride;
-        d.tStride = tStride;
-        d.start = 0;          // (the step that applies the start sets it)
-        d.length = length;
-        d.uid = uid;
-        d.precision = precision;
-        d.active = 1;
-        slotMarkPending(slot, 1);
-        slotTempSet(slot, 1.0f);
-        return true;
-    }
-    // Column `slot` goes idle at the next step (its features are no longer read from then on).
-    bool slotStop(int slot) {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
-        slotDropMel(slot);
-        slotDropResume(slot);
-        m_slotHost[slot].active = 0;
-        slotMarkPending(slot, 2);
-        return true;
-    }
-    // Column `slot` takes a mel utterance at the next step: its frames mel[c * cStride + f * fStride] (device memory,
-    // `precision`-bit floats, n_cond channels; kept alive while the column runs), `frames` of them available so far, final != 0: no
-    // more will come (its length is frames x stride), its uid.  Upsampled with the table of setUpsampling in the steps that generate
-    // them.  Replaces whatever the column held.  false (nothing changes): not in slot mode, no upsampling, slot outside the batch,
-    // non-device mel, bad precision, non-positive strides, frames < 0, 0 frames of a final utterance, or the column is the destination
-    // of a pending move.
-    bool slotStartMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
-        if (!slotStartMelOk(slot, mel, precision, cStride, fStride, frames, final)) return false;
-        if (!m_melDesc) melAllocate();
-        slotDropResume(slot);
-        wn::MelDesc& d = m_melHost[slot];
-        if (!d.state) m_melColumns++;
-        d.mel = mel;
-        d.cStride = cStride;
-        d.fStride = fStride;
-        d.start = 0;          // (the step that applies the start sets it)
-        d.frames = frames;
-        d.uid = uid;
-        d.precision = precision;
-        d.state = final ? 2 : 1;
-        melMarkDirty(slot);
-        m_melTilesDirty = true;
-        m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
-        slotMarkPending(slot, 1);
-        slotTempSet(slot, 1.0f);
-        return true;
-    }
-    // More frames of the mel utterance of column `slot` are available in the same buffer (written by the caller, ordered before the
-    // next step on the step stream); final != 0: no more will come.  false (nothing changes): not a mel column, already final, the
-    // count decreases, or 0 frames made final.
-    bool slotMelFrames(int slot, int frames, int final) {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch) return false;
-        wn::MelDesc& d = m_melHost[slot];
-        if (d.state != 1 || frames < d.frames || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL) return false;
-        d.frames = frames;
-        if (final) d.state = 2;
-        melMarkDirty(slot);
-        return true;
-    }
-    // The utterance of column `slot` samples from softmax(logits / T) from the next step on, from that step's first sample (the
-    // local sample the column has reached then); T as for setTemperatures.  slotStart / slotStartMel put the column back to 1, so
-    // the order is start, then set; slotsBegin and slotsEnd put every column back to 1.  Moves, saves and resumes carry the value
-    // (a blob holds it in SlotStateHeader::pad[0]).  A step with changed columns issues one small launch (slots_set_scales) ahead
-    // of its generation launch.  false (nothing changes): not in slot mode, slot outside the batch, a column that holds no
-    // utterance and has no pending start or resume, or a bad value.
-    bool slotSetTemperature(int slot, float T) {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot) || !wn::temperature_ok(T)) return false;
-        slotTempSet(slot, T);
-        return true;
-    }
-    // the host's value for column `slot`; 0 when it holds no utterance (or outside slot mode, or outside the batch)
-    float slotTemperature(int slot) const {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot)) return 0.f;
-        return m_temp.empty() ? 1.0f : m_temp[slot];
-    }
-    // ---- a column's state as a value (slots_state.hpp) ----
-    // bytes of one column's state blob for this engine's shape and precision (header + its share of its tile's ring)
-    size_t slotStateBytes() const { return wn::slots_state_bytes(m_ringSlots, ringFragsPerSlot()); }
-    // The utterance of column `from` goes on in column `to` from the next step (queued; applied first in that step, so `from` may
-    // take a new start in the same step): ring share, history and descriptors move, start unchanged.  The host's view changes at
-    // once.  false (nothing changes): not in slot mode; an index outside the batch or from == to; `from` holds no utterance or has a
-    // pending start or resume; `to` holds an utterance or has a pending start, resume or move; `from` is an endpoint of a pending
-    // move.  A pending stop on `to` is superseded.
-    bool slotMove(int from, int to) {
-        if (m_slotW <= 0 || from < 0 || from >= m_maxBatch || to < 0 || to >= m_maxBatch || from == to) return false;
-        if (!slotHolds(from) || m_slotPending[from] == 1 || m_slotMoveEnd[from]) return false;
-        if (slotHolds(to) || m_slotPending[to] == 1 || m_slotMoveEnd[to]) return false;
-        m_slotHost[to] = m_slotHost[from];
-        m_slotHost[from].active = 0;
-        if (m_melHost[from].state) {
-            m_melHost[to] = m_melHost[from];
-            m_melHost[from].state = 0;
-            if (m_melDirty[from]) melMarkDirty(to);      // (frames announced since the last step: the update path writes them after the move)
-            m_melTilesDirty = true;
-        }
-        m_slotMoveEnd[from] = 1;
-        m_slotMoveEnd[to] = 2;
-        m_slotMoves.push_back(wn::SlotMove{from, to});
-        slotTempSet(to, temperature(from));
-        return true;
-    }
-    // The state of column `slot` after the steps issued so far into dst (device memory, 16-byte aligned, slotStateBytes() bytes),
-    // asynchronously on `stream` -- the stream of the session's steps, or one ordered after them.  The column goes on running.
-    // Returns done, the local samples it has generated; -1 (nothing written): not in slot mode, slot outside the batch, no
-    // utterance, a pending start, resume or move on the column, or a bad dst.
-    int slotSave(int slot, void* dst, hipStream_t stream = 0) {
-        if (m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || !slotHolds(slot) || m_slotPending[slot] == 1 || m_slotMoveEnd[slot] ||
-            dst == NULL || ((size_t)dst & 15) != 0 || !isDevicePtr(dst))
-            return -1;
-        const bool mel = m_melHost[slot].state != 0;
-        const long long start = mel ? m_melHost[slot].start : m_slotHost[slot].start, done = m_slotCounter - start;
-        if (done < 0 || done > 0x7fffffffLL) return -1;
-        wn::SlotStateHeader h = slotHeaderCommon();
-        h.done = (int)done;
-        h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
-        h.pad[0] = wn::temperature_word(temperature(slot));
-        if (!wn::slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur))
-            return -1;
-        return (int)done;
-    }
-    // slotStart / slotStartMel, but the column continues from the blob `state` (of slotSave, device memory): at the next step its
-    // ring share and history are loaded from it in place of the zeroing, and start = that step's counter - done; uid and done come
-    // from the blob's header, which is read here with a small blocking copy on the null stream: the call waits for a save issued
-    // on the null stream or on a stream that synchronises with it; a save on a non-blocking stream must have completed (or have
-    // been ordered before this call by the caller) first.  The features / frames are those of the saved utterance, handed over again by the caller; `state` stays unchanged until
-    // the next step has been issued (it reads it in stream order).  false (nothing changes): wrong magic or layout version, a shape
-    // or precision that is not this engine's, done >= length (final mel: done >= frames x stride), or what slotStart / slotStartMel
-    // refuse.
-    bool slotResume(int slot, const void* state, const void* x, int precision, long long cStride, long long tStride, int length) {
-        wn::SlotStateHeader h;
-        if (m_slotW <= 0 || !slotStateHeader(state, h) || h.done >= length) return false;
-        if (!slotStart(slot, x, precision, cStride, tStride, length, h.uid)) return false;
-        slotLayers();
-        m_slotResume[slot] = state;
-        m_slotResumeDone[slot] = h.done;
-        slotTempFromHeader(slot, h);
-        return true;
-    }
-    bool slotResumeMel(int slot, const void* state, const void* mel, int precision, long long cStride, long long fStride, int frames, int final) {
-        wn::SlotStateHeader h;
-        if (m_slotW <= 0 || m_upStride <= 0 || !slotStateHeader(state, h) || (final && h.done >= (long long)frames * m_upStride)) return false;
-        if (!slotStartMel(slot, mel, precision, cStride, fStride, frames, final, h.uid)) return false;
-        slotLayers();
-        m_slotResume[slot] = state;
-        m_slotResumeDone[slot] = h.done;
-        slotTempFromHeader(slot, h);
-        return true;
-    }
-    // ---- lists of columns ----
-    // slotSave for the n columns slots[0 .. n): blob i at dst + i * stride, ONE launch after one small staging copy, asynchronously on
-    // `stream`; never synchronises the stream and waits for nothing already queued on it: the entries go through two staging
-    // halves, each released by an event recorded behind its launch, so only a third list save in a row waits -- for the first to
-    // have completed.  The first list save of a session allocates the halves (two small device and two pinned host buffers, once).  dst: 16-byte aligned device memory or pinned host memory (mapped as the outputs of slotsStepRagged);
-    // stride: a multiple of 16, at least slotStateBytes().  saved[i] is filled before the call returns, from host state.  The columns
-    // go on running.  Returns n; -1 with nothing written and nothing launched: not in slot mode, n outside 1..maxBatch, a slot out of
-    // range or listed twice, a slot without an utterance or with a pending start, resume or move, a bad dst or stride.
-    int slotsSaveList(const int* slots, int n, void* dst, long long stride, wn::SlotSaved* saved, hipStream_t stream = 0) {
-        if (m_slotW <= 0 || slots == NULL || saved == NULL || n < 1 || n > m_maxBatch) return -1;
-        bool pinned = false;
-        char* const out = (char*)slotBlobRange(dst, n, stride, &pinned);
-        if (out == NULL) return -1;
-        m_listMark.assign(m_maxBatch, 0);
-        for (int i = 0; i < n; i++) {
-            const int b = slots[i];
-            if (b < 0 || b >= m_maxBatch || m_listMark[b] || !slotHolds(b) || m_slotPending[b] == 1 || m_slotMoveEnd[b]) return -1;
-            m_listMark[b] = i + 1;
-            const bool mel = m_melHost[b].state != 0;
-            const long long done = m_slotCounter - (mel ? m_melHost[b].start : m_slotHost[b].start);
-            if (done < 0 || done > 0x7fffffffLL) return -1;
-        }
-        if (!m_saveDev[0])
-            for (int i = 0; i < 2; i++) {
-                gpuErrChk(hipMalloc((void**)&m_saveDev[i], (size_t)m_maxBatch * sizeof(wn::SlotSave)));
-                gpuErrChk(hipHostMalloc((void**)&m_saveStage[i], (size_t)m_maxBatch * sizeof(wn::SlotSave), hipHostMallocDefault));
-                gpuErrChk(hipEventCreateWithFlags(&m_saveEv[i], hipEventDisableTiming));
-                m_saveUsed[i] = false;
-            }
-        const wn::SlotLayer* const layers = slotLayers();
-        const int at = m_saveParity;
-        if (m_saveUsed[at]) gpuErrChk(hipEventSynchronize(m_saveEv[at]));
-        m_saveUsed[at] = true;
-        wn::SlotSave* const stage = m_saveStage[at];
-        for (int i = 0; i < n; i++) {
-            const int b = slots[i];
-            const bool mel = m_melHost[b].state != 0;
-            const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
-            const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
-            const int done = (int)(m_slotCounter - start);
-            stage[i] = wn::SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, wn::temperature_word(temperature(b)), 0};
-            saved[i] = wn::SlotSaved{b, uid, done, mel ? 1 : 0};
-        }
-        gpuErrChk(hipMemcpyAsync(m_saveDev[at], stage, (size_t)n * sizeof(wn::SlotSave), hipMemcpyHostToDevice, stream));
-        const bool ok = wn::slots_save_list(stream, m_saveDev[at], n, slotHeaderCommon(), layers, m_ring, m_ringSlots, ringFragsPerSlot(),
-                                            m_yInPrev, m_yInCur);
-        gpuErrChk(hipEventRecord(m_saveEv[at], stream));
-        m_saveParity ^= 1;
-        return ok ? n : -1;
-    }
-    // slotResume / slotResumeMel for n requests at once, all or nothing: the blob of reqs[i] is states + i * stride (memory and stride
-    // as for slotsSaveList).  The n headers are read at once -- device memory: one blocking 2-D copy on the null stream (the ordering
-    // rule of slotResume); pinned memory: in place, so the save must have completed -- and checked as slotResume checks them; each
-    // request is then refused for what slotResume / slotResumeMel refuse, and also when its column holds an utterance or has a
-    // pending start or resume (a list never replaces one), or is named twice.  Any refusal: 0, and the session is exactly as before.
-    // Otherwise n: every column has its pending resume, loaded by the next step in its one slot_load_kernel launch.  The blobs stay
-    // unchanged until that step has been issued.
-    int slotsResumeList(const wn::SlotResumeReq* reqs, int n, const void* states, long long stride) {
-        if (m_slotW <= 0 || reqs == NULL || n < 1 || n > m_maxBatch) return 0;
-        bool pinned = false;
-        const char* const dev = (const char*)slotBlobRange(states, n, stride, &pinned);
-        if (dev == NULL) return 0;
-        std::vector<wn::SlotStateHeader> hdr(n);
-        if (pinned)
-            for (int i = 0; i < n; i++) memcpy(&hdr[i], (const char*)states + (size_t)i * (size_t)stride, sizeof(wn::SlotStateHeader));
-        else
-            gpuErrChk(hipMemcpy2D(hdr.data(), sizeof(wn::SlotStateHeader), states, (size_t)stride, sizeof(wn::SlotStateHeader), n,
-                                  hipMemcpyDeviceToHost));
-        m_listMark.assign(m_maxBatch, 0);
-        for (int i = 0; i < n; i++) {
-            const wn::SlotResumeReq& q = reqs[i];
-            const wn::SlotStateHeader& h = hdr[i];
-            if (!slotHeaderOk(h)) return 0;
-            if (q.mel ? !slotStartMelOk(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, q.final)
-                      : !slotStartOk(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length))
-                return 0;
-            if (q.mel ? (q.final && h.done >= (long long)q.length * m_upStride) : h.done >= q.length) return 0;
-            if (m_listMark[q.slot] || slotHolds(q.slot) || m_slotPending[q.slot] == 1) return 0;
-            m_listMark[q.slot] = i + 1;
-        }
-        slotLayers();
-        for (int i = 0; i < n; i++) {
-            const wn::SlotResumeReq& q = reqs[i];
-            const bool ok = q.mel ? slotStartMel(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, q.final, hdr[i].uid)
-                                  : slotStart(q.slot, q.src, q.precision, q.cStride, q.tStride, q.length, hdr[i].uid);
-            assert(ok);
-            (void)ok;
-            m_slotResume[q.slot] = dev + (size_t)i * (size_t)stride;
-            m_slotResumeDone[q.slot] = hdr[i].done;
-            slotTempFromHeader(q.slot, hdr[i]);
-        }
-        return n;
-    }
-    // The largest count the next step accepts: W, or the fewest samples a non-final mel column has frames for beyond its next
-    // sample (0 when one has none).
-    int slotsHeadroom() const {
-        if (m_slotW <= 0) return 0;
-        long long h = m_slotW;
-        if (m_melColumns > 0)
-            for (int b = 0; b < m_maxBatch; b++) {
-                const wn::MelDesc& d = m_melHost[b];
-                if (d.state != 1) continue;
-                const long long next = m_slotPending[b] == 1 ? m_slotResumeDone[b] : m_slotCounter - d.start;      // (a resumed column goes on from done)
-                const long long left = (long long)d.frames * m_upStride - next;
-                if (left < h) h = left;
-            }
-        return h < 0 ? 0 : (int)h;
-    }
-    // debug getter: the window's feature fragments of engine samples [first, first + count) -- within the last W generated -- in the
-    // order of getFeatures (synchronises).  false: outside that range.
-    bool slotsGetFeatures(void* dst, long long first, int count) {
-        if (m_slotW <= 0 || dst == NULL || count <= 0 || first < m_slotCounter - m_slotW || first < 0 || first + count > m_slotCounter)
-            return false;
-        gpuErrChk(hipDeviceSynchronize());
-        for (int done = 0; done < count;) {
-            const int row = (int)((first + done) % m_slotW), c = count - done < m_slotW - row ? count - done : m_slotW - row;
-            gpuErrChk(hipMemcpy((elem*)dst + featureElems(done), m_slotFeat + featureElems(row), featureElems(c) * sizeof(elem), hipMemcpyDefault));
-            done += c;
-        }
-        return true;
-    }
-    // Order within a step (fixed): the pending moves (one launch); then the descriptor updates with the resets of started columns
-    // (one launch) and the loads of resumed ones (one launch); then the feed.  A column that is the source of a move may therefore
-    // take a new start in the same step.  A session that never moves or resumes launches what it launched before these existed.
-    // One step of `count` <= W samples, asynchronously on `stream`: the pending starts and stops (one reset launch), the window feed
-    // (one launch), the generation -- two launches where the window rows wrap -- up to the tile of the highest active column, the PCM
-    // when pcm != NULL, and the copies of the step's samples / PCM into yOut / pcm ([maxBatch][count], host or device; NULL: none).
-    // Columns without an utterance hold unspecified values.  Synchronises the stream when an output is host memory.  With mel columns
-    // also their descriptor updates and their feed (slots_mel.hpp: three launches after the window feed); false (nothing changes)
-    // when count exceeds slotsHeadroom().
-    bool slotsStep(int count, int* yOut, short* pcm, hipStream_t stream = 0) {
-        if (m_slotW <= 0 || count <= 0 || count > m_slotW) return false;
-        if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return false;      // (mel columns short of frames)
-        const int W = m_slotW;
-        int piece[2][2], pieces = 0, cols = 0;
-        bool ok = slotsGenerate(count, piece, pieces, cols, stream);
-        if (cols > 0 && pcm != NULL) {
-            for (int i = 0; i < pieces; i++) {
-                hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * piece[i][1])), dim3(256), 0, stream, m_slotY, m_slotPcm,
-                                   m_mulaw, cols, W, piece[i][0], piece[i][1]);
-                ok = ok && hipGetLastError() == hipSuccess;
-            }
-        }
-        for (int i = 0, off = 0; i < pieces; off += piece[i][1], i++) {
-            if (yOut != NULL)
-                gpuErrChk(hipMemcpy2DAsync(yOut + off, (size_t)count * sizeof(int), m_slotY + piece[i][0], (size_t)W * sizeof(int),
-                                           (size_t)piece[i][1] * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
-            if (pcm != NULL)
-                gpuErrChk(hipMemcpy2DAsync(pcm + off, (size_t)count * sizeof(short), m_slotPcm + piece[i][0], (size_t)W * sizeof(short),
-                                           (size_t)piece[i][1] * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
-        }
-        m_slotCounter += count;
-        if ((yOut != NULL && !isDevicePtr(yOut)) || (pcm != NULL && !isDevicePtr(pcm))) gpuErrChk(hipStreamSynchronize(stream));
-        return ok;
-    }
-    // The launches of a step up to and including the generation (the order above), shared by slotsStep and slotsStepRagged: the
-    // window rows of the launches -> piece[0 .. pieces), the columns they cover -> cols.  The counter is the caller's to advance.
-    bool slotsGenerate(int count, int piece[2][2], int& pieces, int& cols, hipStream_t stream) {
-        const int W = m_slotW;
-        bool ok = true;
-        if (!m_slotMoves.empty()) ok = slotApplyMoves(stream);
-        if (!m_melDirtyList.empty() || m_melTilesDirty) ok = melApplyPending(stream) && ok;      // (before the starts: it reads the pending ones)
-        if (!m_slotPendingList.empty()) ok = slotApplyPending(stream) && ok;
-        if (!m_tempDirtyList.empty()) ok = slotApplyTemperatures(stream) && ok;      // (the host's values: whatever moved or started above)
-        cols = 0;
-        for (int b = m_maxBatch - 1; b >= 0; b--)
-            if (m_slotHost[b].active || (m_melColumns > 0 && m_melHost[b].state)) {
-                cols = b + 1;
-                break;
-            }
-        const int T = (int)(m_slotCounter % W);
-        pieces = 0;      // (first window row, samples) of the launches
-        for (int done = 0; done < count; pieces++) {
-            const int t0 = (T + done) % W, c = count - done < W - t0 ? count - done : W - t0;
-            piece[pieces][0] = t0;
-            piece[pieces][1] = c;
-            done += c;
-        }
-        if (cols > 0) {
-            if (m_featDirty) buildFeatStream(stream);
-            ok = wn::slots_feed<F16>(stream, m_slotFeat, m_slotSel, m_slotDesc, cols, m_maxBatch, m_tiles, m_nCond, m_slotCounter, T, W, count,
-                                     m_rngSeed) && ok;
-            if (m_melTiles > 0)
-                ok = wn::slots_mel_feed<F16>(stream, m_slotFeat, m_slotSel, melStage(count), m_melStage + m_melRecOff, m_melColInfo, m_melDesc,
-                                             (const int*)(m_melUpd + melTileOff()), m_melTiles, m_maxBatch, m_tiles, m_nCond, m_upTab, m_upBias,
-                                             m_upWindow / m_upStride, m_upStride, m_slotCounter, T, W, count, m_rngSeed) && ok;
-            for (int i = 0; i < pieces; i++) ok = slotLaunch(piece[i][0], piece[i][1], cols, stream) && ok;
-        }
-        return ok;
-    }
-    // ---- ragged delivery (slots_deliver.hpp) ----
-    // The address the device stores through for an output of slotsStepRagged: the pointer itself for device memory, the mapped
-    // address for pinned host memory (hipHostMalloc, hipHostRegister); NULL for anything else (pageable host memory).
-    static void* deliverTarget(void* p, bool* pinned = NULL) {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-            (void)hipGetLastError();
-            return NULL;
-        }
-        if (pinned) *pinned = attr.type == hipMemoryTypeHost;
-        if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return p;
-        if (attr.type != hipMemoryTypeHost) return NULL;
-        void* d = NULL;
-        if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return NULL;
-        }
-        return d;
-    }
-    // The pieces a step of `count` samples delivers, from what the host knows (the descriptors with the pending starts, resumes and
-    // moves already in them, the counter): one per column holding an utterance with a sample in this step, ascending.  first = the
-    // local index of its first sample; n = min(count, length - first) for a feature column and a final mel column, count for a
-    // non-final mel column (the headroom rule); offsets packed, each rounded up to kDeliverAlign elements.  out may be NULL (count
-    // only).  Returns the number of pieces; total = the end of the last one.
-    int slotPieces(int count, wn::SlotPiece* out, int maxOut, long long& total) const {
-        int n = 0;
-        long long off = 0;
-        total = 0;
-        for (int b = 0; b < m_maxBatch; b++) {
-            const bool mel = m_melColumns > 0 && m_melHost[b].state != 0;
-            if (!mel && !m_slotHost[b].active) continue;
-            const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
-            const long long first = m_slotPending[b] == 1 ? m_slotResumeDone[b] : m_slotCounter - start;
-            long long len = count, left = count;
-            bool bounded = true;
-            if (!mel) len = m_slotHost[b].length;
-            else if (m_melHost[b].state == 2) len = (long long)m_melHost[b].frames * m_upStride;
-            else bounded = false;
-            if (bounded) left = len - first;
-            if (left <= 0) continue;      // (ended in an earlier step and not stopped since)
-            const int k = left < count ? (int)left : count;
-            if (out != NULL && n < maxOut) {
-                wn::SlotPiece& p = out[n];
-                p.slot = b;
-                p.uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
-                p.first = first;
-                p.n = k;
-                p.finished = bounded && first + k == len ? 1 : 0;
-                p.offset = off;
-            }
-            n++;
-            total = off + k;
-            off = (total + wn::kDeliverAlign - 1) / wn::kDeliverAlign * wn::kDeliverAlign;
-        }
-        return n;
-    }
-    // slotsStep, delivering pieces in place of rows, and never synchronising: the launches of slotsStep up to and including the
-    // generation, then ONE slot_deliver_kernel launch that writes each piece's n samples at its offset of `samples` (int32) and / or
-    // their PCM at the same offset of `pcm` (int16) -- device memory or pinned host memory, `capacity` elements each, NULL: not
-    // wanted --, then an event record.  pieces[0 .. *nPieces) (host) is filled before anything is launched.  *ticket names the step
-    // for slotsWait / slotsDone.  Returns the ragged size (end of the last piece; 0 when no column delivers); -2 when a launch
-    // failed (the step was issued and has its ticket, but its outputs are not to be read: slotsStep returns false there); or -1 with
-    // nothing changed: not in slot mode, count out of range or above the headroom, both outputs NULL, an output that is neither device
-    // nor pinned memory, capacity or maxPieces too small.  Mixes freely with slotsStep.  (A step that reuses a ticket slot waits for
-    // the step kSlotTickets before it: with at most that many steps in flight it waits for nothing.)
-    long long slotsStepRagged(int count, int* samples, short* pcm, long long capacity, wn::SlotPiece* pieces, int maxPieces, int* nPieces,
-                              unsigned long long* ticket, hipStream_t stream = 0) {
-        if (m_slotW <= 0 || count <= 0 || count > m_slotW || (samples == NULL && pcm == NULL) || pieces == NULL || nPieces == NULL ||
-            ticket == NULL)
-            return -1;
-        if (m_melColumns > 0 && (m_upStride <= 0 || count > slotsHeadroom())) return -1;
-        int* const dSamples = samples ? (int*)deliverTarget(samples) : NULL;
-        short* const dPcm = pcm ? (short*)deliverTarget(pcm) : NULL;
-        if ((samples && !dSamples) || (pcm && !dPcm)) return -1;
-        long long total = 0;
-        const int n = slotPieces(count, NULL, 0, total);
-        if (n > maxPieces || total > capacity) return -1;
-        slotPieces(count, pieces, maxPieces, total);
-        *nPieces = n;
-        const int T = (int)(m_slotCounter % m_slotW);
-        const int at = (int)(m_dlvTicket % kSlotTickets);
-        if (m_dlvTicket >= (unsigned long long)kSlotTickets) gpuErrChk(hipEventSynchronize(m_dlvEv[at]));
-        int piece[2][2], launches = 0, cols = 0;
-        bool ok = slotsGenerate(count, piece, launches, cols, stream);
-        if (n > 0) {
-            wn::DeliverPiece* const stage = m_dlvStage[at];
-            for (int i = 0; i < n; i++) stage[i] = wn::DeliverPiece{pieces[i].slot, pieces[i].n, pieces[i].offset};
-            gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(wn::DeliverPiece), hipMemcpyHostToDevice, stream));
-            ok = wn::slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, dPcm) && ok;
-        }
-        gpuErrChk(hipEventRecord(m_dlvEv[at], stream));
-        m_slotCounter += count;
-        *ticket = ++m_dlvTicket;
-        return ok ? total : -2;
-    }
-    // Measurement only (scripts/slots_perf.py --serve): `reps` back-to-back output passes over the last `count` samples generated,
-    // timed with events on `stream`; returns milliseconds for all of them, < 0 when refused.  ragged = false: what slotsStep
-    // issues after the generation -- the PCM launches and the 2-D copies into samples / pcm [maxBatch][count]; ragged = true: the
-    // delivery launch for every column holding an utterance (n = min(count, its samples so far)) into samples / pcm of `capacity`
-    // elements.  Device or pinned outputs, both given.  Synchronises the device; changes nothing of the session.
-    float slotsTimeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t stream = 0) {
-        if (m_slotW <= 0 || count <= 0 || count > m_slotW || count > m_slotCounter || samples == NULL || pcm == NULL || reps <= 0) return -1.f;
-        int* const dSamples = (int*)deliverTarget(samples);
-        short* const dPcm = (short*)deliverTarget(pcm);
-        if (!dSamples || !dPcm) return -1.f;
-        const int W = m_slotW, T = (int)((m_slotCounter - count) % W);
-        gpuErrChk(hipDeviceSynchronize());
-        int n = 0, cols = 0;
-        long long off = 0, total = 0;
-        for (int b = 0; b < m_maxBatch; b++) {
-            const bool mel = m_melColumns > 0 && m_melHost[b].state != 0;
-            if ((!mel && !m_slotHost[b].active) || m_slotPending[b] == 1) continue;
-            cols = b + 1;
-            const long long done = m_slotCounter - (mel ? m_melHost[b].start : m_slotHost[b].start);
-            if (done <= 0) continue;
-            const int k = done < count ? (int)done : count;
-            m_dlvStage[0][n++] = wn::DeliverPiece{b, k, off};
-            total = off + k;
-            off = (total + wn::kDeliverAlign - 1) / wn::kDeliverAlign * wn::kDeliverAlign;
-        }
-        if (n == 0 || (ragged ? total : (long long)m_maxBatch * count) > capacity) return -1.f;
-        gpuErrChk(hipMemcpyAsync(m_dlvDev, m_dlvStage[0], (size_t)n * sizeof(wn::DeliverPiece), hipMemcpyHostToDevice, stream));
-        hipEvent_t t0, t1;
-        gpuErrChk(hipEventCreate(&t0));
-        gpuErrChk(hipEventCreate(&t1));
-        bool ok = true;
-        gpuErrChk(hipEventRecord(t0, stream));
-        for (int r = 0; r < reps; r++) {
-            if (ragged) {
-                ok = wn::slots_deliver(stream, m_slotY, m_mulaw, T, W, count, m_dlvDev, n, dSamples, dPcm) && ok;
-                continue;
-            }
-            for (int done = 0; done < count;) {
-                const int t = (T + done) % W, c = count - done < W - t ? count - done : W - t;
-                hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)cols * c)), dim3(256), 0, stream, m_slotY, m_slotPcm, m_mulaw, cols,
-                                   W, t, c);
-                ok = ok && hipGetLastError() == hipSuccess;
-                gpuErrChk(hipMemcpy2DAsync(samples + done, (size_t)count * sizeof(int), m_slotY + t, (size_t)W * sizeof(int),
-                                           (size_t)c * sizeof(int), m_maxBatch, hipMemcpyDefault, stream));
-                gpuErrChk(hipMemcpy2DAsync(pcm + done, (size_t)count * sizeof(short), m_slotPcm + t, (size_t)W * sizeof(short),
-                                           (size_t)c * sizeof(short), m_maxBatch, hipMemcpyDefault, stream));
-                done += c;
-            }
-        }
-        gpuErrChk(hipEventRecord(t1, stream));
-        gpuErrChk(hipEventSynchronize(t1));
-        float ms = 0.f;
-        gpuErrChk(hipEventElapsedTime(&ms, t0, t1));
-        gpuErrChk(hipEventDestroy(t0));
-        gpuErrChk(hipEventDestroy(t1));
-        return ok ? ms : -1.f;
-    }
-    // Blocks until the outputs of the step with that ticket are complete (true), at once for a ticket older than the events kept;
-    // false: no such ticket.
-    bool slotsWait(unsigned long long ticket) {
-        if (m_slotW <= 0 || ticket == 0 || ticket > m_dlvTicket) return false;
-        if (m_dlvTicket - ticket >= (unsigned long long)kSlotTickets) return true;
-        gpuErrChk(hipEventSynchronize(m_dlvEv[(ticket - 1) % kSlotTickets]));
-        return true;
-    }
-    // 1: complete, 0: not yet, -1: no such ticket.  Never blocks.
-    int slotsDone(unsigned long long ticket) {
-        if (m_slotW <= 0 || ticket == 0 || ticket > m_dlvTicket) return -1;
-        if (m_dlvTicket - ticket >= (unsigned long long)kSlotTickets) return 1;
-        const hipError_t e = hipEventQuery(m_dlvEv[(ticket - 1) % kSlotTickets]);
-        if (e == hipErrorNotReady) {
-            (void)hipGetLastError();
-            return 0;
-        }
-        gpuErrChk(e);
-        return 1;
-    }
-    // Leaves slot mode and frees its buffers (synchronises).  The rings it wrote are cleared by the next resetHistory, as after any run.
-    void slotsEnd() {
-        if (m_slotW <= 0) return;
-        gpuErrChk(hipDeviceSynchronize());
-        gpuErrChk(hipFree(m_slotDesc));
-        gpuErrChk(hipFree(m_slotFeat));
-        gpuErrChk(hipFree(m_slotSel));
-        gpuErrChk(hipFree(m_slotY));
-        gpuErrChk(hipFree(m_slotPcm));
-        gpuErrChk(hipFree(m_slotUpd));
-        for (int i = 0; i < 2; i++) {
-            gpuErrChk(hipHostFree(m_slotStage[i]));
-            gpuErrChk(hipEventDestroy(m_slotEv[i]));
-            m_slotStage[i] = NULL;
-            m_slotEv[i] = NULL;
-        }
-        gpuErrChk(hipFree(m_dlvDev));
-        m_dlvDev = NULL;
-        for (int i = 0; i < 2 && m_saveDev[i]; i++) {
-            gpuErrChk(hipFree(m_saveDev[i]));
-            gpuErrChk(hipHostFree(m_saveStage[i]));
-            gpuErrChk(hipEventDestroy(m_saveEv[i]));
-            m_saveDev[i] = NULL;
-            m_saveStage[i] = NULL;
-            m_saveEv[i] = NULL;
-            m_saveUsed[i] = false;
-        }
-        m_saveParity = 0;
-        for (int i = 0; i < kSlotTickets; i++) {
-            gpuErrChk(hipHostFree(m_dlvStage[i]));
-            gpuErrChk(hipEventDestroy(m_dlvEv[i]));
-            m_dlvStage[i] = NULL;
-            m_dlvEv[i] = NULL;
-        }
-        m_slotDesc = NULL;
-        m_slotFeat = NULL;
-        m_slotSel = NULL;
-        m_slotY = NULL;
-        m_slotPcm = NULL;
-        m_slotUpd = NULL;
-        m_slotW = 0;
-        m_slotHost.clear();
-        m_slotPending.clear();
-        m_slotPendingList.clear();
-        m_slotResume.clear();
-        m_slotResumeDone.clear();
-        m_slotMoveEnd.clear();
-        m_slotMoves.clear();
-        resetTemperatures();
-        if (m_melDesc) {
-            gpuErrChk(hipFree(m_melDesc));
-            gpuErrChk(hipFree(m_melUpd));
-            gpuErrChk(hipFree(m_melColInfo));
-            if (m_melStage) gpuErrChk(hipFree(m_melStage));
-            for (int i = 0; i < 2; i++) {
-                gpuErrChk(hipHostFree(m_melStageHost[i]));
-                gpuErrChk(hipEventDestroy(m_melEv[i]));
-                m_melStageHost[i] = NULL;
-                m_melEv[i] = NULL;
-            }
-            m_melDesc = NULL;
-            m_melUpd = NULL;
-            m_melColInfo = NULL;
-            m_melStage = NULL;
-            m_melStageElems = 0;
-        }
-        m_melHost.clear();
-        m_melDirty.clear();
-        m_melDirtyList.clear();
-        m_melColumns = 0;
-        m_melTiles = 0;
-    }
+    // ---- slot mode: continuous batching (slots_session.hpp; DESIGN.md "Slot mode") ----
+    wn::SlotSession& slots() { return *m_slots; }
+
 
     bool run(int num_samples, int batch_size, int* yOut = NULL, int batch_size_per_block = 1,
              bool dumpActivations = false, hipStream_t stream = 0) {
@@ -2206,352 +1423,79 @@ protected:
         const int bt = wgTiles(tiles);
         return (bt == 4 && (dump || raw != 0)) ? 3 : bt;
     }
-    // ---- slot mode internals ----
-    // a step's staging: the descriptor updates, the loads of resumed columns, the moves, the restarted columns -- [maxBatch] each
-    size_t slotLoadOff() const { return (size_t)m_maxBatch * sizeof(wn::SlotUpdate); }
-    size_t slotMoveOff() const { return slotLoadOff() + (size_t)m_maxBatch * sizeof(wn::SlotLoad); }
-    size_t slotColOff() const { return slotMoveOff() + (size_t)m_maxBatch * sizeof(wn::SlotMove); }
-    size_t slotUpdBytes() const { return slotColOff() + (size_t)m_maxBatch * sizeof(int); }
-    int ringFragsPerSlot() const { return (int)(R * 16 * sizeof(elem) / 1024); }
-    bool slotHolds(int slot) const { return m_slotHost[slot].active || m_melHost[slot].state; }
-    // what slotStart / slotStartMel refuse (shared with slotsResumeList, which checks every request before it changes anything)
-    bool slotStartOk(int slot, const void* x, int precision, long long cStride, long long tStride, int length) const {
-        return !(m_slotW <= 0 || slot < 0 || slot >= m_maxBatch || x == NULL || (precision != 32 && precision != 16) || cStride <= 0 ||
-                 tStride <= 0 || length <= 0 || !isDevicePtr(x) || m_slotMoveEnd[slot] == 2);
+    // ---- what a slot-mode session needs of its engine (wn::SlotHost) ----
+    wn::SlotLive slotLive() const override { return wn::SlotLive{m_nCond, m_upTab, m_upBias, m_upWindow, m_upStride, m_rngSeed}; }
+    const short* slotMulaw() override {
+        ensureMulaw();
+        return m_mulaw;
     }
-    bool slotStartMelOk(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final) const {
-        return !(m_slotW <= 0 || m_upStride <= 0 || slot < 0 || slot >= m_maxBatch || mel == NULL || (precision != 32 && precision != 16) ||
-                 cStride <= 0 || fStride <= 0 || frames < 0 || (final && frames == 0) || (long long)frames * m_upStride > 0x7fffffffLL ||
-                 !isDevicePtr(mel) || m_slotMoveEnd[slot] == 2);
+    void slotFeatStreamReady(hipStream_t stream) override {
+        if (m_featDirty) buildFeatStream(stream);
     }
-    bool slotHeaderOk(const wn::SlotStateHeader& h) const {
-        float T;      // (word 10: zero, or the bits of a valid temperature)
-        return h.magic == wn::kSlotStateMagic && h.version == wn::kSlotStateVersion && h.precision == (F16 ? 16 : 32) && h.R == R &&
-               h.numLayers == m_numLayers && h.maxDilation == m_maxDilation && h.done >= 0 && wn::temperature_of_word(h.pad[0], T);
+    void slotRingsDirty(int tiles) override {
+        if (tiles > m_ringDirtyTiles) m_ringDirtyTiles = tiles;
     }
-    // the fields of a blob's header that every blob of this engine shares
-    wn::SlotStateHeader slotHeaderCommon() const {
-        wn::SlotStateHeader h = {};
-        h.magic = wn::kSlotStateMagic;
-        h.version = wn::kSlotStateVersion;
-        h.precision = F16 ? 16 : 32;
-        h.R = R;
-        h.numLayers = m_numLayers;
-        h.maxDilation = m_maxDilation;
-        return h;
-    }
-    // n blobs of `stride` bytes from `base`: 16-byte aligned device memory (-> base) or mapped pinned host memory (-> its device-side
-    // address; *pinned set), the last blob in the same range as the first; NULL for anything else or a bad stride
-    void* slotBlobRange(const void* base, int n, long long stride, bool* pinned) const {
-        if (base == NULL || ((size_t)base & 15) != 0 || (stride & 15) != 0 || stride < (long long)slotStateBytes()) return NULL;
-        char* const first = (char*)deliverTarget((void*)base, pinned);
-        const size_t span = (size_t)(n - 1) * (size_t)stride;
-        if (first == NULL || (char*)deliverTarget((char*)base + span + slotStateBytes() - 16) != first + span + slotStateBytes() - 16) return NULL;
-        return first;
-    }
-    void slotDropResume(int slot) {
-        m_slotResume[slot] = NULL;
-        m_slotResumeDone[slot] = 0;
-    }
-    // start mod the largest dilation (every dilation divides it), non-negative: the rotation of a column's ring against its blob
-    int slotRotation(long long start) const {
-        const long long D = largestDilation();
-        return (int)(((start % D) + D) % D);
-    }
-    void slotTouchTile(int slot) {
-        if ((slot >> 4) + 1 > m_ringDirtyTiles) m_ringDirtyTiles = (slot >> 4) + 1;
-    }
-    // {first slot, dilation} of its layer for every ring slot, on the device
-    const wn::SlotLayer* slotLayers() {
-        if (!m_slotLayers) {
-            std::vector<wn::SlotLayer> tab;
-            int d = 1;
-            for (int l = 0, off = 0; l < m_numLayers; l++) {
-                for (int i = 0; i < d; i++) tab.push_back(make_int2(off, d));
-                off += d;
-                d <<= 1;
-                if (d > m_maxDilation) d = 1;
-            }
-            assert((int)tab.size() == m_ringSlots);
-            gpuErrChk(hipMalloc(&m_slotLayers, tab.size() * sizeof(wn::SlotLayer)));
-            gpuErrChk(hipMemcpy(m_slotLayers, tab.data(), tab.size() * sizeof(wn::SlotLayer), hipMemcpyHostToDevice));
-        }
-        return m_slotLayers;
-    }
-    // the header of a blob, read back (blocking) and checked against this engine
-    bool slotStateHeader(const void* state, wn::SlotStateHeader& h) const {
-        if (state == NULL || ((size_t)state & 15) != 0 || !isDevicePtr(state)) return false;
-        gpuErrChk(hipMemcpy(&h, state, sizeof(h), hipMemcpyDeviceToHost));
-        return slotHeaderOk(h);
-    }
-    // the pending moves -> pinned staging -> device, then one slot_move_kernel launch (staging halves as slotApplyPending)
-    bool slotApplyMoves(hipStream_t stream) {
-        char* const stage = m_slotStage[m_slotParity];
-        gpuErrChk(hipEventSynchronize(m_slotEv[m_slotParity]));
-        wn::SlotMove* const mv = (wn::SlotMove*)(stage + slotMoveOff());
-        const int n = (int)m_slotMoves.size();
-        for (int i = 0; i < n; i++) {
-            mv[i] = m_slotMoves[i];
-            m_slotMoveEnd[mv[i].from] = 0;
-            m_slotMoveEnd[mv[i].to] = 0;
-            slotTouchTile(mv[i].to);
-        }
-        m_slotMoves.clear();
-        gpuErrChk(hipMemcpyAsync(m_slotUpd + slotMoveOff(), mv, (size_t)n * sizeof(wn::SlotMove), hipMemcpyHostToDevice, stream));
-        gpuErrChk(hipEventRecord(m_slotEv[m_slotParity], stream));
-        m_slotParity ^= 1;
-        return wn::slots_move(stream, (const wn::SlotMove*)(m_slotUpd + slotMoveOff()), n, m_ring, m_ringSlots, ringFragsPerSlot(), m_yInPrev,
-                              m_yInCur, m_slotDesc, m_melDesc);
-    }
-    void slotMarkPending(int slot, int what) {
-        if (!m_slotPending[slot]) m_slotPendingList.push_back(slot);
-        m_slotPending[slot] = what;
-    }
-    // the pending starts and stops -> pinned staging -> device, then one slot_reset_kernel launch (ring + history of the started
-    // columns, every changed descriptor); the staging half is reused two steps later, once its copy has completed
-    bool slotApplyPending(hipStream_t stream) {
-        char* const stage = m_slotStage[m_slotParity];
-        gpuErrChk(hipEventSynchronize(m_slotEv[m_slotParity]));
-        wn::SlotUpdate* const upd = (wn::SlotUpdate*)stage;
-        const size_t colOff = slotColOff();
-        int* const cols = (int*)(stage + colOff);
-        wn::SlotLoad* const loads = (wn::SlotLoad*)(stage + slotLoadOff());
-        int nUpd = 0, nCols = 0, nLoads = 0;
-        for (int b : m_slotPendingList) {
-            wn::SlotUpdate u = {};
-            u.column = b;
-            u.reset = m_slotPending[b] == 1 ? 1 : 0;
-            if (u.reset && m_slotResume[b] != NULL) {      // a resume: ring and history from the blob, local sample `done` by this step
-                m_slotHost[b].start = m_slotCounter - m_slotResumeDone[b];
-                loads[nLoads++] = wn::SlotLoad{m_slotResume[b], b, slotRotation(m_slotHost[b].start)};
-                slotTouchTile(b);
-                slotDropResume(b);
-                u.reset = 0;
-            } else if (u.reset) {
-                m_slotHost[b].start = m_slotCounter;      // local sample 0 is generated by this step
-                cols[nCols++] = b;
-            }
-            u.d = m_slotHost[b];
-            upd[nUpd++] = u;
-            m_slotPending[b] = 0;
-        }
-        m_slotPendingList.clear();
-        gpuErrChk(hipMemcpyAsync(m_slotUpd, upd, (size_t)nUpd * sizeof(wn::SlotUpdate), hipMemcpyHostToDevice, stream));
-        if (nCols) gpuErrChk(hipMemcpyAsync(m_slotUpd + colOff, cols, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, stream));
-        if (nLoads) gpuErrChk(hipMemcpyAsync(m_slotUpd + slotLoadOff(), loads, (size_t)nLoads * sizeof(wn::SlotLoad), hipMemcpyHostToDevice, stream));
-        gpuErrChk(hipEventRecord(m_slotEv[m_slotParity], stream));
-        m_slotParity ^= 1;
-        bool ok = wn::slots_reset(stream, m_slotDesc, (const wn::SlotUpdate*)m_slotUpd, nUpd, (const int*)(m_slotUpd + colOff), nCols, m_ring,
-                                  m_ringSlots, ringFragsPerSlot(), m_yInPrev, m_yInCur);
-        if (nLoads)
-            ok = wn::slots_load(stream, (const wn::SlotLoad*)(m_slotUpd + slotLoadOff()), nLoads, slotLayers(), m_ring, m_ringSlots,
-                                ringFragsPerSlot(), m_yInPrev, m_yInCur) && ok;
-        return ok;
-    }
-    // ---- sampling temperature (slots_sampler.hpp) ----
-    // the host's value of column b; the first value other than 1 makes the device table (filled with log2(e); synchronises)
-    void tempSet(int b, float T) {
-        if (m_temp.empty()) {
-            if (T == 1.0f) return;
-            m_temp.assign(m_maxBatch, 1.0f);
-        }
-        if (T != 1.0f && !m_softScale) {
-            std::vector<float> unit(m_maxBatch, wn::kSoftScaleUnit);
-            gpuErrChk(hipMalloc(&m_softScale, unit.size() * sizeof(float)));
-            gpuErrChk(hipMemcpy(m_softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        m_tempNonUnit += (T != 1.0f) - (m_temp[b] != 1.0f);
-        m_temp[b] = T;
-    }
-    // every column back to T = 1, on the host and in the table (synchronises when the table has to be rewritten)
-    void resetTemperatures() {
-        if (m_softScale && (m_tempNonUnit > 0 || !m_tempDirtyList.empty())) {
-            std::vector<float> unit(m_maxBatch, wn::kSoftScaleUnit);
-            gpuErrChk(hipDeviceSynchronize());
-            gpuErrChk(hipMemcpy(m_softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        m_temp.clear();
-        m_tempNonUnit = 0;
-        m_tempDirty.clear();
-        m_tempDirtyList.clear();
-    }
-    // slot mode: ... and the next step writes the column's table entry when the value changes
-    void slotTempSet(int slot, float T) {
-        if (temperature(slot) == T) return;
-        tempSet(slot, T);
-        if (m_tempDirty.empty()) m_tempDirty.assign(m_maxBatch, 0);
-        if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
-        m_tempDirty[slot] = 1;
-    }
-    void slotTempFromHeader(int slot, const wn::SlotStateHeader& h) {
-        float T = 1.0f;
-        const bool ok = wn::temperature_of_word(h.pad[0], T);      // (slotHeaderOk has checked it)
-        assert(ok);
-        (void)ok;
-        slotTempSet(slot, T);
-    }
-    // the changed columns -> pinned staging -> device, then one slot_scale_kernel launch (staging halves as slotApplyPending, made
-    // by the first step that needs them)
-    bool slotApplyTemperatures(hipStream_t stream) {
-        if (!m_softScale) {      // (only columns that went back to 1 before anything else was set: the table does not exist)
-            for (int b : m_tempDirtyList) m_tempDirty[b] = 0;
-            m_tempDirtyList.clear();
-            return true;
-        }
-        if (!m_scaleDev) {
-            gpuErrChk(hipMalloc((void**)&m_scaleDev, (size_t)m_maxBatch * sizeof(wn::SlotScale)));
-            for (int i = 0; i < 2; i++) {
-                gpuErrChk(hipHostMalloc((void**)&m_scaleStage[i], (size_t)m_maxBatch * sizeof(wn::SlotScale), hipHostMallocDefault));
-                gpuErrChk(hipEventCreateWithFlags(&m_scaleEv[i], hipEventDisableTiming));
-                gpuErrChk(hipEventRecord(m_scaleEv[i], stream));
-            }
-        }
-        wn::SlotScale* const stage = m_scaleStage[m_scaleParity];
-        gpuErrChk(hipEventSynchronize(m_scaleEv[m_scaleParity]));
-        int n = 0;
-        for (int b : m_tempDirtyList) {
-            stage[n++] = wn::SlotScale{b, wn::temperature_scale(m_temp[b])};
-            m_tempDirty[b] = 0;
-        }
-        m_tempDirtyList.clear();
-        gpuErrChk(hipMemcpyAsync(m_scaleDev, stage, (size_t)n * sizeof(wn::SlotScale), hipMemcpyHostToDevice, stream));
-        gpuErrChk(hipEventRecord(m_scaleEv[m_scaleParity], stream));
-        m_scaleParity ^= 1;
-        return wn::slots_set_scales(stream, m_softScale, m_maxBatch, m_scaleDev, n);
-    }
-    // ---- mel columns (slots_mel.hpp) ----
-    size_t melTileOff() const { return (size_t)m_maxBatch * sizeof(wn::MelUpdate); }
-    void melMarkDirty(int slot) {
-        if (!m_melDirty[slot]) m_melDirtyList.push_back(slot);
-        m_melDirty[slot] = 1;
-    }
-    // a column that is started or stopped stops being a mel column
-    void slotDropMel(int slot) {
-        if (m_melHost.empty() || !m_melHost[slot].state) return;
-        m_melHost[slot].state = 0;
-        m_melColumns--;
-        melMarkDirty(slot);
-        m_melTilesDirty = true;
-    }
-    void melAllocate() {
-        gpuErrChk(hipMalloc(&m_melDesc, (size_t)m_maxBatch * sizeof(wn::MelDesc)));
-        gpuErrChk(hipMemset(m_melDesc, 0, (size_t)m_maxBatch * sizeof(wn::MelDesc)));
-        const size_t bytes = melTileOff() + (size_t)m_tiles * sizeof(int);
-        gpuErrChk(hipMalloc(&m_melUpd, bytes));
-        gpuErrChk(hipMalloc(&m_melColInfo, (size_t)m_tiles * 16 * 2 * sizeof(int)));
-        for (int i = 0; i < 2; i++) {
-            gpuErrChk(hipHostMalloc((void**)&m_melStageHost[i], bytes, hipHostMallocDefault));
-            gpuErrChk(hipEventCreateWithFlags(&m_melEv[i], hipEventDisableTiming));
-            gpuErrChk(hipEventRecord(m_melEv[i], 0));
-        }
-        m_melParity = 0;
-        if (!m_melPrepared) m_melPrepared = wn::slots_mel_prepare<F16>();
-        gpuErrChk(hipDeviceSynchronize());
-    }
-    // the stage and records of a step of `count` samples (grown when a longer step needs more; the steps before it are waited for)
-    elem* melStage(int count) {
-        m_melRecOff = (size_t)wn::slots_mel_stage_frames(count, m_upStride, m_upWindow / m_upStride) * featureElems(1);
-        const size_t need = m_melRecOff + featureElems(count);
-        if (need > m_melStageElems) {
-            gpuErrChk(hipDeviceSynchronize());
-            if (m_melStage) gpuErrChk(hipFree(m_melStage));
-            gpuErrChk(hipMalloc(&m_melStage, need * sizeof(elem)));
-            m_melStageElems = need;
-        }
-        return m_melStage;
-    }
-    // the changed mel descriptors (a start takes the counter of this step) and, when it changed, the list of tiles holding mel
-    // columns -> pinned staging -> device, and one slot_mel_apply_kernel launch; the staging half is reused two steps later
-    bool melApplyPending(hipStream_t stream) {
-        char* const stage = m_melStageHost[m_melParity];
-        gpuErrChk(hipEventSynchronize(m_melEv[m_melParity]));
-        wn::MelUpdate* const upd = (wn::MelUpdate*)stage;
-        int* const tileList = (int*)(stage + melTileOff());
-        int nUpd = 0;
-        for (int b : m_melDirtyList) {
-            wn::MelDesc& d = m_melHost[b];
-            if (d.state && m_slotPending[b] == 1) d.start = m_slotCounter - m_slotResumeDone[b];      // local sample 0 (resumed: done) is generated by this step
-            upd[nUpd].column = b;
-            upd[nUpd].pad = 0;
-            upd[nUpd].d = d;
-            nUpd++;
-            m_melDirty[b] = 0;
-        }
-        m_melDirtyList.clear();
-        bool ok = true;
-        if (nUpd) {
-            gpuErrChk(hipMemcpyAsync(m_melUpd, upd, (size_t)nUpd * sizeof(wn::MelUpdate), hipMemcpyHostToDevice, stream));
-            ok = wn::slots_mel_apply(stream, m_melDesc, (const wn::MelUpdate*)m_melUpd, nUpd);
-        }
-        if (m_melTilesDirty) {
-            int n = 0;
-            for (int tile = 0; tile * 16 < m_maxBatch; tile++)
-                for (int j = 0; j < 16 && tile * 16 + j < m_maxBatch; j++)
-                    if (m_melHost[tile * 16 + j].state) {
-                        tileList[n++] = tile;
-                        break;
-                    }
-            if (n) gpuErrChk(hipMemcpyAsync(m_melUpd + melTileOff(), tileList, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
-            m_melTiles = n;
-            m_melTilesDirty = false;
-        }
-        gpuErrChk(hipEventRecord(m_melEv[m_melParity], stream));
-        m_melParity ^= 1;
-        return ok;
-    }
-    // wavenet_wg<.., RAW=3> on window rows [t0, t0 + count) of the first `cols` columns (the launch of run_partial for features,
-    // with the window's buffers and the selector table)
-    bool slotLaunch(int t0, int count, int cols, hipStream_t stream) {
+    // (the launch of run_partial for features, with the window's buffers and the selector table)
+    bool slotGenerate(const void* feat, const float* sel, int* y, int W, int t0, int count, int cols, hipStream_t stream) override {
         const int tiles = (cols + 15) / 16;
-        {
-            int bt = wgTiles(tiles);
-            if (bt >= 3 && wg4Fits()) bt = 12;      // (as run_partial: the rings of every tile a workgroup holds are written)
-            int touched = (tiles + bt - 1) / bt * bt;
-            if (touched > m_tiles) touched = m_tiles;
-            if (touched > m_ringDirtyTiles) m_ringDirtyTiles = touched;
-        }
-        wn::Params p;
+        wgRingsDirty(tiles);
+        wn::Params p = baseParams();
         p.wblob = m_wblobF;
         p.bias = m_biasF;
-        p.embPrev = m_embedPrev;
-        p.embCur = m_embedCur;
         p.cond = NULL;
         p.condRaw = NULL;
         p.condRawKind = 3;
-        p.feat = m_slotFeat;
+        p.feat = feat;
+        p.sel = sel;
+        p.yOut = y;
+        p.batch = cols;
+        p.numSamples = W;
+        p.condSamples = W;
+        p.initSample = t0;
+        p.count = count;
+        p.dump = 0;
+        p.useRng = 0;
+        p.softScale = m_temps.softScale;
+        return launchWg(p, tiles, stream);
+    }
+    // what every launch's Params share: the model, the ring and history, the debug outputs, the shape and schedule, the seed
+    wn::Params baseParams() const {
+        wn::Params p;
+        p.wblob = m_wblob;
+        p.bias = m_bias;
+        p.embPrev = m_embedPrev;
+        p.embCur = m_embedCur;
         p.gate = NULL;
-        p.sel = m_slotSel;
         p.ring = m_ring;
         p.maxDilation = m_maxDilation;
         p.yInPrev = m_yInPrev;
         p.yInCur = m_yInCur;
-        p.yOut = m_slotY;
         p.xtOut = m_XtOut;
         p.skipOut = m_skipOut;
         p.zs = m_Zs;
         p.za = m_Za;
         p.p = m_p;
         p.numLayers = m_numLayers;
-        p.batch = cols;
         p.maxBatch = m_maxBatch;
-        p.numSamples = m_slotW;
-        p.condSamples = m_slotW;
-        p.initSample = t0;
-        p.count = count;
         p.ringSlots = m_ringSlots;
-        p.ldsRingD = 0;
+        p.ldsRingD = 0;                 // (the wavenet_wg launchers place ring slots in the LDS their tables leave free: placeLdsRing)
         p.tiles = m_tiles;
         p.tileBase = 0;
         p.tanhEmbed = m_tanhEmbed ? 1 : 0;
-        p.dump = 0;
         p.embLds = 0;
-        p.useRng = 0;
         p.rngKey0 = (unsigned)m_rngSeed;
         p.rngKey1 = (unsigned)(m_rngSeed >> 32);
         p.clk = m_clkOn ? m_clk : NULL;
-        p.softScale = m_softScale;
         fillSchedule(p);
-        return launchWg(p, tiles, stream);
+        return p;
+    }
+    // the tiles whose rings a wavenet_wg launch on `tiles` tiles writes: a workgroup of BT tiles stores into the rings of ALL its
+    // tiles, the padding tiles beyond the batch included (a later, larger batch must find those slots zero as well)
+    void wgRingsDirty(int tiles) {
+        int bt = wgTiles(tiles);
+        if (bt >= 3 && wg4Fits()) bt = 12;      // (three or four tiles per workgroup by launch: both roundings)
+        const int touched = (tiles + bt - 1) / bt * bt;
+        slotRingsDirty(touched > m_tiles ? m_tiles : touched);
     }
     // wavenet_wg by batch size: one to four tiles per workgroup
     bool launchWg(wn::Params& p, int tiles, hipStream_t stream) {

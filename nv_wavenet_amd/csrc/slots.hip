@@ -103,6 +103,11 @@ bool slots_reset(hipStream_t stream, SlotDesc* desc, const SlotUpdate* upd, int 
     return hipGetLastError() == hipSuccess;
 }
 
+bool slots_pcm(hipStream_t stream, const int* y, short* pcm, const short* table, int cols, int W, int t0, int count) {
+    hipLaunchKernelGGL(mulaw_pcm_kernel, dim3(gridOf((size_t)cols * count, 4096)), dim3(256), 0, stream, y, pcm, table, cols, W, t0, count);
+    return hipGetLastError() == hipSuccess;
+}
+
 template <bool F16>
 bool slots_feed(hipStream_t stream, void* feat, float* sel, const SlotDesc* desc, int cols, int maxBatch, int tiles, int nCond,
                 long long counter, int T, int W, int count, unsigned long long seed) {

@@ -45,5 +45,7 @@ bool slots_reset(hipStream_t stream, SlotDesc* desc, const SlotUpdate* upd, int 
 template <bool F16>
 bool slots_feed(hipStream_t stream, void* feat, float* sel, const SlotDesc* desc, int cols, int maxBatch, int tiles, int nCond,
                 long long counter, int T, int W, int count, unsigned long long seed);
+// pcm[b][t] = table[y[b][t]] for window rows [t0, t0 + count) of the first `cols` columns of the [.][W] windows (mulaw_pcm_kernel)
+bool slots_pcm(hipStream_t stream, const int* y, short* pcm, const short* table, int cols, int W, int t0, int count);
 
 }  // namespace wn

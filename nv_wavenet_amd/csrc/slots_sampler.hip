@@ -2,7 +2,41 @@
 // Compiled once, both precisions.  At most maxBatch entries of 8 bytes per step: one thread per entry.
 #include "slots_sampler.hpp"
 
+#include "gpu_check.hpp"
+
 namespace wn {
+
+TemperatureTable::~TemperatureTable() {
+    if (softScale) gpuErrChk(hipFree(softScale));
+}
+void TemperatureTable::set(int b, float t) {
+    if (T.empty()) {
+        if (t == 1.0f) return;
+        T.assign(columns, 1.0f);
+    }
+    if (t != 1.0f && !softScale) {
+        std::vector<float> unit(columns, kSoftScaleUnit);
+        gpuErrChk(hipMalloc(&softScale, unit.size() * sizeof(float)));
+        gpuErrChk(hipMemcpy(softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    nonUnit += (t != 1.0f) - (T[b] != 1.0f);
+    T[b] = t;
+}
+void TemperatureTable::reset(bool deviceBehind) {
+    const bool rewrite = softScale && (nonUnit > 0 || deviceBehind);
+    T.clear();
+    nonUnit = 0;
+    if (rewrite) {
+        gpuErrChk(hipDeviceSynchronize());
+        upload();
+    }
+}
+void TemperatureTable::upload() {
+    if (!softScale) return;
+    std::vector<float> c(columns);
+    for (int b = 0; b < columns; b++) c[b] = temperature_scale(get(b));      // (T is empty when every value is 1)
+    gpuErrChk(hipMemcpy(softScale, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
+}
 
 __global__ __launch_bounds__(256) void slot_scale_kernel(float* __restrict__ table, int columns, const SlotScale* __restrict__ upd, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {

@@ -12,6 +12,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 namespace wn {
 
 constexpr float kSoftScaleUnit = 1.44269504088896340736f;      // log2(e): T = 1 (wn::kLog2e of wn_kernels.hpp)
@@ -34,6 +36,29 @@ inline bool temperature_of_word(int w, float& T) {
     if (w != 0) memcpy(&T, &w, sizeof(T));
     return temperature_ok(T);
 }
+
+// The table itself, lockstep and slot mode: the host's values are the authority, the device table follows them.  Nothing is
+// allocated, and Params::softScale stays NULL, until a temperature other than 1 has been set: an engine that never uses the
+// feature launches what it launched before.
+struct TemperatureTable {
+    explicit TemperatureTable(int columns) : columns(columns) {}
+    ~TemperatureTable();
+    TemperatureTable(const TemperatureTable&) = delete;      // (owns the device table)
+    // the temperature in force for column b (1 when none was ever set)
+    float get(int b) const { return (b >= 0 && b < (int)T.size()) ? T[b] : 1.0f; }
+    // the host's value of column b; the first value other than 1 makes the device table (filled with log2(e); synchronises)
+    void set(int b, float t);
+    // every column back to T = 1, on the host and in the table (synchronises when the table has to be rewritten: a value other
+    // than 1 is in force, or deviceBehind -- the table holds values the host has since taken back)
+    void reset(bool deviceBehind);
+    // the whole table from the host's values, when it exists (blocking copy)
+    void upload();
+
+    const int columns;
+    std::vector<float> T;                   // [columns] T per column (empty: 1 everywhere)
+    int nonUnit = 0;                        // columns with T != 1
+    float* softScale = NULL;                // [columns] log2(e) / T on the device, made at the first use and filled with log2(e)
+};
 
 // one changed column of a step
 struct SlotScale {

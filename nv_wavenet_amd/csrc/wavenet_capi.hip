@@ -93,9 +93,7 @@ int nvw_set_conditioning_direct_t(nvw_engine* e, const void* Lh, int num_samples
         return 0;
     }
     if (precision == 16) {      // (a host tensor can only take the packing path, which reads fp32)
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, Lh) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
-            (void)hipGetLastError();
+        if (!wn::is_device_ptr(Lh)) {
             fprintf(stderr, "nvw_set_conditioning_direct_t: an fp16 tensor must be device memory to be read in place\n");
             return 0;
         }
@@ -115,14 +113,6 @@ int nvw_set_conditioning_packed_n(nvw_engine* e, const void* frags, int num_samp
 }
 int nvw_cond_tiles(nvw_engine* e) { return e->condTiles(); }
 // ---- conditioning computed in the generation kernel from the upsampled features ------------------------------------------------
-static bool devicePtr(const void* p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
 int nvw_max_cond_channels(void) { return wn::kCondChannelsMax; }
 int nvw_set_conditioning_weights(nvw_engine* e, const float* Wcond, const float* bcond, int n_cond) {
     if (!e->setConditioningWeights(Wcond, bcond, n_cond)) {
@@ -139,7 +129,7 @@ static bool featArgsOk(nvw_engine* e, const char* who, const void* p, int first,
         fprintf(stderr, "%s: call nvw_set_conditioning_weights first\n", who);
         return false;
     }
-    if (!devicePtr(p)) {
+    if (!wn::is_device_ptr(p)) {
         fprintf(stderr, "%s: the features must be device memory\n", who);
         return false;
     }
@@ -175,7 +165,7 @@ int nvw_set_upsampling(nvw_engine* e, const float* up_w, const float* up_b, int 
 }
 int nvw_set_mel(nvw_engine* e, const void* mel, int precision, long long b_stride, long long c_stride, long long f_stride, int frames) {
     const int stride = e->upsamplingStride();
-    if (stride <= 0 || !devicePtr(mel) || (precision != 32 && precision != 16) || frames <= 0 || (long long)frames * stride > e->maxSamples()) {
+    if (stride <= 0 || !wn::is_device_ptr(mel) || (precision != 32 && precision != 16) || frames <= 0 || (long long)frames * stride > e->maxSamples()) {
         fprintf(stderr, "nvw_set_mel: refused (nvw_set_upsampling first; device memory; 16- or 32-bit floats; frames * stride <= the engine's %d samples)\n",
                 e->maxSamples());
         return 0;
@@ -275,71 +265,57 @@ int nvw_slots_begin(nvw_engine* e, int window) {
         fprintf(stderr, "nvw_slots_begin: call nvw_set_conditioning_weights first\n");
         return 0;
     }
-    if (!e->slotsBegin(window)) {
-        fprintf(stderr, "nvw_slots_begin: window %d is not a positive multiple of the largest dilation\n", window);
-        return 0;
-    }
-    return 1;
+    if (e->slots().begin(window)) return 1;
+    fprintf(stderr, "nvw_slots_begin: window %d is not a positive multiple of the largest dilation\n", window);
+    return 0;
 }
 int nvw_slot_start(nvw_engine* e, int slot, const void* x, int precision, long long c_stride, long long t_stride, int length,
                    unsigned uid) {
-    if (!e->slotStart(slot, x, precision, c_stride, t_stride, length, uid)) {
-        fprintf(stderr, "nvw_slot_start: refused (nvw_slots_begin first; slot %d of %d; device features of 16 or 32 bits; strides %lld, %lld "
-                "and length %d positive)\n", slot, e->maxBatch(), c_stride, t_stride, length);
-        return 0;
-    }
-    return 1;
+    if (e->slots().start(slot, x, precision, c_stride, t_stride, length, uid)) return 1;
+    fprintf(stderr, "nvw_slot_start: refused (nvw_slots_begin first; slot %d of %d; device features of 16 or 32 bits; strides %lld, %lld "
+            "and length %d positive)\n", slot, e->maxBatch(), c_stride, t_stride, length);
+    return 0;
 }
 int nvw_slot_stop(nvw_engine* e, int slot) {
-    if (!e->slotStop(slot)) {
-        fprintf(stderr, "nvw_slot_stop: refused (nvw_slots_begin first; slot %d of %d)\n", slot, e->maxBatch());
-        return 0;
-    }
-    return 1;
+    if (e->slots().stop(slot)) return 1;
+    fprintf(stderr, "nvw_slot_stop: refused (nvw_slots_begin first; slot %d of %d)\n", slot, e->maxBatch());
+    return 0;
 }
 int nvw_slots_step(nvw_engine* e, int count, int* yOut, short* pcm, void* stream) {
-    return e->slotsStep(count, yOut, pcm, (hipStream_t)stream) ? 1 : 0;
+    return e->slots().step(count, yOut, pcm, (hipStream_t)stream) ? 1 : 0;
 }
-void nvw_slots_end(nvw_engine* e) { e->slotsEnd(); }
+void nvw_slots_end(nvw_engine* e) { e->slots().end(); }
 // ---- slot mode from mel frames (additive within ABI 7) ---------------------------------------------------------------------------
 int nvw_slot_start_mel(nvw_engine* e, int slot, const void* mel, int precision, long long c_stride, long long f_stride, int frames,
                        int final, unsigned uid) {
-    if (!e->slotStartMel(slot, mel, precision, c_stride, f_stride, frames, final, uid)) {
-        fprintf(stderr, "nvw_slot_start_mel: refused (nvw_slots_begin and nvw_set_upsampling first; slot %d of %d; device frames of 16 or 32 "
-                "bits; strides %lld, %lld positive; frames %d >= 0, > 0 when final)\n", slot, e->maxBatch(), c_stride, f_stride, frames);
-        return 0;
-    }
-    return 1;
+    if (e->slots().startMel(slot, mel, precision, c_stride, f_stride, frames, final, uid)) return 1;
+    fprintf(stderr, "nvw_slot_start_mel: refused (nvw_slots_begin and nvw_set_upsampling first; slot %d of %d; device frames of 16 or 32 "
+            "bits; strides %lld, %lld positive; frames %d >= 0, > 0 when final)\n", slot, e->maxBatch(), c_stride, f_stride, frames);
+    return 0;
 }
 int nvw_slot_mel_frames(nvw_engine* e, int slot, int frames, int final) {
-    if (!e->slotMelFrames(slot, frames, final)) {
-        fprintf(stderr, "nvw_slot_mel_frames: refused (slot %d of %d: not a running mel column, already final, or %d frames is fewer than "
-                "before)\n", slot, e->maxBatch(), frames);
-        return 0;
-    }
-    return 1;
+    if (e->slots().melFrames(slot, frames, final)) return 1;
+    fprintf(stderr, "nvw_slot_mel_frames: refused (slot %d of %d: not a running mel column, already final, or %d frames is fewer than "
+            "before)\n", slot, e->maxBatch(), frames);
+    return 0;
 }
-int nvw_slots_headroom(nvw_engine* e) { return e->slotsHeadroom(); }
+int nvw_slots_headroom(nvw_engine* e) { return e->slots().headroom(); }
 int nvw_slots_get_features(nvw_engine* e, void* dst, long long first_sample, int count) {
-    if (!e->slotsGetFeatures(dst, first_sample, count)) {
-        fprintf(stderr, "nvw_slots_get_features: refused (samples [%lld, %lld) are not among the last window of samples generated)\n",
-                first_sample, first_sample + count);
-        return 0;
-    }
-    return 1;
+    if (e->slots().getFeatures(dst, first_sample, count)) return 1;
+    fprintf(stderr, "nvw_slots_get_features: refused (samples [%lld, %lld) are not among the last window of samples generated)\n",
+            first_sample, first_sample + count);
+    return 0;
 }
 // ---- slot mode: a column's state as a value (additive within ABI 7) --------------------------------------------------------------
-size_t nvw_slot_state_bytes(nvw_engine* e) { return e->slotStateBytes(); }
+size_t nvw_slot_state_bytes(nvw_engine* e) { return e->slots().stateBytes(); }
 int nvw_slot_move(nvw_engine* e, int from, int to) {
-    if (!e->slotMove(from, to)) {
-        fprintf(stderr, "nvw_slot_move: refused (nvw_slots_begin first; %d -> %d of %d columns: a running column without a pending start, "
-                "resume or move into an idle one without them)\n", from, to, e->maxBatch());
-        return 0;
-    }
-    return 1;
+    if (e->slots().move(from, to)) return 1;
+    fprintf(stderr, "nvw_slot_move: refused (nvw_slots_begin first; %d -> %d of %d columns: a running column without a pending start, "
+            "resume or move into an idle one without them)\n", from, to, e->maxBatch());
+    return 0;
 }
 int nvw_slot_save(nvw_engine* e, int slot, void* dst, void* stream) {
-    const int done = e->slotSave(slot, dst, (hipStream_t)stream);
+    const int done = e->slots().save(slot, dst, (hipStream_t)stream);
     if (done < 0)
         fprintf(stderr, "nvw_slot_save: refused (nvw_slots_begin first; slot %d of %d: a running column without a pending start, resume or "
                 "move; dst 16-byte aligned device memory)\n", slot, e->maxBatch());
@@ -347,68 +323,60 @@ int nvw_slot_save(nvw_engine* e, int slot, void* dst, void* stream) {
 }
 int nvw_slot_resume(nvw_engine* e, int slot, const void* state, const void* x, int precision, long long c_stride, long long t_stride,
                     int length) {
-    if (!e->slotResume(slot, state, x, precision, c_stride, t_stride, length)) {
-        fprintf(stderr, "nvw_slot_resume: refused (a state of nvw_slot_save for this shape and precision with fewer than %d samples done, "
-                "device memory; otherwise as nvw_slot_start: slot %d of %d)\n", length, slot, e->maxBatch());
-        return 0;
-    }
-    return 1;
+    if (e->slots().resume(slot, state, x, precision, c_stride, t_stride, length)) return 1;
+    fprintf(stderr, "nvw_slot_resume: refused (a state of nvw_slot_save for this shape and precision with fewer than %d samples done, "
+            "device memory; otherwise as nvw_slot_start: slot %d of %d)\n", length, slot, e->maxBatch());
+    return 0;
 }
 int nvw_slot_resume_mel(nvw_engine* e, int slot, const void* state, const void* mel, int precision, long long c_stride,
                         long long f_stride, int frames, int final) {
-    if (!e->slotResumeMel(slot, state, mel, precision, c_stride, f_stride, frames, final)) {
-        fprintf(stderr, "nvw_slot_resume_mel: refused (a state of nvw_slot_save for this shape and precision, device memory, with fewer "
-                "samples done than %d final frames hold; otherwise as nvw_slot_start_mel: slot %d of %d)\n", frames, slot, e->maxBatch());
-        return 0;
-    }
-    return 1;
+    if (e->slots().resumeMel(slot, state, mel, precision, c_stride, f_stride, frames, final)) return 1;
+    fprintf(stderr, "nvw_slot_resume_mel: refused (a state of nvw_slot_save for this shape and precision, device memory, with fewer "
+            "samples done than %d final frames hold; otherwise as nvw_slot_start_mel: slot %d of %d)\n", frames, slot, e->maxBatch());
+    return 0;
 }
 // ---- slot mode: lists of columns saved and resumed (additive within ABI 7) --------------------------------------------------------
 int nvw_slots_save_list(nvw_engine* e, const int* slots, int n, void* dst, long long stride, nvw_slot_saved* saved, void* stream) {
-    const int got = e->slotsSaveList(slots, n, dst, stride, saved, (hipStream_t)stream);
+    const int got = e->slots().saveList(slots, n, dst, stride, (wn::SlotSaved*)saved, (hipStream_t)stream);
     if (got < 0)
         fprintf(stderr, "nvw_slots_save_list: refused (nvw_slots_begin first; %d slots of %d, each once: running columns without a pending "
                 "start, resume or move; dst 16-byte aligned device or pinned memory; stride %lld a multiple of 16, at least %zu)\n", n,
-                e->maxBatch(), stride, e->slotStateBytes());
+                e->maxBatch(), stride, e->slots().stateBytes());
     return got;
 }
 int nvw_slots_resume_list(nvw_engine* e, const nvw_slot_resume_req* reqs, int n, const void* states, long long stride) {
-    const int got = e->slotsResumeList(reqs, n, states, stride);
+    const int got = e->slots().resumeList((const wn::SlotResumeReq*)reqs, n, states, stride);
     if (got != n || n < 1)
         fprintf(stderr, "nvw_slots_resume_list: refused, nothing changed (%d requests of %d columns, each column once, idle and without a "
                 "pending start; states of nvw_slot_save / nvw_slots_save_list for this shape and precision in device or pinned memory, "
                 "stride %lld a multiple of 16, at least %zu; otherwise as nvw_slot_resume / nvw_slot_resume_mel)\n", n, e->maxBatch(),
-                stride, e->slotStateBytes());
+                stride, e->slots().stateBytes());
     return got;
 }
 // ---- sampling temperature per utterance, lockstep and in slot mode (additive within ABI 7) ---------------------------------------
 int nvw_set_temperatures(nvw_engine* e, const float* T, int n) {
-    if (!e->setTemperatures(T, n)) {
-        fprintf(stderr, "nvw_set_temperatures: refused, nothing changed (not in slot mode; %d values for %d columns; every value finite and in "
-                "[2^-10, 2^10])\n", n, e->maxBatch());
-        return 0;
-    }
-    return 1;
+    if (e->setTemperatures(T, n)) return 1;
+    fprintf(stderr, "nvw_set_temperatures: refused, nothing changed (not in slot mode; %d values for %d columns; every value finite and in "
+            "[2^-10, 2^10])\n", n, e->maxBatch());
+    return 0;
 }
 int nvw_slot_set_temperature(nvw_engine* e, int slot, float T) {
-    if (!e->slotSetTemperature(slot, T)) {
-        fprintf(stderr, "nvw_slot_set_temperature: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
-                "a pending start or resume; T = %g finite and in [2^-10, 2^10])\n", slot, e->maxBatch(), (double)T);
-        return 0;
-    }
-    return 1;
+    if (e->slots().setTemperature(slot, T)) return 1;
+    fprintf(stderr, "nvw_slot_set_temperature: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
+            "a pending start or resume; T = %g finite and in [2^-10, 2^10])\n", slot, e->maxBatch(), (double)T);
+    return 0;
 }
-float nvw_slot_temperature(nvw_engine* e, int slot) { return e->slotTemperature(slot); }
+float nvw_slot_temperature(nvw_engine* e, int slot) { return e->slots().temperature(slot); }
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {
-    return e->slotsStepRagged(count, samples, pcm, capacity, pieces, max_pieces, n_pieces, ticket, (hipStream_t)stream);
+    return e->slots().stepRagged(count, samples, pcm, capacity, (wn::SlotPiece*)pieces, max_pieces, n_pieces, ticket, (hipStream_t)stream);
 }
 float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream) {
-    return e->slotsTimeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);
+    return e->slots().timeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);
 }
-int nvw_slots_wait(nvw_engine* e, unsigned long long ticket) { return e->slotsWait(ticket) ? 1 : 0; }
-int nvw_slots_done(nvw_engine* e, unsigned long long ticket) { return e->slotsDone(ticket) > 0 ? 1 : 0; }
+int nvw_slots_wait(nvw_engine* e, unsigned long long ticket) { return e->slots().wait(ticket) ? 1 : 0; }
+int nvw_slots_done(nvw_engine* e, unsigned long long ticket) { return e->slots().done(ticket) > 0 ? 1 : 0; }
 void* nvw_pinned_alloc(size_t bytes) {
     void* p = NULL;
     if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {

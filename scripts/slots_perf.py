@@ -45,15 +45,21 @@ column 5 of every tile stop, the survivors are compacted to the front --, in one
 Prints one JSON line with medians, min .. max over the rounds, GB/s of blob bytes (read + written), and the verdict on the claim
 that the list save into device memory beats the single saves by more than the run-to-run spread.
 
---temperature times what the per-column sampling temperature costs a slot step, three cases back to back in one
-process, `--rounds` rounds, the cases alternating within a round: the PARENT commit's step (a libwavenet_infer.so built from it,
---parent-lib; loaded beside this commit's and driven through the same ctypes calls), this commit with every T = 1 (no table, the
-kernel argument NULL) and this commit with mixed T (0.7, 0.85, 1, 1.2 cycling over the columns: the table and its scatter launch).
-Every column runs one long utterance (no restarts: the same work in every case and round).  Prints one JSON line per chunk size
-with the per-round ms per step of each case, the medians, the parent's run-to-run spread (max - min over median) and the verdict:
-neither case of this commit slower than the parent by more than twice that spread.
+--parent times the slot step of this commit against the PARENT commit's (a libwavenet_infer.so built from it, --parent-lib; loaded
+beside this commit's and driven through the same ctypes calls) in one process, `--rounds` rounds, the cases alternating within a
+round: the plain step (nvw_slots_step into a device buffer) and the ragged step into pinned memory (nvw_slots_step_ragged, waited
+for at the end of each round's steps), each on both libraries.  Every column runs one long utterance (no restarts: the same work
+in every case and round).  Prints one JSON line per chunk size with the per-round ms per step of each case, the medians, the
+parent's run-to-run spread (max - min over median) and the verdict per kind of step: this commit's median not above the parent's
+by more than twice that spread.  The order of the two libraries within a round alternates from round to round.  The wall time
+the host spends inside the calls is recorded beside the time of a step (host_us_per_call, with the same verdict): at --batch 16
+--chunks 16 a step is one 16-sample launch on one CU, the GPU side is constant and the host's bookkeeping is what can differ.
+--temperature is the same comparison for what the per-column sampling temperature costs a step: the parent's plain
+step, this commit's with every T = 1 (no table, the kernel argument NULL) and with mixed T (0.7, 0.85, 1, 1.2 cycling over the
+columns: the table and its scatter launch); a parent that has the temperature entries is simply run at T = 1.
 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
@@ -84,7 +90,8 @@ def main():
     ap.add_argument("--drain", action="store_true", help="time list saves (device, pinned) and list resumes against one call per column")
     ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
     ap.add_argument("--temperature", action="store_true", help="time the slot step of the parent commit, of this one at T = 1 and at mixed T")
-    ap.add_argument("--parent-lib", default=None, help="--temperature: a libwavenet_infer.so built from the parent commit")
+    ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
+    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
     import torch
     import bench
@@ -93,9 +100,10 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
-    if args.temperature:
+    if args.temperature or args.parent:
+        assert args.parent_lib or not args.parent, "--parent needs --parent-lib"
         for chunk in [int(c) for c in args.chunks.split(",")]:
-            print(json.dumps(time_temperature(args, w, Wc, bc, chunk)), flush=True)
+            print(json.dumps(time_against_parent(args, w, Wc, bc, chunk)), flush=True)
         return
     if args.compact:
         print(json.dumps(time_compact(args, w, Wc, bc)), flush=True)
@@ -189,12 +197,14 @@ def main():
         print(json.dumps(res), flush=True)
 
 
-def time_temperature(args, w, Wc, bc, chunk):
-    """The --temperature measurement (module docstring) for steps of `chunk` samples."""
+def time_against_parent(args, w, Wc, bc, chunk):
+    """The --parent / --temperature measurement (module docstring) for steps of `chunk` samples.  A case is (library, temperatures,
+    kind of step); the cases of one library and temperature setting share an engine."""
     import ctypes as C
     import torch
     import bench
     from nv_wavenet_amd import _lib
+    from nv_wavenet_amd.engine import SLOT_PIECE
     B, W = args.batch, args.window
     sh = bench.HEAD
     vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
@@ -202,7 +212,8 @@ def time_temperature(args, w, Wc, bc, chunk):
             "nvw_set_layer_weights": (None, [vp, ci] + [vp] * 7), "nvw_set_out_weights": (None, [vp] * 5),
             "nvw_set_conditioning_weights": (ci, [vp, vp, vp, ci]), "nvw_set_selector_seed": (None, [vp, C.c_ulonglong]),
             "nvw_slots_begin": (ci, [vp, ci]), "nvw_slot_start": (ci, [vp, ci, vp, ci, ll, ll, ci, C.c_uint]),
-            "nvw_slots_step": (ci, [vp, ci, vp, vp, vp]), "nvw_slots_end": (None, [vp]), "nvw_kernel_info": (None, [vp, ci, ci, C.c_char_p, ci])}
+            "nvw_slots_step": (ci, [vp, ci, vp, vp, vp]), "nvw_slots_end": (None, [vp]), "nvw_kernel_info": (None, [vp, ci, ci, C.c_char_p, ci]),
+            "nvw_slots_step_ragged": (ll, [vp, ci, vp, vp, ll, vp, ci, vp, vp, vp]), "nvw_slots_wait": (ci, [vp, C.c_ulonglong])}
 
     def load(path):
         h = C.CDLL(path)
@@ -212,14 +223,14 @@ def time_temperature(args, w, Wc, bc, chunk):
 
     here = load(_lib.LIB_PATH)
     here.nvw_slot_set_temperature.restype, here.nvw_slot_set_temperature.argtypes = ci, [vp, ci, C.c_float]
-    libs = {"unit": here, "mixed": here}
+    libs = {"unit": here, "mixed": here} if args.temperature else {"here": here}
     if args.parent_lib:
         libs = dict({"parent": load(args.parent_lib)}, **libs)
-        assert not hasattr(libs["parent"], "nvw_slot_set_temperature"), "--parent-lib has the temperature entries: not the parent commit's"
+    kinds = ("step",) if args.temperature else ("step", "ragged")
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
     warm, steps = 2, max(2, args.steps * 256 // chunk)
-    need = (warm + args.rounds * steps) * chunk
+    need = (warm + args.rounds * steps) * chunk * (1 if args.temperature else 2)      # (--parent: plain and ragged steps)
     T_SRC = need + 4096
     src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
     rng = np.random.default_rng(3)
@@ -246,36 +257,64 @@ def time_temperature(args, w, Wc, bc, chunk):
         h.nvw_kernel_info(e, B, 0, buf, 256)
         engines[case], info[case] = e, buf.value.decode()
     y = torch.empty(B, chunk, dtype=torch.int32, device="cuda")
+    yp = torch.empty(B * ((chunk + 7) // 8 * 8), dtype=torch.int32, pin_memory=True)      # (every piece starts at a multiple of 8)
+    pieces, n_pieces, ticket = np.empty(B, dtype=SLOT_PIECE), ci(0), C.c_ulonglong(0)
     s = torch.cuda.current_stream().cuda_stream
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for case, h in libs.items():
-        for _ in range(warm):
-            assert h.nvw_slots_step(engines[case], chunk, y.data_ptr(), None, s)
+
+    def run(case, kind, n):
+        h, e = libs[case], engines[case]
+        for _ in range(n):
+            if kind == "step":
+                assert h.nvw_slots_step(e, chunk, y.data_ptr(), None, s)
+            else:
+                assert h.nvw_slots_step_ragged(e, chunk, yp.data_ptr(), None, yp.numel(), pieces.ctypes.data, B, C.byref(n_pieces),
+                                               C.byref(ticket), s) > 0
+
+    for case in libs:
+        for kind in kinds:
+            run(case, kind, warm)
     torch.cuda.synchronize()
-    ms = {case: [] for case in libs}
-    for _ in range(args.rounds):
-        for case, h in libs.items():
-            ev[0].record()
-            for _ in range(steps):
-                assert h.nvw_slots_step(engines[case], chunk, y.data_ptr(), None, s)
-            ev[1].record()
-            torch.cuda.synchronize()
-            ms[case].append(ev[0].elapsed_time(ev[1]) / steps)
+    ms = {(case, kind): [] for case in libs for kind in kinds}
+    host_us = {k: [] for k in ms}      # wall time of the host inside the calls (they return before the GPU has run them)
+    for r in range(args.rounds):
+        for kind in kinds:
+            for case in (list(libs) if r % 2 == 0 else list(libs)[::-1]):      # (the order within a round alternates)
+                ev[0].record()
+                h0 = time.perf_counter()
+                run(case, kind, steps)
+                h1 = time.perf_counter()
+                ev[1].record()
+                if kind == "ragged":
+                    assert libs[case].nvw_slots_wait(engines[case], ticket.value)
+                torch.cuda.synchronize()
+                ms[(case, kind)].append(ev[0].elapsed_time(ev[1]) / steps)
+                host_us[(case, kind)].append(1e6 * (h1 - h0) / steps)
     for case, h in libs.items():
         h.nvw_slots_end(engines[case])
         h.nvw_destroy(engines[case])
     torch.cuda.empty_cache()
-    med = {case: float(np.median(v)) for case, v in ms.items()}
-    res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps, "mixed_temperatures": mixed,
-           "ms_per_step": {case: [round(v, 3) for v in vs] for case, vs in ms.items()}, "median_ms_per_step": {k: round(v, 3) for k, v in med.items()},
-           "kernel": info["unit"], "device": torch.cuda.get_device_name(0)}
-    if "parent" in ms:
-        spread = (max(ms["parent"]) - min(ms["parent"])) / med["parent"]
-        res.update({"parent_spread": round(spread, 4), "unit_vs_parent": round(med["unit"] / med["parent"], 4),
-                    "mixed_vs_parent": round(med["mixed"] / med["parent"], 4), "parent_kernel": info["parent"],
-                    "within_twice_the_parent_spread": bool(max(med["unit"], med["mixed"]) <= med["parent"] * (1.0 + 2.0 * spread))})
-    else:
+    name = lambda k: k[0] if args.temperature else "%s_%s" % k
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
+           "ms_per_step": {name(k): [round(v, 4) for v in vs] for k, vs in ms.items()}, "median_ms_per_step": {name(k): round(v, 4) for k, v in med.items()},
+           "host_us_per_call": {name(k): [round(v, 2) for v in vs] for k, vs in host_us.items()},
+           "kernel": info["unit" if args.temperature else "here"], "device": torch.cuda.get_device_name(0)}
+    if args.temperature:
+        res["mixed_temperatures"] = mixed
+    if "parent" not in libs:
         res["parent"] = "not measured (no --parent-lib)"
+        return res
+    res["parent_kernel"] = info["parent"]
+    for what, v in (("", ms), ("host_", host_us)):      # the same rule for the time of a step and for the host's time inside the call
+        for kind in kinds:
+            p = ("parent", kind)
+            m = {k: float(np.median(x)) for k, x in v.items()}
+            spread = (max(v[p]) - min(v[p])) / m[p]
+            ratios = {case: m[(case, kind)] / m[p] for case in libs if case != "parent"}
+            res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
+                                     "within_twice_the_parent_spread": bool(max(ratios.values()) <= 1.0 + 2.0 * spread)},
+                                    **{case + "_vs_parent": round(r, 4) for case, r in ratios.items()})
     return res
 
 
