@@ -20,7 +20,10 @@
  * passed as void* (NULL = default stream).  Pointers may be host or device memory wherever the
  * reference accepts both.  Precision is 32 (<float,float>) or 16 (<half2,half>).
  *
- * Errors: unsupported (R,S,A,precision) -> nvw_create returns NULL; run calls return 1 on
+ * Errors: unsupported (R,S,A,precision) -> nvw_create returns NULL; so do num_layers outside
+ * 2..128, max_dilation < 1 (any value >= 1 is a schedule: d doubles per layer and restarts at 1
+ * past it), batch_size < 1 and num_samples < 1 -- one line on stderr, no HIP call made, no
+ * abort; run calls return 1 on
  * success and 0 when the launch failed (the reference's bool); HIP failures print
  * "GPUassert: ..." and exit like the reference's gpuErrChk.
  */

@@ -56,6 +56,13 @@ nvw_engine* nvw_create_ex(int R, int S, int A, int precision, int num_layers, in
         fprintf(stderr, "nvw_create: organisation %d out of range 0..%d\n", organisation, (int)NVW_ORG_LAST);
         return NULL;
     }
+    // (the class asserts these: refused here, before any HIP call, so that a host process gets a NULL instead of an abort --
+    //  and, built with NDEBUG, instead of a schedule written past Params::dil)
+    if (num_layers < 2 || num_layers > wn::kMaxLayers || max_dilation < 1 || batch_size < 1 || num_samples < 1) {
+        fprintf(stderr, "nvw_create: refused (%d layers, 2..%d supported; maxDilation %d, batch %d and %d samples, each >= 1)\n", num_layers,
+                (int)wn::kMaxLayers, max_dilation, batch_size, num_samples);
+        return NULL;
+    }
     nvw_engine* w = e->make(num_layers, max_dilation, batch_size, num_samples, implementation, tanh_embed, organisation);
     if (w && !w->supported()) {   // the shape does not fit a CU in this organisation (message already printed)
         delete w;
