@@ -235,7 +235,8 @@ void nvw_get_y_out(nvw_engine* e, int* yOut, int offset, int size, void* stream)
 /* SLOT MODE: CONTINUOUS BATCHING (ABI 7).  Every column of the batch holds one utterance that starts and stops on its own while
  * the others go on; the samples of an utterance depend on its upsampled features, its uid, the seed of nvw_set_selector_seed (0 if
  * none was set), the model and the sampling temperature in force at each local sample (1 unless nvw_slot_set_temperature says
- * otherwise; see SAMPLING TEMPERATURE below) only -- not on its column, the step it joined at, its neighbours or the chunk sizes.  Local sample k
+ * otherwise; see SAMPLING TEMPERATURE below) and its prime (none unless nvw_slot_prime gives one; see PRIMED GENERATION below) only
+ * -- not on its column, the step it joined at, its neighbours or the chunk sizes.  Local sample k
  * draws its selector from Philox4x32-10 with counter {k, uid, 0, 0}: an utterance with uid = b reproduces column b of a lockstep
  * nvw_set_features + nvw_set_selector_seed run.  Needs nvw_set_conditioning_weights (the conditioning is computed in the kernel).
  *   nvw_slots_begin  enters slot mode with a window of `window` samples, a positive multiple of the largest dilation of the schedule
@@ -439,6 +440,42 @@ void nvw_pinned_free(void* p);
 int nvw_set_temperatures(nvw_engine* e, const float* T, int n);
 int nvw_slot_set_temperature(nvw_engine* e, int slot, float T);
 float nvw_slot_temperature(nvw_engine* e, int slot);
+
+/* PRIMED GENERATION: FORCED SAMPLE PREFIXES, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  An utterance may carry a prime, n
+ * sample indices y[0 .. n) in 0 .. A-1: its local sample k < n IS y[k] -- written to the outputs (samples, PCM, ragged pieces) like
+ * any other, fed back into the history and through the embeddings, so the rings evolve exactly as if it had been drawn --, and its
+ * local sample k >= n is drawn as always, with selector {k, uid} of the seed (or row k of an uploaded table) at the temperature in
+ * force.  Forced samples consume no draw and shift no counter.  So a prime made of the first n samples of an unprimed run
+ * continues that run bit for bit, and the samples are a second, portable form of a state blob: a column primed with the `done`
+ * samples of an interrupted utterance saves the blob the uninterrupted one would have saved.  Only the launches that compute the
+ * conditioning in the kernel honour a prime (as for the temperatures).  At a forced sample nvw_get_p still reports the model's
+ * (tempered) probabilities and nvw_get_za its logits: only the pick is replaced.
+ * The contract of slot mode grows by one clause: an utterance's samples depend on its features (or frames), its uid, the seed, the
+ * model, the temperatures AND ITS PRIME -- and on nothing else.
+ *   nvw_set_prime    lockstep: column b < batch is primed with the first n[b] (0 .. max_n; 0: not primed) values of y + b * stride
+ *                    (int32, host or device, max_n values readable per column, stride >= max_n; copied); y == NULL clears.  In force
+ *                    across nvw_set_features / nvw_set_mel / nvw_reset_history and between chunks, like the temperatures; applies
+ *                    to nvw_run*, nvw_run_range and nvw_generate_stream on the features path.  A launch whose range holds a forced
+ *                    sample is preceded by one small launch that fills its rows of an engine-owned second selector table; the
+ *                    caller's own table is never written, and a launch past every prime is exactly what it was.  While any column
+ *                    is primed, a run on packed or in-place conditioning or on a multi-CU (chain) engine off the features path
+ *                    prints one line and returns 0.  Values in device memory are clamped into 0 .. A-1.  Synchronises.  0 when
+ *                    refused (slot mode, batch outside 1 .. the engine's batch, an n[b] outside 0 .. max_n, max_n above the engine's
+ *                    samples, stride < max_n, a host value outside 0 .. A-1); nothing changes.
+ *   nvw_slot_prime   slot mode: the utterance whose start or resume is pending on column `slot` is primed with y[0 .. n) (device
+ *                    memory, kept alive and unchanged until local sample n has been generated; values clamped into 0 .. A-1).
+ *                    Order: start (or resume), then prime -- nvw_slot_start / _start_mel / _resume* put the column back to "no
+ *                    prime", nvw_slot_stop and nvw_slots_begin / _end drop it, nvw_slot_move carries it.  State blobs know nothing
+ *                    of primes: a blob saved at done < n is resumed by nvw_slot_resume* followed by nvw_slot_prime with the same
+ *                    y, n.  A step with a column inside its prime issues one small launch between the feed and the generation.
+ *                    0 when refused (not in slot mode, slot out of range, no pending start or resume on the column, host memory,
+ *                    n < 1, n above the utterance's length -- a non-final mel column is not bounded by its frames so far, and
+ *                    nvw_slots_headroom governs as before); nothing changes.
+ *   nvw_slot_primed  n of the prime in force on column `slot` (host state: until the step that generates local sample n - 1 has
+ *                    been issued), 0 when none. */
+int nvw_set_prime(nvw_engine* e, const int* y, const int* n, int batch, int max_n, long long stride);
+int nvw_slot_prime(nvw_engine* e, int slot, const int* y, int n);
+int nvw_slot_primed(nvw_engine* e, int slot);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

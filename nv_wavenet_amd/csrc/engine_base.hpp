@@ -59,6 +59,7 @@ struct nvw_engine {
     virtual void getP(float*) = 0;
     virtual void getYOut(int*, int, int, hipStream_t) = 0;
     virtual bool setTemperatures(const float*, int) = 0;
+    virtual bool setPrime(const int*, const int*, int, int, long long) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
@@ -151,6 +152,7 @@ struct EngineImpl : nvw_engine {
     void getP(float* d) override { eng.getP(d); }
     void getYOut(int* y, int off, int size, hipStream_t s) override { eng.getYOut(y, off, size, s); }
     bool setTemperatures(const float* T, int n) override { return eng.setTemperatures(T, n); }
+    bool setPrime(const int* y, const int* n, int batch, int maxN, long long stride) override { return eng.setPrime(y, n, batch, maxN, stride); }
     wn::SlotSession& slots() override { return eng.slots(); }
 };
 

@@ -144,6 +144,7 @@ protected:
 
     // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode
     wn::TemperatureTable m_temps;
+    wn::PrimeTable m_prime;           // the lockstep primes (slots_prime.hpp)
     // slot mode (slots_session.hpp): made at the end of the constructor, when the facts it is given are known
     std::unique_ptr<wn::SlotSession> m_slots;
 
@@ -479,7 +480,7 @@ public:
           m_feat(NULL), m_featPtr(NULL), m_featSamples(0),
           m_mail(NULL), m_chainStatus(NULL), m_mailBytes(0), m_ringShadow(NULL), m_histShadow(NULL),
           m_chainTimeoutTicks(wn::kChainTimeoutTicks), m_stage(NULL), m_stageElems(0), m_useRng(false), m_rngSeed(0), m_pcm(NULL),
-          m_mulaw(NULL), m_pcmUser(NULL), m_pcmUserElems(0), m_clk(NULL), m_clkOn(false), m_temps(batchSize), m_stageUsed(0) {
+          m_mulaw(NULL), m_pcmUser(NULL), m_pcmUserElems(0), m_clk(NULL), m_clkOn(false), m_temps(batchSize), m_prime(batchSize), m_stageUsed(0) {
         assert(numLayers >= 2 && batchSize > 0 && numSamples > 0 && maxDilation > 0);
         m_ringDirtyTiles = 0;
         m_ringLdsMode = 0;
@@ -598,7 +599,7 @@ public:
         }
         gpuErrChk(hipDeviceSynchronize());
         m_slots.reset(new wn::SlotSession(wn::SlotFacts{m_maxBatch, m_tiles, m_numLayers, m_maxDilation, m_ringSlots, (int)(R * 16 * sizeof(elem) / 1024), R,
-                                                        F16, featureElems(1), m_supported, m_ring, m_yInPrev, m_yInCur},
+                                                        F16, featureElems(1), m_supported, m_ring, m_yInPrev, m_yInCur, A},
                                           *this, m_temps));
     }
 
@@ -1201,6 +1202,34 @@ public:
     // the temperature in force for column b (1 when none was ever set)
     float temperature(int b) const { return m_temps.get(b); }
 
+    // ---- primed generation (beyond the reference; slots_prime.hpp) -------------------------------------------------
+    // Column b < batch of the runs that follow starts with the forced samples y[b * stride + k], k < n[b] (0 <= n[b] <= maxN <=
+    // maxSamples; 0: not primed): they are delivered and fed back like drawn samples, and from sample n[b] on the column draws as
+    // always -- selector {t, b} of the seed, or row t of the uploaded table.  y: int32, host or device, maxN values per column, stride
+    // >= maxN; copied.  y == NULL clears.  In force across setFeatures / setMel / resetHistory and between run_partial chunks until the
+    // next call.  A launch whose range holds a forced sample reads an engine-owned second selector table, filled for its rows by one
+    // small launch ahead of it (prime_selectors); the caller's table is never written, and a launch past every prime is what it was.
+    // Only the features path honours a prime: while one is in force a run on packed or in-place conditioning, or a chain launch,
+    // prints one line and returns false.  Synchronises.  false (nothing changes): in slot mode (slotPrime is the call there), batch
+    // outside 1 .. maxBatch, maxN outside 0 .. maxSamples, stride < maxN, an n[b] outside 0 .. maxN, or a value outside 0 .. A-1 in host
+    // memory (device values are clamped into that range by the kernel).
+    bool setPrime(const int* y, const int* n, int batch, int maxN, long long stride) {
+        if (m_slots->active()) return false;
+        if (y == NULL) {
+            gpuErrChk(hipDeviceSynchronize());
+            m_prime.clear();
+            return true;
+        }
+        if (n == NULL || batch < 1 || batch > m_maxBatch || maxN < 0 || maxN > m_maxSamples || stride < maxN) return false;
+        for (int b = 0; b < batch; b++)
+            if (n[b] < 0 || n[b] > maxN) return false;
+        if (!isDevicePtr(y))
+            for (int b = 0; b < batch; b++)
+                for (int k = 0; k < n[b]; k++)
+                    if (y[b * stride + k] < 0 || y[b * stride + k] >= A) return false;
+        m_prime.set(y, n, batch, maxN, stride, m_maxSamples);
+        return true;
+    }
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to
     // consume(yOut, firstSample, count) on the calling thread (role of nv_wavenet.cuh:445-497).  Two
@@ -1287,6 +1316,12 @@ public:
             return false;
         }
 
+        if (m_prime.any() && !m_featPtr) {
+            fprintf(stderr, "nvWavenetInfer: %d columns carry a prime, which packed or in-place conditioning and multi-CU launches cannot "
+                    "honour: use the features path, or setPrime(NULL, ..)\n", m_prime.primed);
+            return false;
+        }
+
         // a new utterance: the dilation rings read as zero until written (wavenet_wg takes x[t-d] = 0 for t < d from the ring
         // itself).  resetHistory() -- every way of handing over a new utterance's conditioning calls it -- has normally done this
         // already, outside the generation's critical path; this covers run() after run() on the same inputs.
@@ -1320,9 +1355,20 @@ public:
         p.softScale = m_featPtr ? m_temps.softScale : NULL;
         m_lastStride = num_samples;
         if (p.count <= 0) return true;
+        bool primeOk = true;
+        if (m_prime.any() && p.initSample < m_prime.maxN) {
+            // the launch's range holds a forced sample: its rows of the second table -- the primes, and beyond them what the launch
+            // would have used
+            primeOk = wn::prime_selectors(stream, m_prime.sel, p.initSample, p.count, batch_size, m_maxBatch, m_prime.yDev, m_prime.yStride,
+                                          m_prime.nDev, p.useRng, m_rngSeed, m_outputSelectors, A);
+            p.sel = m_prime.sel;
+            p.useRng = 0;
+            p.forced = 1;
+        }
 
         // (computing the conditioning from the features is wavenet_wg's: a chain engine runs it for such a launch)
         bool result = (isChain() && !m_featPtr) ? launchChain(p, tiles, stream) : launchWg(p, tiles, stream);
+        result = result && primeOk;
         if (m_pcmUser != NULL) {
             // the indices of a finished sample are final: the expansion is a per-element map of yOut
             hipLaunchKernelGGL(wn::mulaw_pcm_kernel, dim3(gridFor((size_t)batch_size * p.count)), dim3(256), 0, stream,
@@ -1436,7 +1482,8 @@ protected:
         if (tiles > m_ringDirtyTiles) m_ringDirtyTiles = tiles;
     }
     // (the launch of run_partial for features, with the window's buffers and the selector table)
-    bool slotGenerate(const void* feat, const float* sel, int* y, int W, int t0, int count, int cols, hipStream_t stream) override {
+    bool slotGenerate(const void* feat, const float* sel, int* y, int W, int t0, int count, int cols, bool forced,
+                      hipStream_t stream) override {
         const int tiles = (cols + 15) / 16;
         wgRingsDirty(tiles);
         wn::Params p = baseParams();
@@ -1456,6 +1503,7 @@ protected:
         p.dump = 0;
         p.useRng = 0;
         p.softScale = m_temps.softScale;
+        p.forced = forced ? 1 : 0;
         return launchWg(p, tiles, stream);
     }
     // what every launch's Params share: the model, the ring and history, the debug outputs, the shape and schedule, the seed
@@ -1483,6 +1531,7 @@ protected:
         p.tileBase = 0;
         p.tanhEmbed = m_tanhEmbed ? 1 : 0;
         p.embLds = 0;
+        p.forced = 0;
         p.rngKey0 = (unsigned)m_rngSeed;
         p.rngKey1 = (unsigned)(m_rngSeed >> 32);
         p.clk = m_clkOn ? m_clk : NULL;

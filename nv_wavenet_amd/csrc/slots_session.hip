@@ -99,6 +99,10 @@ bool SlotSession::begin(int window) {
     m_slotResumeDone.assign(f.maxBatch, 0);
     m_slotMoveEnd.assign(f.maxBatch, 0);
     m_temps.reset(false);      // (every column at T = 1, a lockstep run's values included)
+    m_primeY.clear();
+    m_primeN.clear();
+    m_primeListed.clear();
+    m_primeList.clear();
     const size_t cells = (size_t)window * f.maxBatch;
     allocZero(m_slotDesc, (size_t)f.maxBatch * sizeof(SlotDesc));
     allocZero(m_slotFeat, featBytes(window));
@@ -128,6 +132,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     d.active = 1;
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
+    slotPrimeSet(slot, NULL, 0);
     return true;
 }
 bool SlotSession::stop(int slot) {
@@ -136,6 +141,7 @@ bool SlotSession::stop(int slot) {
     slotDropResume(slot);
     m_slotHost[slot].active = 0;
     slotMarkPending(slot, 2);
+    slotPrimeSet(slot, NULL, 0);
     return true;
 }
 bool SlotSession::startMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
@@ -157,6 +163,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
+    slotPrimeSet(slot, NULL, 0);
     return true;
 }
 bool SlotSession::melFrames(int slot, int frames, int final) {
@@ -171,6 +178,14 @@ bool SlotSession::melFrames(int slot, int frames, int final) {
 bool SlotSession::setTemperature(int slot, float T) {
     if (!inBatch(slot) || !slotHolds(slot) || !temperature_ok(T)) return false;
     slotTempSet(slot, T);
+    return true;
+}
+bool SlotSession::prime(int slot, const int* y, int n) {
+    if (!inBatch(slot) || m_slotPending[slot] != 1 || y == NULL || n < 1 || !is_device_ptr(y)) return false;
+    const MelDesc& m = m_melHost[slot];
+    if (m.state == 2 && n > (long long)m.frames * m_host.slotLive().upStride) return false;
+    if (m.state == 0 && n > m_slotHost[slot].length) return false;
+    slotPrimeSet(slot, y, n);
     return true;
 }
 bool SlotSession::move(int from, int to) {
@@ -189,6 +204,10 @@ bool SlotSession::move(int from, int to) {
     m_slotMoveEnd[to] = 2;
     m_slotMoves.push_back(SlotMove{from, to});
     slotTempSet(to, m_temps.get(from));
+    if (primed(from)) {
+        slotPrimeSet(to, m_primeY[from], m_primeN[from]);
+        slotPrimeSet(from, NULL, 0);
+    }
     return true;
 }
 int SlotSession::save(int slot, void* dst, hipStream_t stream) {
@@ -369,9 +388,11 @@ bool SlotSession::generate(int count, int& cols, hipStream_t stream) {
                                                                        f.tiles, v.nCond, v.upTab, v.upBias, v.upWindow / v.upStride, v.upStride,
                                                                        m_slotCounter, T, W, count, v.seed) && ok;
         }
+        bool forced = false;
+        if (!m_primeList.empty()) ok = slotApplyPrimes(count, forced, stream) && ok;      // (behind the feeds: it replaces their draws)
         for (int done = 0, t0, c; done < count; done += c) {      // (two launches where the window rows wrap)
             c = rowsFrom(T + done, count - done, t0);
-            ok = m_host.slotGenerate(m_slotFeat, m_slotSel, m_slotY, W, t0, c, cols, stream) && ok;
+            ok = m_host.slotGenerate(m_slotFeat, m_slotSel, m_slotY, W, t0, c, cols, forced, stream) && ok;
         }
     }
     return ok;
@@ -505,13 +526,20 @@ int SlotSession::done(unsigned long long ticket) {
 void SlotSession::end() {
     if (m_slotW <= 0) return;
     gpuErrChk(hipDeviceSynchronize());
-    freeDev(m_slotDesc, m_slotFeat, m_slotSel, m_slotY, m_slotPcm, m_slotUpd, m_dlvDev, m_saveDev, m_scaleDev, m_melDesc, m_melUpd, m_melColInfo,
-            m_melStage);
+    freeDev(m_slotDesc, m_slotFeat, m_slotSel, m_slotY, m_slotPcm, m_slotUpd, m_dlvDev, m_saveDev, m_scaleDev, m_primeDev, m_melDesc, m_melUpd,
+            m_melColInfo, m_melStage);
     m_melStageBytes = 0;
     m_slotStage.reset();
     m_dlv.reset();
     m_saveStage.reset();
     m_scaleStage.reset();
+    m_primeStage.reset();
+    m_primeDevN = 0;
+    m_primeDirty = false;
+    m_primeY.clear();
+    m_primeN.clear();
+    m_primeListed.clear();
+    m_primeList.clear();
     m_melStageHost.reset();
     m_slotW = 0;
     m_slotPendingList.clear();      // (the per-column tables keep their storage: the next begin() fills them afresh)
@@ -666,6 +694,64 @@ bool SlotSession::slotApplyTemperatures(hipStream_t stream) {
     gpuErrChk(hipMemcpyAsync(m_scaleDev, stage, (size_t)n * sizeof(SlotScale), hipMemcpyHostToDevice, stream));
     m_scaleStage.release(stream);
     return slots_set_scales(stream, m_temps.softScale, f.maxBatch, m_scaleDev, n);
+}
+// ---- primed generation (slots_prime.hpp) ----
+void SlotSession::slotPrimeSet(int slot, const int* y, int n) {
+    if (m_primeN.empty()) {
+        if (n == 0) return;
+        m_primeY.assign(f.maxBatch, NULL);
+        m_primeN.assign(f.maxBatch, 0);
+        m_primeListed.assign(f.maxBatch, 0);
+    }
+    if (m_primeN[slot] != 0 || n != 0) m_primeDirty = true;
+    m_primeY[slot] = y;
+    m_primeN[slot] = n;
+    if (n > 0 && !m_primeListed[slot]) {      // (a column that lost its prime leaves the list at the next step)
+        m_primeList.push_back(slot);
+        m_primeListed[slot] = 1;
+    }
+}
+// A step of `count` samples from the counter with primed columns.  When the set of primed columns has changed since the table was
+// written: the columns inside their prime in this step -> pinned staging -> device (staging halves as slotApplyPending, made by the
+// first step that needs them).  Then one slot_prime_kernel launch over the window rows of the step, which takes every column's
+// local sample from its descriptor; forced: it writes a forced sample.  Runs behind slotApplyPending and the feeds.  A column whose
+// prime ends within the step has none afterwards, and the table is rewritten without it before it is read again.
+bool SlotSession::slotApplyPrimes(int count, bool& forced, hipStream_t stream) {
+    if (!m_primeDev) {
+        gpuErrChk(hipMalloc((void**)&m_primeDev, (size_t)f.maxBatch * sizeof(SlotPrime)));
+        m_primeStage.make(2, (size_t)f.maxBatch * sizeof(SlotPrime));
+    }
+    m_primeScratch.clear();
+    size_t kept = 0;
+    bool dropped = false;
+    for (int b : m_primeList) {
+        const int len = m_primeN[b];
+        const long long k0 = m_slotCounter - (m_melHost[b].state ? m_melHost[b].start : m_slotHost[b].start);
+        if (len > 0 && slotHolds(b) && k0 >= 0 && k0 < len) m_primeScratch.push_back(SlotPrime{m_primeY[b], len, b});
+        if (len > 0 && slotHolds(b) && k0 >= 0 && k0 + count < len) {
+            m_primeList[kept++] = b;
+            continue;
+        }
+        m_primeY[b] = NULL;
+        m_primeN[b] = 0;
+        m_primeListed[b] = 0;
+        dropped = true;
+    }
+    m_primeList.resize(kept);
+    const int n = (int)m_primeScratch.size();
+    forced = n > 0;
+    if (n > 0 && (m_primeDirty || n != m_primeDevN)) {
+        SlotPrime* const stage = (SlotPrime*)m_primeStage.acquire();
+        memcpy(stage, m_primeScratch.data(), (size_t)n * sizeof(SlotPrime));
+        gpuErrChk(hipMemcpyAsync(m_primeDev, stage, (size_t)n * sizeof(SlotPrime), hipMemcpyHostToDevice, stream));
+        m_primeStage.release(stream);
+        m_primeDevN = n;
+        m_primeDirty = false;
+    }
+    if (dropped) m_primeDirty = true;      // (the table still names a column that has left its prime: rewritten before its next use)
+    if (n == 0) return true;
+    return slots_prime(stream, m_slotSel, f.maxBatch, m_slotCounter, (int)(m_slotCounter % m_slotW), m_slotW, count, m_primeDev, m_primeDevN, m_slotDesc,
+                       m_melDesc, f.A);
 }
 // ---- mel columns (slots_mel.hpp) ----
 void SlotSession::melMarkDirty(int slot) {

@@ -1,4 +1,4 @@
-// slots_session.hpp -- the host half of slot mode (slots.hpp; DESIGN.md "Slot mode", §6c-§6g): wn::SlotSession keeps the window, the
+// slots_session.hpp -- the host half of slot mode (slots.hpp; DESIGN.md "Slot mode", §6c-§6h): wn::SlotSession keeps the window, the
 // descriptor tables, the pending lists, the staging copies and the tickets, and issues the slot kernels.  It is bookkeeping around
 // kernels that are compiled once for both precisions, so it is compiled once as well (slots_session.hip): the precision is a
 // run-time fact, and what belongs to the engine -- the model, the ring, the generation launch -- is reached through wn::SlotHost.
@@ -13,6 +13,7 @@
 #include "slots.hpp"
 #include "slots_deliver.hpp"
 #include "slots_mel.hpp"
+#include "slots_prime.hpp"
 #include "slots_sampler.hpp"
 #include "slots_state.hpp"
 
@@ -28,6 +29,7 @@ struct SlotFacts {
     bool supported;            // the shape fits a CU
     void* ring;                // the engine's dilation ring and sample history
     int *yInPrev, *yInCur;
+    int A;                     // the alphabet: a forced sample is clamped into 0 .. A-1 (slots_prime.hpp)
 };
 // what a call reads afresh (the caller may hand over weights, an upsampling or a seed between two calls)
 struct SlotLive {
@@ -46,8 +48,9 @@ struct SlotHost {
     // launches have written the rings of the leading `tiles` tiles
     virtual void slotRingsDirty(int tiles) = 0;
     // wavenet_wg<.., RAW=3> on window rows [t0, t0 + count) of the first `cols` columns: features feat [W][tiles][KFC], selector
-    // table sel [W][maxBatch], samples into y [maxBatch][W]
-    virtual bool slotGenerate(const void* feat, const float* sel, int* y, int W, int t0, int count, int cols, hipStream_t stream) = 0;
+    // table sel [W][maxBatch], samples into y [maxBatch][W]; forced: the rows hold forced samples (Params::forced; slots_prime.hpp)
+    virtual bool slotGenerate(const void* feat, const float* sel, int* y, int W, int t0, int count, int cols, bool forced,
+                              hipStream_t stream) = 0;
 };
 
 // n pinned host buffers with an event each, used in turn: acquire() hands out the next buffer, waiting first for the work that
@@ -80,8 +83,8 @@ public:
 
     // ---- slot mode: continuous batching (slots.hpp; DESIGN.md "Slot mode") ------------------------------------------------------
     // Every column holds one utterance that starts and stops on its own while the others go on.  An utterance's samples depend on
-    // its features, its uid, the seed, the model and the temperature in force at each local sample (slotSetTemperature; 1 by default)
-    // only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
+    // its features, its uid, the seed, the model, the temperature in force at each local sample (slotSetTemperature; 1 by default)
+    // and its prime (prime(); none by default) only: local sample k draws philox_selector(seed, {k, uid}) -- column uid of a
     // lockstep setFeatures + setSelectorSeed run --, its rings start at zero and its history at 128.  The state between steps lives
     // in a window of W samples that wraps; the generation kernel is wavenet_wg<.., RAW=3> as the features path launches it, on
     // window rows, reading the selectors from a table (useRng = 0).  Needs setConditioningWeights; the seed is the one of
@@ -119,6 +122,19 @@ public:
     bool setTemperature(int slot, float T);
     // the host's value for column `slot`; 0 when it holds no utterance (or outside slot mode, or outside the batch)
     float temperature(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot) : 0.f; }
+    // ---- primed generation (slots_prime.hpp) ----
+    // The utterance whose start or resume is pending on column `slot` carries the prime y[0 .. n) (device memory, int32; kept alive and
+    // unchanged until local sample n has been generated): its local samples k < n are y[k], clamped into the alphabet, delivered and
+    // fed back like drawn ones; from k = n on it draws {k, uid} as always.  Order: start (or resume), then prime -- slotStart /
+    // slotStartMel / slotResume* put the column back to "no prime", slotStop, slotsBegin and slotsEnd drop it, slotMove carries it.  A
+    // resumed column whose blob has done < n is primed again with the same y, n: the samples below done are never reached.  A step
+    // with a column inside its prime issues one small launch (slot_prime_kernel) between the feed and the generation, whose launches
+    // then decode forced selectors; a step without issues what it issued before.  false (nothing changes): not in slot mode, slot
+    // outside the batch, no pending start or resume on the column, y not device memory, n < 1, or n above the utterance's length
+    // (a non-final mel column: unbounded -- a forced sample still needs its features, slotsHeadroom governs as before).
+    bool prime(int slot, const int* y, int n);
+    // n of the prime in force on column `slot` (host state: until the step that generates local sample n - 1 has been issued); 0: none
+    int primed(int slot) const { return inBatch(slot) && !m_primeN.empty() ? m_primeN[slot] : 0; }
     // ---- a column's state as a value (slots_state.hpp) ----
     // bytes of one column's state blob for this engine's shape and precision (header + its share of its tile's ring)
     size_t stateBytes() const { return slots_state_bytes(f.ringSlots, f.ringFragsPerSlot); }
@@ -256,6 +272,16 @@ private:
     std::vector<int> m_tempDirtyList;
     SlotScale* m_scaleDev = NULL;           // [maxBatch] on the device: a step's changed entries (made by the first step that needs it)
     StageRing m_scaleStage;                 // ... their pinned host staging: two halves
+    // ... and the primes (slots_prime.hpp)
+    std::vector<const int*> m_primeY;       // per column: the prime in force (made by the first prime of a session) ...
+    std::vector<int> m_primeN;              // ... and its length (0: none)
+    std::vector<char> m_primeListed;
+    std::vector<int> m_primeList;           // the columns with one (and those that lost theirs since the last step)
+    SlotPrime* m_primeDev = NULL;           // [maxBatch] on the device: the primed columns, m_primeDevN of them ...
+    int m_primeDevN = 0;
+    std::vector<SlotPrime> m_primeScratch;  // (the columns inside their prime in the step being issued, before they are staged)
+    bool m_primeDirty = false;              // ... which the next step with a column inside its prime rewrites: the set has changed
+    StageRing m_primeStage;                 // ... through pinned host staging: two halves
 
     size_t elemBytes() const { return f.f16 ? 2 : 4; }
     size_t featBytes(long long samples) const { return (size_t)samples * f.featRowElems * elemBytes(); }
@@ -293,6 +319,8 @@ private:
     void slotTempSet(int slot, float T);
     void slotSetResume(int slot, const void* state, const SlotStateHeader& h);
     bool slotApplyTemperatures(hipStream_t stream);
+    void slotPrimeSet(int slot, const int* y, int n);
+    bool slotApplyPrimes(int count, bool& forced, hipStream_t stream);
     void melMarkDirty(int slot);
     void slotDropMel(int slot);
     void melAllocate();

@@ -374,6 +374,20 @@ int nvw_slot_set_temperature(nvw_engine* e, int slot, float T) {
     return 0;
 }
 float nvw_slot_temperature(nvw_engine* e, int slot) { return e->slots().temperature(slot); }
+// ---- primed generation: forced sample prefixes, lockstep and in slot mode (additive within ABI 7) -----------------------------------
+int nvw_set_prime(nvw_engine* e, const int* y, const int* n, int batch, int max_n, long long stride) {
+    if (e->setPrime(y, n, batch, max_n, stride)) return 1;
+    fprintf(stderr, "nvw_set_prime: refused, nothing changed (not in slot mode; batch %d of 1 .. %d; every n[b] in 0 .. max_n = %d, max_n "
+            "within the engine's samples, stride %lld >= max_n; host values in 0 .. A-1)\n", batch, e->maxBatch(), max_n, stride);
+    return 0;
+}
+int nvw_slot_prime(nvw_engine* e, int slot, const int* y, int n) {
+    if (e->slots().prime(slot, y, n)) return 1;
+    fprintf(stderr, "nvw_slot_prime: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with a pending start or "
+            "resume; y in device memory; n = %d in 1 .. the utterance's length)\n", slot, e->maxBatch(), n);
+    return 0;
+}
+int nvw_slot_primed(nvw_engine* e, int slot) { return e->slots().primed(slot); }
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

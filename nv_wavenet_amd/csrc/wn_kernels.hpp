@@ -334,6 +334,9 @@ struct Params {
     Dil dil[kMaxLayers + 2]; // schedule of layer l; entries L and L+1 repeat layers 0 and 1 (of the next sample)
     const float* softScale;  // RAW = 3 only: [maxBatch] floats, log2(e) / T of every column's sampling temperature T; NULL: T = 1 everywhere.
                              // Behind everything else: no other argument's offset depends on it.
+    int forced;              // RAW = 3 only, launch-uniform: != 0: a selector <= -1 is a forced sample, -(1 + y) stands for "the sample is
+                             // y" (slots_prime.hpp: only its two kernels write such values); 0: every selector is a draw, as before.
+                             // Behind softScale, for the same reason.
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1785,8 +1788,11 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                 float total;
                 const float* lrow = lgbuf + (bl * 16 + su) * C::LROW + sq * C::RPL;
                 int pick;
-                if constexpr (FEAT) pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
-                else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total);
+                if constexpr (FEAT) {
+                    pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
+                    // a forced sample (Params::forced): the selector names it; e and total stay the model's
+                    if (p.forced) pick = selv[bt] <= -1.0f ? (int)(-selv[bt]) - 1 : pick;
+                } else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total);
                 const int sb = (tile0 + bt) * 16 + su;
                 if (sq == 0) {
                     ybuf[bt * 16 + su] = pick;

@@ -588,6 +588,48 @@ class WavenetEngine:
         """The temperature in force for column `slot` (host state); 0.0 when the column holds no utterance."""
         return float(lib.nvw_slot_temperature(self._h, int(slot)))
 
+    # ---- primed generation: forced sample prefixes (include/nv_wavenet_c.h, "PRIMED GENERATION"; DESIGN.md §6h) ----
+    def setPrime(self, y=None, lengths=None):
+        """Lockstep: column b of the features-path runs that follow starts with the forced samples y[b][:lengths[b]] and draws from
+        there on as always.  y: None (no column primed) or a [batch][n] integer array -- numpy (values checked against 0..A-1) or a
+        CUDA int32 tensor (values clamped into it by the kernel); lengths: None (n for every column) or `batch` values in 0..n.
+        In force until the next call.  While any column is primed, runs on packed or in-place conditioning and chain launches
+        return False.  ValueError when refused (nothing changes)."""
+        if y is None:
+            if not lib.nvw_set_prime(self._h, None, None, 0, 0, 0):
+                raise ValueError("nvw_set_prime refused to clear")
+            return
+        if hasattr(y, "data_ptr"):
+            if y.dim() != 2 or str(y.dtype) != "torch.int32" or not y.is_cuda or y.stride(1) != 1:
+                raise ValueError("a prime tensor is [batch][n] int32 on the GPU with unit stride along n")
+            batch, n, ptr, stride = int(y.size(0)), int(y.size(1)), y.data_ptr(), int(y.stride(0))
+        else:
+            y = np.ascontiguousarray(np.asarray(y, dtype=np.int32))
+            if y.ndim != 2:
+                raise ValueError("a prime is [batch][n]")
+            batch, n, ptr, stride = y.shape[0], y.shape[1], y.ctypes.data, y.shape[1]
+        ln = np.full(batch, n, dtype=np.int32) if lengths is None else np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        if ln.size != batch:
+            raise ValueError("%d prime lengths for %d columns" % (ln.size, batch))
+        if n == 0 or not lib.nvw_set_prime(self._h, ptr, ln.ctypes.data, batch, n, stride):
+            raise ValueError("nvw_set_prime refused a prime of %d columns x %d samples" % (batch, n))
+
+    def slotPrime(self, slot, y):
+        """Slot mode: the utterance whose start or resume is pending on column `slot` starts with the forced samples y (a 1-D int32
+        tensor, contiguous; a CPU tensor is uploaded; kept alive here while the column runs; values clamped into 0..A-1).  Order:
+        slotStart / slotResume, then slotPrime.  ValueError when refused (nothing changes)."""
+        if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous():
+            raise ValueError("a slot prime is a contiguous 1-D int32 tensor")
+        if not y.is_cuda:
+            y = y.cuda()
+        if not lib.nvw_slot_prime(self._h, int(slot), y.data_ptr(), int(y.numel())):
+            raise ValueError("nvw_slot_prime refused slot %d, n = %d" % (slot, y.numel()))
+        self._slot_keep[int(slot)] = (self._slot_keep.get(int(slot)), y)      # (beside the source: it moves and goes with it)
+
+    def slotPrimed(self, slot):
+        """n of the prime in force on column `slot` (host state; 0 when none, or once its last forced sample has been issued)."""
+        return int(lib.nvw_slot_primed(self._h, int(slot)))
+
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):
         if yOut is None:

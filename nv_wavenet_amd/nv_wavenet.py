@@ -421,7 +421,7 @@ class NVWaveNetEngine(NVWaveNet):
         return self._engine(batch_size, sample_count, implementation).condTiles()
 
     def infer(self, cond_input, implementation=Impl.AUTO, seed=None, return_audio=False, layout="CBLN",
-              generator=None, batch_size=None, temperature=None):
+              generator=None, batch_size=None, temperature=None, prime=None):
         """cond_input: 2R x batch x layers x samples (layout "CBLN", the reference's: converted to the engine's fragment order
         by the one permuting copy any layout change needs), [samples][layers][batch][2R] contiguous (layout "NLBC", read in
         place), or the engine's own fragment order
@@ -430,7 +430,11 @@ class NVWaveNetEngine(NVWaveNet):
         seed: int -> selectors drawn in-kernel by Philox4x32-10; None -> torch.rand on the device.
         Returns int32 [batch][samples] (and int16 audio [batch][samples] when return_audio).
         temperature: not here -- only the kernels that compute the conditioning from the features sample at a temperature
-        (infer_features); anything but None raises ValueError."""
+        (infer_features); anything but None raises ValueError.
+        prime: not here either, for the same reason (infer_features(..., prime=)); anything but None raises ValueError."""
+        if prime is not None:
+            raise ValueError("infer() runs on a conditioning tensor, whose kernels cannot force samples: use "
+                             "infer_features(x, cond_weight, cond_bias, prime=...)")
         if temperature is not None:
             raise ValueError("infer() runs on a conditioning tensor, whose kernels sample at temperature 1 only: use "
                              "infer_features(x, cond_weight, cond_bias, temperature=...)")
@@ -467,14 +471,29 @@ class NVWaveNetEngine(NVWaveNet):
         return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
 
     def infer_features(self, x, cond_weight, cond_bias, implementation=Impl.AUTO, seed=None, return_audio=False, generator=None,
-                       temperature=None):
+                       temperature=None, prime=None, prime_lengths=None):
         """Generation with the conditioning convolution INSIDE the kernel (round 5): x = the upsampled features [batch][n_cond][samples]
         on the GPU (upsample_features(...) / the model's self.upsample output, trimmed), cond_weight / cond_bias = the model's
         cond_layers.weight / .bias.  Equivalent to infer(model.get_cond_input(features)) without ever building the
         2R x batch x layers x samples tensor.
         temperature: None (1), a float, or a sequence of `batch` floats -- utterance b is drawn from softmax(logits / T_b); each
-        finite and in [2^-10, 2^10] (ValueError otherwise)."""
+        finite and in [2^-10, 2^10] (ValueError otherwise).
+        prime: None, or a [batch][n] integer tensor (n <= samples, values in 0..A-1) -- utterance b starts with the forced samples
+        prime[b][:prime_lengths[b]] (prime_lengths None: all n) and is drawn from there on; the forced samples are part of the
+        result.  The continuation of existing audio: infer_features(x, .., seed=s, prime=y[:, :n]) of a run y with the same x and
+        seed returns y.  ValueError for a bad shape, length or value."""
         batch_size, sample_count = x.size(0), x.size(2)
+        if prime is not None:
+            if prime.dim() != 2 or prime.size(0) != batch_size or not 0 < prime.size(1) <= sample_count or prime.is_floating_point():
+                raise ValueError("prime: an integer tensor [batch = %d][1 .. %d], got %s" % (batch_size, sample_count, tuple(prime.shape)))
+            if prime_lengths is not None:
+                prime_lengths = [int(n) for n in prime_lengths]
+                if len(prime_lengths) != batch_size or not all(0 <= n <= prime.size(1) for n in prime_lengths):
+                    raise ValueError("prime_lengths: %d values in 0 .. %d" % (batch_size, prime.size(1)))
+            if int(prime.min()) < 0 or int(prime.max()) >= self.A:
+                raise ValueError("prime: values in 0 .. %d" % (self.A - 1))
+        elif prime_lengths is not None:
+            raise ValueError("prime_lengths without a prime")
         if temperature is not None and not isinstance(temperature, (int, float)):
             temperature = [float(t) for t in temperature]
             if len(temperature) != batch_size:
@@ -490,10 +509,14 @@ class NVWaveNetEngine(NVWaveNet):
         e.setFeatures(x, sample_count)
         e.setTemperatures(temperature)
         try:
+            if prime is not None:
+                e.setPrime(prime.to(device=dev, dtype=torch.int32).contiguous(), prime_lengths)
             return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
         finally:
             if temperature is not None:
                 e.setTemperatures(None)      # (the engine is shared with infer(), whose kernels refuse to run at another temperature)
+            if prime is not None:
+                e.setPrime(None)             # (... or while a column is primed)
 
     def _infer_packed(self, frags, batch_size, implementation, seed, return_audio, generator):
         sample_count = frags.size(0) - 1

@@ -52,6 +52,12 @@ resume, compact and to_bytes / from_bytes keep it (a blob holds it in word 10 of
     h = stream.submit(features, temperature=0.8)
     stream.set_temperature(h, 1.1)                      # waiting or running: the samples of the steps that follow
 
+A request may carry a prime (nvw_slot_prime): its first n samples are given -- the tail of the previous sentence,
+the samples a lost stream had already delivered -- and it is drawn from sample n on.  The forced samples are delivered like the
+others.  suspend, drain, resume, compact and to_bytes / from_bytes keep what is left of it.
+
+    h = stream.submit(features, prime=delivered)        # integer tensor [n], values in 0..A-1
+
 step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
 (DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
 owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
@@ -87,6 +93,19 @@ def check_temperature(T):
     return t
 
 
+def check_prime(prime, length=None):
+    """prime as the engine takes it: a 1-D integer tensor of 1..length values, returned as contiguous int32 (None stays None);
+    ValueError otherwise.  The values are clamped into the alphabet by the engine."""
+    if prime is None:
+        return None
+    import torch
+    if not isinstance(prime, torch.Tensor) or prime.dim() != 1 or prime.is_floating_point() or prime.dtype == torch.bool:
+        raise ValueError("prime: a 1-D integer tensor")
+    if prime.numel() < 1 or (length is not None and prime.numel() > length):
+        raise ValueError("prime: %d samples for an utterance of %s" % (prime.numel(), length))
+    return prime.to(torch.int32).contiguous()
+
+
 def window_pieces(counter, count, window):
     """The generation launches of a step: (first window row, samples) for samples [counter, counter + count) of a window of
     `window` rows -- one piece, or two where the rows wrap (the split nvWavenetInfer::slotsStep makes)."""
@@ -100,7 +119,8 @@ class SlotState:
     """A suspended request (SlotStream.suspend): blob = the column's state, a CUDA uint8 tensor of WavenetEngine.slotSave (None: the
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
     frames, final = of a mel request (frames written so far, no more to come); temperature = its sampling temperature (the one in
-    the blob's header, word 10; a resume goes on at this attribute's value)."""
+    the blob's header, word 10; a resume goes on at this attribute's value); prime = its prime (an int32 tensor [n], None: none; a
+    resume applies it again when done < n)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -108,8 +128,12 @@ class SlotState:
     RECORD_MAGIC, RECORD_VERSION = b"NWSS", 1
     BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid,
     TEMPERATURE_WORD = 10                    # word 10 the temperature as the bits of the float (zero: 1.0)
+    # to_bytes() of a state with done < n of its prime: behind the blob this record, then the n - done values y[done .. n) (int32)
+    PRIME = struct.Struct("<4sII")           # magic, first (= done), count (= n - done)
+    PRIME_MAGIC = b"NWSP"
 
-    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0):
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None):
+        self.prime = check_prime(prime)
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
         self.temperature = check_temperature(temperature)
         self._blob_temperature = self.temperature if blob is not None else 1.0      # (what the engine reads from the header on resume)
@@ -121,7 +145,9 @@ class SlotState:
         """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
         tensor is not included.  A blob on the GPU is copied to the host here -- a synchronising copy --, and for a pinned blob
         the call waits for the device to have written it.  A request that had not started has no blob; with a temperature other
-        than 1 it carries the 64 bytes of a header alone (magic, uid, done = 0 and word 10), so that the value survives."""
+        than 1 it carries the 64 bytes of a header alone (magic, uid, done = 0 and word 10), so that the value survives.  A state
+        still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
+        what they were before primes existed."""
         blob = b""
         if self.blob is None and self.temperature != 1.0:
             hdr = np.zeros(16, dtype="<u4")
@@ -138,7 +164,13 @@ class SlotState:
                 blob = self.blob.numpy().tobytes()
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
-                                1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob
+                                1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob + self._prime_bytes()
+
+    def _prime_bytes(self):
+        if self.prime is None or self.done >= self.prime.numel():
+            return b""
+        rest = self.prime[int(self.done):].cpu().numpy().astype("<i4")
+        return self.PRIME.pack(self.PRIME_MAGIC, int(self.done), int(rest.size)) + rest.tobytes()
 
     @classmethod
     def from_bytes(cls, data, source, pinned=False):
@@ -152,7 +184,15 @@ class SlotState:
         magic, version, kind, frames, final, uid, done, nblob = cls.RECORD.unpack_from(data)
         if magic != cls.RECORD_MAGIC or version != cls.RECORD_VERSION or kind not in (0, 1):
             raise ValueError("not a SlotState record (magic %r, version %d, kind %d)" % (magic, version, kind))
-        if len(data) != cls.RECORD_BYTES + nblob or (nblob and (nblob < 64 or nblob % 16)):
+        prime, tail = None, len(data) - cls.RECORD_BYTES - nblob
+        if tail >= cls.PRIME.size:
+            pmagic, first, count = cls.PRIME.unpack_from(data, cls.RECORD_BYTES + nblob)
+            if pmagic != cls.PRIME_MAGIC or first != done or count < 1 or tail != cls.PRIME.size + 4 * count:
+                raise ValueError("not a prime record behind the blob (magic %r, first %d, count %d, %d bytes)" % (pmagic, first, count, tail))
+            y = np.zeros(first + count, dtype=np.int32)      # (the samples below done are never reached)
+            y[first:] = np.frombuffer(data, dtype="<i4", count=count, offset=cls.RECORD_BYTES + nblob + cls.PRIME.size)
+            prime, tail = torch.from_numpy(y), 0
+        if tail != 0 or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
         temperature = 1.0
@@ -168,7 +208,7 @@ class SlotState:
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   temperature)
+                   temperature, prime)
 
 
 class StepOutput:
@@ -252,6 +292,7 @@ class SlotStream:
         self._src = {}                                 # handle -> (source tensor, uid) of the running requests
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
+        self._prime = {}                               # handle -> prime (int32 tensor) of the requests (queued or running) that carry one
         self._temp = {}                                # handle -> sampling temperature of the requests (queued or running) whose T is not 1
         # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
         # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
@@ -268,13 +309,16 @@ class SlotStream:
         self._next_handle = 0
         self._next_uid = 0
 
-    def submit(self, features, uid=None, temperature=1.0):
+    def submit(self, features, uid=None, temperature=1.0, prime=None):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
         run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
-        [2^-10, 2^10])."""
+        [2^-10, 2^10]).  prime: an integer tensor [n], n <= samples -- its first n samples are these (clamped into 0..A-1) and are
+        delivered like the others; it is drawn from sample n on (ValueError for a bad shape or length).  The stream keeps the
+        tensor while the request is in it."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
         temperature = check_temperature(temperature)
+        prime = check_prime(prime, features.size(1))
         handle = self._next_handle
         self._next_handle += 1
         if uid is None:
@@ -282,15 +326,19 @@ class SlotStream:
         self._next_uid = max(self._next_uid, int(uid) + 1)
         self._queue.append((handle, features, int(uid), None))
         self._note_temperature(handle, temperature)
+        if prime is not None:
+            self._prime[handle] = prime
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
-        final: no more will come); returns its handle.  uid and temperature as for submit."""
+        final: no more will come); returns its handle.  uid, temperature and prime as for submit; the prime of a request that is
+        not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one)."""
         assert mel.dim() == 2, "mel: [n_cond][frames]"
         n = mel.size(1) if frames is None else int(frames)
         assert 0 <= n <= mel.size(1) and (n > 0 or not final)
         temperature = check_temperature(temperature)
+        prime = check_prime(prime, n * self.engine.upStride if final else None)
         handle = self._next_handle
         self._next_handle += 1
         if uid is None:
@@ -300,6 +348,8 @@ class SlotStream:
         self._mel[handle] = req
         self._queue.append((handle, mel, int(uid), req))
         self._note_temperature(handle, temperature)
+        if prime is not None:
+            self._prime[handle] = prime
         return handle
 
     def _note_temperature(self, handle, T):
@@ -394,6 +444,7 @@ class SlotStream:
         """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
         handle, req = item[0], item[3]
         T = self._temp.pop(handle, 1.0)
+        prime = self._prime.pop(handle, None)
         if req is not None:
             del self._mel[handle]
         if len(item) > 4:
@@ -402,8 +453,8 @@ class SlotStream:
             item[4].temperature = T                                 # (... or given another temperature)
             return item[4]
         if req is None:
-            return SlotState(None, item[1], item[2], 0, "features", temperature=T)
-        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T)
+            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime)
+        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime)
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
@@ -411,16 +462,17 @@ class SlotStream:
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
         T = self._temp.pop(handle, 1.0)      # (the engine has written the same value into the blob's header)
+        prime = self._prime.pop(handle, None)
         heapq.heappush(self._free, col)
         self._ch[col] = -1
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T)
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime)
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T)
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime)
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -491,6 +543,8 @@ class SlotStream:
             req = self._mel[handle] = [int(state.frames), bool(state.final), None, int(state.done)]
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
         self._note_temperature(handle, check_temperature(state.temperature))
+        if state.prime is not None and state.done < state.prime.numel():      # (still inside it: applied again when it is admitted)
+            self._prime[handle] = state.prime
         return handle
 
     def _use_arrays(self, on):
@@ -513,6 +567,7 @@ class SlotStream:
     def _admit(self, count):
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
+        primed = []      # (column, handle) of the admitted requests that carry a prime
         tempered = []    # (column, temperature) of the admitted requests whose temperature is not what their start leaves the column at
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
@@ -523,6 +578,8 @@ class SlotStream:
             # a row of a shared buffer, or a CPU tensor still to be uploaded: by list; a CUDA blob of its own (suspend()): singly
             by_list = blob is not None and (state.buffer is not None or not getattr(blob, "is_cuda", True))
             self._src[handle] = (x, uid)
+            if handle in self._prime:
+                primed.append((col, handle))
             T = self._temp.get(handle, 1.0)
             if T != (state._blob_temperature if blob is not None else 1.0):      # (a start leaves 1, a resume the header's value)
                 tempered.append((col, T))
@@ -551,6 +608,8 @@ class SlotStream:
             self._resume_listed(listed)
         for col, T in tempered:      # (start, then set: the engine applies both at the step that follows)
             self.engine.slotSetTemperature(col, T)
+        for col, handle in primed:   # (start or resume, then prime)
+            self.engine.slotPrime(col, self._prime[handle])
 
     def _resume_listed(self, listed):
         """One slotsResumeList call per run of consecutive rows of a shared buffer, in the order admitted (after drain() and
@@ -609,6 +668,7 @@ class SlotStream:
                 del self._running[col]
                 del self._src[rec[0]]
                 self._temp.pop(rec[0], None)
+                self._prime.pop(rec[0], None)
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
                 self._done.append(rec[0])
@@ -619,6 +679,7 @@ class SlotStream:
         handle = self._running.pop(col)[0]
         self._mel.pop(handle, None)
         self._temp.pop(handle, None)
+        self._prime.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1
         self.engine.slotStop(col)

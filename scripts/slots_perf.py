@@ -57,10 +57,15 @@ the host spends inside the calls is recorded beside the time of a step (host_us_
 --temperature is the same comparison for what the per-column sampling temperature costs a step: the parent's plain
 step, this commit's with every T = 1 (no table, the kernel argument NULL) and with mixed T (0.7, 0.85, 1, 1.2 cycling over the
 columns: the table and its scatter launch); a parent that has the temperature entries is simply run at T = 1.
+--prime is that comparison for primed generation: the parent's plain step, this commit's with no prime anywhere
+(Params::forced = 0: the launches the parent issues) and with every column inside a prime for the whole measurement (one
+slot_prime_kernel launch per step and the select behind softmax_pick in every sample).  The verdict is about the case without a
+prime -- not above the parent by more than twice the parent's own spread --; the primed case is reported beside it, not barred.
 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
+    python scripts/slots_perf.py --prime --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --drain [--batch 12288] [--rounds 5]
@@ -90,8 +95,9 @@ def main():
     ap.add_argument("--drain", action="store_true", help="time list saves (device, pinned) and list resumes against one call per column")
     ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
     ap.add_argument("--temperature", action="store_true", help="time the slot step of the parent commit, of this one at T = 1 and at mixed T")
+    ap.add_argument("--prime", action="store_true", help="time the slot step of the parent commit, of this one without a prime and with every column primed")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
-    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature: a libwavenet_infer.so built from the parent commit")
+    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
     import torch
     import bench
@@ -100,7 +106,7 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
-    if args.temperature or args.parent:
+    if args.temperature or args.parent or args.prime:
         assert args.parent_lib or not args.parent, "--parent needs --parent-lib"
         for chunk in [int(c) for c in args.chunks.split(",")]:
             print(json.dumps(time_against_parent(args, w, Wc, bc, chunk)), flush=True)
@@ -198,8 +204,8 @@ def main():
 
 
 def time_against_parent(args, w, Wc, bc, chunk):
-    """The --parent / --temperature measurement (module docstring) for steps of `chunk` samples.  A case is (library, temperatures,
-    kind of step); the cases of one library and temperature setting share an engine."""
+    """The --parent / --temperature / --prime measurement (module docstring) for steps of `chunk` samples.  A case is (library,
+    temperatures or primes, kind of step); the cases of one library and setting share an engine."""
     import ctypes as C
     import torch
     import bench
@@ -223,19 +229,22 @@ def time_against_parent(args, w, Wc, bc, chunk):
 
     here = load(_lib.LIB_PATH)
     here.nvw_slot_set_temperature.restype, here.nvw_slot_set_temperature.argtypes = ci, [vp, ci, C.c_float]
-    libs = {"unit": here, "mixed": here} if args.temperature else {"here": here}
+    here.nvw_slot_prime.restype, here.nvw_slot_prime.argtypes = ci, [vp, ci, vp, ci]
+    libs = {"unit": here, "mixed": here} if args.temperature else {"noprime": here, "primed": here} if args.prime else {"here": here}
+    single = args.temperature or args.prime      # (one kind of step, several settings of this commit)
     if args.parent_lib:
         libs = dict({"parent": load(args.parent_lib)}, **libs)
-    kinds = ("step",) if args.temperature else ("step", "ragged")
+    kinds = ("step",) if single else ("step", "ragged")
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
     warm, steps = 2, max(2, args.steps * 256 // chunk)
-    need = (warm + args.rounds * steps) * chunk * (1 if args.temperature else 2)      # (--parent: plain and ragged steps)
+    need = (warm + args.rounds * steps) * chunk * (1 if single else 2)      # (--parent: plain and ragged steps)
     T_SRC = need + 4096
     src = torch.randn(bench.N_COND, T_SRC, device="cuda", generator=g).half()
     rng = np.random.default_rng(3)
     offs = rng.integers(0, 4096, size=B)
     mixed = (0.7, 0.85, 1.0, 1.2)
+    forced = torch.randint(0, sh.A, (need,), device="cuda", generator=g, dtype=torch.int32)      # one prime for every column, as long as the run
     a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
     engines, info = {}, {}
     for case, h in libs.items():
@@ -253,6 +262,8 @@ def time_against_parent(args, w, Wc, bc, chunk):
             assert h.nvw_slot_start(e, b, x.data_ptr(), 16, x.stride(0), x.stride(1), need, b)
             if case == "mixed":
                 assert h.nvw_slot_set_temperature(e, b, mixed[b % len(mixed)])
+            if case == "primed":
+                assert h.nvw_slot_prime(e, b, forced.data_ptr(), need)
         buf = C.create_string_buffer(256)
         h.nvw_kernel_info(e, B, 0, buf, 256)
         engines[case], info[case] = e, buf.value.decode()
@@ -294,12 +305,12 @@ def time_against_parent(args, w, Wc, bc, chunk):
         h.nvw_slots_end(engines[case])
         h.nvw_destroy(engines[case])
     torch.cuda.empty_cache()
-    name = lambda k: k[0] if args.temperature else "%s_%s" % k
+    name = lambda k: k[0] if single else "%s_%s" % k
     med = {k: float(np.median(v)) for k, v in ms.items()}
     res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
            "ms_per_step": {name(k): [round(v, 4) for v in vs] for k, vs in ms.items()}, "median_ms_per_step": {name(k): round(v, 4) for k, v in med.items()},
            "host_us_per_call": {name(k): [round(v, 2) for v in vs] for k, vs in host_us.items()},
-           "kernel": info["unit" if args.temperature else "here"], "device": torch.cuda.get_device_name(0)}
+           "kernel": info["unit" if args.temperature else "noprime" if args.prime else "here"], "device": torch.cuda.get_device_name(0)}
     if args.temperature:
         res["mixed_temperatures"] = mixed
     if "parent" not in libs:
@@ -312,8 +323,9 @@ def time_against_parent(args, w, Wc, bc, chunk):
             m = {k: float(np.median(x)) for k, x in v.items()}
             spread = (max(v[p]) - min(v[p])) / m[p]
             ratios = {case: m[(case, kind)] / m[p] for case in libs if case != "parent"}
+            barred = [r for case, r in ratios.items() if case != "primed"]      # (--prime: the primed case is reported, not barred)
             res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
-                                     "within_twice_the_parent_spread": bool(max(ratios.values()) <= 1.0 + 2.0 * spread)},
+                                     "within_twice_the_parent_spread": bool(max(barred) <= 1.0 + 2.0 * spread)},
                                     **{case + "_vs_parent": round(r, 4) for case, r in ratios.items()})
     return res
 
