@@ -96,7 +96,9 @@ void nvw_set_conditioning_n(nvw_engine* e, float* Lh, int num_samples);
  * previous chunk on another stream.  Does not touch the sample history. */
 void nvw_pack_conditioning(nvw_engine* e, float* Lh, int first_sample, int count, void* stream);
 /* Device-resident conditioning consumed IN PLACE (no packed copy; pytorch/README.md:44 recommends keeping cond_input on
- * the device, wavenet_infer.cu:124-143 still copies it): Lh is fp32 [num_samples][L][batch][2R] in device memory, owned by
+ * the device, wavenet_infer.cu:124-143 still copies it): Lh is fp32 [num_samples][L][batch_size][2R] in device memory --
+ * batch_size is the ENGINE's, the capacity given to nvw_create, exactly as for nvw_set_inputs and the selectors: a run of fewer
+ * utterances reads the first columns of every [batch_size][2R] row and never touches the others -- owned by
  * the caller and kept alive and unchanged until the run calls that follow have completed.  Resets the history like
  * nvw_set_inputs; pair with nvw_set_selector_seed.  Same samples as the packed path, bit for bit. */
 void nvw_set_conditioning_direct(nvw_engine* e, float* Lh, int num_samples);
