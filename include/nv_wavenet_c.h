@@ -479,6 +479,42 @@ int nvw_set_prime(nvw_engine* e, const int* y, const int* n, int batch, int max_
 int nvw_slot_prime(nvw_engine* e, int slot, const int* y, int n);
 int nvw_slot_primed(nvw_engine* e, int slot);
 
+/* PREFILL: A PRIME'S STATE BLOB FROM A TIME-PARALLEL PASS (additive within ABI 7).  A prime of n samples costs n samples of
+ * generation when it is forced through a column.  Every forced sample is known, though, so the state behind the prime can be
+ * computed layer by layer over 16 samples at a time, without the skip path, the head or the softmax: one launch per layer over the
+ * last W = nvw_prefill_window samples of the prime, which are all the state depends on -- a prime of ten seconds costs what one of W
+ * samples costs.  The result is the blob of nvw_slot_save: prefill(y[0 .. n), features, uid, temperature) EQUALS, BYTE FOR BYTE,
+ * header and payload, in fp16 and in fp32, what nvw_slot_start, nvw_slot_set_temperature, nvw_slot_prime(y, n), steps up to local
+ * sample n and nvw_slot_save produce with the same features, uid and temperature -- the samples that follow a resume do not depend on
+ * how the state was made.  The pass reads the engine's own weight streams and touches no ring, column or session.
+ *   nvw_prefill_window  W: the number of trailing samples that determine a state (the sum of the dilations + the two history samples
+ *                       the embedding reads); 0 when the engine has no conditioning weights.
+ *   nvw_prefill_states  `count` requests with one set of layer launches, blob i to dst + i * stride: device memory or pinned host
+ *                       memory, 16-byte aligned, stride a multiple of 16 and at least nvw_slot_state_bytes.  y: the prime, int32 in
+ *                       device memory, n >= 1 values (clamped into 0 .. A-1 as nvw_slot_prime clamps them); x, precision, c_stride,
+ *                       t_stride: the utterance's features as for nvw_slot_start, of which only columns [t0, n) are read, t0 =
+ *                       max(0, n - W) rounded down to a multiple of 16; uid and temperature go into the header (word 10: the bits of
+ *                       the temperature, zero for 1).  Asynchronous on `stream`: y and x stay alive until it has run, and the blobs
+ *                       are complete when the stream has passed it (nvw_slot_resume / nvw_slots_resume_list read headers with
+ *                       the ordering rules stated there).  Works inside and outside slot mode; calls of one engine share its
+ *                       scratch (grown on demand, sized by W and count, freed with the engine): issue them on one stream, or order
+ *                       them.  Needs nvw_set_conditioning_weights.  Returns count; 0 with nothing written: no conditioning weights,
+ *                       count outside 1 .. 65535, an n < 1, a temperature outside [2^-10, 2^10], a bad precision, pointer,
+ *                       alignment or stride.
+ * Mel frames (a prefill that upsamples), lockstep engines taking a prefilled state, and per-sample log-likelihoods of the prime are
+ * not offered. */
+typedef struct {
+    const int* y;
+    int n;
+    const void* x;
+    int precision;
+    long long c_stride, t_stride;
+    unsigned uid;
+    float temperature;
+} nvw_prefill_req;
+int nvw_prefill_window(nvw_engine* e);
+int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, void* dst, long long stride, void* stream);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

@@ -106,6 +106,8 @@ SIGNATURES = {
     "nvw_set_prime": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_longlong]),
     "nvw_slot_prime": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
     "nvw_slot_primed": (C.c_int, [C.c_void_p, C.c_int]),
+    "nvw_prefill_window": (C.c_int, [C.c_void_p]),
+    "nvw_prefill_states": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong, C.c_void_p]),
     "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),
     "nvw_pinned_free": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),

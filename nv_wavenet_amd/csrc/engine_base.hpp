@@ -60,6 +60,8 @@ struct nvw_engine {
     virtual void getYOut(int*, int, int, hipStream_t) = 0;
     virtual bool setTemperatures(const float*, int) = 0;
     virtual bool setPrime(const int*, const int*, int, int, long long) = 0;
+    virtual int prefillWindow() = 0;
+    virtual int prefillStates(const wn::PrefillReq*, int, void*, long long, hipStream_t) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
@@ -80,6 +82,14 @@ static_assert(sizeof(nvw_slot_resume_req) == sizeof(wn::SlotResumeReq) && offset
               offsetof(nvw_slot_resume_req, length) == offsetof(wn::SlotResumeReq, length) &&
               offsetof(nvw_slot_resume_req, final) == offsetof(wn::SlotResumeReq, final),
               "nvw_slot_resume_req is wn::SlotResumeReq");
+
+static_assert(sizeof(nvw_prefill_req) == sizeof(wn::PrefillReq) && offsetof(nvw_prefill_req, y) == offsetof(wn::PrefillReq, y) &&
+              offsetof(nvw_prefill_req, n) == offsetof(wn::PrefillReq, n) && offsetof(nvw_prefill_req, x) == offsetof(wn::PrefillReq, x) &&
+              offsetof(nvw_prefill_req, precision) == offsetof(wn::PrefillReq, precision) &&
+              offsetof(nvw_prefill_req, c_stride) == offsetof(wn::PrefillReq, cStride) &&
+              offsetof(nvw_prefill_req, t_stride) == offsetof(wn::PrefillReq, tStride) && offsetof(nvw_prefill_req, uid) == offsetof(wn::PrefillReq, uid) &&
+              offsetof(nvw_prefill_req, temperature) == offsetof(wn::PrefillReq, temperature),
+              "nvw_prefill_req is wn::PrefillReq");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -153,6 +163,10 @@ struct EngineImpl : nvw_engine {
     void getYOut(int* y, int off, int size, hipStream_t s) override { eng.getYOut(y, off, size, s); }
     bool setTemperatures(const float* T, int n) override { return eng.setTemperatures(T, n); }
     bool setPrime(const int* y, const int* n, int batch, int maxN, long long stride) override { return eng.setPrime(y, n, batch, maxN, stride); }
+    int prefillWindow() override { return eng.prefillWindow(); }
+    int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t s) override {
+        return eng.prefillStates(reqs, count, dst, stride, s);
+    }
     wn::SlotSession& slots() override { return eng.slots(); }
 };
 

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "gpu_check.hpp"
+#include "prefill.hpp"
 #include "slots_session.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
@@ -145,6 +146,7 @@ protected:
     // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode
     wn::TemperatureTable m_temps;
     wn::PrimeTable m_prime;           // the lockstep primes (slots_prime.hpp)
+    wn::Prefill m_prefill;            // scratch and staging of prefillStates (prefill.hpp), nothing until the first call
     // slot mode (slots_session.hpp): made at the end of the constructor, when the facts it is given are known
     std::unique_ptr<wn::SlotSession> m_slots;
 
@@ -1229,6 +1231,46 @@ public:
                     if (y[b * stride + k] < 0 || y[b * stride + k] >= A) return false;
         m_prime.set(y, n, batch, maxN, stride, m_maxSamples);
         return true;
+    }
+    // ---- prefill: a prime's state blob from a time-parallel pass (beyond the reference; prefill.hpp) ------------------
+    // W: the trailing samples of a prime that determine the state behind it (sum of the dilations + the two history words); 0 without
+    // conditioning weights
+    int prefillWindow() const { return m_nCond > 0 ? wn::prefill_window(m_ringSlots) : 0; }
+    // For request i < count the blob that slotStart(x, uid), slotSetTemperature, slotPrime(y, n), steps up to local sample n and slotSave
+    // would have produced -- byte for byte -- at dst + i * stride (16-byte aligned device or mapped pinned memory, stride a multiple of
+    // 16 and at least slotStateBytes()), from ONE set of layer launches over the last W samples of every prime, asynchronously on
+    // `stream`; y and x stay alive until it has run.  Works in and outside slot mode and touches no ring, column or session.  Calls
+    // of one engine share its scratch: one stream, or ordered by the caller.  Returns count; 0 with nothing written: no conditioning
+    // weights, a shape that does not fit a CU, count outside 1 .. 65535, an n < 1, a temperature outside [2^-10, 2^10], a bad
+    // precision, pointer, alignment or stride.
+    int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported) return 0;
+        const int L = m_numLayers;
+        wn::PrefillModel m;
+        m.f16 = F16;
+        m.R = R;
+        m.A = A;
+        m.numLayers = L;
+        m.maxDilation = m_maxDilation;
+        m.ringSlots = m_ringSlots;
+        m.nCond = m_nCond;
+        m.tanhEmbed = m_tanhEmbed ? 1 : 0;
+        m.waveStreamFrags = CF::waveStreamFrags(L);
+        m.biasL = C::BIAS_L;
+        m.embPrev = m_embedPrev;
+        m.embCur = m_embedCur;
+        for (int l = 0, d = 1, off = 0; l < L; l++) {
+            int dN = d << 1;
+            if (dN > m_maxDilation) dN = 1;
+            m.layers[l] = wn::PrefillLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
+                                           (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L), l, d, dN, off + d};
+            off += d;
+            d = dN;
+        }
+        if (m_featDirty) buildFeatStream(stream);
+        m.wblob = m_wblobF;
+        m.bias = m_biasF;
+        return m_prefill.run(m, reqs, count, dst, stride, stream) ? count : 0;
     }
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to

@@ -388,6 +388,16 @@ int nvw_slot_prime(nvw_engine* e, int slot, const int* y, int n) {
     return 0;
 }
 int nvw_slot_primed(nvw_engine* e, int slot) { return e->slots().primed(slot); }
+// ---- prefill: a prime's state blob from a time-parallel pass (additive within ABI 7) -----------------------------------------------
+int nvw_prefill_window(nvw_engine* e) { return e->prefillWindow(); }
+int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, void* dst, long long stride, void* stream) {
+    const int got = e->prefillStates((const wn::PrefillReq*)reqs, count, dst, stride, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_prefill_states: refused, nothing written (nvw_set_conditioning_weights first; %d requests of 1 .. 65535; every n "
+                ">= 1, y and x in device memory, precision 32 or 16, positive strides, temperature in [2^-10, 2^10]; dst 16-byte aligned "
+                "device or pinned memory, stride %lld a multiple of 16, at least %zu)\n", count, stride, e->slots().stateBytes());
+    return got;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

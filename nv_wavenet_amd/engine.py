@@ -19,6 +19,10 @@ SLOT_RESUME_REQ = np.dtype({"names": ["slot", "mel", "src", "precision", "c_stri
                             "formats": ["<i4", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<i4"],
                             "offsets": [0, 4, 8, 16, 24, 32, 40, 44], "itemsize": 48})
 assert SLOT_SAVED.itemsize == 16
+# ... nvw_prefill_req of nvw_prefill_states
+PREFILL_REQ = np.dtype({"names": ["y", "n", "x", "precision", "c_stride", "t_stride", "uid", "temperature"],
+                        "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<u4", "<f4"],
+                        "offsets": [0, 8, 16, 24, 32, 40, 48, 52], "itemsize": 56})
 
 
 class Impl:
@@ -629,6 +633,40 @@ class WavenetEngine:
     def slotPrimed(self, slot):
         """n of the prime in force on column `slot` (host state; 0 when none, or once its last forced sample has been issued)."""
         return int(lib.nvw_slot_primed(self._h, int(slot)))
+
+    # ---- prefill: a prime's state blob from a time-parallel pass (include/nv_wavenet_c.h, "PREFILL"; DESIGN.md §6i) ----
+    def prefillWindow(self):
+        """W: the trailing samples of a prime that determine the state behind it; 0 without conditioning weights."""
+        return int(lib.nvw_prefill_window(self._h))
+
+    def prefillStates(self, requests, pinned=False, stream=None, out=None):
+        """The state blobs behind primes, with one set of layer launches: requests = [(y, x, uid, temperature), ...] with y the
+        prime (1-D contiguous int32 CUDA tensor, n >= 1 values) and x the utterance's features (CUDA tensor [n_cond][>= n], float32
+        or float16, any strides).  Returns a uint8 tensor [n][stride] on the GPU, or in pinned host memory (pinned=True), or `out`
+        (as for slotsSaveList): row i is byte for byte the blob that slotStart(x, uid) + slotSetTemperature + slotPrime(y), steps up
+        to local sample len(y) and slotSave produce.  Asynchronous on `stream`; the tensors of `requests` must stay alive until it
+        has run.  Works in and outside slot mode.  ValueError when refused (nothing written): see nvw_prefill_states."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        if out is None:
+            out = torch.empty((max(n, 1), self.slotStateBytes()), dtype=torch.uint8, device=None if pinned else "cuda", pin_memory=bool(pinned))
+        assert out.dtype == torch.uint8 and out.dim() == 2 and out.stride(1) == 1 and out.size(0) >= n and (out.is_cuda or out.is_pinned()), \
+            "out: a uint8 CUDA or pinned tensor [>= n][stride]"
+        reqs = np.zeros(max(n, 1), dtype=PREFILL_REQ)
+        for i, (y, x, uid, T) in enumerate(requests):
+            if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous() or not y.is_cuda:
+                raise ValueError("a prime is a contiguous 1-D int32 CUDA tensor")
+            assert hasattr(x, "data_ptr") and x.is_cuda and x.dim() == 2 and x.size(0) == self.nCond, "features: CUDA tensors [n_cond][samples]"
+            bits = {torch.float32: 32, torch.float16: 16}.get(x.dtype)
+            assert bits, "features must be float32 or float16"
+            if y.numel() > x.size(1):
+                raise ValueError("a prime of %d samples against features of %d" % (y.numel(), x.size(1)))
+            reqs[i] = (y.data_ptr(), y.numel(), x.data_ptr(), bits, x.stride(0), x.stride(1), int(uid) & 0xFFFFFFFF, float(T))
+        got = lib.nvw_prefill_states(self._h, reqs.ctypes.data, n, out.data_ptr(), out.stride(0), stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_prefill_states refused %d requests" % n)
+        return out[:n]
 
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):

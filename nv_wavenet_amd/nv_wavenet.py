@@ -393,13 +393,14 @@ class NVWaveNetEngine(NVWaveNet):
         return e
 
     def slot_stream(self, columns, window, cond_weight, cond_bias, seed=0, implementation=Impl.AUTO, pcm=True, upsample_weight=None,
-                    upsample_bias=None, upsample_stride=None, compact=False):
+                    upsample_bias=None, upsample_stride=None, compact=False, prefill=False):
         """Continuous batching (nv_wavenet_amd/slots.py): a SlotStream over an engine of its own with `columns` columns and a window of
         `window` samples (a multiple of max_dilation), the conditioning convolution in the kernel as infer_features has it
         (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
         request; with the model's `upsample` ConvTranspose1d (upsample_weight [n_cond][n_cond][window], upsample_bias, its stride)
         mel frames [n_cond][frames] as well (submit_mel).  compact: every step first packs the running requests into the front of the
-        batch (SlotStream.compact).  stream.step(n) waits for its samples; stream.step_async(n) issues the step and returns a
+        batch (SlotStream.compact).  prefill: submit(prime=) makes the state behind a prime with the engine's time-parallel pass and
+        enters the request at sample n, unless the call says prefill=False (SlotStream.submit).  stream.step(n) waits for its samples; stream.step_async(n) issues the step and returns a
         PendingStep, two of which may be in flight (the pipelined service loop of INTEGRATION.md §2g).  close() the stream to free
         the engine."""
         from .slots import SlotStream
@@ -409,7 +410,7 @@ class NVWaveNetEngine(NVWaveNet):
             assert upsample_bias is not None and upsample_stride is not None, "upsampling needs its weight, bias and stride"
             e.setUpsampling(upsample_weight.float().contiguous(), upsample_bias.float().contiguous(), int(upsample_stride))
         e.setSelectorSeed(seed)
-        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact)
+        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact, prefill=prefill)
 
     def close(self):
         for e in self._engines.values():

@@ -58,6 +58,14 @@ others.  suspend, drain, resume, compact and to_bytes / from_bytes keep what is 
 
     h = stream.submit(features, prime=delivered)        # integer tensor [n], values in 0..A-1
 
+Forcing a prime through a column costs one sample of generation per forced sample.  The state behind it can be computed instead
+(nvw_prefill_states): a time-parallel pass over the last W samples of the prime writes the blob the column would
+have saved after them -- byte for byte --, and the request enters as a resume at sample n.  Its delivery then starts at sample n:
+the caller has the forced samples already.
+
+    h = stream.submit(features, prime=delivered, prefill=True)
+    state = stream.prefill(features, delivered)         # or the state itself: resume() / resume_many() / to_bytes()
+
 step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
 (DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
 owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
@@ -279,8 +287,9 @@ class PendingStep:
 
 
 class SlotStream:
-    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False):
+    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False, prefill=False):
         self.engine = engine
+        self._prefill = bool(prefill)                  # what submit(prefill=None) does with a prime
         self.columns = engine.maxBatch
         self.window = int(window)
         self.pcm = pcm
@@ -309,16 +318,50 @@ class SlotStream:
         self._next_handle = 0
         self._next_uid = 0
 
-    def submit(self, features, uid=None, temperature=1.0, prime=None):
+    def prefill(self, features, prime, uid=None, temperature=1.0):
+        """The state of the utterance (features, uid, temperature) behind the forced samples `prime` (an integer tensor [n], 1 <= n
+        <= samples), computed by the engine's time-parallel pass instead of n samples of generation: a SlotState with done = n whose
+        blob is byte for byte the one a column primed with them saves after them.  resume() / resume_many() take it (a prime that
+        covers the whole utterance leaves nothing to resume), and it survives to_bytes() / from_bytes().  Nothing is queued, no
+        column is touched.  uid: as for submit (default: the next one).  The blob is complete once the engine's stream has run
+        the pass; a resume orders itself behind it."""
+        assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
+        temperature = check_temperature(temperature)
+        prime = check_prime(prime, features.size(1))
+        if prime is None:
+            raise ValueError("prefill needs a prime")
+        if uid is None:
+            uid = self._next_uid
+        self._next_uid = max(self._next_uid, int(uid) + 1)
+        y = prime if prime.is_cuda else prime.cuda()
+        blobs = self.engine.prefillStates([(y, features, int(uid), temperature)])
+        state = SlotState(blobs[0], features, int(uid), int(y.numel()), "features", buffer=blobs, row=0, temperature=temperature)
+        state._prefilled_from = y      # (read by the pass in stream order: kept with the state)
+        return state
+
+    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
         run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
         [2^-10, 2^10]).  prime: an integer tensor [n], n <= samples -- its first n samples are these (clamped into 0..A-1) and are
         delivered like the others; it is drawn from sample n on (ValueError for a bad shape or length).  The stream keeps the
-        tensor while the request is in it."""
+        tensor while the request is in it.  prefill (None: the stream's default, False unless it was made with prefill=True): True
+        with a prime of n < samples values makes the state behind the prime at once (prefill()) and queues the request as a resume
+        at sample n -- its delivery starts there, the forced samples are not delivered again, and the samples from n on are bit
+        for bit those of prefill=False; ValueError for a prime that covers the whole utterance.  Without a prime it changes
+        nothing."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
         temperature = check_temperature(temperature)
         prime = check_prime(prime, features.size(1))
+        if (self._prefill if prefill is None else prefill) and prime is not None:
+            if prime.numel() >= features.size(1):
+                raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), features.size(1)))
+            state = self.prefill(features, prime, uid, temperature)
+            handle = self._next_handle
+            self._next_handle += 1
+            self._queue.append((handle, features, int(state.uid), None, state))
+            self._note_temperature(handle, temperature)
+            return handle
         handle = self._next_handle
         self._next_handle += 1
         if uid is None:
@@ -330,10 +373,12 @@ class SlotStream:
             self._prime[handle] = prime
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=False):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
         final: no more will come); returns its handle.  uid, temperature and prime as for submit; the prime of a request that is
         not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one)."""
+        if prefill:
+            raise ValueError("prefill of a mel request is not offered: the pass reads upsampled features (submit), not frames")
         assert mel.dim() == 2, "mel: [n_cond][frames]"
         n = mel.size(1) if frames is None else int(frames)
         assert 0 <= n <= mel.size(1) and (n > 0 or not final)

@@ -61,8 +61,16 @@ columns: the table and its scatter launch); a parent that has the temperature en
 (Params::forced = 0: the launches the parent issues) and with every column inside a prime for the whole measurement (one
 slot_prime_kernel launch per step and the select behind softmax_pick in every sample).  The verdict is about the case without a
 prime -- not above the parent by more than twice the parent's own spread --; the primed case is reported beside it, not barred.
+--prefill times what a prime costs before its utterance draws its first sample, C3 fp16, one process: the
+sequential path -- nvw_slot_start + nvw_slot_prime for every request, steps of at most the window up to local sample n, one
+nvw_slots_save_list -- against nvw_prefill_states on the same primes and features, for 1 request and for 256, at n = W / 2, W, 4 W and
+24 000 (W = nvw_prefill_window); `--rounds` rounds, the two paths alternating, events around each path and a check that the two
+sets of blobs are equal bytes.  Prints one JSON line with the per-round milliseconds, the medians, the ratio, the 4 W against W
+prefill time and the verdict on the one fixed bar: one request at n = W is faster prefilled than sequential.  With --parent-lib
+it then prints the --parent comparison of the plain step (nothing on that path changes: a guard, not a goal).
 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --prime --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
@@ -96,6 +104,7 @@ def main():
     ap.add_argument("--serve", action="store_true", help="time SlotStream.step / step_async against the engine-level step, and the delivery paths")
     ap.add_argument("--temperature", action="store_true", help="time the slot step of the parent commit, of this one at T = 1 and at mixed T")
     ap.add_argument("--prime", action="store_true", help="time the slot step of the parent commit, of this one without a prime and with every column primed")
+    ap.add_argument("--prefill", action="store_true", help="time the sequential prime against nvw_prefill_states, 1 and 256 requests")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
@@ -106,6 +115,11 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.prefill:
+        print(json.dumps(time_prefill(args, w, Wc, bc)), flush=True)
+        if not args.parent_lib:
+            return
+        args.parent = True
     if args.temperature or args.parent or args.prime:
         assert args.parent_lib or not args.parent, "--parent needs --parent-lib"
         for chunk in [int(c) for c in args.chunks.split(",")]:
@@ -327,6 +341,74 @@ def time_against_parent(args, w, Wc, bc, chunk):
             res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
                                      "within_twice_the_parent_spread": bool(max(barred) <= 1.0 + 2.0 * spread)},
                                     **{case + "_vs_parent": round(r, 4) for case, r in ratios.items()})
+    return res
+
+
+def time_prefill(args, w, Wc, bc):
+    """The --prefill measurement (module docstring)."""
+    import torch
+    import bench
+    sh = bench.HEAD
+    window = 4096
+    g = torch.Generator(device="cuda")
+    g.manual_seed(11)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "rounds": args.rounds, "window": window,
+           "device": torch.cuda.get_device_name(0), "cases": {}}
+    for count in (1, 256):
+        e = bench.build_engine(w, count, window)
+        e.setConditioningWeights(Wc, bc)
+        e.setSelectorSeed(5)
+        W = e.prefillWindow()
+        res["W"] = W
+        lengths = (W // 2, W, 4 * W, 24000)
+        top = max(lengths)
+        src = torch.randn(bench.N_COND, top + count, device="cuda", generator=g).half()
+        xs = [src[:, b:b + top] for b in range(count)]                      # a request's features: the shared ones, shifted by b
+        ys = torch.randint(0, sh.A, (count, top), device="cuda", generator=g, dtype=torch.int32)
+        seq_out = torch.empty((count, e.slotStateBytes()), dtype=torch.uint8, device="cuda")
+        pre_out = torch.empty_like(seq_out)
+        s = torch.cuda.current_stream().cuda_stream
+
+        def sequential(n):
+            e.slotsBegin(window)
+            for b in range(count):
+                e.slotStart(b, xs[b], b, n)
+                e.slotPrime(b, ys[b, :n])
+            done = 0
+            while done < n:
+                c = min(window, n - done)
+                assert e.slotsStep(c, stream=s)
+                done += c
+            e.slotsSaveList(range(count), stream=s, out=seq_out)
+
+        def prefilled(n):
+            e.prefillStates([(ys[b, :n], xs[b], b, 1.0) for b in range(count)], stream=s, out=pre_out)
+
+        for n in lengths:
+            ms = {"sequential": [], "prefill": []}
+            for r in range(args.rounds + 1):                                # (round 0 warms both paths up: allocations, first launches)
+                for name, fn in ((("sequential", sequential), ("prefill", prefilled)) if r % 2 else (("prefill", prefilled), ("sequential", sequential))):
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                    fn(n)
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    if r:
+                        ms[name].append(ev[0].elapsed_time(ev[1]))
+                    if name == "sequential":
+                        e.slotsEnd()
+                assert torch.equal(seq_out, pre_out), "count %d, n %d: the prefilled blobs are not the sequential ones" % (count, n)
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            res["cases"]["%d x %d" % (count, n)] = {"sequential_ms": [round(v, 3) for v in ms["sequential"]], "prefill_ms": [round(v, 3) for v in ms["prefill"]],
+                                                   "median_sequential_ms": round(med["sequential"], 3), "median_prefill_ms": round(med["prefill"], 3),
+                                                   "sequential_over_prefill": round(med["sequential"] / med["prefill"], 2)}
+        c = res["cases"]
+        res["prefill_4W_over_W_%d" % count] = round(c["%d x %d" % (count, 4 * W)]["median_prefill_ms"] / c["%d x %d" % (count, W)]["median_prefill_ms"], 3)
+        e.close()
+        torch.cuda.empty_cache()
+    one = res["cases"]["1 x %d" % res["W"]]
+    res["one_request_at_W_faster_prefilled"] = bool(one["median_prefill_ms"] < one["median_sequential_ms"])
     return res
 
 
