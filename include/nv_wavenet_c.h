@@ -501,8 +501,8 @@ int nvw_slot_primed(nvw_engine* e, int slot);
  *                       them.  Needs nvw_set_conditioning_weights.  Returns count; 0 with nothing written: no conditioning weights,
  *                       count outside 1 .. 65535, an n < 1, a temperature outside [2^-10, 2^10], a bad precision, pointer,
  *                       alignment or stride.
- * Mel frames (a prefill that upsamples), lockstep engines taking a prefilled state, and per-sample log-likelihoods of the prime are
- * not offered. */
+ * Mel frames (a prefill that upsamples) and lockstep engines taking a prefilled state are not offered; the per-sample
+ * log-likelihoods of a prime are a pass of their own (SCORING, below). */
 typedef struct {
     const int* y;
     int n;
@@ -514,6 +514,41 @@ typedef struct {
 } nvw_prefill_req;
 int nvw_prefill_window(nvw_engine* e);
 int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, void* dst, long long stride, void* stream);
+
+/* SCORING: PER-SAMPLE LOG-LIKELIHOODS FROM A TIME-PARALLEL PASS (additive within ABI 7).  What probability the model gives to a
+ * waveform: logp[t] = log softmax(Za_t / T)[y[t]] (natural logarithm, fp32) for every t in [0, n), where Za_t are the logits of sample
+ * t of a column that started from silence (history 128, 128), was fed y[0 .. t) and reads feature column t -- the logits the
+ * generation kernel hands to its sampler at that sample when y is forced.  Every sample is known, so the pass runs layer by layer
+ * over 16 samples at a time like the prefill pass, but over all of [0, n), through every layer, with the skip path, the head and the
+ * softmax; it reads the engine's own weight streams and touches no ring, column or session.
+ *   nvw_score_max_samples  the largest sum of n, each rounded up to a multiple of 16, that one call accepts: the scratch of a call
+ *                          (per sample the fp32 residual, two T_data images of x and the fp32 skip sum) stays under 1 GiB.  0 when
+ *                          the engine has no conditioning weights.
+ *   nvw_score_samples      `count` requests with one set of layer launches.  y: the samples, int32 in device memory, n >= 1 values
+ *                          (clamped into 0 .. A-1 as nvw_slot_prime clamps them); x, precision, c_stride, t_stride: the utterance's
+ *                          features as for nvw_slot_start, columns [0, n); temperature: T.  logp: n floats, device memory or pinned
+ *                          host memory, 4-byte aligned.  rows: NULL, or n * A floats in device memory, 16-byte aligned:
+ *                          rows[t * A + a] = log softmax(Za_t / T)[a], and rows[t * A + y[t]] is logp[t] bit for bit.  Nothing is
+ *                          written past n.  Asynchronous on `stream`: y, x and the outputs stay alive until it has run.  Works
+ *                          inside and outside slot mode; calls of one engine share its scratch (grown on demand, freed with the
+ *                          engine): issue them on one stream, or order them.  Needs nvw_set_conditioning_weights.  Returns count;
+ *                          0 with nothing written and nothing launched: no conditioning weights, count outside 1 .. 65535, an
+ *                          n < 1, a temperature outside [2^-10, 2^10], a bad precision or stride, y or x not in device memory, a
+ *                          misaligned or unreachable output, a total over nvw_score_max_samples.
+ * Scoring from mel frames, in time chunks with carried state (utterances past the cap), and on the packed, in-place and chain
+ * conditioning paths is not offered. */
+typedef struct {
+    const int* y;
+    int n;
+    const void* x;
+    int precision;
+    long long c_stride, t_stride;
+    float temperature;
+    float* logp;
+    float* rows;
+} nvw_score_req;
+int nvw_score_max_samples(nvw_engine* e);
+int nvw_score_samples(nvw_engine* e, const nvw_score_req* reqs, int count, void* stream);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

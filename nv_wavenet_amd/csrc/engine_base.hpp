@@ -62,6 +62,8 @@ struct nvw_engine {
     virtual bool setPrime(const int*, const int*, int, int, long long) = 0;
     virtual int prefillWindow() = 0;
     virtual int prefillStates(const wn::PrefillReq*, int, void*, long long, hipStream_t) = 0;
+    virtual int scoreMaxSamples() = 0;
+    virtual int scoreSamples(const wn::ScoreReq*, int, hipStream_t) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
@@ -90,6 +92,15 @@ static_assert(sizeof(nvw_prefill_req) == sizeof(wn::PrefillReq) && offsetof(nvw_
               offsetof(nvw_prefill_req, t_stride) == offsetof(wn::PrefillReq, tStride) && offsetof(nvw_prefill_req, uid) == offsetof(wn::PrefillReq, uid) &&
               offsetof(nvw_prefill_req, temperature) == offsetof(wn::PrefillReq, temperature),
               "nvw_prefill_req is wn::PrefillReq");
+
+static_assert(sizeof(nvw_score_req) == sizeof(wn::ScoreReq) && offsetof(nvw_score_req, y) == offsetof(wn::ScoreReq, y) &&
+              offsetof(nvw_score_req, n) == offsetof(wn::ScoreReq, n) && offsetof(nvw_score_req, x) == offsetof(wn::ScoreReq, x) &&
+              offsetof(nvw_score_req, precision) == offsetof(wn::ScoreReq, precision) &&
+              offsetof(nvw_score_req, c_stride) == offsetof(wn::ScoreReq, cStride) &&
+              offsetof(nvw_score_req, t_stride) == offsetof(wn::ScoreReq, tStride) &&
+              offsetof(nvw_score_req, temperature) == offsetof(wn::ScoreReq, temperature) &&
+              offsetof(nvw_score_req, logp) == offsetof(wn::ScoreReq, logp) && offsetof(nvw_score_req, rows) == offsetof(wn::ScoreReq, rows),
+              "nvw_score_req is wn::ScoreReq");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -167,6 +178,8 @@ struct EngineImpl : nvw_engine {
     int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t s) override {
         return eng.prefillStates(reqs, count, dst, stride, s);
     }
+    int scoreMaxSamples() override { return eng.scoreMaxSamples(); }
+    int scoreSamples(const wn::ScoreReq* reqs, int count, hipStream_t s) override { return eng.scoreSamples(reqs, count, s); }
     wn::SlotSession& slots() override { return eng.slots(); }
 };
 

@@ -38,6 +38,7 @@
 
 #include "gpu_check.hpp"
 #include "prefill.hpp"
+#include "score.hpp"
 #include "slots_session.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
@@ -146,6 +147,7 @@ protected:
     // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode
     wn::TemperatureTable m_temps;
     wn::PrimeTable m_prime;           // the lockstep primes (slots_prime.hpp)
+    wn::Score m_score;                // scratch and staging of scoreSamples (score.hpp), nothing until the first call
     wn::Prefill m_prefill;            // scratch and staging of prefillStates (prefill.hpp), nothing until the first call
     // slot mode (slots_session.hpp): made at the end of the constructor, when the facts it is given are known
     std::unique_ptr<wn::SlotSession> m_slots;
@@ -1271,6 +1273,48 @@ public:
         m.wblob = m_wblobF;
         m.bias = m_biasF;
         return m_prefill.run(m, reqs, count, dst, stride, stream) ? count : 0;
+    }
+    // ---- scoring: per-sample log-likelihoods from a time-parallel pass (beyond the reference; score.hpp) ---------------
+    // the largest sum of n, each rounded up to 16, that one scoreSamples call accepts (its scratch stays under wn::kScoreScratchCap);
+    // 0 without conditioning weights
+    int scoreMaxSamples() const { return m_nCond > 0 && m_supported ? wn::score_max_samples(F16, R, S) : 0; }
+    // For request i < count: logp[t] = log softmax(Za_t / T)[y[t]] for t < n (natural logarithm, fp32; and, where rows is not NULL,
+    // rows[t][a] = log softmax(Za_t / T)[a]), with Za_t the logits of sample t of a column started from silence, fed y[0 .. t) and
+    // reading feature column t.  ONE set of layer launches over all of [0, n) of every request, asynchronously on `stream`; y, x and
+    // the outputs stay alive until it has run.  Works in and outside slot mode and touches no ring, column or session.  Calls of one
+    // engine share its scratch: one stream, or ordered by the caller.  Returns count; 0 with nothing written or launched: no
+    // conditioning weights, count outside 1 .. 65535, an n < 1, a temperature outside [2^-10, 2^10], a bad precision, stride or
+    // pointer, a misaligned or unreachable output, a total over scoreMaxSamples().
+    int scoreSamples(const wn::ScoreReq* reqs, int count, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported) return 0;
+        const int L = m_numLayers;
+        wn::ScoreModel m;
+        m.f16 = F16;
+        m.R = R;
+        m.S = S;
+        m.A = A;
+        m.numLayers = L;
+        m.nCond = m_nCond;
+        m.tanhEmbed = m_tanhEmbed ? 1 : 0;
+        m.waveStreamFrags = CF::waveStreamFrags(L);
+        m.headZs = (unsigned)(CF::headOffsetFrags(L) + CF::O_ZS);
+        m.headZa = (unsigned)(CF::headOffsetFrags(L) + CF::O_ZA);
+        m.biasL = C::BIAS_L;
+        m.embPrev = m_embedPrev;
+        m.embCur = m_embedCur;
+        for (int l = 0, d = 1; l < L; l++) {
+            m.layers[l] = wn::ScoreLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
+                                         (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L),
+                                         (unsigned)CF::streamPos(l, CF::O_SKIP, L), d};
+            d <<= 1;
+            if (d > m_maxDilation) d = 1;
+        }
+        // (checked before anything is queued: a refused call launches nothing, the stream rebuild included)
+        if (!wn::Score::acceptable(m, reqs, count)) return 0;
+        if (m_featDirty) buildFeatStream(stream);
+        m.wblob = m_wblobF;
+        m.bias = m_biasF;
+        return m_score.run(m, reqs, count, stream) ? count : 0;
     }
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to

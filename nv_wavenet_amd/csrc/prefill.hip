@@ -5,31 +5,11 @@
 
 #include <vector>
 
-#include "wn_kernels.hpp"
+#include "time_tiles.hpp"
 
 namespace wn {
 
 namespace {
-
-template <bool F16, int R> struct PCfg {
-    using P = Prec<F16>;
-    static constexpr int TPF = P::TPF;
-    static constexpr int RT = R / 16, NW = RT >= 4 ? 4 : RT, HTW = RT / NW, KF_R = RT / TPF;      // (as Cfg: wave w owns tiles w, w + NW, ..)
-    static constexpr int THREADS = NW * 64;
-    static constexpr int KFC = feat_kfc<F16>();
-    static constexpr int ROWB = KF_R * 64;                   // bytes of one sample's x in T_data = of one blob slot
-};
-// where the quad of channels 16 * tile + 4g .. + 3 lies in a scratch row / blob slot: piece [fragment][g], as slot_save_kernel lays them out
-template <bool F16> WN_DEV int quad_off(int tile, int g) {
-    if constexpr (F16) return (((tile >> 1) * 4 + g) << 4) + ((tile & 1) << 3);
-    else return (tile * 4 + g) << 4;
-}
-// the rounding of lds_put_tile
-template <bool F16> WN_DEV void put_quad(char* at, floatx4 v) {
-    if constexpr (F16) *(half4*)at = half4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-    else *(floatx4*)at = v;
-}
-WN_DEV int clamp_sample(int y, int A) { return y < 0 ? 0 : y >= A ? A - 1 : y; }
 
 // x_0[k] = embPrev[y[k-2]] + embCur[y[k-1]] (history 128 before the start), tanh when the model says so: the embedding of wavenet_wg.
 // blockIdx.y: request, x: time tile.  Rows at and past n (the padding of the last tile) are zero.
@@ -186,19 +166,6 @@ __global__ __launch_bounds__(256) void prefill_finish_kernel(const PrefillJob* _
     }
 }
 
-// device memory (-> p) or mapped pinned host memory (-> its device-side address); NULL for anything else
-void* storeTarget(void* p) {
-    const int type = pointer_type(p);
-    if (type == hipMemoryTypeDevice || type == hipMemoryTypeManaged) return p;
-    if (type != hipMemoryTypeHost) return NULL;
-    void* d = NULL;
-    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return NULL;
-    }
-    return d;
-}
-
 template <bool F16, int R>
 bool launchLayers(const PrefillModel& m, const PrefillJob* jobs, int count, int maxTiles, float* xf, char* xd0, char* xd1, int rows,
                   hipStream_t stream) {
@@ -232,9 +199,9 @@ bool Prefill::run(const PrefillModel& m, const PrefillReq* reqs, int count, void
     const int rowB = m.R * (m.f16 ? 2 : 4);
     const size_t blobBytes = sizeof(SlotStateHeader) + (size_t)m.ringSlots * rowB;
     if (dst == NULL || ((size_t)dst & 15) != 0 || (stride & 15) != 0 || stride < (long long)blobBytes) return false;
-    char* const first = (char*)storeTarget(dst);
+    char* const first = (char*)store_target(dst);
     const size_t span = (size_t)(count - 1) * (size_t)stride + blobBytes - 16;
-    if (first == NULL || (char*)storeTarget((char*)dst + span) != first + span) return false;
+    if (first == NULL || (char*)store_target((char*)dst + span) != first + span) return false;
     const int W = prefill_window(m.ringSlots);
     std::vector<PrefillJob> jobs(count);
     int maxTiles = 0;

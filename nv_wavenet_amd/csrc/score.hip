@@ -1,0 +1,455 @@
+// score.hip -- the kernels and the host side of wn::Score (score.hpp).  Compiled once: the (R, S) and (S, A) of the built shapes, both precisions.
+#include "score.hpp"
+
+#include <string.h>
+
+#include <vector>
+
+#include "time_tiles.hpp"
+
+// the (R, S, A) the Makefile builds engines for
+#define WN_SCORE_SHAPES(X) X(32, 128, 256) X(64, 128, 256) X(64, 256, 256) X(128, 256, 256) X(64, 128, 512) X(256, 256, 256) X(32, 256, 256) X(128, 256, 1024)
+
+namespace wn {
+
+namespace {
+
+// x_0[t] = embPrev[y[t-2]] + embCur[y[t-1]] (history 128 before the start), tanh when the model says so: as prefill_embed_kernel.
+// blockIdx.y: request, x: time tile.  Rows at and past n (the padding of the last tile) are zero.
+template <bool F16>
+__global__ __launch_bounds__(256) void score_embed_kernel(const ScoreJob* __restrict__ jobs, int R, int A, const void* __restrict__ embPrevV,
+                                                          const void* __restrict__ embCurV, int tanhEmbed, float* __restrict__ xf,
+                                                          char* __restrict__ xd) {
+    using elem = typename Prec<F16>::elem;
+    using quad = typename Prec<F16>::quad;
+    const ScoreJob jb = jobs[blockIdx.y];
+    const int tile0 = blockIdx.x;
+    if (tile0 >= jb.tiles) return;
+    const elem* const embPrev = (const elem*)embPrevV;
+    const elem* const embCur = (const elem*)embCurV;
+    const int rowB = R * (int)sizeof(elem), quads = R / 4;
+    for (int it = threadIdx.x; it < 16 * quads; it += blockDim.x) {
+        const int q = it % quads, k = tile0 * 16 + it / quads;
+        const int tile = q >> 2, g = q & 3;
+        floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (k < jb.n) {
+            const int yc = k >= 1 ? clamp_sample(jb.y[k - 1], A) : 128, yp = k >= 2 ? clamp_sample(jb.y[k - 2], A) : 128;
+            const floatx4 ep = quad_to_f32(*(const quad*)(embPrev + (size_t)yp * R + q * 4));
+            const floatx4 ec = quad_to_f32(*(const quad*)(embCur + (size_t)yc * R + q * 4));
+            v = ep + ec;
+            if (tanhEmbed) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) v[e] = tanh_t<F16>(v[e]);
+            }
+        }
+        const size_t row = (size_t)jb.row0 + k;
+        *(floatx4*)(xf + row * R + q * 4) = v;
+        put_quad<F16>(xd + row * rowB + quad_off<F16>(tile, g), v);
+    }
+}
+
+// One layer over one time tile of one request: gate pre-activation (bias, conditioning, dilated tap, current tap), gate, residual --
+// prefill_layer_kernel's, operand for operand --, then the skip GEMM on the h fragments: skip[t] (+)= Wskip_l h, fp32, read and
+// written by the same lane.  first: the sum starts here (from zero); last: no residual.  blockIdx.y: request, x: time tile.
+template <bool F16, int R, int S>
+__global__ __launch_bounds__((PCfg<F16, R>::THREADS)) void score_layer_kernel(const ScoreJob* __restrict__ jobs, const ScoreLayer ly, int first, int last,
+                                                                              const char* __restrict__ wblob, size_t waveBytes,
+                                                                              const float* __restrict__ bl, int nCond, float* __restrict__ xf,
+                                                                              const char* __restrict__ xdIn, char* __restrict__ xdOut,
+                                                                              float* __restrict__ skf) {
+    using C = PCfg<F16, R>;
+    using P = Prec<F16>;
+    using frag = typename P::frag;
+    constexpr int NW = C::NW, HTW = C::HTW, KF_R = C::KF_R, KFC = C::KFC, RT = C::RT, ROWB = C::ROWB;
+    constexpr int STW = S / 16 / NW;
+    static_assert((S / 16) % NW == 0, "skip tiles must split evenly over the waves");
+    __shared__ __attribute__((aligned(16))) char hbuf[KF_R * 1024];
+
+    const ScoreJob jb = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= jb.tiles) return;      // (uniform over the workgroup)
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, j = lane & 15;
+    const int r = blockIdx.x * 16 + j;            // this lane's column: the sample
+    const unsigned laneOff = (unsigned)lane * 16u;
+    const char* const wbase = wblob + (size_t)w * waveBytes;
+    const size_t jobRow = (size_t)jb.row0;
+
+    // gate bias
+    floatx4 acc[1][2 * HTW];
+#pragma unroll
+    for (int i = 0; i < HTW; i++) {
+        acc[0][2 * i] = *(const floatx4*)(bl + (w + NW * i) * 16 + g * 4);
+        acc[0][2 * i + 1] = *(const floatx4*)(bl + (w + NW * i + RT) * 16 + g * 4);
+    }
+    // + Wcond c: feature column t; columns past n - 1 (the padding of the last tile) repeat the last sample
+    {
+        frag cf[1][KFC];
+        feature_frags<F16, KFC>(jb.x, jb.precision, jb.cStride, jb.tStride, r < jb.n ? r : jb.n - 1, nCond, g, cf[0]);
+        gemm_direct<F16, 1, 2 * HTW, KFC>(wbase + (size_t)ly.cond * 1024, laneOff, acc, cf);
+    }
+    // + Wprev x_l[t - d]: zero before the start, as at a start from silence
+    const char* const inJob = xdIn + jobRow * ROWB;
+    {
+        frag xp[1][KF_R];
+        const int rp = r - ly.d;
+#pragma unroll
+        for (int kf = 0; kf < KF_R; kf++) {
+            frag v = {};
+            if (rp >= 0) v = *(const frag*)(inJob + (size_t)rp * ROWB + (kf * 4 + g) * 16);
+            xp[0][kf] = v;
+        }
+        gemm_direct<F16, 1, 2 * HTW, KF_R>(wbase + (size_t)ly.prev * 1024, laneOff, acc, xp);
+    }
+    // + Wcur x_l[t]
+    {
+        frag xb[1][KF_R];
+#pragma unroll
+        for (int kf = 0; kf < KF_R; kf++) xb[0][kf] = *(const frag*)(inJob + (size_t)r * ROWB + (kf * 4 + g) * 16);
+        gemm_direct<F16, 1, 2 * HTW, KF_R>(wbase + (size_t)ly.cur * 1024, laneOff, acc, xb);
+    }
+    // gate -> h as B fragments
+#pragma unroll
+    for (int i = 0; i < HTW; i++) lds_put_tile<F16>(hbuf, w + NW * i, lane, gate4<F16>(acc[0][2 * i], acc[0][2 * i + 1]));
+    __syncthreads();
+    frag hb[1][KF_R];
+    lds_get_frags<F16, KF_R>(hbuf, lane, hb[0]);
+    // residual: (Bres + x) + Wres h -> x_{l+1}[t], the running residual in fp32 (read again by this lane only) and the operand in T_data
+    if (!last) {
+        float* const xrow = xf + (jobRow + r) * R;
+        floatx4 xa[1][HTW];
+#pragma unroll
+        for (int i = 0; i < HTW; i++)
+            xa[0][i] = *(const floatx4*)(bl + 2 * R + (w + NW * i) * 16 + g * 4) + *(const floatx4*)(xrow + (w + NW * i) * 16 + g * 4);
+        gemm_direct<F16, 1, HTW, KF_R>(wbase + (size_t)ly.res * 1024, laneOff, xa, hb);
+        char* const orow = xdOut + (jobRow + r) * ROWB;
+#pragma unroll
+        for (int i = 0; i < HTW; i++) {
+            const int tile = w + NW * i;
+            *(floatx4*)(xrow + tile * 16 + g * 4) = xa[0][i];
+            put_quad<F16>(orow + quad_off<F16>(tile, g), xa[0][i]);
+        }
+    }
+    // skip[t] (+)= Wskip_l h: the engine's accumulator, kept in memory between the layers (fp32: nothing is rounded on the way)
+    float* const srow = skf + (jobRow + r) * S;
+    floatx4 sk[1][STW];
+#pragma unroll
+    for (int i = 0; i < STW; i++) {
+        floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (!first) v = *(const floatx4*)(srow + (w + NW * i) * 16 + g * 4);
+        sk[0][i] = v;
+    }
+    gemm_direct<F16, 1, STW, KF_R>(wbase + (size_t)ly.skip * 1024, laneOff, sk, hb);
+#pragma unroll
+    for (int i = 0; i < STW; i++) *(floatx4*)(srow + (w + NW * i) * 16 + g * 4) = sk[0][i];
+}
+
+// ---- head ------------------------------------------------------------------------------------------------------------------
+constexpr int kScoreLdsMax = 80 * 1024;      // two head workgroups share a CU's 160 KiB
+template <bool F16, int NW, int S, int A, int TT> struct HCfg {
+    static constexpr int TPF = Prec<F16>::TPF;
+    static constexpr int ST = S / 16, AT = A / 16, STW = ST / NW, ATW = AT / NW, KF_S = ST / TPF, KF_A = AT / TPF;
+    static constexpr int THREADS = NW * 64;
+    static constexpr int LPU = 4 * NW, RPL = A / LPU;       // softmax lanes per sample, logits per lane (as Cfg)
+    static constexpr int LROW = A + 4;                      // padded logits row (floats)
+    static constexpr int SKBUF = TT * KF_S * 1024, ZSBUF = TT * KF_A * 1024, LGBUF = TT * 16 * LROW * 4;
+    // the logits take the place of the two exchange images (a barrier between the last zs read and the first logit write)
+    static constexpr int LDS = SKBUF + ZSBUF > LGBUF ? SKBUF + ZSBUF : LGBUF;
+    static constexpr bool FITS = LDS <= kScoreLdsMax && TT * ATW * 4 <= 128;      // ... and the logits' accumulators leave room for operands
+};
+// Time tiles of 16 samples per head workgroup: Wzs and Wza are read from L2 once per workgroup, so once per TT tiles.  Two where
+// they fit (LDS, accumulators), else one; WN_SCORE_HEAD_TILES asks for 1, 2 or 4.  Measured at C3 fp16, 256 requests x 2 048
+// samples, the whole pass: 10.90 / 10.46 / 10.75 ms with 1 / 2 / 4 (LABNOTES.md, "Scoring").
+template <bool F16, int NW, int S, int A> constexpr int score_head_tiles() {
+    constexpr int want = WN_SCORE_HEAD_TILES > 0 ? WN_SCORE_HEAD_TILES : 2;
+    if constexpr (want >= 4 && HCfg<F16, NW, S, A, 4>::FITS) return 4;
+    else if constexpr (want >= 2 && HCfg<F16, NW, S, A, 2>::FITS) return 2;
+    else return 1;
+}
+
+// acc[bt][mt] += W(tile mt) * b[bt] with the weight fragments loaded on the spot (fragment order of gemm()) and the B fragments read
+// from their LDS image as they are needed
+template <bool F16, int BT, int MT, int KF>
+WN_DEV void gemm_direct_ldsb(const char* src, unsigned laneOff, floatx4 (&acc)[BT][MT], const char* bimg, int lane) {
+    using frag = typename Prec<F16>::frag;
+    constexpr int G = MT >= 4 ? 4 : MT, UK = KF <= 16 ? KF : 8;      // (the long K loops of A = 1024 stay loops)
+#pragma unroll
+    for (int mg = 0; mg < MT / G; mg++)
+#pragma unroll UK
+        for (int kf = 0; kf < KF; kf++) {
+            frag b[BT];
+#pragma unroll
+            for (int bt = 0; bt < BT; bt++) b[bt] = *(const frag*)(bimg + (((bt * KF + kf) * 64 + lane) << 4));
+#pragma unroll
+            for (int mi = 0; mi < G; mi++) {
+                const frag a = *(const frag*)(src + (size_t)((mg * KF + kf) * G + mi) * 1024 + laneOff);
+#pragma unroll
+                for (int bt = 0; bt < BT; bt++) acc[bt][mg * G + mi] = mma(a, b[bt], acc[bt][mg * G + mi]);
+            }
+        }
+}
+
+constexpr float kLn2 = 0.693147180559945309417f;
+// log softmax of one logit: z' - m' - log2(sum) in the exponent's units (mneg = -m * scale, as softmax_pick forms it), then * ln 2
+WN_DEV float log_softmax1(float z, float scale, float mneg, float l2sum) { return (__builtin_fmaf(z, scale, mneg) - l2sum) * kLn2; }
+
+// The head over TT time tiles of one request: relu(skip + sum of the skip biases) -> Zs = relu(Bzs + Wzs .) -> Za = Bza + Wza . ->
+// log softmax(Za / T), the picked row's to logp and (when asked for) all of them to rows.  blockIdx.y: request, x: group of TT tiles.
+template <bool F16, int NW, int S, int A, int TT>
+__global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head_kernel(const ScoreJob* __restrict__ jobs, const char* __restrict__ wblob,
+                                                                                        size_t waveBytes, unsigned headZs, unsigned headZa,
+                                                                                        const float* __restrict__ bias, int biasL, int skipBiasAt,
+                                                                                        int L, const float* __restrict__ skf) {
+    using H = HCfg<F16, NW, S, A, TT>;
+    constexpr int STW = H::STW, ATW = H::ATW, KF_S = H::KF_S, KF_A = H::KF_A, LPU = H::LPU, RPL = H::RPL, LROW = H::LROW;
+    static_assert(H::ST % NW == 0 && H::AT % NW == 0 && RPL % 4 == 0, "tiles must split evenly over the waves");
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    char* const skbuf = lds;
+    char* const zsbuf = lds + H::SKBUF;
+    float* const lgbuf = (float*)lds;
+
+    const ScoreJob jb = jobs[blockIdx.y];
+    const int tile0 = blockIdx.x * TT;
+    if (tile0 >= jb.tiles) return;      // (uniform over the workgroup)
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, j = lane & 15;
+    const unsigned laneOff = (unsigned)lane * 16u;
+    const char* const wbase = wblob + (size_t)w * waveBytes;
+    const float* const headBias = bias + (size_t)L * biasL;      // Bzs[A], Bza[A]
+
+    // relu(skip + (Bskip_0 + ... + Bskip_{L-1})): the biases summed in layer order, as wavenet_wg folds them
+    floatx4 sbs[STW];
+#pragma unroll
+    for (int i = 0; i < STW; i++) {
+        const float* const at = bias + skipBiasAt + (w + NW * i) * 16 + g * 4;
+        floatx4 run = *(const floatx4*)at;
+        for (int l = 1; l < L; l++) run += *(const floatx4*)(at + (size_t)l * biasL);
+        sbs[i] = run;
+    }
+#pragma unroll
+    for (int bt = 0; bt < TT; bt++) {
+        // (a group's tiles past the request's last repeat it: computed, never written)
+        const int tile = tile0 + bt < jb.tiles ? tile0 + bt : jb.tiles - 1;
+        const float* const srow = skf + ((size_t)jb.row0 + tile * 16 + j) * S;
+#pragma unroll
+        for (int i = 0; i < STW; i++) {
+            floatx4 v = *(const floatx4*)(srow + (w + NW * i) * 16 + g * 4) + sbs[i];
+#pragma unroll
+            for (int r = 0; r < 4; r++) v[r] = __builtin_fmaxf(v[r], 0.f);
+            lds_put_tile<F16>(skbuf + bt * KF_S * 1024, w + NW * i, lane, v);
+        }
+    }
+    __syncthreads();
+    {
+        floatx4 zs[TT][ATW];
+#pragma unroll
+        for (int bt = 0; bt < TT; bt++)
+#pragma unroll
+            for (int i = 0; i < ATW; i++) zs[bt][i] = *(const floatx4*)(headBias + (w + NW * i) * 16 + g * 4);
+        gemm_direct_ldsb<F16, TT, ATW, KF_S>(wbase + (size_t)headZs * 1024, laneOff, zs, skbuf, lane);
+#pragma unroll
+        for (int bt = 0; bt < TT; bt++)
+#pragma unroll
+            for (int i = 0; i < ATW; i++) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) zs[bt][i][r] = __builtin_fmaxf(zs[bt][i][r], 0.f);
+                lds_put_tile<F16>(zsbuf + bt * KF_A * 1024, w + NW * i, lane, zs[bt][i]);
+            }
+    }
+    __syncthreads();
+    floatx4 za[TT][ATW];
+#pragma unroll
+    for (int bt = 0; bt < TT; bt++)
+#pragma unroll
+        for (int i = 0; i < ATW; i++) za[bt][i] = *(const floatx4*)(headBias + A + (w + NW * i) * 16 + g * 4);
+    gemm_direct_ldsb<F16, TT, ATW, KF_A>(wbase + (size_t)headZa * 1024, laneOff, za, zsbuf, lane);
+    __syncthreads();      // every wave is done with the exchange images: the logits take their place
+    // logits -> LDS [sample][row] (row stride padded by 4 floats: conflict-free b128 writes)
+#pragma unroll
+    for (int bt = 0; bt < TT; bt++)
+#pragma unroll
+        for (int i = 0; i < ATW; i++) *(floatx4*)(lgbuf + (bt * 16 + j) * LROW + (w + NW * i) * 16 + g * 4) = za[bt][i];
+    __syncthreads();
+
+    // ---- log softmax: LPU lanes per sample, RPL consecutive rows per lane; maximum, exp2 and sum as softmax_pick does them ----
+    const int su = tid / LPU, sq = tid % LPU;
+#pragma unroll
+    for (int bt = 0; bt < TT; bt++) {
+        const float* const lrow = lgbuf + (bt * 16 + su) * LROW + sq * RPL;
+        float m = lrow[0];
+        for (int i = 0; i < RPL / 4; i++) {
+            const floatx4 v = *(const floatx4*)(lrow + i * 4);
+#pragma unroll
+            for (int r = 0; r < 4; r++) m = __builtin_fmaxf(m, v[r]);
+        }
+        m = group_reduce_f<LPU>(m, [](float a, float b) { return __builtin_fmaxf(a, b); });
+        const float scale = jb.scale, mneg = -m * scale;
+        float lsum = 0.f;
+        for (int i = 0; i < RPL / 4; i++) {
+            const floatx4 v = *(const floatx4*)(lrow + i * 4);
+#pragma unroll
+            for (int r = 0; r < 4; r++) lsum += __builtin_amdgcn_exp2f(__builtin_fmaf(v[r], scale, mneg));
+        }
+        // the group's total as softmax_pick forms it: inclusive scan of the lane sums, the largest prefix sum
+        float incl = lsum;
+        {
+            float up = dpp_f<0x111>(incl);
+            if (sq >= 1) incl += up;
+            up = dpp_f<0x112>(incl);
+            if (sq >= 2) incl += up;
+            if (LPU >= 8) {
+                up = dpp_f<0x114>(incl);
+                if (sq >= 4) incl += up;
+            }
+            if (LPU >= 16) {
+                up = dpp_f<0x118>(incl);
+                if (sq >= 8) incl += up;
+            }
+        }
+        const float total = group_reduce_f<LPU>(incl, [](float a, float b) { return __builtin_fmaxf(a, b); });
+        const float l2sum = __builtin_log2f(total);
+        const int k = (tile0 + bt) * 16 + su;
+        if (tile0 + bt < jb.tiles && k < jb.n) {      // nothing for the padding columns
+            if (sq == 0) {
+                const int y = clamp_sample(jb.y[k], A);
+                jb.logp[k] = log_softmax1(lgbuf[(bt * 16 + su) * LROW + y], scale, mneg, l2sum);
+            }
+            if (jb.rows != nullptr) {
+                float* const out = jb.rows + (size_t)k * A + sq * RPL;
+                for (int i = 0; i < RPL / 4; i++) {
+                    const floatx4 v = *(const floatx4*)(lrow + i * 4);
+                    *(floatx4*)(out + i * 4) = floatx4{log_softmax1(v[0], scale, mneg, l2sum), log_softmax1(v[1], scale, mneg, l2sum),
+                                                       log_softmax1(v[2], scale, mneg, l2sum), log_softmax1(v[3], scale, mneg, l2sum)};
+                }
+            }
+        }
+    }
+}
+
+constexpr int score_nw(int R) { return R / 16 >= 4 ? 4 : R / 16; }
+
+template <bool F16, int R, int S, int A>
+bool launchScore(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, float* xf, char* xd0, char* xd1, float* skf,
+                 hipStream_t stream) {
+    using C = PCfg<F16, R>;
+    constexpr int NW = score_nw(R), TT = score_head_tiles<F16, NW, S, A>();
+    using H = HCfg<F16, NW, S, A, TT>;
+    static_assert(H::FITS, "the head does not fit a CU");
+    const auto head = score_head_kernel<F16, NW, S, A, TT>;
+    static const bool ldsOk = hipFuncSetAttribute((const void*)head, hipFuncAttributeMaxDynamicSharedMemorySize, H::LDS) == hipSuccess;
+    if (!ldsOk) return false;
+    hipLaunchKernelGGL((score_embed_kernel<F16>), dim3(maxTiles, count), dim3(256), 0, stream, jobs, R, A, m.embPrev, m.embCur, m.tanhEmbed, xf, xd0);
+    if (hipGetLastError() != hipSuccess) return false;
+    char* in = xd0;
+    char* out = xd1;
+    const int L = m.numLayers;
+    for (int l = 0; l < L; l++) {
+        hipLaunchKernelGGL((score_layer_kernel<F16, R, S>), dim3(maxTiles, count), dim3(C::THREADS), 0, stream, jobs, m.layers[l], l == 0 ? 1 : 0,
+                           l == L - 1 ? 1 : 0, (const char*)m.wblob, m.waveStreamFrags * 1024, m.bias + (size_t)l * m.biasL, m.nCond, xf,
+                           (const char*)in, out, skf);
+        if (hipGetLastError() != hipSuccess) return false;
+        char* const t = in;
+        in = out;
+        out = t;
+    }
+    hipLaunchKernelGGL(head, dim3((maxTiles + TT - 1) / TT, count), dim3(H::THREADS), H::LDS, stream, jobs, (const char*)m.wblob,
+                       m.waveStreamFrags * 1024, m.headZs, m.headZa, m.bias, m.biasL, 3 * R, L, (const float*)skf);
+    return hipGetLastError() == hipSuccess;
+}
+
+long long paddedSamples(int n) { return ((long long)n + 15) & ~15LL; }
+
+}  // namespace
+
+Score::~Score() {
+    if (m_scratch) gpuErrChk(hipFree(m_scratch));
+    if (m_jobs) gpuErrChk(hipFree(m_jobs));
+}
+
+bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count) {
+    if (m.nCond <= 0 || reqs == NULL || count < 1 || count > 65535) return false;
+    bool shape = false;
+#define WN_SCORE_IS(RR, SS, AA) shape = shape || (m.R == RR && m.S == SS && m.A == AA);
+    WN_SCORE_SHAPES(WN_SCORE_IS)
+#undef WN_SCORE_IS
+    if (!shape) return false;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        const ScoreReq& q = reqs[i];
+        if (q.n < 1 || q.y == NULL || q.x == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
+            !temperature_ok(q.temperature) || !is_device_ptr(q.y) || !is_device_ptr(q.x))
+            return false;
+        if (q.logp == NULL || ((size_t)q.logp & 3) != 0) return false;
+        char* const lp = (char*)store_target(q.logp);
+        const size_t span = (size_t)(q.n - 1) * sizeof(float);
+        if (lp == NULL || (char*)store_target((char*)q.logp + span) != lp + span) return false;
+        if (q.rows != NULL && (((size_t)q.rows & 15) != 0 || !is_device_ptr(q.rows) || !is_device_ptr(q.rows + (size_t)q.n * m.A - 1))) return false;
+        total += paddedSamples(q.n);
+        if (total > score_max_samples(m.f16, m.R, m.S)) return false;
+    }
+    return true;
+}
+
+bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream) {
+    if (!acceptable(m, reqs, count)) return false;
+    std::vector<ScoreJob> jobs(count);
+    int maxTiles = 0;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        const ScoreReq& q = reqs[i];
+        ScoreJob& jb = jobs[i];
+        memset(&jb, 0, sizeof(jb));
+        jb.y = q.y;
+        jb.x = q.x;
+        jb.cStride = q.cStride;
+        jb.tStride = q.tStride;
+        jb.logp = (float*)store_target(q.logp);
+        jb.rows = q.rows;
+        jb.row0 = total;
+        jb.n = q.n;
+        jb.tiles = (int)(paddedSamples(q.n) / 16);
+        jb.precision = q.precision;
+        jb.scale = temperature_scale(q.temperature);
+        total += paddedSamples(q.n);
+        if (jb.tiles > maxTiles) maxTiles = jb.tiles;
+    }
+    // scratch, [total padded samples] each: the fp32 running residual, two T_data images of x, the fp32 skip sum
+    const int rowB = m.R * (m.f16 ? 2 : 4);
+    const size_t cells = (size_t)total, need = cells * score_row_bytes(m.f16, m.R, m.S);
+    if (need > m_scratchBytes || count > m_jobCap) {
+        gpuErrChk(hipDeviceSynchronize());      // (an earlier call may still be using what is replaced)
+        if (need > m_scratchBytes) {
+            if (m_scratch) gpuErrChk(hipFree(m_scratch));
+            m_scratch = NULL;
+            m_scratchBytes = 0;
+            gpuErrChk(hipMalloc((void**)&m_scratch, need));
+            m_scratchBytes = need;
+        }
+        if (count > m_jobCap) {
+            if (m_jobs) gpuErrChk(hipFree(m_jobs));
+            gpuErrChk(hipMalloc((void**)&m_jobs, 2 * (size_t)count * sizeof(ScoreJob)));
+            m_stage.make(2, (size_t)count * sizeof(ScoreJob));
+            m_jobCap = count;
+        }
+    }
+    float* const xf = (float*)m_scratch;
+    char* const xd0 = m_scratch + cells * m.R * 4;
+    char* const xd1 = xd0 + cells * rowB;
+    float* const skf = (float*)(xd1 + cells * rowB);
+    // the requests through pinned staging, two halves used by alternate calls (as prefill stages its requests)
+    ScoreJob* const dev = m_jobs + (size_t)m_stage.at() * m_jobCap;
+    void* const host = m_stage.acquire();
+    memcpy(host, jobs.data(), (size_t)count * sizeof(ScoreJob));
+    gpuErrChk(hipMemcpyAsync(dev, host, (size_t)count * sizeof(ScoreJob), hipMemcpyHostToDevice, stream));
+    m_stage.release(stream);
+
+    bool ok = false;
+#define WN_SCORE_CASE(RR, SS, AA)                                                                                              \
+    if (m.R == RR && m.S == SS && m.A == AA)                                                                                   \
+        ok = m.f16 ? launchScore<true, RR, SS, AA>(m, dev, count, maxTiles, xf, xd0, xd1, skf, stream)                         \
+                   : launchScore<false, RR, SS, AA>(m, dev, count, maxTiles, xf, xd0, xd1, skf, stream);
+    WN_SCORE_SHAPES(WN_SCORE_CASE)
+#undef WN_SCORE_CASE
+    return ok;
+}
+
+}  // namespace wn

@@ -398,6 +398,17 @@ int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, vo
                 "device or pinned memory, stride %lld a multiple of 16, at least %zu)\n", count, stride, e->slots().stateBytes());
     return got;
 }
+// ---- scoring: per-sample log-likelihoods from a time-parallel pass (additive within ABI 7) ------------------------------------------
+int nvw_score_max_samples(nvw_engine* e) { return e->scoreMaxSamples(); }
+int nvw_score_samples(nvw_engine* e, const nvw_score_req* reqs, int count, void* stream) {
+    const int got = e->scoreSamples((const wn::ScoreReq*)reqs, count, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_score_samples: refused, nothing written (nvw_set_conditioning_weights first; %d requests of 1 .. 65535; every n "
+                ">= 1, y and x in device memory, precision 32 or 16, positive strides, temperature in [2^-10, 2^10]; logp device or pinned "
+                "memory, rows NULL or 16-byte aligned device memory; at most %d samples, each n rounded up to 16)\n", count,
+                e->scoreMaxSamples());
+    return got;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

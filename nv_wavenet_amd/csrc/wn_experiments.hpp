@@ -40,6 +40,9 @@
 #ifndef WN_HEADREGS4
 #define WN_HEADREGS4 0       // ... four tiles per workgroup: the whole head is streamed (428 - 440 registers without it)
 #endif
+#ifndef WN_SCORE_HEAD_TILES
+#define WN_SCORE_HEAD_TILES 0  // score_head_kernel: time tiles of 16 samples per workgroup (0: the measured choice, two -- score.hip: score_head_tiles --; else 1, 2 or 4, capped by what fits)
+#endif
 #ifndef WN_ZS_B_REGS
 #define WN_ZS_B_REGS 4096    // wavenet_wg head: ... of the A x S GEMM (4096: always in registers)
 #endif

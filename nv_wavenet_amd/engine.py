@@ -23,6 +23,10 @@ assert SLOT_SAVED.itemsize == 16
 PREFILL_REQ = np.dtype({"names": ["y", "n", "x", "precision", "c_stride", "t_stride", "uid", "temperature"],
                         "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<u4", "<f4"],
                         "offsets": [0, 8, 16, 24, 32, 40, 48, 52], "itemsize": 56})
+# ... nvw_score_req of nvw_score_samples
+SCORE_REQ = np.dtype({"names": ["y", "n", "x", "precision", "c_stride", "t_stride", "temperature", "logp", "rows"],
+                      "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<f4", "<u8", "<u8"],
+                      "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64], "itemsize": 72})
 
 
 class Impl:
@@ -667,6 +671,44 @@ class WavenetEngine:
         if got != n or n == 0:
             raise ValueError("nvw_prefill_states refused %d requests" % n)
         return out[:n]
+
+    # ---- scoring: per-sample log-likelihoods from a time-parallel pass (include/nv_wavenet_c.h, "SCORING") ----
+    def scoreMaxSamples(self):
+        """The largest sum of n, each rounded up to a multiple of 16, that one scoreSamples call accepts; 0 without conditioning weights."""
+        return int(lib.nvw_score_max_samples(self._h))
+
+    def scoreSamples(self, requests, rows=False, stream=None):
+        """Per-sample log-likelihoods with one set of layer launches: requests = [(y, x, temperature), ...] with y the samples (1-D
+        contiguous int32 CUDA tensor, n >= 1 values, clamped into 0 .. A-1) and x the utterance's features (CUDA tensor
+        [n_cond][>= n], float32 or float16, any strides).  Returns a list of float32 CUDA tensors [n]: logp[t] = log softmax(Za_t /
+        temperature)[y[t]] with Za_t the logits of sample t of a column started from silence and fed y[0 .. t); with rows=True a
+        list of pairs (logp, rows [n][A]): the whole log-distribution of every step.  Asynchronous on `stream`; the tensors of
+        `requests` must stay alive until it has run.  Works in and outside slot mode, touches no column.  ValueError when refused
+        (nothing written, nothing launched): see nvw_score_samples."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        if not getattr(self, "nCond", 0):
+            raise ValueError("scoring needs setConditioningWeights")
+        reqs = np.zeros(max(n, 1), dtype=SCORE_REQ)
+        out = []
+        for i, (y, x, T) in enumerate(requests):
+            if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous() or not y.is_cuda or y.numel() < 1:
+                raise ValueError("samples to score are a contiguous 1-D int32 CUDA tensor of at least one value")
+            assert hasattr(x, "data_ptr") and x.is_cuda and x.dim() == 2 and x.size(0) == self.nCond, "features: CUDA tensors [n_cond][samples]"
+            bits = {torch.float32: 32, torch.float16: 16}.get(x.dtype)
+            assert bits, "features must be float32 or float16"
+            if y.numel() > x.size(1):
+                raise ValueError("%d samples against features of %d" % (y.numel(), x.size(1)))
+            logp = torch.empty(y.numel(), dtype=torch.float32, device="cuda")
+            full = torch.empty((y.numel(), self.A), dtype=torch.float32, device="cuda") if rows else None
+            reqs[i] = (y.data_ptr(), y.numel(), x.data_ptr(), bits, x.stride(0), x.stride(1), float(T), logp.data_ptr(),
+                       full.data_ptr() if rows else 0)
+            out.append((logp, full) if rows else logp)
+        got = lib.nvw_score_samples(self._h, reqs.ctypes.data, n, stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_score_samples refused %d requests" % n)
+        return out
 
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):

@@ -519,6 +519,70 @@ class NVWaveNetEngine(NVWaveNet):
             if prime is not None:
                 e.setPrime(None)             # (... or while a column is primed)
 
+    def score(self, x, cond_weight, cond_bias, samples, lengths=None, temperature=None, return_rows=False):
+        """Per-sample log-likelihoods of known samples under the model: x = the upsampled features
+        [batch][n_cond][samples] on the GPU and cond_weight / cond_bias as for infer_features; samples = an integer tensor
+        [batch][n], n <= x.size(2) (values clamped into 0 .. A-1); lengths: None (all n), or `batch` values in 0 .. n.  Returns
+        logp [batch][n] float32 on the GPU, logp[b][t] = log softmax(Za_t / T_b)[samples[b][t]] (natural logarithm) with Za_t the
+        logits of utterance b at sample t when it started from silence and was fed samples[b][:t]; zero past an utterance's length.
+        The negative log-likelihood of utterance b is -logp[b].sum(), its bits per sample -logp[b].mean() / ln 2.
+        temperature: None (1), a float, or `batch` floats, each finite and in [2^-10, 2^10].  return_rows: also rows
+        [batch][n][A], the whole log-distribution of every step (zero past a length).  One time-parallel pass per call of the
+        engine (nvw_score_samples); a batch whose padded lengths exceed the engine's scoreMaxSamples() is split into several calls,
+        ValueError for a single utterance that does not fit, and for a bad shape, length or temperature."""
+        from .slots import check_temperature
+        batch_size, sample_count = x.size(0), x.size(2)
+        if samples.dim() != 2 or samples.size(0) != batch_size or not 0 < samples.size(1) <= sample_count or samples.is_floating_point():
+            raise ValueError("samples: an integer tensor [batch = %d][1 .. %d], got %s" % (batch_size, sample_count, tuple(samples.shape)))
+        n = samples.size(1)
+        lengths = [n] * batch_size if lengths is None else [int(k) for k in lengths]
+        if len(lengths) != batch_size or not all(0 <= k <= n for k in lengths):
+            raise ValueError("lengths: %d values in 0 .. %d" % (batch_size, n))
+        if temperature is None or isinstance(temperature, (int, float)):
+            temps = [check_temperature(1.0 if temperature is None else temperature)] * batch_size
+        else:
+            temps = [check_temperature(t) for t in temperature]
+            if len(temps) != batch_size:
+                raise ValueError("%d temperatures for a batch of %d" % (len(temps), batch_size))
+        # (the pass does not depend on the kernel organisation: an engine that generation already keeps for this batch serves)
+        capacity = -(-sample_count // self.BUCKET) * self.BUCKET
+        kept = [k for k in self._engines if k[:2] == (batch_size, capacity)]
+        e = self._engine(batch_size, sample_count, kept[-1][2] if kept else Impl.AUTO)
+        dev = x.device
+        key = (cond_weight.data_ptr(), cond_weight._version, cond_bias.data_ptr(), cond_bias._version)
+        if getattr(e, "_cond_w_key", None) != key:
+            e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
+            e._cond_w_key = key
+        cap = e.scoreMaxSamples()
+        y = samples.to(device=dev, dtype=torch.int32).contiguous()
+        logp = torch.zeros((batch_size, n), dtype=torch.float32, device=dev)
+        rows = torch.zeros((batch_size, n, self.A), dtype=torch.float32, device=dev) if return_rows else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def call(group):
+            got = e.scoreSamples([(y[b, :lengths[b]], x[b], temps[b]) for b in group], rows=return_rows, stream=stream)
+            for b, r in zip(group, got):
+                if return_rows:
+                    logp[b, :lengths[b]], rows[b, :lengths[b]] = r
+                else:
+                    logp[b, :lengths[b]] = r
+
+        group, used = [], 0
+        for b in range(batch_size):
+            padded = -(-lengths[b] // 16) * 16
+            if padded == 0:
+                continue
+            if padded > cap:
+                raise ValueError("utterance %d: %d samples, one scoring pass takes %d (scoring in time chunks is not offered)" % (b, lengths[b], cap))
+            if used + padded > cap or len(group) == 65535:
+                call(group)
+                group, used = [], 0
+            group.append(b)
+            used += padded
+        if group:
+            call(group)
+        return (logp, rows) if return_rows else logp
+
     def _infer_packed(self, frags, batch_size, implementation, seed, return_audio, generator):
         sample_count = frags.size(0) - 1
         e = self._engine(batch_size, sample_count, implementation)

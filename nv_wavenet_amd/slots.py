@@ -339,6 +339,18 @@ class SlotStream:
         state._prefilled_from = y      # (read by the pass in stream order: kept with the state)
         return state
 
+    def score(self, features, samples, temperature=1.0):
+        """log softmax(Za_t / temperature)[samples[t]] for every t < n of the utterance `features` [n_cond][>= n] fed the known
+        `samples` (an integer tensor [n]) from silence: a float32 CUDA tensor [n] from the engine's time-parallel scoring pass
+        (WavenetEngine.scoreSamples).  Nothing is queued, no column is touched: the stream's steps deliver what
+        they deliver without it.  Complete once the engine's stream has run the pass."""
+        assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
+        temperature = check_temperature(temperature)
+        y = check_prime(samples, features.size(1))
+        if y is None:
+            raise ValueError("score needs samples")
+        return self.engine.scoreSamples([(y if y.is_cuda else y.cuda(), features, temperature)])[0]
+
     def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they

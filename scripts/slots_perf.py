@@ -68,8 +68,18 @@ nvw_slots_save_list -- against nvw_prefill_states on the same primes and feature
 sets of blobs are equal bytes.  Prints one JSON line with the per-round milliseconds, the medians, the ratio, the 4 W against W
 prefill time and the verdict on the one fixed bar: one request at n = W is faster prefilled than sequential.  With --parent-lib
 it then prints the --parent comparison of the plain step (nothing on that path changes: a guard, not a goal).
+--score times scoring, C3 fp16, one process: nvw_score_samples for 1 and 256 requests at n = 2 048 and 24 000, with
+and without rows (a set of requests over nvw_score_max_samples goes in as many calls as it needs, like NVWaveNetEngine.score), and
+beside it -- with --parent-lib -- the only way the parent commit can teacher-force: the same samples forced through primed columns
+of the PARENT's library (nvw_slot_start + nvw_slot_prime for every request, steps of the window up to sample n).  Prints one JSON
+line with the per-round milliseconds, the medians, the time per sample of both, the fraction of the fp16 MFMA peak the 256-request
+cases reach (useful multiply-adds of the model over the dense peak of 2.5 PFLOP/s) and the verdict on the one fixed bar: scoring
+256 utterances costs less than forcing them.  With --parent-lib it then prints nvw_prefill_states of both libraries (256 requests
+at n = W) and the --parent comparison of the plain step: nothing on their paths changes, so both are guards, held to the spread
+the parent itself shows.
 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --score [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
@@ -105,6 +115,7 @@ def main():
     ap.add_argument("--temperature", action="store_true", help="time the slot step of the parent commit, of this one at T = 1 and at mixed T")
     ap.add_argument("--prime", action="store_true", help="time the slot step of the parent commit, of this one without a prime and with every column primed")
     ap.add_argument("--prefill", action="store_true", help="time the sequential prime against nvw_prefill_states, 1 and 256 requests")
+    ap.add_argument("--score", action="store_true", help="time nvw_score_samples against forcing the samples through primed columns of the parent")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
@@ -115,6 +126,12 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.score:
+        print(json.dumps(time_score(args, w, Wc, bc)), flush=True)
+        if not args.parent_lib:
+            return
+        print(json.dumps(time_prefill_against_parent(args, w, Wc, bc)), flush=True)
+        args.parent = True
     if args.prefill:
         print(json.dumps(time_prefill(args, w, Wc, bc)), flush=True)
         if not args.parent_lib:
@@ -410,6 +427,169 @@ def time_prefill(args, w, Wc, bc):
     one = res["cases"]["1 x %d" % res["W"]]
     res["one_request_at_W_faster_prefilled"] = bool(one["median_prefill_ms"] < one["median_sequential_ms"])
     return res
+
+
+def _c_engine(path, w, Wc, bc, columns, window):
+    """(library, engine handle) of the C3 fp16 engine through the C ABI of the library at `path` (this commit's or a parent's)"""
+    import ctypes as C
+    import bench
+    sh = bench.HEAD
+    vp, ci, ll = C.c_void_p, C.c_int, C.c_longlong
+    sigs = {"nvw_create_ex": (vp, [ci] * 11), "nvw_destroy": (None, [vp]), "nvw_set_embeddings": (None, [vp, vp, vp]),
+            "nvw_set_layer_weights": (None, [vp, ci] + [vp] * 7), "nvw_set_out_weights": (None, [vp] * 5),
+            "nvw_set_conditioning_weights": (ci, [vp, vp, vp, ci]), "nvw_set_selector_seed": (None, [vp, C.c_ulonglong]),
+            "nvw_slots_begin": (ci, [vp, ci]), "nvw_slot_start": (ci, [vp, ci, vp, ci, ll, ll, ci, C.c_uint]),
+            "nvw_slots_step": (ci, [vp, ci, vp, vp, vp]), "nvw_slots_end": (None, [vp]), "nvw_slot_prime": (ci, [vp, ci, vp, ci]),
+            "nvw_prefill_window": (ci, [vp]), "nvw_prefill_states": (ci, [vp, vp, ci, vp, ll, vp]), "nvw_slot_state_bytes": (C.c_size_t, [vp])}
+    h = C.CDLL(path)
+    for name, (res, argt) in sigs.items():
+        getattr(h, name).restype, getattr(h, name).argtypes = res, argt
+    a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
+    e = h.nvw_create_ex(sh.R, sh.S, sh.A, 16, sh.L, sh.maxD, columns, window, 0, 1, 0)
+    assert e, path
+    h.nvw_set_embeddings(e, a(w["embP"]), a(w["embC"]))
+    for l in range(sh.L):
+        h.nvw_set_layer_weights(e, l, *[a(w[k][l]) for k in ("Wprev", "Wcur", "Bh", "Wres", "Bres", "Wskip", "Bskip")])
+    h.nvw_set_out_weights(e, a(w["Wzs"]), a(w["Bzs"]), a(w["Wza"]), a(w["Bza"]))
+    assert h.nvw_set_conditioning_weights(e, a(Wc), a(bc), bench.N_COND)
+    h.nvw_set_selector_seed(e, 5)
+    return h, e
+
+
+def time_score(args, w, Wc, bc):
+    """The --score measurement (module docstring)."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import SCORE_REQ
+    sh = bench.HEAD
+    window = 4096
+    peak = 2.5e15                                   # dense fp16 MFMA, FLOP/s
+    macs = sh.L * (2 * 2 * sh.R * sh.R + 2 * sh.R * bench.N_COND + sh.R * sh.S) + (sh.L - 1) * sh.R * sh.R + sh.A * sh.S + sh.A * sh.A
+    g = torch.Generator(device="cuda")
+    g.manual_seed(13)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    s = torch.cuda.current_stream().cuda_stream
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "rounds": args.rounds, "window": window,
+           "multiply_adds_per_sample": macs, "device": torch.cuda.get_device_name(0), "cases": {}}
+    for count in (1, 256):
+        e = bench.build_engine(w, count, window)
+        e.setConditioningWeights(Wc, bc)
+        cap = e.scoreMaxSamples()
+        res["score_max_samples"] = cap
+        parent = _c_engine(args.parent_lib, w, Wc, bc, count, window) if args.parent_lib else None
+        lengths = (2048, 24000)
+        top = max(lengths)
+        src = torch.randn(bench.N_COND, top + count, device="cuda", generator=g).half()
+        xs = [src[:, b:b + top] for b in range(count)]                      # a request's features: the shared ones, shifted by b
+        ys = torch.randint(0, sh.A, (count, top), device="cuda", generator=g, dtype=torch.int32)
+        logp = torch.empty((count, top), dtype=torch.float32, device="cuda")
+        for n in lengths:
+            per_call = max(1, min(count, cap // (-(-n // 16) * 16)))
+            rows = torch.empty((per_call, n, sh.A), dtype=torch.float32, device="cuda")      # (of one call: the next one writes over it)
+            calls = []
+            for with_rows in (False, True):
+                groups = []
+                for b0 in range(0, count, per_call):
+                    reqs = np.zeros(per_call, dtype=SCORE_REQ)
+                    k = min(per_call, count - b0)
+                    for i in range(k):
+                        b = b0 + i
+                        reqs[i] = (ys[b].data_ptr(), n, xs[b].data_ptr(), 16, xs[b].stride(0), xs[b].stride(1), 1.0, logp[b].data_ptr(),
+                                   rows[i].data_ptr() if with_rows else 0)
+                    groups.append((reqs, k))
+                calls.append(groups)
+
+            def score(groups):
+                for reqs, k in groups:
+                    assert lib.nvw_score_samples(e._h, reqs.ctypes.data, k, s) == k
+
+            def forced():
+                h, pe = parent
+                assert h.nvw_slots_begin(pe, window)
+                for b in range(count):
+                    assert h.nvw_slot_start(pe, b, xs[b].data_ptr(), 16, xs[b].stride(0), xs[b].stride(1), n, b)
+                    assert h.nvw_slot_prime(pe, b, ys[b].data_ptr(), n)
+                done = 0
+                while done < n:
+                    c = min(window, n - done)
+                    assert h.nvw_slots_step(pe, c, None, None, s)
+                    done += c
+
+            paths = [("score", lambda: score(calls[0])), ("score_rows", lambda: score(calls[1]))] + ([("parent_forced", forced)] if parent else [])
+            ms = {name: [] for name, _ in paths}
+            for r in range(args.rounds + 1):                                # (round 0 warms every path up: allocations, first launches)
+                for name, fn in (paths if r % 2 else paths[::-1]):
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                    fn()
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    if r:
+                        ms[name].append(ev[0].elapsed_time(ev[1]))
+                    if name == "parent_forced":
+                        parent[0].nvw_slots_end(parent[1])
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            case = {"calls": len(calls[0]), "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+                    "median_ms": {k: round(v, 3) for k, v in med.items()},
+                    "us_per_sample": {k: round(1e3 * v / (count * n), 4) for k, v in med.items()},
+                    "fraction_of_fp16_mfma_peak": round(2.0 * macs * count * n / (1e-3 * med["score"]) / peak, 4)}
+            if parent:
+                case["parent_forced_over_score"] = round(med["parent_forced"] / med["score"], 2)
+            res["cases"]["%d x %d" % (count, n)] = case
+            del rows
+        if parent:
+            parent[0].nvw_destroy(parent[1])
+        e.close()
+        torch.cuda.empty_cache()
+    if args.parent_lib:
+        res["scoring_256_costs_less_than_forcing_them"] = bool(all(c["median_ms"]["score"] < c["median_ms"]["parent_forced"]
+                                                                    for k, c in res["cases"].items() if k.startswith("256 ")))
+    return res
+
+
+def time_prefill_against_parent(args, w, Wc, bc):
+    """nvw_prefill_states of the parent's library and of this one, 256 requests at n = W, alternating rounds (a guard: nothing on
+    that path changes)."""
+    import torch
+    import bench
+    from nv_wavenet_amd import _lib
+    from nv_wavenet_amd.engine import PREFILL_REQ
+    sh = bench.HEAD
+    count, window = 256, 4096
+    g = torch.Generator(device="cuda")
+    g.manual_seed(17)
+    libs = {"parent": _c_engine(args.parent_lib, w, Wc, bc, count, window), "here": _c_engine(_lib.LIB_PATH, w, Wc, bc, count, window)}
+    W = libs["here"][0].nvw_prefill_window(libs["here"][1])
+    src = torch.randn(bench.N_COND, W + count, device="cuda", generator=g).half()
+    ys = torch.randint(0, sh.A, (count, W), device="cuda", generator=g, dtype=torch.int32)
+    nbytes = int(libs["here"][0].nvw_slot_state_bytes(libs["here"][1]))
+    out = {k: torch.empty((count, nbytes), dtype=torch.uint8, device="cuda") for k in libs}
+    reqs = np.zeros(count, dtype=PREFILL_REQ)
+    for b in range(count):
+        x = src[:, b:b + W]
+        reqs[b] = (ys[b].data_ptr(), W, x.data_ptr(), 16, x.stride(0), x.stride(1), b, 1.0)
+    s = torch.cuda.current_stream().cuda_stream
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = {k: [] for k in libs}
+    for r in range(args.rounds + 1):
+        for name in (list(libs) if r % 2 else list(libs)[::-1]):
+            h, e = libs[name]
+            torch.cuda.synchronize()
+            ev[0].record()
+            assert h.nvw_prefill_states(e, reqs.ctypes.data, count, out[name].data_ptr(), nbytes, s) == count
+            ev[1].record()
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(ev[0].elapsed_time(ev[1]))
+    assert torch.equal(out["parent"], out["here"]), "the prefilled blobs of the two libraries differ"
+    for h, e in libs.values():
+        h.nvw_destroy(e)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread = (max(ms["parent"]) - min(ms["parent"])) / med["parent"]
+    return {"prefill_256_at_W": W, "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()}, "median_ms": {k: round(v, 3) for k, v in med.items()},
+            "parent_spread": round(spread, 4), "here_vs_parent": round(med["here"] / med["parent"], 4),
+            "within_twice_the_parent_spread": bool(med["here"] / med["parent"] <= 1.0 + 2.0 * spread), "blobs_equal": True}
 
 
 def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
