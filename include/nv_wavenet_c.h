@@ -501,8 +501,8 @@ int nvw_slot_primed(nvw_engine* e, int slot);
  *                       them.  Needs nvw_set_conditioning_weights.  Returns count; 0 with nothing written: no conditioning weights,
  *                       count outside 1 .. 65535, an n < 1, a temperature outside [2^-10, 2^10], a bad precision, pointer,
  *                       alignment or stride.
- * Mel frames (a prefill that upsamples) and lockstep engines taking a prefilled state are not offered; the per-sample
- * log-likelihoods of a prime are a pass of their own (SCORING, below). */
+ * A prefill from mel frames is nvw_prefill_states_mel (FROM MEL FRAMES, below).  Lockstep engines taking a prefilled state are not
+ * offered; the per-sample log-likelihoods of a prime are a pass of their own (SCORING, below). */
 typedef struct {
     const int* y;
     int n;
@@ -535,8 +535,8 @@ int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, vo
  *                          0 with nothing written and nothing launched: no conditioning weights, count outside 1 .. 65535, an
  *                          n < 1, a temperature outside [2^-10, 2^10], a bad precision or stride, y or x not in device memory, a
  *                          misaligned or unreachable output, a total over nvw_score_max_samples.
- * Scoring from mel frames, in time chunks with carried state (utterances past the cap), and on the packed, in-place and chain
- * conditioning paths is not offered. */
+ * Scoring from mel frames is nvw_score_samples_mel (FROM MEL FRAMES, below).  Scoring in time chunks with carried state (utterances
+ * past the cap), and on the packed, in-place and chain conditioning paths is not offered. */
 typedef struct {
     const int* y;
     int n;
@@ -549,6 +549,67 @@ typedef struct {
 } nvw_score_req;
 int nvw_score_max_samples(nvw_engine* e);
 int nvw_score_samples(nvw_engine* e, const nvw_score_req* reqs, int count, void* stream);
+
+/* PREFILL AND SCORING FROM MEL FRAMES: A TIME-PARALLEL UPSAMPLING PASS (additive within ABI 7).  The two passes above read upsampled
+ * features; the path that ships end to end (nvw_generate_stream, nvw_slot_start_mel) takes mel frames.  This pass upsamples by
+ * REQUEST and SAMPLE RANGE: for frames mel[c * c_stride + f * f_stride] (`precision`-bit floats in device memory, n_cond channels,
+ * `frames` of them written) and a range [first_sample, first_sample + count) it writes
+ *     dst[(t - first_sample) * row + c] = b[c] + sum_{j < m} sum_ci mel[ci][f - j] W[ci][c][j * stride + r],   t = f * stride + r,
+ * in the engine's precision, row = nvw_upsample_row_elems elements, channels >= n_cond exactly zero -- BIT FOR BIT what
+ * nvw_upsample_features stores for that utterance and sample, and what a mel column's feed computes: the pass reads the engine's own
+ * operand table and bias (no second copy of the weights) and sums in the same order.  Frames max(0, first_sample / stride - (m - 1))
+ * .. (first_sample + count - 1) / stride are read, in place, and no others.  One launch per call.
+ *   nvw_upsample_row_elems  16 * ceil(n_cond / 16); 0 without nvw_set_upsampling.
+ *   nvw_upsample_requests   `count` requests (1 .. 65535); dst: count rows, 16-byte aligned device memory.  The rows are features as
+ *                           nvw_prefill_states / nvw_score_samples / nvw_slot_start take them with precision = the engine's,
+ *                           c_stride = 1, t_stride = row (for a range that starts at first_sample: x = dst - first_sample * row
+ *                           elements).  Asynchronous on `stream`; mel and dst stay alive until it has run.
+ *   nvw_prefill_states_mel  nvw_prefill_states from frames: the samples [t0, n) of every request are upsampled into an engine-owned
+ *                           scratch (grown on demand, (n - t0) * row elements per request, freed with the engine), then the prefill
+ *                           launches run on those rows.  The blob EQUALS, BYTE FOR BYTE, what nvw_slot_start_mel,
+ *                           nvw_slot_set_temperature, nvw_slot_prime(y, n), steps up to local sample n and nvw_slot_save produce.
+ *   nvw_score_samples_mel   nvw_score_samples from frames, range [0, n): accepts what nvw_score_max_samples accepts.  The feature
+ *                           rows are an allocation of their own, row * sizeof(T_data) bytes per sample (160 B in fp16, 320 B in fp32
+ *                           at 80 channels): at most nvw_score_max_samples * that, beside the 1 GiB of the scoring scratch.
+ * Each returns count, or 0 with nothing written and nothing launched (every request check of both passes comes before the upsampling is
+ * queued; should the feature pass itself then fail -- its scratch cannot be allocated, a launch is rejected -- the two mel entries
+ * return 0 with the engine-owned rows already written, and nothing of the caller's): everything nvw_prefill_states / nvw_score_samples refuse, and
+ * no nvw_set_upsampling, mel not in device memory, a non-positive stride, frames * stride short of the range (< first_sample + count,
+ * or < n), first_sample < 0 or count < 1, dst not 16-byte aligned device memory.  All three work inside and outside slot mode, touch
+ * no ring, column or session, and share the engine's scratch: issue them on one stream, or order them. */
+typedef struct {
+    const void* mel;
+    int precision;
+    long long c_stride, f_stride;
+    int frames;
+    int first_sample, count;
+    void* dst;
+} nvw_upsample_req;
+typedef struct {
+    const int* y;
+    int n;
+    const void* mel;
+    int precision;
+    long long c_stride, f_stride;
+    int frames;
+    unsigned uid;
+    float temperature;
+} nvw_prefill_mel_req;
+typedef struct {
+    const int* y;
+    int n;
+    const void* mel;
+    int precision;
+    long long c_stride, f_stride;
+    int frames;
+    float temperature;
+    float* logp;
+    float* rows;
+} nvw_score_mel_req;
+int nvw_upsample_row_elems(nvw_engine* e);
+int nvw_upsample_requests(nvw_engine* e, const nvw_upsample_req* reqs, int count, void* stream);
+int nvw_prefill_states_mel(nvw_engine* e, const nvw_prefill_mel_req* reqs, int count, void* dst, long long stride, void* stream);
+int nvw_score_samples_mel(nvw_engine* e, const nvw_score_mel_req* reqs, int count, void* stream);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

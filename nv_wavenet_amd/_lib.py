@@ -110,6 +110,10 @@ SIGNATURES = {
     "nvw_prefill_states": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong, C.c_void_p]),
     "nvw_score_max_samples": (C.c_int, [C.c_void_p]),
     "nvw_score_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nvw_upsample_row_elems": (C.c_int, [C.c_void_p]),
+    "nvw_upsample_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nvw_prefill_states_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong, C.c_void_p]),
+    "nvw_score_samples_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),
     "nvw_pinned_free": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),

@@ -64,6 +64,10 @@ struct nvw_engine {
     virtual int prefillStates(const wn::PrefillReq*, int, void*, long long, hipStream_t) = 0;
     virtual int scoreMaxSamples() = 0;
     virtual int scoreSamples(const wn::ScoreReq*, int, hipStream_t) = 0;
+    virtual int upsampleRowElems() = 0;
+    virtual int upsampleRequests(const wn::MelTimeReq*, int, hipStream_t) = 0;
+    virtual int prefillStatesMel(const wn::PrefillMelReq*, int, void*, long long, hipStream_t) = 0;
+    virtual int scoreSamplesMel(const wn::ScoreMelReq*, int, hipStream_t) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
@@ -101,6 +105,32 @@ static_assert(sizeof(nvw_score_req) == sizeof(wn::ScoreReq) && offsetof(nvw_scor
               offsetof(nvw_score_req, temperature) == offsetof(wn::ScoreReq, temperature) &&
               offsetof(nvw_score_req, logp) == offsetof(wn::ScoreReq, logp) && offsetof(nvw_score_req, rows) == offsetof(wn::ScoreReq, rows),
               "nvw_score_req is wn::ScoreReq");
+static_assert(sizeof(nvw_upsample_req) == sizeof(wn::MelTimeReq) && offsetof(nvw_upsample_req, mel) == offsetof(wn::MelTimeReq, mel) &&
+              offsetof(nvw_upsample_req, precision) == offsetof(wn::MelTimeReq, precision) &&
+              offsetof(nvw_upsample_req, c_stride) == offsetof(wn::MelTimeReq, cStride) &&
+              offsetof(nvw_upsample_req, f_stride) == offsetof(wn::MelTimeReq, fStride) &&
+              offsetof(nvw_upsample_req, frames) == offsetof(wn::MelTimeReq, frames) &&
+              offsetof(nvw_upsample_req, first_sample) == offsetof(wn::MelTimeReq, first) &&
+              offsetof(nvw_upsample_req, count) == offsetof(wn::MelTimeReq, count) && offsetof(nvw_upsample_req, dst) == offsetof(wn::MelTimeReq, dst),
+              "nvw_upsample_req is wn::MelTimeReq");
+static_assert(sizeof(nvw_prefill_mel_req) == sizeof(wn::PrefillMelReq) && offsetof(nvw_prefill_mel_req, y) == offsetof(wn::PrefillMelReq, y) &&
+              offsetof(nvw_prefill_mel_req, n) == offsetof(wn::PrefillMelReq, n) && offsetof(nvw_prefill_mel_req, mel) == offsetof(wn::PrefillMelReq, mel) &&
+              offsetof(nvw_prefill_mel_req, precision) == offsetof(wn::PrefillMelReq, precision) &&
+              offsetof(nvw_prefill_mel_req, c_stride) == offsetof(wn::PrefillMelReq, cStride) &&
+              offsetof(nvw_prefill_mel_req, f_stride) == offsetof(wn::PrefillMelReq, fStride) &&
+              offsetof(nvw_prefill_mel_req, frames) == offsetof(wn::PrefillMelReq, frames) &&
+              offsetof(nvw_prefill_mel_req, uid) == offsetof(wn::PrefillMelReq, uid) &&
+              offsetof(nvw_prefill_mel_req, temperature) == offsetof(wn::PrefillMelReq, temperature),
+              "nvw_prefill_mel_req is wn::PrefillMelReq");
+static_assert(sizeof(nvw_score_mel_req) == sizeof(wn::ScoreMelReq) && offsetof(nvw_score_mel_req, y) == offsetof(wn::ScoreMelReq, y) &&
+              offsetof(nvw_score_mel_req, n) == offsetof(wn::ScoreMelReq, n) && offsetof(nvw_score_mel_req, mel) == offsetof(wn::ScoreMelReq, mel) &&
+              offsetof(nvw_score_mel_req, precision) == offsetof(wn::ScoreMelReq, precision) &&
+              offsetof(nvw_score_mel_req, c_stride) == offsetof(wn::ScoreMelReq, cStride) &&
+              offsetof(nvw_score_mel_req, f_stride) == offsetof(wn::ScoreMelReq, fStride) &&
+              offsetof(nvw_score_mel_req, frames) == offsetof(wn::ScoreMelReq, frames) &&
+              offsetof(nvw_score_mel_req, temperature) == offsetof(wn::ScoreMelReq, temperature) &&
+              offsetof(nvw_score_mel_req, logp) == offsetof(wn::ScoreMelReq, logp) && offsetof(nvw_score_mel_req, rows) == offsetof(wn::ScoreMelReq, rows),
+              "nvw_score_mel_req is wn::ScoreMelReq");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -180,6 +210,12 @@ struct EngineImpl : nvw_engine {
     }
     int scoreMaxSamples() override { return eng.scoreMaxSamples(); }
     int scoreSamples(const wn::ScoreReq* reqs, int count, hipStream_t s) override { return eng.scoreSamples(reqs, count, s); }
+    int upsampleRowElems() override { return eng.upsampleRowElems(); }
+    int upsampleRequests(const wn::MelTimeReq* reqs, int count, hipStream_t s) override { return eng.upsampleRequests(reqs, count, s); }
+    int prefillStatesMel(const wn::PrefillMelReq* reqs, int count, void* dst, long long stride, hipStream_t s) override {
+        return eng.prefillStatesMel(reqs, count, dst, stride, s);
+    }
+    int scoreSamplesMel(const wn::ScoreMelReq* reqs, int count, hipStream_t s) override { return eng.scoreSamplesMel(reqs, count, s); }
     wn::SlotSession& slots() override { return eng.slots(); }
 };
 

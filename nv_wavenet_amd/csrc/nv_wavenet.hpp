@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "gpu_check.hpp"
+#include "mel_time.hpp"
 #include "prefill.hpp"
 #include "score.hpp"
 #include "slots_session.hpp"
@@ -148,6 +149,7 @@ protected:
     wn::TemperatureTable m_temps;
     wn::PrimeTable m_prime;           // the lockstep primes (slots_prime.hpp)
     wn::Score m_score;                // scratch and staging of scoreSamples (score.hpp), nothing until the first call
+    wn::MelTime m_melTime;            // staging and feature rows of upsampleRequests / prefillStatesMel / scoreSamplesMel (mel_time.hpp), nothing until the first call
     wn::Prefill m_prefill;            // scratch and staging of prefillStates (prefill.hpp), nothing until the first call
     // slot mode (slots_session.hpp): made at the end of the constructor, when the facts it is given are known
     std::unique_ptr<wn::SlotSession> m_slots;
@@ -1247,6 +1249,14 @@ public:
     // precision, pointer, alignment or stride.
     int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported) return 0;
+        wn::PrefillModel m = prefillModel();
+        if (m_featDirty) buildFeatStream(stream);
+        m.wblob = m_wblobF;
+        m.bias = m_biasF;
+        return m_prefill.run(m, reqs, count, dst, stride, stream) ? count : 0;
+    }
+    // (without the weight stream and the bias table: buildFeatStream may still replace them)
+    wn::PrefillModel prefillModel() const {
         const int L = m_numLayers;
         wn::PrefillModel m;
         m.f16 = F16;
@@ -1257,7 +1267,9 @@ public:
         m.ringSlots = m_ringSlots;
         m.nCond = m_nCond;
         m.tanhEmbed = m_tanhEmbed ? 1 : 0;
+        m.wblob = NULL;
         m.waveStreamFrags = CF::waveStreamFrags(L);
+        m.bias = NULL;
         m.biasL = C::BIAS_L;
         m.embPrev = m_embedPrev;
         m.embCur = m_embedCur;
@@ -1269,10 +1281,7 @@ public:
             off += d;
             d = dN;
         }
-        if (m_featDirty) buildFeatStream(stream);
-        m.wblob = m_wblobF;
-        m.bias = m_biasF;
-        return m_prefill.run(m, reqs, count, dst, stride, stream) ? count : 0;
+        return m;
     }
     // ---- scoring: per-sample log-likelihoods from a time-parallel pass (beyond the reference; score.hpp) ---------------
     // the largest sum of n, each rounded up to 16, that one scoreSamples call accepts (its scratch stays under wn::kScoreScratchCap);
@@ -1287,6 +1296,15 @@ public:
     // pointer, a misaligned or unreachable output, a total over scoreMaxSamples().
     int scoreSamples(const wn::ScoreReq* reqs, int count, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported) return 0;
+        wn::ScoreModel m = scoreModel();
+        // (checked before anything is queued: a refused call launches nothing, the stream rebuild included)
+        if (!wn::Score::acceptable(m, reqs, count)) return 0;
+        if (m_featDirty) buildFeatStream(stream);
+        m.wblob = m_wblobF;
+        m.bias = m_biasF;
+        return m_score.run(m, reqs, count, stream) ? count : 0;
+    }
+    wn::ScoreModel scoreModel() const {
         const int L = m_numLayers;
         wn::ScoreModel m;
         m.f16 = F16;
@@ -1296,9 +1314,11 @@ public:
         m.numLayers = L;
         m.nCond = m_nCond;
         m.tanhEmbed = m_tanhEmbed ? 1 : 0;
+        m.wblob = NULL;
         m.waveStreamFrags = CF::waveStreamFrags(L);
         m.headZs = (unsigned)(CF::headOffsetFrags(L) + CF::O_ZS);
         m.headZa = (unsigned)(CF::headOffsetFrags(L) + CF::O_ZA);
+        m.bias = NULL;
         m.biasL = C::BIAS_L;
         m.embPrev = m_embedPrev;
         m.embCur = m_embedCur;
@@ -1309,12 +1329,88 @@ public:
             d <<= 1;
             if (d > m_maxDilation) d = 1;
         }
-        // (checked before anything is queued: a refused call launches nothing, the stream rebuild included)
-        if (!wn::Score::acceptable(m, reqs, count)) return 0;
+        return m;
+    }
+    // ---- prefill and scoring from mel frames: a time-parallel upsampling pass (beyond the reference; mel_time.hpp) ----
+    // elements of a row of upsampled features: 16 * ceil(nCond / 16); 0 without setUpsampling
+    int upsampleRowElems() const { return m_upStride > 0 ? wn::mel_time_row(m_nCond) : 0; }
+    wn::MelTimeModel melTimeModel() const { return wn::MelTimeModel{F16, m_nCond, m_upWindow, m_upStride, m_upTab, m_upBias}; }
+    // For request i < count the upsampled features of samples [first, first + count) of its frames, as rows of upsampleRowElems()
+    // T_data elements (channels >= nCond zero) -- bit for bit what upsampleFeatures stores for that utterance and sample --, from ONE
+    // launch, asynchronously on `stream`.  Frames max(0, first / stride - (m - 1)) .. (first + count - 1) / stride are read, in
+    // place.  Returns count; 0 with nothing written or launched: no setUpsampling, count outside 1 .. 65535, mel not in device
+    // memory, a bad precision or stride, frames * stride short of the range, first < 0, count < 1, dst not 16-byte aligned device
+    // memory.
+    int upsampleRequests(const wn::MelTimeReq* reqs, int count, hipStream_t stream = 0) {
+        if (m_upStride <= 0) return 0;
+        return m_melTime.run(melTimeModel(), reqs, count, stream) ? count : 0;
+    }
+    // prefillStates from frames: samples [t0, n) of every request are upsampled into the engine's own rows, and the prefill launches
+    // read those -- each job's base is the address row t0 would have if the rows started at sample 0, since the kernels index by
+    // the absolute sample.  The blob is byte for byte the one slotStartMel, slotPrime(y, n), steps to n and slotSave produce.
+    int prefillStatesMel(const wn::PrefillMelReq* reqs, int count, void* dst, long long stride, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
+        wn::PrefillModel pm = prefillModel();
+        const wn::MelTimeModel mm = melTimeModel();
+        const int W = wn::prefill_window(m_ringSlots);
+        const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
+        std::vector<wn::MelTimeReq> ur(count);
+        std::vector<wn::PrefillReq> pr(count);
+        std::vector<size_t> at(count);
+        size_t bytes = 0;
+        for (int i = 0; i < count; i++) {
+            const wn::PrefillMelReq& q = reqs[i];
+            if (q.n < 1) return 0;
+            const int t0 = wn::prefill_first(q.n, W);
+            ur[i] = wn::MelTimeReq{q.mel, q.precision, q.cStride, q.fStride, q.frames, t0, q.n - t0, NULL};
+            pr[i] = wn::PrefillReq{q.y, q.n, NULL, F16 ? 16 : 32, 1, (long long)wn::mel_time_row(m_nCond), q.uid, q.temperature};
+            at[i] = bytes;
+            bytes += (size_t)(q.n - t0) * rowB;
+        }
+        // (checked before anything is queued: a refused call launches nothing)
+        if (!wn::MelTime::acceptable(mm, ur.data(), count, true) || !wn::Prefill::acceptable(pm, pr.data(), count, dst, stride, true)) return 0;
+        char* const rows = m_melTime.rows(bytes);
+        for (int i = 0; i < count; i++) {
+            ur[i].dst = rows + at[i];
+            pr[i].x = (const void*)((uintptr_t)(rows + at[i]) - (uintptr_t)ur[i].first * rowB);
+        }
         if (m_featDirty) buildFeatStream(stream);
-        m.wblob = m_wblobF;
-        m.bias = m_biasF;
-        return m_score.run(m, reqs, count, stream) ? count : 0;
+        pm.wblob = m_wblobF;
+        pm.bias = m_biasF;
+        if (!m_melTime.run(mm, ur.data(), count, stream, true)) return 0;
+        return m_prefill.run(pm, pr.data(), count, dst, stride, stream, true) ? count : 0;
+    }
+    // scoreSamples from frames: samples [0, n) of every request are upsampled into the engine's own rows (an allocation beside the
+    // scoring scratch: upsampleRowElems() * sizeof(T_data) bytes per sample, at most scoreMaxSamples() of them), and the scoring
+    // launches read those.  Accepts what scoreMaxSamples() accepts.
+    int scoreSamplesMel(const wn::ScoreMelReq* reqs, int count, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
+        wn::ScoreModel sm = scoreModel();
+        const wn::MelTimeModel mm = melTimeModel();
+        const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
+        std::vector<wn::MelTimeReq> ur(count);
+        std::vector<wn::ScoreReq> sr(count);
+        std::vector<size_t> at(count);
+        size_t bytes = 0;
+        for (int i = 0; i < count; i++) {
+            const wn::ScoreMelReq& q = reqs[i];
+            if (q.n < 1) return 0;
+            ur[i] = wn::MelTimeReq{q.mel, q.precision, q.cStride, q.fStride, q.frames, 0, q.n, NULL};
+            sr[i] = wn::ScoreReq{q.y, q.n, NULL, F16 ? 16 : 32, 1, (long long)wn::mel_time_row(m_nCond), q.temperature, q.logp, q.rows};
+            at[i] = bytes;
+            bytes += (size_t)q.n * rowB;
+        }
+        if (!wn::MelTime::acceptable(mm, ur.data(), count, true) || !wn::Score::acceptable(sm, sr.data(), count, true)) return 0;
+        char* const rows = m_melTime.rows(bytes);
+        for (int i = 0; i < count; i++) {
+            ur[i].dst = rows + at[i];
+            sr[i].x = rows + at[i];
+        }
+        if (m_featDirty) buildFeatStream(stream);
+        sm.wblob = m_wblobF;
+        sm.bias = m_biasF;
+        if (!m_melTime.run(mm, ur.data(), count, stream, true)) return 0;
+        return m_score.run(sm, sr.data(), count, stream, true) ? count : 0;
     }
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to

@@ -193,7 +193,7 @@ Prefill::~Prefill() {
     if (m_jobs) gpuErrChk(hipFree(m_jobs));
 }
 
-bool Prefill::run(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream) {
+bool Prefill::acceptable(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, bool ownX) {
     if (m.nCond <= 0 || reqs == NULL || count < 1 || count > 65535) return false;
     if (m.R != 32 && m.R != 64 && m.R != 128 && m.R != 256) return false;
     const int rowB = m.R * (m.f16 ? 2 : 4);
@@ -202,14 +202,25 @@ bool Prefill::run(const PrefillModel& m, const PrefillReq* reqs, int count, void
     char* const first = (char*)store_target(dst);
     const size_t span = (size_t)(count - 1) * (size_t)stride + blobBytes - 16;
     if (first == NULL || (char*)store_target((char*)dst + span) != first + span) return false;
+    for (int i = 0; i < count; i++) {
+        const PrefillReq& q = reqs[i];
+        if (q.n < 1 || q.y == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
+            !temperature_ok(q.temperature) || !is_device_ptr(q.y))
+            return false;
+        if (!ownX && (q.x == NULL || !is_device_ptr(q.x))) return false;
+    }
+    return true;
+}
+
+bool Prefill::run(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream, bool ownX) {
+    if (!acceptable(m, reqs, count, dst, stride, ownX)) return false;
+    const int rowB = m.R * (m.f16 ? 2 : 4);
+    char* const first = (char*)store_target(dst);
     const int W = prefill_window(m.ringSlots);
     std::vector<PrefillJob> jobs(count);
     int maxTiles = 0;
     for (int i = 0; i < count; i++) {
         const PrefillReq& q = reqs[i];
-        if (q.n < 1 || q.y == NULL || q.x == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
-            !temperature_ok(q.temperature) || !is_device_ptr(q.y) || !is_device_ptr(q.x))
-            return false;
         PrefillJob& jb = jobs[i];
         memset(&jb, 0, sizeof(jb));
         jb.y = q.y;
@@ -218,7 +229,7 @@ bool Prefill::run(const PrefillModel& m, const PrefillReq* reqs, int count, void
         jb.tStride = q.tStride;
         jb.dst = first + (size_t)i * (size_t)stride;
         jb.n = q.n;
-        jb.t0 = (q.n > W ? q.n - W : 0) & ~15;
+        jb.t0 = prefill_first(q.n, W);
         jb.tiles = (q.n - jb.t0 + 15) / 16;
         jb.precision = q.precision;
         jb.uid = q.uid;

@@ -70,6 +70,8 @@ struct PrefillModel {
 
 // samples that determine a state: sum of the dilations + the two history words
 inline int prefill_window(int ringSlots) { return ringSlots + 2; }
+// first sample of the pass over a prime of n: max(0, n - W) rounded down to a tile of 16
+inline int prefill_first(int n, int W) { return (n > W ? n - W : 0) & ~15; }
 
 // The engine-owned side: scratch sized by W (grown on demand), the requests' staging.  Calls of one engine are issued on one
 // stream, or ordered by the caller: they share the scratch.
@@ -78,8 +80,12 @@ public:
     Prefill() {}
     Prefill(const Prefill&) = delete;
     ~Prefill();
+    // what run() refuses, without touching the GPU's queues (wblob and bias of m are not looked at).  ownX: x is a base derived
+    // from the engine's own feature rows (mel_time.hpp) -- possibly in front of the allocation, since the kernels index it by the
+    // absolute sample -- and is not looked at.
+    static bool acceptable(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, bool ownX = false);
     // count blobs to dst + i * stride, asynchronously on `stream`.  false with nothing written or launched: a refused request.
-    bool run(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream);
+    bool run(const PrefillModel& m, const PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream, bool ownX = false);
 
 private:
     char* m_scratch = NULL;

@@ -365,7 +365,7 @@ Score::~Score() {
     if (m_jobs) gpuErrChk(hipFree(m_jobs));
 }
 
-bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count) {
+bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count, bool ownX) {
     if (m.nCond <= 0 || reqs == NULL || count < 1 || count > 65535) return false;
     bool shape = false;
 #define WN_SCORE_IS(RR, SS, AA) shape = shape || (m.R == RR && m.S == SS && m.A == AA);
@@ -375,9 +375,10 @@ bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count) {
     long long total = 0;
     for (int i = 0; i < count; i++) {
         const ScoreReq& q = reqs[i];
-        if (q.n < 1 || q.y == NULL || q.x == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
-            !temperature_ok(q.temperature) || !is_device_ptr(q.y) || !is_device_ptr(q.x))
+        if (q.n < 1 || q.y == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
+            !temperature_ok(q.temperature) || !is_device_ptr(q.y))
             return false;
+        if (!ownX && (q.x == NULL || !is_device_ptr(q.x))) return false;
         if (q.logp == NULL || ((size_t)q.logp & 3) != 0) return false;
         char* const lp = (char*)store_target(q.logp);
         const size_t span = (size_t)(q.n - 1) * sizeof(float);
@@ -389,8 +390,8 @@ bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count) {
     return true;
 }
 
-bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream) {
-    if (!acceptable(m, reqs, count)) return false;
+bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream, bool ownX) {
+    if (!acceptable(m, reqs, count, ownX)) return false;
     std::vector<ScoreJob> jobs(count);
     int maxTiles = 0;
     long long total = 0;

@@ -84,8 +84,9 @@ public:
     ~Score();
     // logp (and rows) of count requests, asynchronously on `stream`.  false with nothing written or launched: a refused request.
     // what run() refuses, without touching the GPU's queues (wblob and bias of m are not looked at)
-    static bool acceptable(const ScoreModel& m, const ScoreReq* reqs, int count);
-    bool run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream);
+    // ownX: x lies in the engine's own feature rows (mel_time.hpp) and is not looked at
+    static bool acceptable(const ScoreModel& m, const ScoreReq* reqs, int count, bool ownX = false);
+    bool run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream, bool ownX = false);
 
 private:
     char* m_scratch = NULL;

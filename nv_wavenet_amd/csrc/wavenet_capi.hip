@@ -409,6 +409,34 @@ int nvw_score_samples(nvw_engine* e, const nvw_score_req* reqs, int count, void*
                 e->scoreMaxSamples());
     return got;
 }
+// ---- prefill and scoring from mel frames: a time-parallel upsampling pass (additive within ABI 7) -----------------------------------
+int nvw_upsample_row_elems(nvw_engine* e) { return e->upsampleRowElems(); }
+int nvw_upsample_requests(nvw_engine* e, const nvw_upsample_req* reqs, int count, void* stream) {
+    const int got = e->upsampleRequests((const wn::MelTimeReq*)reqs, count, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_upsample_requests: refused, nothing written (nvw_set_upsampling first; %d requests of 1 .. 65535; mel in device "
+                "memory, precision 32 or 16, positive strides, first_sample >= 0, count >= 1, frames * stride covering the range; dst 16-byte "
+                "aligned device memory)\n", count);
+    return got;
+}
+int nvw_prefill_states_mel(nvw_engine* e, const nvw_prefill_mel_req* reqs, int count, void* dst, long long stride, void* stream) {
+    const int got = e->prefillStatesMel((const wn::PrefillMelReq*)reqs, count, dst, stride, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_prefill_states_mel: refused, nothing written (nvw_set_conditioning_weights and nvw_set_upsampling first; %d "
+                "requests of 1 .. 65535; every n >= 1, y and mel in device memory, precision 32 or 16, positive strides, frames * stride >= n, "
+                "temperature in [2^-10, 2^10]; dst 16-byte aligned device or pinned memory, stride %lld a multiple of 16, at least %zu)\n",
+                count, stride, e->slots().stateBytes());
+    return got;
+}
+int nvw_score_samples_mel(nvw_engine* e, const nvw_score_mel_req* reqs, int count, void* stream) {
+    const int got = e->scoreSamplesMel((const wn::ScoreMelReq*)reqs, count, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_score_samples_mel: refused, nothing written (nvw_set_conditioning_weights and nvw_set_upsampling first; %d "
+                "requests of 1 .. 65535; every n >= 1, y and mel in device memory, precision 32 or 16, positive strides, frames * stride >= n, "
+                "temperature in [2^-10, 2^10]; logp device or pinned memory, rows NULL or 16-byte aligned device memory; at most %d samples, "
+                "each n rounded up to 16)\n", count, e->scoreMaxSamples());
+    return got;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

@@ -27,6 +27,16 @@ PREFILL_REQ = np.dtype({"names": ["y", "n", "x", "precision", "c_stride", "t_str
 SCORE_REQ = np.dtype({"names": ["y", "n", "x", "precision", "c_stride", "t_stride", "temperature", "logp", "rows"],
                       "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<f4", "<u8", "<u8"],
                       "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64], "itemsize": 72})
+# ... nvw_upsample_req, nvw_prefill_mel_req and nvw_score_mel_req of the entries that take mel frames
+UPSAMPLE_REQ = np.dtype({"names": ["mel", "precision", "c_stride", "f_stride", "frames", "first_sample", "count", "dst"],
+                         "formats": ["<u8", "<i4", "<i8", "<i8", "<i4", "<i4", "<i4", "<u8"],
+                         "offsets": [0, 8, 16, 24, 32, 36, 40, 48], "itemsize": 56})
+PREFILL_MEL_REQ = np.dtype({"names": ["y", "n", "mel", "precision", "c_stride", "f_stride", "frames", "uid", "temperature"],
+                            "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<u4", "<f4"],
+                            "offsets": [0, 8, 16, 24, 32, 40, 48, 52, 56], "itemsize": 64})
+SCORE_MEL_REQ = np.dtype({"names": ["y", "n", "mel", "precision", "c_stride", "f_stride", "frames", "temperature", "logp", "rows"],
+                          "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<f4", "<u8", "<u8"],
+                          "offsets": [0, 8, 16, 24, 32, 40, 48, 52, 56, 64], "itemsize": 72})
 
 
 class Impl:
@@ -708,6 +718,96 @@ class WavenetEngine:
         got = lib.nvw_score_samples(self._h, reqs.ctypes.data, n, stream)
         if got != n or n == 0:
             raise ValueError("nvw_score_samples refused %d requests" % n)
+        return out
+
+    # ---- prefill and scoring from mel frames (include/nv_wavenet_c.h, "FROM MEL FRAMES") ----
+    def upsampleRowElems(self):
+        """Elements of a row of upsampleRequests: 16 * ceil(n_cond / 16); 0 without setUpsampling."""
+        return int(lib.nvw_upsample_row_elems(self._h))
+
+    def _mel_args(self, mel, frames=None):
+        import torch
+        assert hasattr(mel, "data_ptr") and mel.is_cuda and mel.dim() == 2 and mel.size(0) == self.nCond, "mel: a CUDA tensor [n_cond][frames]"
+        bits = {torch.float32: 32, torch.float16: 16}.get(mel.dtype)
+        assert bits, "mel must be float32 or float16"
+        frames = mel.size(1) if frames is None else int(frames)
+        assert 0 <= frames <= mel.size(1), "frames: at most the tensor's"
+        return bits, mel.stride(0), mel.stride(1), frames
+
+    def upsampleRequests(self, requests, stream=None):
+        """Upsampled features by request and sample range, one launch: requests = [(mel, first_sample, count), ...] with mel an
+        utterance's frames (CUDA tensor [n_cond][frames], float32 or float16, any strides).  Returns a list of CUDA tensors
+        [count][upsampleRowElems()] of the engine's dtype: row t - first_sample holds the features of sample t, bit for bit those of
+        setMel + upsampleFeatures, channels >= n_cond zero; rows.t()[:n_cond] is a [n_cond][count] view that prefillStates and
+        scoreSamples take as it is.  Asynchronous on `stream`.  ValueError when refused (nothing written): see nvw_upsample_requests."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        row = self.upsampleRowElems()
+        if not row:
+            raise ValueError("upsampleRequests needs setUpsampling")
+        reqs = np.zeros(max(n, 1), dtype=UPSAMPLE_REQ)
+        out = []
+        for i, (mel, first, count) in enumerate(requests):
+            bits, sc, sf, frames = self._mel_args(mel)
+            if int(count) < 1 or int(first) < 0:
+                raise ValueError("a range is first_sample >= 0, count >= 1")
+            dst = torch.empty((int(count), row), dtype=torch.float16 if self.precision == 16 else torch.float32, device="cuda")
+            reqs[i] = (mel.data_ptr(), bits, sc, sf, frames, int(first), int(count), dst.data_ptr())
+            out.append(dst)
+        got = lib.nvw_upsample_requests(self._h, reqs.ctypes.data, n, stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_upsample_requests refused %d requests" % n)
+        return out
+
+    def prefillStatesMel(self, requests, pinned=False, stream=None, out=None):
+        """prefillStates from frames: requests = [(y, mel, uid, temperature[, frames]), ...] with mel the utterance's frames (CUDA
+        tensor [n_cond][capacity], float32 or float16, any strides) of which the first `frames` (default: all) are written and
+        frames x stride >= len(y).  Row i is byte for byte the blob that slotStartMel(mel, uid) + slotSetTemperature + slotPrime(y),
+        steps up to local sample len(y) and slotSave produce.  Otherwise as prefillStates.  ValueError when refused (nothing
+        written): see nvw_prefill_states_mel."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        if out is None:
+            out = torch.empty((max(n, 1), self.slotStateBytes()), dtype=torch.uint8, device=None if pinned else "cuda", pin_memory=bool(pinned))
+        assert out.dtype == torch.uint8 and out.dim() == 2 and out.stride(1) == 1 and out.size(0) >= n and (out.is_cuda or out.is_pinned()), \
+            "out: a uint8 CUDA or pinned tensor [>= n][stride]"
+        reqs = np.zeros(max(n, 1), dtype=PREFILL_MEL_REQ)
+        for i, rq in enumerate(requests):
+            y, mel, uid, T = rq[:4]
+            if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous() or not y.is_cuda:
+                raise ValueError("a prime is a contiguous 1-D int32 CUDA tensor")
+            bits, sc, sf, frames = self._mel_args(mel, rq[4] if len(rq) > 4 else None)
+            reqs[i] = (y.data_ptr(), y.numel(), mel.data_ptr(), bits, sc, sf, frames, int(uid) & 0xFFFFFFFF, float(T))
+        got = lib.nvw_prefill_states_mel(self._h, reqs.ctypes.data, n, out.data_ptr(), out.stride(0), stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_prefill_states_mel refused %d requests" % n)
+        return out[:n]
+
+    def scoreSamplesMel(self, requests, rows=False, stream=None):
+        """scoreSamples from frames: requests = [(y, mel, temperature[, frames]), ...], mel as for prefillStatesMel.  Returns what
+        scoreSamples returns -- bit for bit what it returns for the upsampled features of those frames.  ValueError when refused
+        (nothing written, nothing launched): see nvw_score_samples_mel."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        if not getattr(self, "nCond", 0):
+            raise ValueError("scoring needs setConditioningWeights")
+        reqs = np.zeros(max(n, 1), dtype=SCORE_MEL_REQ)
+        out = []
+        for i, rq in enumerate(requests):
+            y, mel, T = rq[:3]
+            if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous() or not y.is_cuda or y.numel() < 1:
+                raise ValueError("samples to score are a contiguous 1-D int32 CUDA tensor of at least one value")
+            bits, sc, sf, frames = self._mel_args(mel, rq[3] if len(rq) > 3 else None)
+            logp = torch.empty(y.numel(), dtype=torch.float32, device="cuda")
+            full = torch.empty((y.numel(), self.A), dtype=torch.float32, device="cuda") if rows else None
+            reqs[i] = (y.data_ptr(), y.numel(), mel.data_ptr(), bits, sc, sf, frames, float(T), logp.data_ptr(), full.data_ptr() if rows else 0)
+            out.append((logp, full) if rows else logp)
+        got = lib.nvw_score_samples_mel(self._h, reqs.ctypes.data, n, stream)
+        if got != n or n == 0:
+            raise ValueError("nvw_score_samples_mel refused %d requests" % n)
         return out
 
     # ---- run --------------------------------------------------------------------------------

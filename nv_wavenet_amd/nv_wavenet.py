@@ -530,8 +530,22 @@ class NVWaveNetEngine(NVWaveNet):
         [batch][n][A], the whole log-distribution of every step (zero past a length).  One time-parallel pass per call of the
         engine (nvw_score_samples); a batch whose padded lengths exceed the engine's scoreMaxSamples() is split into several calls,
         ValueError for a single utterance that does not fit, and for a bad shape, length or temperature."""
+        return self._score(x, x.size(2), None, cond_weight, cond_bias, samples, lengths, temperature, return_rows)
+
+    def score_mel(self, mel, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, samples, lengths=None,
+                  temperature=None, return_rows=False):
+        """score() from mel frames: mel = the frames before upsampling [batch][n_cond][frames] on the GPU,
+        upsample_weight / upsample_bias / upsample_stride = the model's `upsample` ConvTranspose1d as for slot_stream; samples = an
+        integer tensor [batch][n], n <= frames x stride.  The engine upsamples every utterance's range itself
+        (nvw_score_samples_mel) -- bit for bit the features of its own lockstep upsampling -- and the result is what score()
+        returns for them, split into calls that fit in the same way."""
+        up = (upsample_weight, upsample_bias, int(upsample_stride))
+        return self._score(mel, mel.size(2) * int(upsample_stride), up, cond_weight, cond_bias, samples, lengths, temperature, return_rows)
+
+    def _score(self, x, sample_count, up, cond_weight, cond_bias, samples, lengths, temperature, return_rows):
+        """score (up None: x holds features) and score_mel (up = upsampling weight, bias, stride: x holds frames)."""
         from .slots import check_temperature
-        batch_size, sample_count = x.size(0), x.size(2)
+        batch_size = x.size(0)
         if samples.dim() != 2 or samples.size(0) != batch_size or not 0 < samples.size(1) <= sample_count or samples.is_floating_point():
             raise ValueError("samples: an integer tensor [batch = %d][1 .. %d], got %s" % (batch_size, sample_count, tuple(samples.shape)))
         n = samples.size(1)
@@ -553,6 +567,11 @@ class NVWaveNetEngine(NVWaveNet):
         if getattr(e, "_cond_w_key", None) != key:
             e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
             e._cond_w_key = key
+        if up is not None:
+            key = (up[0].data_ptr(), up[0]._version, up[1].data_ptr(), up[1]._version, up[2])
+            if getattr(e, "_up_w_key", None) != key or getattr(e, "_up_cond_key", None) != e._cond_w_key:
+                e.setUpsampling(up[0].float().contiguous(), up[1].float().contiguous(), up[2])
+                e._up_w_key, e._up_cond_key = key, e._cond_w_key
         cap = e.scoreMaxSamples()
         y = samples.to(device=dev, dtype=torch.int32).contiguous()
         logp = torch.zeros((batch_size, n), dtype=torch.float32, device=dev)
@@ -560,7 +579,8 @@ class NVWaveNetEngine(NVWaveNet):
         stream = torch.cuda.current_stream(dev).cuda_stream
 
         def call(group):
-            got = e.scoreSamples([(y[b, :lengths[b]], x[b], temps[b]) for b in group], rows=return_rows, stream=stream)
+            reqs = [(y[b, :lengths[b]], x[b], temps[b]) for b in group]
+            got = (e.scoreSamples if up is None else e.scoreSamplesMel)(reqs, rows=return_rows, stream=stream)
             for b, r in zip(group, got):
                 if return_rows:
                     logp[b, :lengths[b]], rows[b, :lengths[b]] = r

@@ -66,6 +66,12 @@ the caller has the forced samples already.
     h = stream.submit(features, prime=delivered, prefill=True)
     state = stream.prefill(features, delivered)         # or the state itself: resume() / resume_many() / to_bytes()
 
+A mel request is prefilled in the same way (nvw_prefill_states_mel): the engine upsamples the samples the state
+depends on from the request's own frames, bit for bit as its feed would have.
+
+    h = stream.submit_mel(mel, prime=delivered, prefill=True)
+    state = stream.prefill_mel(mel, delivered)          # kind "mel"; score_mel(mel, samples) scores from frames likewise
+
 step() waits for its samples, and nothing the host does between steps depends on them: step_async() issues a step and returns
 (DESIGN.md §6e).  The engine delivers each running request's valid samples contiguously into one of two pinned buffers the stream
 owns (nvw_slots_step_ragged) and names them at once -- column, length, offset, whether the request ends --, so the bookkeeping of
@@ -351,6 +357,51 @@ class SlotStream:
             raise ValueError("score needs samples")
         return self.engine.scoreSamples([(y if y.is_cuda else y.cuda(), features, temperature)])[0]
 
+    def _mel_frames(self, mel, frames, final=True):
+        assert mel.dim() == 2, "mel: [n_cond][frames]"
+        n = mel.size(1) if frames is None else int(frames)
+        assert 0 <= n <= mel.size(1) and (n > 0 or not final)
+        return n
+
+    def prefill_mel(self, mel, prime, uid=None, temperature=1.0, frames=None, final=True):
+        """prefill() for a mel utterance (mel [n_cond][capacity], its first `frames` -- default all -- written; final: no more will
+        come): the engine upsamples the samples the state depends on and runs the time-parallel pass on them
+        (WavenetEngine.prefillStatesMel).  Returns a SlotState of kind "mel" with done = n, frames and final
+        recorded, whose blob is byte for byte the one a mel column primed with `prime` saves after it.  ValueError, with nothing
+        counted, when the engine has no upsampling table or the frames written so far do not cover the prime."""
+        stride = getattr(self.engine, "upStride", 0)
+        if not stride or not self.engine.upsampleRowElems():
+            raise ValueError("prefill of a mel request needs setUpsampling")
+        n = self._mel_frames(mel, frames, final)
+        temperature = check_temperature(temperature)
+        prime = check_prime(prime, None)
+        if prime is None:
+            raise ValueError("prefill needs a prime")
+        if prime.numel() > n * stride:
+            raise ValueError("prefill: a prime of %d samples, the %d frames written so far upsample to %d" % (prime.numel(), n, n * stride))
+        if uid is None:
+            uid = self._next_uid
+        y = prime if prime.is_cuda else prime.cuda()
+        blobs = self.engine.prefillStatesMel([(y, mel, int(uid), temperature, n)])
+        self._next_uid = max(self._next_uid, int(uid) + 1)
+        state = SlotState(blobs[0], mel, int(uid), int(y.numel()), "mel", frames=n, final=bool(final), buffer=blobs, row=0, temperature=temperature)
+        state._prefilled_from = y      # (read by the pass in stream order: kept with the state)
+        return state
+
+    def score_mel(self, mel, samples, temperature=1.0, frames=None):
+        """score() for a mel utterance: log softmax(Za_t / temperature)[samples[t]] for every t < n, the features upsampled by the
+        engine from the first `frames` (default all) frames of mel [n_cond][capacity] -- bit for bit what score() returns for the
+        upsampled features (WavenetEngine.scoreSamplesMel).  Nothing is queued, no column is touched."""
+        stride = getattr(self.engine, "upStride", 0)
+        if not stride or not self.engine.upsampleRowElems():
+            raise ValueError("scoring a mel request needs setUpsampling")
+        n = self._mel_frames(mel, frames)
+        temperature = check_temperature(temperature)
+        y = check_prime(samples, n * stride)
+        if y is None:
+            raise ValueError("score needs samples")
+        return self.engine.scoreSamplesMel([(y if y.is_cuda else y.cuda(), mel, temperature, n)])[0]
+
     def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
@@ -385,15 +436,34 @@ class SlotStream:
             self._prime[handle] = prime
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=False):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=None):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
         final: no more will come); returns its handle.  uid, temperature and prime as for submit; the prime of a request that is
-        not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one)."""
-        if prefill:
-            raise ValueError("prefill of a mel request is not offered: the pass reads upsampled features (submit), not frames")
-        assert mel.dim() == 2, "mel: [n_cond][frames]"
-        n = mel.size(1) if frames is None else int(frames)
-        assert 0 <= n <= mel.size(1) and (n > 0 or not final)
+        not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one).
+        prefill (None: the stream's default): True with a prime of n values makes the state behind the prime at once
+        (prefill_mel()) and queues the request as a mel resume at sample n -- its delivery starts there, the samples from n on are
+        bit for bit those of prefill=False, and extend_mel works as for any queued mel request.  ValueError, before anything is
+        queued or counted: the engine has no upsampling table, the frames written so far do not cover the prime, a final
+        request's prime covers the whole utterance.  Without a prime it changes nothing."""
+        if (self._prefill if prefill is None else prefill) and prime is not None:
+            stride = getattr(self.engine, "upStride", 0)
+            if not stride or not self.engine.upsampleRowElems():
+                raise ValueError("prefill of a mel request needs the engine's upsampling table (setUpsampling)")
+            n = self._mel_frames(mel, frames, final)
+            temperature = check_temperature(temperature)
+            prime = check_prime(prime, n * stride if final else None)
+            if prime.numel() > n * stride:
+                raise ValueError("prefill: a prime of %d samples, the %d frames written so far upsample to %d" % (prime.numel(), n, n * stride))
+            if final and prime.numel() >= n * stride:
+                raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), n * stride))
+            state = self.prefill_mel(mel, prime, uid, temperature, n, final)
+            handle = self._next_handle
+            self._next_handle += 1
+            req = self._mel[handle] = [n, bool(final), None, int(state.done)]
+            self._queue.append((handle, mel, int(state.uid), req, state))
+            self._note_temperature(handle, temperature)
+            return handle
+        n = self._mel_frames(mel, frames, final)
         temperature = check_temperature(temperature)
         prime = check_prime(prime, n * self.engine.upStride if final else None)
         handle = self._next_handle

@@ -77,8 +77,16 @@ cases reach (useful multiply-adds of the model over the dense peak of 2.5 PFLOP/
 256 utterances costs less than forcing them.  With --parent-lib it then prints nvw_prefill_states of both libraries (256 requests
 at n = W) and the --parent comparison of the plain step: nothing on their paths changes, so both are guards, held to the spread
 the parent itself shows.
+--prefill-mel and --score-mel time the same two passes fed from mel frames, C3 fp16, window 1024 / stride 256, one
+process: nvw_prefill_states_mel (1 and 256 requests at n = W / 2, W, 4 W, 24 000) and nvw_score_samples_mel (n = 2 048, 24 000)
+beside the feature entries of this commit on rows upsampled beforehand -- the difference is the upsampling's share -- and beside
+nvw_upsample_requests alone; with --parent-lib the primes are also forced through mel columns of the PARENT's library
+(nvw_slot_start_mel + nvw_slot_prime, steps of the window up to sample n), the only way the parent can prime from frames.  The
+results of the paths are checked to be equal bytes.  One JSON line each: median and min .. max of the rounds per path.
 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --prefill-mel [--parent-lib PATH] [--rounds 5]
+    python scripts/slots_perf.py --score-mel [--rounds 5]
     python scripts/slots_perf.py --score [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
@@ -116,6 +124,8 @@ def main():
     ap.add_argument("--prime", action="store_true", help="time the slot step of the parent commit, of this one without a prime and with every column primed")
     ap.add_argument("--prefill", action="store_true", help="time the sequential prime against nvw_prefill_states, 1 and 256 requests")
     ap.add_argument("--score", action="store_true", help="time nvw_score_samples against forcing the samples through primed columns of the parent")
+    ap.add_argument("--prefill-mel", action="store_true", help="time nvw_prefill_states_mel against nvw_prefill_states on rows upsampled beforehand and against mel columns of the parent")
+    ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
@@ -126,6 +136,12 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.prefill_mel or args.score_mel:
+        if args.prefill_mel:
+            print(json.dumps(time_prefill_mel(args, w, Wc, bc)), flush=True)
+        if args.score_mel:
+            print(json.dumps(time_score_mel(args, w, Wc, bc)), flush=True)
+        return
     if args.score:
         print(json.dumps(time_score(args, w, Wc, bc)), flush=True)
         if not args.parent_lib:
@@ -590,6 +606,191 @@ def time_prefill_against_parent(args, w, Wc, bc):
     return {"prefill_256_at_W": W, "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()}, "median_ms": {k: round(v, 3) for k, v in med.items()},
             "parent_spread": round(spread, 4), "here_vs_parent": round(med["here"] / med["parent"], 4),
             "within_twice_the_parent_spread": bool(med["here"] / med["parent"] <= 1.0 + 2.0 * spread), "blobs_equal": True}
+
+
+def _up_weights():
+    """the upsampling of time_mel: window 1024 / stride 256"""
+    import bench
+    r = np.random.default_rng(11)
+    up_w = ((r.random((bench.N_COND, bench.N_COND, bench.UP_WINDOW), dtype=np.float32) - 0.5) *
+            (np.sqrt(12.0) / np.sqrt(4 * bench.N_COND))).astype(np.float32)
+    return up_w, np.zeros(bench.N_COND, dtype=np.float32)
+
+
+def _timed_rounds(paths, rounds, after=None):
+    """{name: [ms per round]} of the paths, alternating their order; round 0 warms every path up and is dropped"""
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = {name: [] for name, _ in paths}
+    for r in range(rounds + 1):
+        for name, fn in (paths if r % 2 else paths[::-1]):
+            torch.cuda.synchronize()
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if r:
+                ms[name].append(ev[0].elapsed_time(ev[1]))
+            if after:
+                after(name)
+    return ms
+
+
+def time_prefill_mel(args, w, Wc, bc):
+    """The --prefill-mel measurement (C3 fp16, window 1024 / stride 256, one process): nvw_prefill_states_mel for 1 and 256 requests
+    at n = W/2, W, 4W and 24 000, beside nvw_prefill_states of this commit on rows upsampled beforehand (the difference is the
+    upsampling's share), beside nvw_upsample_requests alone, and -- with --parent-lib -- beside the same primes forced through mel
+    columns of the PARENT's library (nvw_slot_start_mel + nvw_slot_prime, steps of the window up to sample n): the only way the
+    parent can do it."""
+    import ctypes as C
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import PREFILL_MEL_REQ, PREFILL_REQ, UPSAMPLE_REQ
+    sh = bench.HEAD
+    window, stride = 4096, bench.UP_STRIDE
+    up_w, up_b = _up_weights()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(19)
+    s = torch.cuda.current_stream().cuda_stream
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "upsampling": "%d / %d" % (bench.UP_WINDOW, stride),
+           "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "cases": {}}
+    for count in (1, 256):
+        e = bench.build_engine(w, count, window)
+        e.setConditioningWeights(Wc, bc)
+        e.setUpsampling(up_w, up_b, stride)
+        e.setSelectorSeed(5)
+        W, row = e.prefillWindow(), e.upsampleRowElems()
+        res["W"] = W
+        parent = None
+        if args.parent_lib:
+            parent = _c_engine(args.parent_lib, w, Wc, bc, count, window)
+            h = parent[0]
+            h.nvw_set_upsampling.restype, h.nvw_set_upsampling.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            h.nvw_slot_start_mel.restype = C.c_int
+            h.nvw_slot_start_mel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_uint]
+            assert h.nvw_set_upsampling(parent[1], up_w.ctypes.data, up_b.ctypes.data, bench.UP_WINDOW, stride)
+        lengths = (W // 2, W, 4 * W, 24000)
+        top = max(lengths)
+        frames = -(-top // stride)
+        mel = torch.randn(count, bench.N_COND, frames, device="cuda", generator=g).half()      # distinct frames for every request
+        ys = torch.randint(0, sh.A, (count, top), device="cuda", generator=g, dtype=torch.int32)
+        nbytes = e.slotStateBytes()
+        out = {k: torch.empty((count, nbytes), dtype=torch.uint8, device="cuda") for k in ("mel", "rows")}
+        for n in lengths:
+            t0 = (max(0, n - W) // 16) * 16
+            # (a feature pass indexes by the absolute sample: t0 rows of padding in front keep every derived base inside the buffer)
+            buf = torch.empty((t0 + count * (n - t0), row), dtype=torch.float16, device="cuda")
+            rows = buf[t0:].view(count, n - t0, row)
+            rm, rr, ru = np.zeros(count, dtype=PREFILL_MEL_REQ), np.zeros(count, dtype=PREFILL_REQ), np.zeros(count, dtype=UPSAMPLE_REQ)
+            for b in range(count):
+                m = mel[b]
+                rm[b] = (ys[b].data_ptr(), n, m.data_ptr(), 16, m.stride(0), m.stride(1), frames, b, 1.0)
+                ru[b] = (m.data_ptr(), 16, m.stride(0), m.stride(1), frames, t0, n - t0, rows[b].data_ptr())
+                rr[b] = (ys[b].data_ptr(), n, rows[b].data_ptr() - t0 * row * 2, 16, 1, row, b, 1.0)
+
+            def from_mel():
+                assert lib.nvw_prefill_states_mel(e._h, rm.ctypes.data, count, out["mel"].data_ptr(), nbytes, s) == count
+
+            def from_rows():
+                assert lib.nvw_prefill_states(e._h, rr.ctypes.data, count, out["rows"].data_ptr(), nbytes, s) == count
+
+            def upsample():
+                assert lib.nvw_upsample_requests(e._h, ru.ctypes.data, count, s) == count
+
+            def forced():
+                h, pe = parent
+                assert h.nvw_slots_begin(pe, window)
+                for b in range(count):
+                    assert h.nvw_slot_start_mel(pe, b, mel[b].data_ptr(), 16, mel[b].stride(0), mel[b].stride(1), frames, 1, b)
+                    assert h.nvw_slot_prime(pe, b, ys[b].data_ptr(), n)
+                done = 0
+                while done < n:
+                    c = min(window, n - done)
+                    assert h.nvw_slots_step(pe, c, None, None, s)
+                    done += c
+
+            upsample()
+            paths = [("prefill_mel", from_mel), ("prefill_rows", from_rows), ("upsample", upsample)] + ([("parent_forced", forced)] if parent else [])
+            ms = _timed_rounds(paths, args.rounds, lambda name: parent[0].nvw_slots_end(parent[1]) if name == "parent_forced" else None)
+            assert torch.equal(out["mel"], out["rows"]), "count %d, n %d: the blobs from mel are not those from the rows" % (count, n)
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            case = {"ms": {k: _stats(v) for k, v in ms.items()}, "upsampling_share": round((med["prefill_mel"] - med["prefill_rows"]) / med["prefill_mel"], 3)}
+            if parent:
+                case["parent_forced_over_prefill_mel"] = round(med["parent_forced"] / med["prefill_mel"], 2)
+            res["cases"]["%d x %d" % (count, n)] = case
+            del rows, buf
+        if parent:
+            parent[0].nvw_destroy(parent[1])
+        e.close()
+        torch.cuda.empty_cache()
+    return res
+
+
+def time_score_mel(args, w, Wc, bc):
+    """The --score-mel measurement: nvw_score_samples_mel for 1 and 256 requests at n = 2 048 and 24 000 beside nvw_score_samples of
+    this commit on rows upsampled beforehand, and nvw_upsample_requests alone; calls split at nvw_score_max_samples as --score does."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import SCORE_MEL_REQ, SCORE_REQ, UPSAMPLE_REQ
+    sh = bench.HEAD
+    window, stride = 4096, bench.UP_STRIDE
+    up_w, up_b = _up_weights()
+    g = torch.Generator(device="cuda")
+    g.manual_seed(23)
+    s = torch.cuda.current_stream().cuda_stream
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "upsampling": "%d / %d" % (bench.UP_WINDOW, stride),
+           "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "cases": {}}
+    for count in (1, 256):
+        e = bench.build_engine(w, count, window)
+        e.setConditioningWeights(Wc, bc)
+        e.setUpsampling(up_w, up_b, stride)
+        cap, row = e.scoreMaxSamples(), e.upsampleRowElems()
+        lengths = (2048, 24000)
+        top = max(lengths)
+        frames = -(-top // stride)
+        mel = torch.randn(count, bench.N_COND, frames, device="cuda", generator=g).half()
+        ys = torch.randint(0, sh.A, (count, top), device="cuda", generator=g, dtype=torch.int32)
+        logp = {k: torch.empty((count, top), dtype=torch.float32, device="cuda") for k in ("mel", "rows")}
+        for n in lengths:
+            per_call = max(1, min(count, cap // (-(-n // 16) * 16)))
+            rows = torch.empty((count, n, row), dtype=torch.float16, device="cuda")
+            groups = []
+            for b0 in range(0, count, per_call):
+                k = min(per_call, count - b0)
+                rm, rr, ru = np.zeros(k, dtype=SCORE_MEL_REQ), np.zeros(k, dtype=SCORE_REQ), np.zeros(k, dtype=UPSAMPLE_REQ)
+                for i in range(k):
+                    b = b0 + i
+                    m = mel[b]
+                    rm[i] = (ys[b].data_ptr(), n, m.data_ptr(), 16, m.stride(0), m.stride(1), frames, 1.0, logp["mel"][b].data_ptr(), 0)
+                    ru[i] = (m.data_ptr(), 16, m.stride(0), m.stride(1), frames, 0, n, rows[b].data_ptr())
+                    rr[i] = (ys[b].data_ptr(), n, rows[b].data_ptr(), 16, 1, row, 1.0, logp["rows"][b].data_ptr(), 0)
+                groups.append((rm, rr, ru, k))
+
+            def from_mel():
+                for rm, rr, ru, k in groups:
+                    assert lib.nvw_score_samples_mel(e._h, rm.ctypes.data, k, s) == k
+
+            def from_rows():
+                for rm, rr, ru, k in groups:
+                    assert lib.nvw_score_samples(e._h, rr.ctypes.data, k, s) == k
+
+            def upsample():
+                for rm, rr, ru, k in groups:
+                    assert lib.nvw_upsample_requests(e._h, ru.ctypes.data, k, s) == k
+
+            upsample()
+            ms = _timed_rounds([("score_mel", from_mel), ("score_rows", from_rows), ("upsample", upsample)], args.rounds)
+            assert torch.equal(logp["mel"][:, :n], logp["rows"][:, :n]), "count %d, n %d: the scores from mel are not those from the rows" % (count, n)
+            med = {k: float(np.median(v)) for k, v in ms.items()}
+            res["cases"]["%d x %d" % (count, n)] = {"calls": len(groups), "ms": {k: _stats(v) for k, v in ms.items()},
+                                                   "upsampling_share": round((med["score_mel"] - med["score_rows"]) / med["score_mel"], 3),
+                                                   "upsample_GB_per_s_written": round(count * n * row * 2 / (1e-3 * med["upsample"]) / 1e9, 1)}
+            del rows
+        e.close()
+        torch.cuda.empty_cache()
+    return res
 
 
 def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
