@@ -535,8 +535,9 @@ int nvw_prefill_states(nvw_engine* e, const nvw_prefill_req* reqs, int count, vo
  *                          0 with nothing written and nothing launched: no conditioning weights, count outside 1 .. 65535, an
  *                          n < 1, a temperature outside [2^-10, 2^10], a bad precision or stride, y or x not in device memory, a
  *                          misaligned or unreachable output, a total over nvw_score_max_samples.
- * Scoring from mel frames is nvw_score_samples_mel (FROM MEL FRAMES, below).  Scoring in time chunks with carried state (utterances
- * past the cap), and on the packed, in-place and chain conditioning paths is not offered. */
+ * Scoring from mel frames is nvw_score_samples_mel (FROM MEL FRAMES, below); scoring in time chunks with carried state (utterances
+ * past the cap, candidates behind a shared prefix, streams) is nvw_score_chunks (SCORING WITH CARRIED STATE, below).  Scoring on the
+ * packed, in-place and chain conditioning paths is not offered. */
 typedef struct {
     const int* y;
     int n;
@@ -576,7 +577,8 @@ int nvw_score_samples(nvw_engine* e, const nvw_score_req* reqs, int count, void*
  * return 0 with the engine-owned rows already written, and nothing of the caller's): everything nvw_prefill_states / nvw_score_samples refuse, and
  * no nvw_set_upsampling, mel not in device memory, a non-positive stride, frames * stride short of the range (< first_sample + count,
  * or < n), first_sample < 0 or count < 1, dst not 16-byte aligned device memory.  All three work inside and outside slot mode, touch
- * no ring, column or session, and share the engine's scratch: issue them on one stream, or order them. */
+ * no ring, column or session, and share the engine's scratch: issue them on one stream, or order them.  Scoring a time chunk of a mel
+ * utterance from and to a state blob is nvw_score_chunks_mel (SCORING WITH CARRIED STATE, below). */
 typedef struct {
     const void* mel;
     int precision;
@@ -610,6 +612,59 @@ int nvw_upsample_row_elems(nvw_engine* e);
 int nvw_upsample_requests(nvw_engine* e, const nvw_upsample_req* reqs, int count, void* stream);
 int nvw_prefill_states_mel(nvw_engine* e, const nvw_prefill_mel_req* reqs, int count, void* dst, long long stride, void* stream);
 int nvw_score_samples_mel(nvw_engine* e, const nvw_score_mel_req* reqs, int count, void* stream);
+
+/* SCORING WITH CARRIED STATE: TIME CHUNKS, FROM AND TO A STATE BLOB (additive within ABI 7).  nvw_score_samples starts from silence at
+ * local sample 0 and leaves nothing behind.  Here a request is a CHUNK: y[0 .. n) are local samples done .. done + n - 1 of an
+ * utterance, where done is that of `state` -- a blob of nvw_slot_save / nvw_slots_save_list / nvw_prefill_states* / this call -- or 0
+ * when state is NULL (from silence).  The blob holds exactly what the chunk needs from before it (every layer's last d_l inputs and
+ * the two history words), and everything else of the pass is per sample, so each sample is computed with the operands of the whole
+ * pass in its order: logp and rows are BIT FOR BIT those nvw_score_samples gives for these samples in one pass over [0, done + n),
+ * and state_out, where not NULL, is BYTE FOR BYTE the blob nvw_prefill_states gives for the first done + n samples (uid: the
+ * in-state's, or the request's from silence; word 10: the request's temperature) -- it resumes, and scores on, like any other.
+ *   nvw_score_chunks      `count` requests with one set of layer launches.  x holds the CHUNK's feature columns (column done + i at
+ *                         index i).  done need not be a multiple of 16.  States are read only, and several requests may point at
+ *                         one (candidates behind a shared prefix).  The headers of the states are read before anything is queued:
+ *                         pinned ones in place, device ones with blocking copies on the null stream, each distinct pointer once,
+ *                         pointers in an arithmetic progression (the rows of one earlier call) with one 2-D copy -- a state written
+ *                         on a non-blocking stream must have been ordered before this call, as for nvw_slot_resume.  The pass uses
+ *                         the scoring scratch: nvw_score_max_samples bounds the sum of n, each rounded up to 16, of a chunk call too.
+ *                         Asynchronous on `stream`.  Returns count; 0 with nothing written and nothing launched: everything
+ *                         nvw_score_samples refuses; a state with a wrong magic or layout version, of another precision, R, layer
+ *                         count or largest dilation, with a header word 10 that is neither zero nor a valid temperature; a state
+ *                         that is not device or pinned memory, or not 16-byte aligned; done + n beyond INT_MAX - 16; a state_out
+ *                         that is misaligned, unreachable, or overlaps any state or another state_out of the call.
+ *   nvw_score_chunks_mel  the same from frames: mel, precision, c_stride, f_stride, frames are the utterance's frames from frame 0
+ *                         as nvw_score_samples_mel takes them; samples [done, done + n) are upsampled into the engine-owned rows.
+ *                         Refuses what nvw_score_samples_mel and nvw_score_chunks refuse, and frames * stride < done + n. */
+typedef struct {
+    const void* state;
+    const int* y;
+    int n;
+    const void* x;
+    int precision;
+    long long c_stride, t_stride;
+    unsigned uid;
+    float temperature;
+    float* logp;
+    float* rows;
+    void* state_out;
+} nvw_score_chunk_req;
+typedef struct {
+    const void* state;
+    const int* y;
+    int n;
+    const void* mel;
+    int precision;
+    long long c_stride, f_stride;
+    int frames;
+    unsigned uid;
+    float temperature;
+    float* logp;
+    float* rows;
+    void* state_out;
+} nvw_score_chunk_mel_req;
+int nvw_score_chunks(nvw_engine* e, const nvw_score_chunk_req* reqs, int count, void* stream);
+int nvw_score_chunks_mel(nvw_engine* e, const nvw_score_chunk_mel_req* reqs, int count, void* stream);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

@@ -114,6 +114,8 @@ SIGNATURES = {
     "nvw_upsample_requests": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_prefill_states_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong, C.c_void_p]),
     "nvw_score_samples_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nvw_score_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nvw_score_chunks_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),
     "nvw_pinned_free": (None, [C.c_void_p]),
     "nvw_device_synchronize": (None, []),

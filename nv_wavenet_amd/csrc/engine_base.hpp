@@ -68,6 +68,8 @@ struct nvw_engine {
     virtual int upsampleRequests(const wn::MelTimeReq*, int, hipStream_t) = 0;
     virtual int prefillStatesMel(const wn::PrefillMelReq*, int, void*, long long, hipStream_t) = 0;
     virtual int scoreSamplesMel(const wn::ScoreMelReq*, int, hipStream_t) = 0;
+    virtual int scoreChunks(const wn::ScoreChunkReq*, int, hipStream_t) = 0;
+    virtual int scoreChunksMel(const wn::ScoreChunkMelReq*, int, hipStream_t) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
 };
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
@@ -131,6 +133,33 @@ static_assert(sizeof(nvw_score_mel_req) == sizeof(wn::ScoreMelReq) && offsetof(n
               offsetof(nvw_score_mel_req, temperature) == offsetof(wn::ScoreMelReq, temperature) &&
               offsetof(nvw_score_mel_req, logp) == offsetof(wn::ScoreMelReq, logp) && offsetof(nvw_score_mel_req, rows) == offsetof(wn::ScoreMelReq, rows),
               "nvw_score_mel_req is wn::ScoreMelReq");
+static_assert(sizeof(nvw_score_chunk_req) == sizeof(wn::ScoreChunkReq) && offsetof(nvw_score_chunk_req, state) == offsetof(wn::ScoreChunkReq, state) &&
+              offsetof(nvw_score_chunk_req, y) == offsetof(wn::ScoreChunkReq, y) && offsetof(nvw_score_chunk_req, n) == offsetof(wn::ScoreChunkReq, n) &&
+              offsetof(nvw_score_chunk_req, x) == offsetof(wn::ScoreChunkReq, x) &&
+              offsetof(nvw_score_chunk_req, precision) == offsetof(wn::ScoreChunkReq, precision) &&
+              offsetof(nvw_score_chunk_req, c_stride) == offsetof(wn::ScoreChunkReq, cStride) &&
+              offsetof(nvw_score_chunk_req, t_stride) == offsetof(wn::ScoreChunkReq, tStride) &&
+              offsetof(nvw_score_chunk_req, uid) == offsetof(wn::ScoreChunkReq, uid) &&
+              offsetof(nvw_score_chunk_req, temperature) == offsetof(wn::ScoreChunkReq, temperature) &&
+              offsetof(nvw_score_chunk_req, logp) == offsetof(wn::ScoreChunkReq, logp) &&
+              offsetof(nvw_score_chunk_req, rows) == offsetof(wn::ScoreChunkReq, rows) &&
+              offsetof(nvw_score_chunk_req, state_out) == offsetof(wn::ScoreChunkReq, stateOut),
+              "nvw_score_chunk_req is wn::ScoreChunkReq");
+static_assert(sizeof(nvw_score_chunk_mel_req) == sizeof(wn::ScoreChunkMelReq) &&
+              offsetof(nvw_score_chunk_mel_req, state) == offsetof(wn::ScoreChunkMelReq, state) &&
+              offsetof(nvw_score_chunk_mel_req, y) == offsetof(wn::ScoreChunkMelReq, y) &&
+              offsetof(nvw_score_chunk_mel_req, n) == offsetof(wn::ScoreChunkMelReq, n) &&
+              offsetof(nvw_score_chunk_mel_req, mel) == offsetof(wn::ScoreChunkMelReq, mel) &&
+              offsetof(nvw_score_chunk_mel_req, precision) == offsetof(wn::ScoreChunkMelReq, precision) &&
+              offsetof(nvw_score_chunk_mel_req, c_stride) == offsetof(wn::ScoreChunkMelReq, cStride) &&
+              offsetof(nvw_score_chunk_mel_req, f_stride) == offsetof(wn::ScoreChunkMelReq, fStride) &&
+              offsetof(nvw_score_chunk_mel_req, frames) == offsetof(wn::ScoreChunkMelReq, frames) &&
+              offsetof(nvw_score_chunk_mel_req, uid) == offsetof(wn::ScoreChunkMelReq, uid) &&
+              offsetof(nvw_score_chunk_mel_req, temperature) == offsetof(wn::ScoreChunkMelReq, temperature) &&
+              offsetof(nvw_score_chunk_mel_req, logp) == offsetof(wn::ScoreChunkMelReq, logp) &&
+              offsetof(nvw_score_chunk_mel_req, rows) == offsetof(wn::ScoreChunkMelReq, rows) &&
+              offsetof(nvw_score_chunk_mel_req, state_out) == offsetof(wn::ScoreChunkMelReq, stateOut),
+              "nvw_score_chunk_mel_req is wn::ScoreChunkMelReq");
 
 template <typename Tw, typename Td, int R, int S, int A>
 struct EngineImpl : nvw_engine {
@@ -216,6 +245,8 @@ struct EngineImpl : nvw_engine {
         return eng.prefillStatesMel(reqs, count, dst, stride, s);
     }
     int scoreSamplesMel(const wn::ScoreMelReq* reqs, int count, hipStream_t s) override { return eng.scoreSamplesMel(reqs, count, s); }
+    int scoreChunks(const wn::ScoreChunkReq* reqs, int count, hipStream_t s) override { return eng.scoreChunks(reqs, count, s); }
+    int scoreChunksMel(const wn::ScoreChunkMelReq* reqs, int count, hipStream_t s) override { return eng.scoreChunksMel(reqs, count, s); }
     wn::SlotSession& slots() override { return eng.slots(); }
 };
 

@@ -40,6 +40,7 @@
 #include "mel_time.hpp"
 #include "prefill.hpp"
 #include "score.hpp"
+#include "score_carry.hpp"
 #include "slots_session.hpp"
 #include "wn_chain.hpp"
 #include "wn_kernels.hpp"
@@ -1322,6 +1323,8 @@ public:
         m.biasL = C::BIAS_L;
         m.embPrev = m_embedPrev;
         m.embCur = m_embedCur;
+        m.maxDilation = m_maxDilation;
+        m.ringSlots = m_ringSlots;
         for (int l = 0, d = 1; l < L; l++) {
             m.layers[l] = wn::ScoreLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
                                          (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L),
@@ -1411,6 +1414,62 @@ public:
         sm.bias = m_biasF;
         if (!m_melTime.run(mm, ur.data(), count, stream, true)) return 0;
         return m_score.run(sm, sr.data(), count, stream, true) ? count : 0;
+    }
+    // ---- scoring with carried state: time chunks, from and to a state blob (beyond the reference; score_carry.hpp) ----
+    // For request i < count the chunk y[0 .. n) is scored as local samples done .. done + n - 1 of an utterance, done = that of the
+    // in-state (a blob of slotSave / slotsSaveList / prefillStates* / this call; NULL: from silence at 0), x the CHUNK's feature
+    // columns: logp (and rows) are BIT FOR BIT those scoreSamples gives for these samples in a pass over [0, done + n), and
+    // stateOut, where not NULL, is BYTE FOR BYTE the blob prefillStates gives for the first done + n samples.  In-states are read
+    // only and may be shared; their headers are read with blocking copies on the null stream (pinned ones in place) before anything
+    // is queued.  Uses the scoring scratch: scoreMaxSamples() bounds the sum of padded n.  Returns count; 0 with nothing written or
+    // launched: what scoreSamples refuses, a state of another engine shape, precision or layout version, a misaligned or
+    // unreachable state, done + n beyond INT_MAX - 16, a stateOut that overlaps a state or another stateOut of the call.
+    int scoreChunks(const wn::ScoreChunkReq* reqs, int count, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported) return 0;
+        wn::ScoreModel m = scoreModel();
+        std::vector<wn::ScoreChunkIn> in;
+        if (!wn::Score::chunksCheck(m, reqs, count, false, in)) return 0;
+        if (m_featDirty) buildFeatStream(stream);
+        m.wblob = m_wblobF;
+        m.bias = m_biasF;
+        return m_score.runChunks(m, reqs, count, in, stream) ? count : 0;
+    }
+    // scoreChunks from frames: mel holds the utterance's frames from frame 0; samples [done, done + n) of every request are upsampled
+    // into the engine's own rows (which start at the chunk), and the chunk pass reads those.
+    int scoreChunksMel(const wn::ScoreChunkMelReq* reqs, int count, hipStream_t stream = 0) {
+        if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
+        wn::ScoreModel sm = scoreModel();
+        const wn::MelTimeModel mm = melTimeModel();
+        const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
+        std::vector<wn::MelTimeReq> ur(count);
+        std::vector<wn::ScoreChunkReq> sr(count);
+        std::vector<size_t> at(count);
+        size_t bytes = 0;
+        for (int i = 0; i < count; i++) {
+            const wn::ScoreChunkMelReq& q = reqs[i];
+            if (q.n < 1) return 0;
+            sr[i] = wn::ScoreChunkReq{q.state, q.y, q.n, NULL, F16 ? 16 : 32, 1, (long long)wn::mel_time_row(m_nCond), q.uid, q.temperature,
+                                      q.logp, q.rows, q.stateOut};
+            at[i] = bytes;
+            bytes += (size_t)q.n * rowB;
+        }
+        std::vector<wn::ScoreChunkIn> in;
+        if (!wn::Score::chunksCheck(sm, sr.data(), count, true, in)) return 0;
+        for (int i = 0; i < count; i++) {
+            const wn::ScoreChunkMelReq& q = reqs[i];
+            ur[i] = wn::MelTimeReq{q.mel, q.precision, q.cStride, q.fStride, q.frames, in[i].k0, q.n, NULL};
+        }
+        if (!wn::MelTime::acceptable(mm, ur.data(), count, true)) return 0;
+        char* const rows = m_melTime.rows(bytes);
+        for (int i = 0; i < count; i++) {
+            ur[i].dst = rows + at[i];
+            sr[i].x = rows + at[i];
+        }
+        if (m_featDirty) buildFeatStream(stream);
+        sm.wblob = m_wblobF;
+        sm.bias = m_biasF;
+        if (!m_melTime.run(mm, ur.data(), count, stream, true)) return 0;
+        return m_score.runChunks(sm, sr.data(), count, in, stream) ? count : 0;
     }
     // ---- generation --------------------------------------------------------------------------
     // Generates num_samples in pieces of num_samples_per_chunk and hands every finished piece to

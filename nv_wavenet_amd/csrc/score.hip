@@ -7,9 +7,6 @@
 
 #include "time_tiles.hpp"
 
-// the (R, S, A) the Makefile builds engines for
-#define WN_SCORE_SHAPES(X) X(32, 128, 256) X(64, 128, 256) X(64, 256, 256) X(128, 256, 256) X(64, 128, 512) X(256, 256, 256) X(32, 256, 256) X(128, 256, 1024)
-
 namespace wn {
 
 namespace {
@@ -328,15 +325,25 @@ __global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head
 constexpr int score_nw(int R) { return R / 16 >= 4 ? 4 : R / 16; }
 
 template <bool F16, int R, int S, int A>
-bool launchScore(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, float* xf, char* xd0, char* xd1, float* skf,
-                 hipStream_t stream) {
-    using C = PCfg<F16, R>;
+bool launchHead(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
     constexpr int NW = score_nw(R), TT = score_head_tiles<F16, NW, S, A>();
     using H = HCfg<F16, NW, S, A, TT>;
     static_assert(H::FITS, "the head does not fit a CU");
     const auto head = score_head_kernel<F16, NW, S, A, TT>;
     static const bool ldsOk = hipFuncSetAttribute((const void*)head, hipFuncAttributeMaxDynamicSharedMemorySize, H::LDS) == hipSuccess;
     if (!ldsOk) return false;
+    hipLaunchKernelGGL(head, dim3((maxTiles + TT - 1) / TT, count), dim3(H::THREADS), H::LDS, stream, jobs, (const char*)m.wblob,
+                       m.waveStreamFrags * 1024, m.headZs, m.headZa, m.bias, m.biasL, 3 * R, m.numLayers, skf);
+    return hipGetLastError() == hipSuccess;
+}
+
+template <bool F16, int R, int S, int A>
+bool launchScore(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, float* xf, char* xd0, char* xd1, float* skf,
+                 hipStream_t stream) {
+    using C = PCfg<F16, R>;
+    // (named here first, as it always was: the kernels of the object keep their order, and with it the object its bytes)
+    const auto head = score_head_kernel<F16, score_nw(R), S, A, score_head_tiles<F16, score_nw(R), S, A>()>;
+    (void)head;
     hipLaunchKernelGGL((score_embed_kernel<F16>), dim3(maxTiles, count), dim3(256), 0, stream, jobs, R, A, m.embPrev, m.embCur, m.tanhEmbed, xf, xd0);
     if (hipGetLastError() != hipSuccess) return false;
     char* in = xd0;
@@ -351,9 +358,7 @@ bool launchScore(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTi
         in = out;
         out = t;
     }
-    hipLaunchKernelGGL(head, dim3((maxTiles + TT - 1) / TT, count), dim3(H::THREADS), H::LDS, stream, jobs, (const char*)m.wblob,
-                       m.waveStreamFrags * 1024, m.headZs, m.headZa, m.bias, m.biasL, 3 * R, L, (const float*)skf);
-    return hipGetLastError() == hipSuccess;
+    return launchHead<F16, R, S, A>(m, jobs, count, maxTiles, skf, stream);
 }
 
 long long paddedSamples(int n) { return ((long long)n + 15) & ~15LL; }
@@ -363,6 +368,19 @@ long long paddedSamples(int n) { return ((long long)n + 15) & ~15LL; }
 Score::~Score() {
     if (m_scratch) gpuErrChk(hipFree(m_scratch));
     if (m_jobs) gpuErrChk(hipFree(m_jobs));
+    if (m_chunkJobs) gpuErrChk(hipFree(m_chunkJobs));
+}
+
+char* Score::scratch(size_t need) {
+    if (need > m_scratchBytes) {
+        gpuErrChk(hipDeviceSynchronize());      // (an earlier call may still be using what is replaced)
+        if (m_scratch) gpuErrChk(hipFree(m_scratch));
+        m_scratch = NULL;
+        m_scratchBytes = 0;
+        gpuErrChk(hipMalloc((void**)&m_scratch, need));
+        m_scratchBytes = need;
+    }
+    return m_scratch;
 }
 
 bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count, bool ownX) {
@@ -416,21 +434,13 @@ bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_
     // scratch, [total padded samples] each: the fp32 running residual, two T_data images of x, the fp32 skip sum
     const int rowB = m.R * (m.f16 ? 2 : 4);
     const size_t cells = (size_t)total, need = cells * score_row_bytes(m.f16, m.R, m.S);
-    if (need > m_scratchBytes || count > m_jobCap) {
+    scratch(need);
+    if (count > m_jobCap) {
         gpuErrChk(hipDeviceSynchronize());      // (an earlier call may still be using what is replaced)
-        if (need > m_scratchBytes) {
-            if (m_scratch) gpuErrChk(hipFree(m_scratch));
-            m_scratch = NULL;
-            m_scratchBytes = 0;
-            gpuErrChk(hipMalloc((void**)&m_scratch, need));
-            m_scratchBytes = need;
-        }
-        if (count > m_jobCap) {
-            if (m_jobs) gpuErrChk(hipFree(m_jobs));
-            gpuErrChk(hipMalloc((void**)&m_jobs, 2 * (size_t)count * sizeof(ScoreJob)));
-            m_stage.make(2, (size_t)count * sizeof(ScoreJob));
-            m_jobCap = count;
-        }
+        if (m_jobs) gpuErrChk(hipFree(m_jobs));
+        gpuErrChk(hipMalloc((void**)&m_jobs, 2 * (size_t)count * sizeof(ScoreJob)));
+        m_stage.make(2, (size_t)count * sizeof(ScoreJob));
+        m_jobCap = count;
     }
     float* const xf = (float*)m_scratch;
     char* const xd0 = m_scratch + cells * m.R * 4;
@@ -450,6 +460,18 @@ bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_
                    : launchScore<false, RR, SS, AA>(m, dev, count, maxTiles, xf, xd0, xd1, skf, stream);
     WN_SCORE_SHAPES(WN_SCORE_CASE)
 #undef WN_SCORE_CASE
+    return ok;
+}
+
+// (defined behind Score::run, so that the kernels are instantiated in the order they always were)
+bool score_launch_head(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
+    bool ok = false;
+#define WN_SCORE_HEAD(RR, SS, AA)                                                                                              \
+    if (m.R == RR && m.S == SS && m.A == AA)                                                                                   \
+        ok = m.f16 ? launchHead<true, RR, SS, AA>(m, jobs, count, maxTiles, skf, stream)                                       \
+                   : launchHead<false, RR, SS, AA>(m, jobs, count, maxTiles, skf, stream);
+    WN_SCORE_SHAPES(WN_SCORE_HEAD)
+#undef WN_SCORE_HEAD
     return ok;
 }
 

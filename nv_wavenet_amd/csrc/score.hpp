@@ -15,11 +15,20 @@
 //     logp = (z'_y - m' - log2(sum)) * ln 2 in fp32 -- and, when asked for, the same for every row a.
 // The kernels read the engine's own weight streams and bias table at positions from Cfg (ScoreModel): no second copy of the model.
 // logp is written for t < n only, rows likewise; nothing for the padding columns of the last tile.
+//
+// With carried state (score_carry.hpp) the same pass runs over a time chunk [k0, k0 + n) of an utterance: from a state
+// blob at done = k0 instead of silence, and, when asked, to the blob at done = k0 + n.  Its layer kernels are score_carry.hip's;
+// the head is this file's, launched through score_launch_head, and the scratch is this class's: one allocation, one cap.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "slots_session.hpp"
+
+// the (R, S, A) the Makefile builds engines for
+#define WN_SCORE_SHAPES(X) X(32, 128, 256) X(64, 128, 256) X(64, 256, 256) X(128, 256, 256) X(64, 128, 512) X(256, 256, 256) X(32, 256, 256) X(128, 256, 1024)
 
 namespace wn {
 
@@ -65,6 +74,7 @@ struct ScoreModel {
     int biasL;
     const void *embPrev, *embCur;
     ScoreLayer layers[128];
+    int maxDilation, ringSlots;      // the ring of a state blob (slots_state.hpp): read by the pass with carried state only
 };
 
 // bytes of scratch per padded sample: the fp32 residual, two T_data images of x, the fp32 skip sum
@@ -74,6 +84,13 @@ inline int score_max_samples(bool f16, int R, int S) {
     const size_t rows = (kScoreScratchCap / score_row_bytes(f16, R, S)) & ~(size_t)15;
     return rows > 0x7ffffff0u ? 0x7ffffff0 : (int)rows;
 }
+
+// the head over the skip sums of `count` jobs (at most maxTiles time tiles each): score_head_kernel for the model's shape, as the
+// whole pass launches it.  false: a shape that is not built, or a rejected launch.
+bool score_launch_head(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream);
+
+struct ScoreChunkReq;      // (score_carry.hpp)
+struct ScoreChunkIn;
 
 // The engine-owned side: scratch (grown on demand, at most kScoreScratchCap), the requests' staging.  Calls of one engine are issued
 // on one stream, or ordered by the caller: they share the scratch.  Touches no ring, column or session.
@@ -88,12 +105,24 @@ public:
     static bool acceptable(const ScoreModel& m, const ScoreReq* reqs, int count, bool ownX = false);
     bool run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream, bool ownX = false);
 
+    // ---- with carried state (score_carry.hip) ----
+    // Every check of a chunk call, the blocking reads of the in-states' headers included; queues nothing.  in[i]: where request i
+    // starts and what its embedding and out-state take from its in-state.
+    static bool chunksCheck(const ScoreModel& m, const ScoreChunkReq* reqs, int count, bool ownX, std::vector<ScoreChunkIn>& in);
+    // logp (rows, out-states) of count checked requests, asynchronously on `stream`
+    bool runChunks(const ScoreModel& m, const ScoreChunkReq* reqs, int count, const std::vector<ScoreChunkIn>& in, hipStream_t stream);
+
 private:
+    // the scratch, at least `need` bytes (synchronises when it has to grow)
+    char* scratch(size_t need);
     char* m_scratch = NULL;
     size_t m_scratchBytes = 0;
     ScoreJob* m_jobs = NULL;
     int m_jobCap = 0;
     StageRing m_stage;
+    char* m_chunkJobs = NULL;      // two halves of [cap] CarryJob + [cap] ScoreJob, nothing until the first chunk call
+    int m_chunkCap = 0;
+    StageRing m_chunkStage;
 };
 
 }  // namespace wn

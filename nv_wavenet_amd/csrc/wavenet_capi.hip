@@ -437,6 +437,23 @@ int nvw_score_samples_mel(nvw_engine* e, const nvw_score_mel_req* reqs, int coun
                 "each n rounded up to 16)\n", count, e->scoreMaxSamples());
     return got;
 }
+// ---- scoring with carried state: time chunks, from and to a state blob (additive within ABI 7) --------------------------------------
+int nvw_score_chunks(nvw_engine* e, const nvw_score_chunk_req* reqs, int count, void* stream) {
+    const int got = e->scoreChunks((const wn::ScoreChunkReq*)reqs, count, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_score_chunks: refused, nothing written (as nvw_score_samples, at most %d samples, each n rounded up to 16; state "
+                "NULL or a blob of this engine's shape, precision and layout in 16-byte aligned device or pinned memory, done + n <= INT_MAX "
+                "- 16; state_out NULL or %zu bytes of 16-byte aligned device or pinned memory that overlap no state and no other state_out "
+                "of the %d requests)\n", e->scoreMaxSamples(), e->slots().stateBytes(), count);
+    return got;
+}
+int nvw_score_chunks_mel(nvw_engine* e, const nvw_score_chunk_mel_req* reqs, int count, void* stream) {
+    const int got = e->scoreChunksMel((const wn::ScoreChunkMelReq*)reqs, count, (hipStream_t)stream);
+    if (got != count || count < 1)
+        fprintf(stderr, "nvw_score_chunks_mel: refused, nothing written (as nvw_score_samples_mel and nvw_score_chunks: %d requests, frames * "
+                "stride >= done + n, states and state_out of %zu bytes)\n", count, e->slots().stateBytes());
+    return got;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

@@ -37,6 +37,15 @@ PREFILL_MEL_REQ = np.dtype({"names": ["y", "n", "mel", "precision", "c_stride", 
 SCORE_MEL_REQ = np.dtype({"names": ["y", "n", "mel", "precision", "c_stride", "f_stride", "frames", "temperature", "logp", "rows"],
                           "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<f4", "<u8", "<u8"],
                           "offsets": [0, 8, 16, 24, 32, 40, 48, 52, 56, 64], "itemsize": 72})
+# ... nvw_score_chunk_req and nvw_score_chunk_mel_req of scoring with carried state
+SCORE_CHUNK_REQ = np.dtype({"names": ["state", "y", "n", "x", "precision", "c_stride", "t_stride", "uid", "temperature", "logp", "rows",
+                                      "state_out"],
+                            "formats": ["<u8", "<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<u4", "<f4", "<u8", "<u8", "<u8"],
+                            "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 60, 64, 72, 80], "itemsize": 88})
+SCORE_CHUNK_MEL_REQ = np.dtype({"names": ["state", "y", "n", "mel", "precision", "c_stride", "f_stride", "frames", "uid", "temperature",
+                                          "logp", "rows", "state_out"],
+                                "formats": ["<u8", "<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<u4", "<f4", "<u8", "<u8", "<u8"],
+                                "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 60, 64, 72, 80, 88], "itemsize": 96})
 
 
 class Impl:
@@ -809,6 +818,72 @@ class WavenetEngine:
         if got != n or n == 0:
             raise ValueError("nvw_score_samples_mel refused %d requests" % n)
         return out
+
+    # ---- scoring with carried state (include/nv_wavenet_c.h, "SCORING WITH CARRIED STATE") ----
+    def _score_chunks(self, requests, mel, rows, states, pinned, stream, out=None):
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        if not getattr(self, "nCond", 0):
+            raise ValueError("scoring needs setConditioningWeights")
+        reqs = np.zeros(max(n, 1), dtype=SCORE_CHUNK_MEL_REQ if mel else SCORE_CHUNK_REQ)
+        blobs = out
+        if out is not None:
+            assert out.dtype == torch.uint8 and out.dim() == 2 and out.stride(1) == 1 and out.size(0) >= n and \
+                out.size(1) >= self.slotStateBytes() and (out.is_cuda or out.is_pinned()), "out: a uint8 CUDA or pinned tensor [>= n][stride]"
+            states = True
+        elif states:
+            blobs = torch.empty((max(n, 1), self.slotStateBytes()), dtype=torch.uint8, device=None if pinned else "cuda", pin_memory=bool(pinned))
+        out = []
+        for i, rq in enumerate(requests):
+            state, y, src, uid, T = rq[:5]
+            if not hasattr(y, "data_ptr") or y.dim() != 1 or str(y.dtype) != "torch.int32" or not y.is_contiguous() or not y.is_cuda or y.numel() < 1:
+                raise ValueError("samples to score are a contiguous 1-D int32 CUDA tensor of at least one value")
+            if state is not None and (not hasattr(state, "data_ptr") or state.dtype != torch.uint8 or not state.is_contiguous() or
+                                      state.numel() != self.slotStateBytes() or not (state.is_cuda or state.is_pinned())):
+                raise ValueError("a state is a contiguous uint8 CUDA or pinned tensor of slotStateBytes()")
+            logp = torch.empty(y.numel(), dtype=torch.float32, device="cuda")
+            full = torch.empty((y.numel(), self.A), dtype=torch.float32, device="cuda") if rows else None
+            tail = (int(uid) & 0xFFFFFFFF, float(T), logp.data_ptr(), full.data_ptr() if rows else 0, blobs[i].data_ptr() if states else 0)
+            if mel:
+                bits, sc, sf, frames = self._mel_args(src, rq[5] if len(rq) > 5 else None)
+                reqs[i] = (state.data_ptr() if state is not None else 0, y.data_ptr(), y.numel(), src.data_ptr(), bits, sc, sf, frames) + tail
+            else:
+                assert hasattr(src, "data_ptr") and src.is_cuda and src.dim() == 2 and src.size(0) == self.nCond, \
+                    "features: CUDA tensors [n_cond][samples]"
+                bits = {torch.float32: 32, torch.float16: 16}.get(src.dtype)
+                assert bits, "features must be float32 or float16"
+                if y.numel() > src.size(1):
+                    raise ValueError("%d samples against features of %d" % (y.numel(), src.size(1)))
+                reqs[i] = (state.data_ptr() if state is not None else 0, y.data_ptr(), y.numel(), src.data_ptr(), bits, src.stride(0),
+                           src.stride(1)) + tail
+            out.append((logp, full) if rows else logp)
+        name = "nvw_score_chunks_mel" if mel else "nvw_score_chunks"
+        got = getattr(lib, name)(self._h, reqs.ctypes.data, n, stream)
+        if got != n or n == 0:
+            raise ValueError("%s refused %d requests" % (name, n))
+        return (out, blobs[:n]) if states else out
+
+    def scoreChunks(self, requests, rows=False, states=False, pinned=False, stream=None, out=None):
+        """scoreSamples over time chunks with carried state: requests = [(state, y, x, uid, temperature), ...] with state a uint8
+        CUDA or pinned tensor of slotStateBytes() -- a blob of slotSave / slotsSaveList / prefillStates* / this call -- or None (from
+        silence at local sample 0), y the chunk's samples = local samples done .. done + n - 1 of the utterance (done: the
+        state's), and x the CHUNK's features [n_cond][>= n]: column i belongs to sample done + i.  Returns what scoreSamples
+        returns, bit for bit what it gives for these samples in one pass over [0, done + n); with states=True the pair (that,
+        blobs): a uint8 tensor [n][slotStateBytes()] on the GPU, or in pinned host memory (pinned=True), row i byte for byte the
+        blob of prefillStates for the first done + n samples (uid: the state's, or the request's from silence).  States are read
+        only and may be shared by several requests; their headers are read on the null stream before anything is queued (a save
+        on a non-blocking stream must have been ordered before this call).  Asynchronous on `stream`; the tensors of `requests`
+        must stay alive until it has run.  out: a buffer the caller keeps for the blobs, as for prefillStates (implies states).
+        ValueError when refused (nothing written, nothing launched): see nvw_score_chunks."""
+        return self._score_chunks(requests, False, rows, states, pinned, stream, out)
+
+    def scoreChunksMel(self, requests, rows=False, states=False, pinned=False, stream=None, out=None):
+        """scoreChunks from frames: requests = [(state, y, mel, uid, temperature[, frames]), ...] with mel the utterance's frames
+        from frame 0, as scoreSamplesMel takes them; the engine upsamples samples [done, done + n) itself.  Bit for bit what
+        scoreSamplesMel returns for these samples; the blobs byte for byte those of prefillStatesMel.  ValueError when refused: see
+        nvw_score_chunks_mel."""
+        return self._score_chunks(requests, True, rows, states, pinned, stream, out)
 
     # ---- run --------------------------------------------------------------------------------
     def _yout(self, yOut, need=None):

@@ -519,7 +519,7 @@ class NVWaveNetEngine(NVWaveNet):
             if prime is not None:
                 e.setPrime(None)             # (... or while a column is primed)
 
-    def score(self, x, cond_weight, cond_bias, samples, lengths=None, temperature=None, return_rows=False):
+    def score(self, x, cond_weight, cond_bias, samples, lengths=None, temperature=None, return_rows=False, chunk=None, return_state=False):
         """Per-sample log-likelihoods of known samples under the model: x = the upsampled features
         [batch][n_cond][samples] on the GPU and cond_weight / cond_bias as for infer_features; samples = an integer tensor
         [batch][n], n <= x.size(2) (values clamped into 0 .. A-1); lengths: None (all n), or `batch` values in 0 .. n.  Returns
@@ -529,20 +529,28 @@ class NVWaveNetEngine(NVWaveNet):
         temperature: None (1), a float, or `batch` floats, each finite and in [2^-10, 2^10].  return_rows: also rows
         [batch][n][A], the whole log-distribution of every step (zero past a length).  One time-parallel pass per call of the
         engine (nvw_score_samples); a batch whose padded lengths exceed the engine's scoreMaxSamples() is split into several calls,
-        ValueError for a single utterance that does not fit, and for a bad shape, length or temperature."""
-        return self._score(x, x.size(2), None, cond_weight, cond_bias, samples, lengths, temperature, return_rows)
+        ValueError for a single utterance that does not fit, and for a bad shape, length or temperature.
+        chunk: None, or a positive number of samples (rounded up to a multiple of 16): the utterances are scored in time chunks of
+        that many samples with carried state (nvw_score_chunks), all advancing together, a step whose batch x chunk
+        exceeds scoreMaxSamples() split over the batch -- so any length fits, the scratch is bounded by the caller's choice, and
+        the result is bit for bit that of the whole pass.  ValueError if one chunk of one utterance exceeds scoreMaxSamples().
+        return_state: also the state blobs behind every utterance's last sample, a uint8 tensor [batch][slotStateBytes()] on the GPU,
+        byte for byte those of prefillStates (uid = the batch index; a row of zeros for a length of 0)."""
+        return self._score(x, x.size(2), None, cond_weight, cond_bias, samples, lengths, temperature, return_rows, chunk, return_state)
 
     def score_mel(self, mel, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, samples, lengths=None,
-                  temperature=None, return_rows=False):
+                  temperature=None, return_rows=False, chunk=None, return_state=False):
         """score() from mel frames: mel = the frames before upsampling [batch][n_cond][frames] on the GPU,
         upsample_weight / upsample_bias / upsample_stride = the model's `upsample` ConvTranspose1d as for slot_stream; samples = an
         integer tensor [batch][n], n <= frames x stride.  The engine upsamples every utterance's range itself
         (nvw_score_samples_mel) -- bit for bit the features of its own lockstep upsampling -- and the result is what score()
-        returns for them, split into calls that fit in the same way."""
+        returns for them, split into calls that fit in the same way.  chunk, return_state: as for score() (nvw_score_chunks_mel; the
+        blobs are those of prefillStatesMel)."""
         up = (upsample_weight, upsample_bias, int(upsample_stride))
-        return self._score(mel, mel.size(2) * int(upsample_stride), up, cond_weight, cond_bias, samples, lengths, temperature, return_rows)
+        return self._score(mel, mel.size(2) * int(upsample_stride), up, cond_weight, cond_bias, samples, lengths, temperature, return_rows,
+                           chunk, return_state)
 
-    def _score(self, x, sample_count, up, cond_weight, cond_bias, samples, lengths, temperature, return_rows):
+    def _score(self, x, sample_count, up, cond_weight, cond_bias, samples, lengths, temperature, return_rows, chunk=None, return_state=False):
         """score (up None: x holds features) and score_mel (up = upsampling weight, bias, stride: x holds frames)."""
         from .slots import check_temperature
         batch_size = x.size(0)
@@ -577,6 +585,15 @@ class NVWaveNetEngine(NVWaveNet):
         logp = torch.zeros((batch_size, n), dtype=torch.float32, device=dev)
         rows = torch.zeros((batch_size, n, self.A), dtype=torch.float32, device=dev) if return_rows else None
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if chunk is not None or return_state:
+            if chunk is not None and (isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1):
+                raise ValueError("chunk: None or a positive number of samples, got %r" % (chunk,))
+            step = -(-(n if chunk is None else int(chunk)) // 16) * 16
+            if step > cap:
+                raise ValueError("a chunk of %d samples, one scoring pass takes %d" % (step, cap))
+            blobs = self._score_chunked(e, x, up, y, lengths, temps, logp, rows, step, cap, stream, dev)
+            out = (logp, rows) if return_rows else (logp,)
+            return out + (blobs,) if return_state else out if return_rows else logp
 
         def call(group):
             reqs = [(y[b, :lengths[b]], x[b], temps[b]) for b in group]
@@ -593,7 +610,7 @@ class NVWaveNetEngine(NVWaveNet):
             if padded == 0:
                 continue
             if padded > cap:
-                raise ValueError("utterance %d: %d samples, one scoring pass takes %d (scoring in time chunks is not offered)" % (b, lengths[b], cap))
+                raise ValueError("utterance %d: %d samples, one scoring pass takes %d (chunk= scores it in time chunks)" % (b, lengths[b], cap))
             if used + padded > cap or len(group) == 65535:
                 call(group)
                 group, used = [], 0
@@ -602,6 +619,40 @@ class NVWaveNetEngine(NVWaveNet):
         if group:
             call(group)
         return (logp, rows) if return_rows else logp
+
+    def _score_chunked(self, e, x, up, y, lengths, temps, logp, rows, step, cap, stream, dev):
+        """_score in time chunks of `step` samples: every utterance advances by one chunk per step, from the out-state of its
+        previous one (two buffers, used in turn); fills logp and rows, returns the final blobs [batch][slotStateBytes()]."""
+        batch_size = len(lengths)
+        nbytes = e.slotStateBytes()
+        bufs = [torch.empty((batch_size, nbytes), dtype=torch.uint8, device=dev) for _ in range(2)]
+        final = torch.zeros((batch_size, nbytes), dtype=torch.uint8, device=dev)
+        score = e.scoreChunks if up is None else e.scoreChunksMel
+        per_call = max(1, min(cap // step, 65535))
+        at = {}                                        # utterance -> its row in the buffer the previous step wrote
+        for s in range(-(-max(lengths) // step) if lengths else 0):
+            k0 = s * step
+            live = [b for b in range(batch_size) if lengths[b] > k0]
+            if s and stream != 0:
+                torch.cuda.current_stream(dev).synchronize()      # (the headers of the in-states are read on the null stream)
+            src, dst = bufs[(s + 1) % 2], bufs[s % 2]
+            for g in range(0, len(live), per_call):
+                group = live[g:g + per_call]
+                reqs = []
+                for b in group:
+                    m = min(step, lengths[b] - k0)
+                    reqs.append((src[at[b]] if s else None, y[b, k0:k0 + m], x[b][:, k0:k0 + m] if up is None else x[b], b, temps[b]))
+                got, _ = score(reqs, rows=rows is not None, stream=stream, out=dst[g:g + len(group)])
+                for i, b in enumerate(group):
+                    m = min(step, lengths[b] - k0)
+                    if rows is not None:
+                        logp[b, k0:k0 + m], rows[b, k0:k0 + m] = got[i]
+                    else:
+                        logp[b, k0:k0 + m] = got[i]
+                    if lengths[b] <= k0 + step:
+                        final[b] = dst[g + i]
+            at = {b: i for i, b in enumerate(live)}
+        return final
 
     def _infer_packed(self, frags, batch_size, implementation, seed, return_audio, generator):
         sample_count = frags.size(0) - 1

@@ -357,6 +357,48 @@ class SlotStream:
             raise ValueError("score needs samples")
         return self.engine.scoreSamples([(y if y.is_cuda else y.cuda(), features, temperature)])[0]
 
+    def score_from(self, state, samples, temperature=None, return_state=False):
+        """score() behind a state: `samples` (an integer tensor [m]) are scored as local samples state.done .. state.done + m - 1
+        of the SlotState's own source -- features or mel frames by state.kind --, from its blob instead of from silence (no blob:
+        the request had not started, from silence): a float32 CUDA tensor [m], bit for bit the tail of score() over the whole
+        prefix (WavenetEngine.scoreChunks / scoreChunksMel).  temperature: default the state's.  return_state: also
+        a SlotState with done + m whose blob is byte for byte the one a column primed with the samples saves there; it resumes
+        like any other and survives to_bytes() / from_bytes().  The given state is left as it is.  Nothing is queued, no column
+        is touched.  Complete once the engine's stream has run the pass."""
+        import torch
+        temperature = check_temperature(state.temperature if temperature is None else temperature)
+        mel = state.kind == "mel"
+        done = int(state.done) if state.blob is not None else 0
+        if mel:
+            stride = getattr(self.engine, "upStride", 0)
+            if not stride or not self.engine.upsampleRowElems():
+                raise ValueError("scoring a mel request needs setUpsampling")
+            frames = self._mel_frames(state.source, state.frames, bool(state.final))
+            room = frames * stride - done
+        else:
+            room = state.source.size(1) - done
+        y = check_prime(samples, None)
+        if y is None or room < 1 or y.numel() > room:
+            raise ValueError("score_from: 1 .. %d samples behind the %d done" % (max(room, 0), done))
+        y = y if y.is_cuda else y.cuda()
+        blob = state.blob
+        if blob is not None and not (blob.is_cuda or blob.is_pinned()):
+            blob = blob.cuda()                         # (a CPU blob of from_bytes())
+        if mel:
+            req = (blob, y, state.source, int(state.uid), temperature, frames)
+            got = self.engine.scoreChunksMel([req], states=bool(return_state))
+        else:
+            req = (blob, y, state.source[:, done:done + y.numel()], int(state.uid), temperature)
+            got = self.engine.scoreChunks([req], states=bool(return_state))
+        if not return_state:
+            return got[0]
+        logp, blobs = got
+        prime = state.prime if state.prime is not None and state.prime.numel() > done + y.numel() else None
+        after = SlotState(blobs[0], state.source, int(state.uid), done + int(y.numel()), state.kind, frames=state.frames if mel else None,
+                          final=state.final if mel else None, buffer=blobs, row=0, temperature=temperature, prime=prime)
+        after._prefilled_from = (y, blob)              # (read by the pass in stream order: kept with the state)
+        return logp[0], after
+
     def _mel_frames(self, mel, frames, final=True):
         assert mel.dim() == 2, "mel: [n_cond][frames]"
         n = mel.size(1) if frames is None else int(frames)

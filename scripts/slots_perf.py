@@ -77,6 +77,12 @@ cases reach (useful multiply-adds of the model over the dense peak of 2.5 PFLOP/
 256 utterances costs less than forcing them.  With --parent-lib it then prints nvw_prefill_states of both libraries (256 requests
 at n = W) and the --parent comparison of the plain step: nothing on their paths changes, so both are guards, held to the spread
 the parent itself shows.
+--score-chunks times scoring with carried state, C3 fp16, one process: nvw_score_samples of this commit against the
+parent's over 256 requests of 24 000 samples (a guard); nvw_score_chunks over the same samples in time chunks of 2 048 and 16 384
+against the whole pass; one request of 1 500 000 samples, which the whole pass refuses, in chunks of 65 536; and 64 candidates of
+256 samples behind one prefix of 24 000 against 64 whole scorings of 24 256.  Every result is checked bit for bit against the whole
+pass before it is timed.  With --parent-lib it then prints the nvw_prefill_states and plain-step comparisons as --score does.
+
 --prefill-mel and --score-mel time the same two passes fed from mel frames, C3 fp16, window 1024 / stride 256, one
 process: nvw_prefill_states_mel (1 and 256 requests at n = W / 2, W, 4 W, 24 000) and nvw_score_samples_mel (n = 2 048, 24 000)
 beside the feature entries of this commit on rows upsampled beforehand -- the difference is the upsampling's share -- and beside
@@ -87,6 +93,7 @@ results of the paths are checked to be equal bytes.  One JSON line each: median 
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
     python scripts/slots_perf.py --prefill-mel [--parent-lib PATH] [--rounds 5]
     python scripts/slots_perf.py --score-mel [--rounds 5]
+    python scripts/slots_perf.py --score-chunks [--parent-lib PATH] [--rounds 5]
     python scripts/slots_perf.py --score [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
@@ -124,6 +131,7 @@ def main():
     ap.add_argument("--prime", action="store_true", help="time the slot step of the parent commit, of this one without a prime and with every column primed")
     ap.add_argument("--prefill", action="store_true", help="time the sequential prime against nvw_prefill_states, 1 and 256 requests")
     ap.add_argument("--score", action="store_true", help="time nvw_score_samples against forcing the samples through primed columns of the parent")
+    ap.add_argument("--score-chunks", action="store_true", help="time nvw_score_chunks against the whole pass, a request past the cap, and candidates behind a shared prefix")
     ap.add_argument("--prefill-mel", action="store_true", help="time nvw_prefill_states_mel against nvw_prefill_states on rows upsampled beforehand and against mel columns of the parent")
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
@@ -142,6 +150,12 @@ def main():
         if args.score_mel:
             print(json.dumps(time_score_mel(args, w, Wc, bc)), flush=True)
         return
+    if args.score_chunks:
+        print(json.dumps(time_score_chunks(args, w, Wc, bc)), flush=True)
+        if not args.parent_lib:
+            return
+        print(json.dumps(time_prefill_against_parent(args, w, Wc, bc)), flush=True)
+        args.parent = True
     if args.score:
         print(json.dumps(time_score(args, w, Wc, bc)), flush=True)
         if not args.parent_lib:
@@ -457,9 +471,13 @@ def _c_engine(path, w, Wc, bc, columns, window):
             "nvw_slots_begin": (ci, [vp, ci]), "nvw_slot_start": (ci, [vp, ci, vp, ci, ll, ll, ci, C.c_uint]),
             "nvw_slots_step": (ci, [vp, ci, vp, vp, vp]), "nvw_slots_end": (None, [vp]), "nvw_slot_prime": (ci, [vp, ci, vp, ci]),
             "nvw_prefill_window": (ci, [vp]), "nvw_prefill_states": (ci, [vp, vp, ci, vp, ll, vp]), "nvw_slot_state_bytes": (C.c_size_t, [vp])}
+    more = {"nvw_score_max_samples": (ci, [vp]), "nvw_score_samples": (ci, [vp, vp, ci, vp]), "nvw_score_chunks": (ci, [vp, vp, ci, vp])}
     h = C.CDLL(path)
     for name, (res, argt) in sigs.items():
         getattr(h, name).restype, getattr(h, name).argtypes = res, argt
+    for name, (res, argt) in more.items():          # (a parent's library may lack the later entries)
+        if hasattr(h, name):
+            getattr(h, name).restype, getattr(h, name).argtypes = res, argt
     a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
     e = h.nvw_create_ex(sh.R, sh.S, sh.A, 16, sh.L, sh.maxD, columns, window, 0, 1, 0)
     assert e, path
@@ -561,6 +579,166 @@ def time_score(args, w, Wc, bc):
     if args.parent_lib:
         res["scoring_256_costs_less_than_forcing_them"] = bool(all(c["median_ms"]["score"] < c["median_ms"]["parent_forced"]
                                                                     for k, c in res["cases"].items() if k.startswith("256 ")))
+    return res
+
+
+def time_score_chunks(args, w, Wc, bc):
+    """The --score-chunks measurement (C3 fp16, one process, medians of --rounds rounds with every round listed):
+    nvw_score_samples of this commit's library against the parent's over 256 requests of 24 000 samples (a guard, held to twice the
+    parent's own spread); nvw_score_chunks over the same samples in time chunks of 2 048 and 16 384 against the whole pass (the
+    blocking reads of the in-states' headers included); one request of 1 500 000 samples, which the whole pass refuses, in chunks
+    of 65 536; and 64 candidates of 256 samples behind one prefix of 24 000 -- the candidates alone behind a state at hand, the
+    prefix scored once with its out-state and then the candidates, and the only way without carried state: 64 whole scorings of
+    24 256."""
+    import torch
+    import bench
+    from nv_wavenet_amd import _lib
+    from nv_wavenet_amd.engine import SCORE_CHUNK_REQ, SCORE_REQ
+    sh = bench.HEAD
+    count, n, window = 256, 24000, 4096
+    g = torch.Generator(device="cuda")
+    g.manual_seed(19)
+    s = torch.cuda.current_stream().cuda_stream
+    libs = {"here": _c_engine(_lib.LIB_PATH, w, Wc, bc, count, window)}
+    if args.parent_lib:
+        libs["parent"] = _c_engine(args.parent_lib, w, Wc, bc, count, window)
+    h, e = libs["here"]
+    cap = h.nvw_score_max_samples(e)
+    nbytes = int(h.nvw_slot_state_bytes(e))
+    src = torch.randn(bench.N_COND, n + 256 + count, device="cuda", generator=g).half()
+    xs = [src[:, b:b + n + 256] for b in range(count)]
+    ys = torch.randint(0, sh.A, (count, n + 256), device="cuda", generator=g, dtype=torch.int32)
+    logp = torch.empty((count, n + 256), dtype=torch.float32, device="cuda")
+    keep = logp.clone()
+    states = [torch.empty((count, nbytes), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "rounds": args.rounds, "score_max_samples": cap,
+           "state_bytes": nbytes, "device": torch.cuda.get_device_name(0)}
+
+    def pad(k):
+        return -(-k // 16) * 16
+
+    def whole_calls(length, first=0, many=count):
+        per, out = max(1, min(many, cap // pad(length))), []
+        for b0 in range(0, many, per):
+            k = min(per, many - b0)
+            reqs = np.zeros(k, dtype=SCORE_REQ)
+            for i in range(k):
+                b = first + b0 + i
+                reqs[i] = (ys[b].data_ptr(), length, xs[b].data_ptr(), 16, xs[b].stride(0), xs[b].stride(1), 1.0, logp[b].data_ptr(), 0)
+            out.append((reqs, k))
+        return out
+
+    def whole(lib, calls):
+        for reqs, k in calls:
+            assert lib[0].nvw_score_samples(lib[1], reqs.ctypes.data, k, s) == k
+
+    def chunk_calls(step):
+        """[(requests, count)] of all of [0, n) in time chunks of `step`, every request from the out-state of its previous chunk"""
+        per, out = max(1, min(count, cap // pad(step))), []
+        for si, k0 in enumerate(range(0, n, step)):
+            m = min(step, n - k0)
+            src_st, dst_st = states[(si + 1) % 2], states[si % 2]
+            for b0 in range(0, count, per):
+                k = min(per, count - b0)
+                reqs = np.zeros(k, dtype=SCORE_CHUNK_REQ)
+                for i in range(k):
+                    b = b0 + i
+                    reqs[i] = (src_st[b].data_ptr() if si else 0, ys[b].data_ptr() + 4 * k0, m, xs[b].data_ptr() + 2 * k0 * xs[b].stride(1), 16,
+                               xs[b].stride(0), xs[b].stride(1), b, 1.0, logp[b].data_ptr() + 4 * k0, 0, dst_st[b].data_ptr())
+                out.append((reqs, k))
+        return out
+
+    def chunks(calls):
+        for reqs, k in calls:
+            assert h.nvw_score_chunks(e, reqs.ctypes.data, k, s) == k
+
+    calls = whole_calls(n)
+    by_step = {step: chunk_calls(step) for step in (2048, 16384)}
+    paths = [("whole_here", lambda: whole(libs["here"], calls))] + ([("whole_parent", lambda: whole(libs["parent"], calls))] if args.parent_lib else [])
+    paths += [("chunks_%d" % step, (lambda c: lambda: chunks(c))(c)) for step, c in by_step.items()]
+    whole(libs["here"], calls)
+    torch.cuda.synchronize()
+    keep.copy_(logp)
+    for step, c in by_step.items():
+        logp.zero_()
+        chunks(c)
+        torch.cuda.synchronize()
+        assert torch.equal(logp[:, :n].view(torch.int32), keep[:, :n].view(torch.int32)), "chunks of %d differ from the whole pass" % step
+    ms = _timed_rounds(paths, args.rounds)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    case = {"calls": {"whole": len(calls), **{"chunks_%d" % st: len(c) for st, c in by_step.items()}},
+            "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()}, "median_ms": {k: round(v, 3) for k, v in med.items()},
+            "spread": {k: round((max(v) - min(v)) / med[k], 4) for k, v in ms.items()},
+            "chunks_over_whole": {k: round(med[k] / med["whole_here"], 4) for k in med if k.startswith("chunks_")}, "bit_equal": True}
+    if args.parent_lib:
+        spread = (max(ms["whole_parent"]) - min(ms["whole_parent"])) / med["whole_parent"]
+        case.update(parent_spread=round(spread, 4), here_vs_parent=round(med["whole_here"] / med["whole_parent"], 4),
+                    within_twice_the_parent_spread=bool(med["whole_here"] / med["whole_parent"] <= 1.0 + 2.0 * spread))
+    res["256 x 24000"] = case
+
+    # one request past the cap
+    long_n, step = 1500000, 65536
+    assert pad(long_n) > cap
+    lx = torch.randn(bench.N_COND, long_n, device="cuda", generator=g).half()
+    ly = torch.randint(0, sh.A, (long_n,), device="cuda", generator=g, dtype=torch.int32)
+    ll = torch.empty(long_n, dtype=torch.float32, device="cuda")
+    one = np.zeros(1, dtype=SCORE_REQ)
+    one[0] = (ly.data_ptr(), long_n, lx.data_ptr(), 16, lx.stride(0), lx.stride(1), 1.0, ll.data_ptr(), 0)
+    refused = {name: lib[0].nvw_score_samples(lib[1], one.ctypes.data, 1, s) == 0 for name, lib in libs.items()}
+    lcalls = []
+    for si, k0 in enumerate(range(0, long_n, step)):
+        m = min(step, long_n - k0)
+        reqs = np.zeros(1, dtype=SCORE_CHUNK_REQ)
+        reqs[0] = (states[(si + 1) % 2][0].data_ptr() if si else 0, ly.data_ptr() + 4 * k0, m, lx.data_ptr() + 2 * k0 * lx.stride(1), 16,
+                   lx.stride(0), lx.stride(1), 1, 1.0, ll.data_ptr() + 4 * k0, 0, states[si % 2][0].data_ptr())
+        lcalls.append((reqs, 1))
+    ms = _timed_rounds([("chunks_65536", lambda: chunks(lcalls))], args.rounds)
+    m0 = float(np.median(ms["chunks_65536"]))
+    # (its first 24 000 samples are what the whole pass gives for them)
+    head = np.zeros(1, dtype=SCORE_REQ)
+    head[0] = (ly.data_ptr(), n, lx.data_ptr(), 16, lx.stride(0), lx.stride(1), 1.0, logp[0].data_ptr(), 0)
+    assert h.nvw_score_samples(e, head.ctypes.data, 1, s) == 1
+    torch.cuda.synchronize()
+    res["1 x 1500000"] = {"whole_pass_refuses": refused, "calls": len(lcalls), "ms": [round(x, 3) for x in ms["chunks_65536"]], "median_ms": round(m0, 3),
+                          "us_per_sample": round(1e3 * m0 / long_n, 4), "seconds_of_24_kHz_audio": round(long_n / 24000.0, 1),
+                          "first_24000_bit_equal_to_the_whole_pass": bool(torch.equal(ll[:n].view(torch.int32), logp[0, :n].view(torch.int32)))}
+    del lx, ly, ll
+
+    # 64 candidates of 256 behind one prefix of 24 000 (utterance 0's; candidate c = the samples of utterance c behind it)
+    K, m = 64, 256
+    prefix = np.zeros(1, dtype=SCORE_CHUNK_REQ)
+    prefix[0] = (0, ys[0].data_ptr(), n, xs[0].data_ptr(), 16, xs[0].stride(0), xs[0].stride(1), 0, 1.0, logp[0].data_ptr(), 0, states[0][0].data_ptr())
+    cand_y = ys[:K, n:n + m].contiguous()
+    cand_lp = torch.empty((K, m), dtype=torch.float32, device="cuda")
+    cands = np.zeros(K, dtype=SCORE_CHUNK_REQ)
+    for c in range(K):
+        cands[c] = (states[0][0].data_ptr(), cand_y[c].data_ptr(), m, xs[0].data_ptr() + 2 * n * xs[0].stride(1), 16, xs[0].stride(0), xs[0].stride(1),
+                    0, 1.0, cand_lp[c].data_ptr(), 0, 0)
+    full_y = torch.cat([ys[0, :n].unsqueeze(0).expand(K, n), cand_y], dim=1).contiguous()
+    full_lp = torch.empty((K, n + m), dtype=torch.float32, device="cuda")
+    per = max(1, min(K, cap // pad(n + m)))
+    fcalls = []
+    for b0 in range(0, K, per):
+        k = min(per, K - b0)
+        reqs = np.zeros(k, dtype=SCORE_REQ)
+        for i in range(k):
+            reqs[i] = (full_y[b0 + i].data_ptr(), n + m, xs[0].data_ptr(), 16, xs[0].stride(0), xs[0].stride(1), 1.0, full_lp[b0 + i].data_ptr(), 0)
+        fcalls.append((reqs, k))
+    paths = [("candidates_behind_a_state", lambda: chunks([(cands, K)])), ("prefix_then_candidates", lambda: chunks([(prefix, 1), (cands, K)])),
+             ("whole_scorings", lambda: whole(libs["parent" if args.parent_lib else "here"], fcalls))]
+    chunks([(prefix, 1), (cands, K)])
+    whole(libs["here"], fcalls)
+    torch.cuda.synchronize()
+    assert torch.equal(cand_lp.view(torch.int32), full_lp[:, n:].view(torch.int32)), "the candidates' tails differ from the whole scorings"
+    ms = _timed_rounds(paths, args.rounds)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    res["64 x 256 behind 24000"] = {"whole_scorings_by": "parent" if args.parent_lib else "here", "whole_calls": len(fcalls),
+                                    "ms": {k: [round(x, 3) for x in v] for k, v in ms.items()}, "median_ms": {k: round(v, 3) for k, v in med.items()},
+                                    "whole_over_prefix_then_candidates": round(med["whole_scorings"] / med["prefix_then_candidates"], 2),
+                                    "whole_over_candidates_behind_a_state": round(med["whole_scorings"] / med["candidates_behind_a_state"], 2),
+                                    "bit_equal": True}
+    for lib in libs.values():
+        lib[0].nvw_destroy(lib[1])
     return res
 
 
