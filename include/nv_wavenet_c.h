@@ -203,6 +203,11 @@ void nvw_set_clock_probe(nvw_engine* e, int on);
  * free, loaded from / spilled to the HBM ring at the launch's ends (1-KiB rows).  mode >= 0 (default): as many layers as fit -- a model
  * whose whole ring fits has no ring traffic to HBM during the launch; -1: never.  Same samples either way. */
 void nvw_set_ring_in_lds(nvw_engine* e, int mode);
+/* The dilation schedule compiled into the kernel: a three-tile fp16 launch with packed conditioning of a model whose dilations run
+ * 1 .. 512 in whole cycles of ten layers, with ring slots in LDS, runs a kernel that knows every layer's dilation and slot placement at
+ * compile time (nvw_kernel_info ends in `sched=cycle10`).  mode >= 0 (default): where eligible; -1: never.  Same samples and ring
+ * either way: launches of both kinds mix within an utterance. */
+void nvw_set_compiled_schedule(nvw_engine* e, int mode);
 double nvw_last_launch_clock_ghz(nvw_engine* e);
 /* Samples [init_sample, init_sample + count) of a num_samples-long utterance, asynchronously on `stream`
  * (one chunk of run_chunks, for hosts that drive the chunks themselves); nvw_reset_history starts a new

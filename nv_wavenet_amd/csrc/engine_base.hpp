@@ -43,6 +43,7 @@ struct nvw_engine {
     virtual void setChainTimeoutMs(double) = 0;
     virtual void setClockProbe(bool) = 0;
     virtual void setRingInLds(int) = 0;
+    virtual void setCompiledSchedule(int) = 0;
     virtual double lastLaunchClockGHz() = 0;
     virtual int precisionBits() = 0;
     virtual int maxSamples() = 0;
@@ -208,6 +209,7 @@ struct EngineImpl : nvw_engine {
     void setChainTimeoutMs(double ms) override { eng.setChainTimeoutMs(ms); }
     void setClockProbe(bool on) override { eng.setClockProbe(on); }
     void setRingInLds(int mode) override { eng.setRingInLds(mode); }
+    void setCompiledSchedule(int mode) override { eng.setCompiledSchedule(mode); }
     double lastLaunchClockGHz() override { return eng.lastLaunchClockGHz(); }
     int precisionBits() override { return std::is_same<Td, float>::value ? 32 : 16; }
     int maxSamples() override { return cap; }

@@ -91,6 +91,7 @@ protected:
     int m_num_samples_per_chunk;
     int m_ringSlots;
     int m_ringDirtyTiles;         // leading tiles whose rings launches have written since they were last zero
+    int m_schedMode;              // compiled dilation schedule (wavenet_wg_cs) where a launch is eligible: 0 yes (default), -1 never
     int m_ringLdsMode;            // ring slots of the short dilations in LDS during wavenet_wg launches: 0 as many as fit (default), -1 never
     int m_lastStride;    // row stride of m_yOut in the latest launch (= its num_samples)
 
@@ -269,6 +270,28 @@ protected:
         p = q;
         return bytes;
     }
+    // The kernels with a compiled dilation schedule (wavenet_wg<.., LR, CYC = 10, LD>): the three-tile fp16 dump-free launch with packed
+    // conditioning of a model whose dilations run 1 .. 512 in whole cycles, with the slots of d <= 1 (LD = 1) or d <= 2 (LD = 2) in LDS.
+    // Returns LD for a launch whose ring plan keeps d <= ringD on chip, 0 for a launch that reads its schedule at run time.  (More may
+    // fit than LD = 2 holds: placing fewer layers than fit is always legal; the caller caps the plan to 2^(LD-1).)
+    static constexpr int kCycle = 10;
+    static constexpr bool schedBuilt(int bt, bool dump, int raw) { return F16 && WG3 && bt == 3 && !dump && raw == 0; }
+    int compiledSchedule(int bt, bool dump, int raw, int ringD) const {
+        if (!schedBuilt(bt, dump, raw) || m_schedMode < 0) return 0;
+        if (m_maxDilation != (1 << (kCycle - 1)) || m_numLayers % kCycle != 0 || ringD < 1) return 0;
+        return ringD >= 2 ? 2 : 1;
+    }
+    // caps a ring plan to the layers with d <= D: the LDS slot numbers of the schedule table as placeLdsRing counts them
+    void capLdsRing(wn::Params& p, int D) const {
+        p.ldsRingD = D;
+        int slot = 0;
+        for (int l = 0; l < m_numLayers; l++) {
+            p.dil[l].lds = slot;
+            if (p.dil[l].d <= D) slot += p.dil[l].d;
+        }
+        p.dil[m_numLayers] = p.dil[0];
+        p.dil[m_numLayers + 1] = p.dil[1];
+    }
     template <int BT, bool EMB, bool DUMP, int RAW> bool launchK(wn::Params& p, int tiles, int nEmb, hipStream_t stream) {
         using CB = wn::Cfg<F16, R, S, A, BT>;
         const int grid = (tiles + BT - 1) / BT;
@@ -276,6 +299,15 @@ protected:
         const size_t need = ldsNeed<BT>(m_numLayers, nEmb, DUMP);
         if constexpr (lrBuilt(DUMP, RAW)) {
             const size_t ringBytes = ringPlan<BT>(p, need, DUMP, RAW);
+            if constexpr (schedBuilt(BT, DUMP, RAW)) {
+                const int ld = compiledSchedule(BT, DUMP, RAW, p.ldsRingD);
+                if (ld > 0) {
+                    capLdsRing(p, 1 << (ld - 1));      // (the LDS of the plan stays: no smaller than what the capped one needs)
+                    if (ld == 2) hipLaunchKernelGGL((wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 2>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
+                    else hipLaunchKernelGGL((wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 1>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
+                    return hipGetLastError() == hipSuccess;
+                }
+            }
             if (p.ldsRingD > 0) {
                 hipLaunchKernelGGL((wn::wavenet_wg<F16, R, S, A, BT, EMB, DUMP, RAW, true>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
                 return hipGetLastError() == hipSuccess;
@@ -331,6 +363,12 @@ protected:
             if constexpr (lrBuilt(DUMP, RAW))      // (the whole LDS: what the tables leave free holds ring slots, placeLdsRing)
                 gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg<F16, R, S, A, BT, EMB, DUMP, RAW, true>,
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            if constexpr (schedBuilt(BT, DUMP, RAW)) {
+                gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 1>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+                gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 2>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            }
         }
     }
     template <int BT, bool DUMP> void allowLdsD() {
@@ -491,6 +529,7 @@ public:
         assert(numLayers >= 2 && batchSize > 0 && numSamples > 0 && maxDilation > 0);
         m_ringDirtyTiles = 0;
         m_ringLdsMode = 0;
+        m_schedMode = 0;
         assert(numLayers <= wn::kMaxLayers);
         {
             int dev = 0;
@@ -687,6 +726,9 @@ public:
     // touches the HBM ring at the ends of a launch only; C3 (maxDilation 512) keeps d <= 4 / 2 / 1 / 1 at one / two / three / four tiles
     // per workgroup --; -1: never.  Samples are identical either way (tests/test_parity_gpu.py).
     void setRingInLds(int mode) { m_ringLdsMode = mode < 0 ? -1 : 0; }
+    // The dilation schedule compiled into the kernel (see compiledSchedule): mode >= 0 (default 0): where a launch is eligible; -1: never
+    // (every launch reads its schedule at run time).  Samples and ring are identical either way, so launches of both kinds mix.
+    void setCompiledSchedule(int mode) { m_schedMode = mode < 0 ? -1 : 0; }
     // bound of every hand-off spin of the chain (default 1.5 s)
     void setChainTimeoutMs(double ms) { m_chainTimeoutTicks = (long long)(ms * 1e5); }
 
@@ -1154,8 +1196,11 @@ public:
             lds += rb;
             ringD = q.ldsRingD;
         }
-        char ring[48] = "";
-        if (ringD > 0) snprintf(ring, sizeof(ring), " ring_in_lds=d<=%d", ringD);
+        // compiled dilation schedule (compiledSchedule): its kernels hold d <= 2 at the most
+        const int ld = compiledSchedule(bt, dump, raw, ringD);
+        if (ld > 0) ringD = 1 << (ld - 1);
+        char ring[64] = "";
+        if (ringD > 0) snprintf(ring, sizeof(ring), " ring_in_lds=d<=%d%s", ringD, ld > 0 ? " sched=cycle10" : "");
         snprintf(buf, n, "wn::wavenet_wg<%s,%d,%d,%d,BT=%d,EMBLDS=%d,DUMP=%d,RAW=%d%s> tiles/wg=%d wgs=%d lds=%zu%s",
                  F16 ? "fp16" : "fp32", R, S, A, bt, nEmb, dump ? 1 : 0, raw, ringD > 0 ? ",LR=1" : "", bt, (tiles + bt - 1) / bt, lds, ring);
     }

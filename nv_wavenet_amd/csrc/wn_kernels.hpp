@@ -286,6 +286,16 @@ WN_DEV Dil dil_next(Dil s, int maxDilation, bool wrapToFirst, int ldsD = 0) {
     return n;
 }
 
+// The same entry for a layer whose place in its dilation cycle is a compile-time value (wavenet_wg_cs): layer I of a cycle has
+// d = 2^I, and of its first slots only the cycle's bases are run-time values -- slot (2^I - 1) behind the cycle's first in the HBM ring,
+// and, for the first LD layers of a cycle, which keep their slots in LDS, likewise in the LDS part.  Same member names as Dil: the layer
+// body of wavenet_wg takes either.
+template <int I, int LD> struct DilC {
+    static constexpr int d = 1 << I;
+    int off, lds;
+    WN_DEV DilC(int cycleOff, int cycleLds) : off(cycleOff + (1 << I) - 1), lds(cycleLds + (1 << (I < LD ? I : LD)) - 1) {}
+};
+
 // Everything the kernel needs, passed by value (role of nv_wavenet_params, nv_wavenet.cuh:40-85).
 struct Params {
     const void* wblob;       // NW per-wave streams: [L][FLW] layer fragments | [FHW] head fragments
@@ -922,14 +932,14 @@ template <bool F16> WN_DEV void cond_add(floatx4* a, typename Prec<F16>::frag c,
 // its uniform branches are in every layer, whether the layer's slots are in LDS or not.  Measured on one box, arms alternating, C3 at
 // three tiles per workgroup and 12 288 utterances (LABNOTES, "Exchange images on the head's image"): ring in HBM 37.6 us per sample,
 // d <= 1 in LDS (two layers of twenty) 37.2, d <= 2 (four layers, with the in-place slots of Cfg::OVERLAY) 36.7.
-template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP = true, int RAW = 0, bool LR = false>
-// (WN_EXP_TWO_WG, experiment build of round 6: the one-tile kernel with a register budget that lets TWO workgroups share a CU -- two waves per
-//  SIMD, each with its own tile and its own weight stream; the A/B the round-5 review asked for at 8 192 utterances.  LABNOTES round 6.)
-#ifdef WN_EXP_TWO_WG
-__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), (BT == 1 ? 2 : 1)) void wavenet_wg(const Params p) {
-#else
-__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_wg(const Params p) {
-#endif
+// CYC, LD (wavenet_wg_cs): the dilation schedule compiled in.  CYC > 0: the model's dilations run 1 .. 2^(CYC-1) in L / CYC whole cycles and
+// the first LD layers of every cycle (d <= 2^(LD-1) = Params::ldsRingD) keep their slots in LDS; the sample's layers then are a run-time loop
+// over the cycles whose body is the CYC layers one behind the other, each with its dilation, its slots' places inside the cycle, the
+// placement (LDS or HBM) of its own and the next two layers' slots and its register-set parity as constants.  0: the schedule is read at
+// run time (Dil entries travelling with a layer-pair loop).  One body for both: `layer` below takes its schedule entries as Dil or as DilC.
+// Same barriers, same stream order, same refill and request points, same summation order: samples and ring are bit-identical.
+template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP, int RAW, bool LR, int CYC, int LD>
+WN_DEV void wavenet_wg_body(const Params& p) {
     constexpr bool FEAT = RAW == 3;
     constexpr int KFC = FEAT ? feat_kfc<F16>() : 0;
     using C = Cfg<F16, R, S, A, BT, KFC>;
@@ -952,6 +962,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
     float* const biasLds = (float*)(lds + C::OFF_BIAS);
 
     static_assert(RAW == 0 || RAW == 1 || (RAW == 2 && F16) || RAW == 3, "RAW: 0 packed, 1 fp32 in place, 2 fp16 in place (fp16 engine), 3 features");
+    static_assert(CYC == 0 || (LR && !DUMP && LD >= 1 && LD <= CYC - 2 && CYC % 2 == 0), "compiled schedule: an LR kernel with an even cycle, its first LD layers' slots in LDS");
     if (p.gate != nullptr && __builtin_nontemporal_load(p.gate) == 0u) return;   // (a fallback launch that is not needed)
 
     const int tid = threadIdx.x;
@@ -1099,7 +1110,8 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
     const rsrc_t rsRing = make_rsrc(ringMine);
     const unsigned ringTileB = (unsigned)ringTile;
     // the part of the ring that is in LDS for the length of the launch (see ring_lds_copy below): layers with dilation <= ldsD
-    const int ldsD = LR ? p.ldsRingD : 0;
+    // (compiled schedule: the launcher sets p.ldsRingD = 2^(LD-1))
+    const int ldsD = CYC > 0 ? 1 << (LD > 0 ? LD - 1 : 0) : LR ? p.ldsRingD : 0;
     // (slot -> place: Cfg::ringSlotOffset, whose first slot follows the tables)
     char* const ringLds = lds + C::ringSlotOffset(0, (int)C::ldsBytes(L, EMBLDS ? p.embLds : 0, DUMP));
     const char* condNext = condMine + (size_t)p.initSample * L * condStride;
@@ -1113,8 +1125,9 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
     unsigned rawOff[BT];
 #pragma unroll
     for (int bt = 0; bt < BT; bt++) rawOff[bt] = ((unsigned)ub[bt] * (unsigned)(2 * R) + (unsigned)g * 4u) * RAWE;
-    auto prefetch = [&](int tn, int ln, Dil dl, frag (&xd)[BT][XPW], frag (&cdd)[BT][CR]) {
-        if (ln >= L) { ln -= L; tn += 1; }
+    // (wraps: ln is past the last layer -- the layer is ln - L of sample tn + 1; a run-time value or std::false_type)
+    auto prefetch = [&](int tn, int ln, auto wraps, const auto dl, frag (&xd)[BT][XPW], frag (&cdd)[BT][CR]) {
+        if (wraps) { ln -= L; tn += 1; }
         const unsigned slot = (unsigned)(dl.off + (tn & (dl.d - 1)));
         const unsigned rp0 = slot * (unsigned)(KF_R * 1024);
         const rsrc_t rsCond = make_rsrc(condNext);
@@ -1184,13 +1197,13 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
         }
     };
     ring_lds_copy(std::true_type{});
-    prefetch(p.initSample, 0, p.dil[0], xpA, cdA);
-    prefetch(p.initSample, 1, p.dil[1], xpB, cdB);
+    prefetch(p.initSample, 0, std::false_type{}, p.dil[0], xpA, cdA);
+    prefetch(p.initSample, 1, L <= 1, p.dil[1], xpB, cdB);
     // publish this wave's fragments of the NEXT layer's dilated tap to LDS.  Before the start (t < d) the tap is zero (reference
     // :287): the ring slot read then has not been written in this utterance, and the engine clears the rings when a new utterance
     // is handed over (nvWavenetInfer::resetHistory / clearRings), so the load itself brings the zeros -- no branch here.
     // (dN: schedule entry of the layer the tap belongs to -- its slots in LDS need no publication)
-    auto publish_xp = [&](const frag (&xpN)[BT][XPW], const Dil dN) {
+    auto publish_xp = [&](const frag (&xpN)[BT][XPW], const auto dN) {
         if (dN.d <= ldsD) return;
 #pragma unroll
         for (int i = 0; i < XPW; i++) {
@@ -1202,7 +1215,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
         }
     };
     // where the waves read the tap of (layer dN, sample tn) as B fragments: its ring slot in LDS, or the tap image
-    auto tap_image = [&](const Dil dN, int tn) -> const char* {
+    auto tap_image = [&](const auto dN, int tn) -> const char* {
         return dN.d <= ldsD ? ringLds + (size_t)(dN.lds + (tn & (dN.d - 1))) * C::RING_SLOT : xpbuf;
     };
     publish_xp(xpA, p.dil[0]);   // layer 0 (d = 1) of the first sample
@@ -1341,7 +1354,10 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
         // (xpC, cdC): register set of this layer's parity: both were consumed during the previous layer (tap
         // published, conditioning added), the prefetch for layer l+2 refills them; (xpN, cdN): the other set,
         // holding tap and conditioning of layer l+1.  dN: dilation of layer l+1, tN: the sample it belongs to.
-        auto layer = [&](auto withSkip, const int l, const Dil dl, const Dil dN, const Dil dl2, frag (&xpC)[BT][XPW],
+        // dl, dN, dl2: schedule entries of layers l, l+1, l+2, run-time values (Dil) or, in a kernel with a compiled schedule, entries
+        // whose dilation is a constant (DilC): every test of a dilation below then folds.  wrapN, wrap2: layer l+1 / l+2 is layer 0 / 0 or 1
+        // of sample t+1 (run-time values, or std::false_type where the place in the cycle rules it out).
+        auto layer = [&](auto withSkip, const int l, auto wrapN, auto wrap2, const auto dl, const auto dN, const auto dl2, frag (&xpC)[BT][XPW],
                          frag (&cdC)[BT][CR], const frag (&xpN)[BT][XPW], const frag (&cdN)[BT][CR]) {
             constexpr bool SKIP = decltype(withSkip)::value;
             // fragment positions (Cfg::P_*) count from the start of the part of layer l-1; layer 0 (the instance without a
@@ -1352,7 +1368,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
             constexpr int PB = SKIP ? 0 : FLW;
             const int wl = SKIP ? (l - 1) * FLW : 0;
             const float* bl = biasLds + l * BLS;
-            const int lN = l + 1 < L ? l + 1 : 0;
+            const int lN = wrapN ? 0 : l + 1;
             const float* blN = biasLds + lN * BLS;
             const int d = dl.d;
 
@@ -1382,7 +1398,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                         for (int bt = 0; bt < BT; bt++) xkeep[bt][k / NW] = xb[bt][k];
                     }
             }
-            if constexpr (!SKIP) prefetch(t, l + 2, dl2, xpC, cdC);      // (layer 0 has no skip GEMM under its gate)
+            if constexpr (!SKIP) prefetch(t, l + 2, wrap2, dl2, xpC, cdC);      // (layer 0 has no skip GEMM under its gate)
             __builtin_amdgcn_sched_barrier(0);
             WN_TMARK(2)
 
@@ -1442,7 +1458,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                     if constexpr (!EARLY || fi == NFS + NFC - 1) refill_group<F16, PF, 0, ws_pin, 1>(ws, rsW, pos, wl, 0, laneOff);
                     // dilated tap of layer l+2 (HBM) into the register set this layer has finished with (see the packed path below)
                     if constexpr (SKIP && fi == (NFS + NFC) * WN_REQ_AT_FEAT / 8) {
-                        prefetch(t, l + 2, dl2, xpC, cdC);
+                        prefetch(t, l + 2, wrap2, dl2, xpC, cdC);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 });
@@ -1509,7 +1525,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
                         // such stretch of a layer (issued right behind the current-tap GEMM instead: 34.2 instead of
                         // 31.7 us per sample at 8192 utterances, 41.9 instead of 39.7 at 12 288).
                         if constexpr (gi == (STW * KF_R / G) * WN_REQ_AT / 8) {
-                            prefetch(t, l + 2, dl2, xpC, cdC);
+                            prefetch(t, l + 2, wrap2, dl2, xpC, cdC);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     });
@@ -1607,7 +1623,7 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
             WN_TMARK(7)
             // the next layer's tap and x fragments are requested; the dilated-tap GEMM runs while the latter come back
             frag xp[BT][KF_R];
-            const char* const tapImg = tap_image(dN, l + 1 < L ? t : t + 1);
+            const char* const tapImg = tap_image(dN, wrapN ? t + 1 : t);
 #pragma unroll
             for (int bt = 0; bt < BT; bt++) lds_get_frags<F16, KF_R>(tapImg + bt * KF_R * 1024, lane, xp[bt]);
 #pragma unroll
@@ -1615,22 +1631,61 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
             __builtin_amdgcn_sched_barrier(0);
             gemm_b<F16, PF, 0, BT, 2 * HTW, KF_R>(ws, rsW, C::P_PREV - PB, wl, 0, laneOff, acc, xp);
         };
-        {
+        if constexpr (CYC > 0) {
+            // Compiled schedule: a run-time loop over the L / CYC dilation cycles, its body the CYC layers one behind the other.  Layer i
+            // of a cycle knows its dilation, its slots' places inside the cycle, which of layers i .. i+2 have their slots in LDS and its
+            // register-set parity (CYC is even); per cycle only the bases advance.  Run-time, each at one place of the cycle: layer 0 of
+            // the first cycle runs without a skip GEMM, the last cycle's last layers pair with layers 0, 1 of sample t+1, and the slot
+            // index t & (d - 1).
+            constexpr int SLOTS = (1 << CYC) - 1, LSLOTS = (1 << LD) - 1;      // ring slots of a cycle: all of them, those in LDS
+            int ro = 0, lo = 0;                                                // first slot of the cycle: in the HBM ring, in LDS
+            for (int c0 = 0; c0 < L; c0 += CYC) {
+                const bool last = c0 + CYC >= L;
+                const int roN = last ? 0 : ro + SLOTS, loN = last ? 0 : lo + LSLOTS;      // ... of the cycle that follows
+                static_for<CYC>([&](auto I) {
+                    constexpr int i = decltype(I)::value;
+                    auto entry = [&](auto J) {
+                        constexpr int jj = decltype(J)::value;
+                        if constexpr (jj < CYC) return DilC<jj, LD>(ro, lo);
+                        else return DilC<jj - CYC, LD>(roN, loN);
+                    };
+                    auto wraps = [&](auto J) {
+                        if constexpr (decltype(J)::value < CYC) return std::false_type{};
+                        else return last;
+                    };
+                    const auto dl = entry(I);
+                    const auto dN = entry(std::integral_constant<int, i + 1>{});
+                    const auto dl2 = entry(std::integral_constant<int, i + 2>{});
+                    const auto wrapN = wraps(std::integral_constant<int, i + 1>{});
+                    const auto wrap2 = wraps(std::integral_constant<int, i + 2>{});
+                    auto run = [&](auto withSkip) {
+                        if constexpr (i % 2 == 0) layer(withSkip, c0 + i, wrapN, wrap2, dl, dN, dl2, xpA, cdA, xpB, cdB);
+                        else layer(withSkip, c0 + i, wrapN, wrap2, dl, dN, dl2, xpB, cdB, xpA, cdA);
+                    };
+                    if constexpr (i == 0) {
+                        if (c0 == 0) run(std::false_type{});
+                        else run(std::true_type{});
+                    } else run(std::true_type{});
+                });
+                ro = roN;
+                lo = loN;
+            }
+        } else {
             // schedule entries of layers l, l+1, l+2 (the latter two may be layers 0, 1 of the next sample: table entries L, L+1)
             // the three schedule entries travel with the loop (scalar arithmetic: the scalar LOADS of the table in the kernel arguments
             // return out of order, so every LDS wait near one became an lgkmcnt(0); round 4)
             Dil da = dil_first(), db = dil_next(da, p.maxDilation, L == 1, ldsD), dc = dil_next(db, p.maxDilation, L == 2, ldsD);
             auto adv = [&](int l) { da = db; db = dc; dc = dil_next(dc, p.maxDilation, l + 3 == L, ldsD); };
-            layer(std::false_type{}, 0, da, db, dc, xpA, cdA, xpB, cdB);
+            layer(std::false_type{}, 0, 1 >= L, 2 >= L, da, db, dc, xpA, cdA, xpB, cdB);
             adv(0);
             int l = 1;
             for (; l + 1 < L; l += 2) {
-                layer(std::true_type{}, l, da, db, dc, xpB, cdB, xpA, cdA);
+                layer(std::true_type{}, l, l + 1 >= L, l + 2 >= L, da, db, dc, xpB, cdB, xpA, cdA);
                 adv(l);
-                layer(std::true_type{}, l + 1, da, db, dc, xpA, cdA, xpB, cdB);
+                layer(std::true_type{}, l + 1, l + 2 >= L, l + 3 >= L, da, db, dc, xpA, cdA, xpB, cdB);
                 adv(l + 1);
             }
-            if (l < L) layer(std::true_type{}, l, da, db, dc, xpB, cdB, xpA, cdA);
+            if (l < L) layer(std::true_type{}, l, l + 1 >= L, l + 2 >= L, da, db, dc, xpB, cdB, xpA, cdA);
             if (L & 1) {
                 // odd layer count: layer 0 of the next sample was prefetched into the odd set
 #pragma unroll
@@ -1834,6 +1889,22 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
         p.clk[2] = __builtin_amdgcn_s_memtime();
         p.clk[3] = __builtin_amdgcn_s_memrealtime();
     }
+}
+template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP = true, int RAW = 0, bool LR = false>
+// (WN_EXP_TWO_WG, experiment build of round 6: the one-tile kernel with a register budget that lets TWO workgroups share a CU -- two waves per
+//  SIMD, each with its own tile and its own weight stream; the A/B the round-5 review asked for at 8 192 utterances.  LABNOTES round 6.)
+#ifdef WN_EXP_TWO_WG
+__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), (BT == 1 ? 2 : 1)) void wavenet_wg(const Params p) {
+#else
+__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_wg(const Params p) {
+#endif
+    wavenet_wg_body<F16, R, S, A, BT, EMBLDS, DUMP, RAW, LR, 0, 0>(p);
+}
+// ... and with the dilation schedule compiled in (CYC, LD above): the dump-free LR kernel with packed conditioning.  A kernel of its own
+// name, so that the kernels with a run-time schedule keep theirs.
+template <bool F16, int R, int S, int A, int BT, bool EMBLDS, int CYC, int LD>
+__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_wg_cs(const Params p) {
+    wavenet_wg_body<F16, R, S, A, BT, EMBLDS, false, 0, true, CYC, LD>(p);
 }
 
 // mu-law expansion of the generated indices to int16 PCM (pytorch/utils.py:62-70 +

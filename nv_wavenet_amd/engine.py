@@ -334,6 +334,12 @@ class WavenetEngine:
         as fit in LDS; -1 = never.  Same samples either way."""
         lib.nvw_set_ring_in_lds(self._h, int(mode))
 
+    def setCompiledSchedule(self, mode=0):
+        """The dilation schedule compiled into the kernel: mode >= 0 (default) = eligible launches (three tiles, fp16, packed conditioning,
+        maxDilation 512, whole cycles of ten layers, ring slots in LDS) run it, kernelInfo then ends in `sched=cycle10`; -1 = never.  Same
+        samples either way."""
+        lib.nvw_set_compiled_schedule(self._h, int(mode))
+
     def setClockProbe(self, on=True):
         """Measurement aid: workgroup 0 of every wavenet_wg launch that follows records shader and wall clock counters."""
         lib.nvw_set_clock_probe(self._h, 1 if on else 0)

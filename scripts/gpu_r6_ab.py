@@ -4,7 +4,7 @@ given batches: us per sample, kHz per utterance, the clock the launch ran at, so
 gpu_metrics table while the launch repeats for `--seconds`), and a checksum of the samples of a small O(1) run (an experiment build
 must reproduce the shipped library's unless it says why not).  Appends JSON lines to gpurun_out/r6_ab.jsonl.
 
-usage: NVW_LIB=... gpu_r6_ab.py <tag> [--batches 12288,16384] [--mode packed|features] [--org 0] [--seconds 3]
+usage: NVW_LIB=... gpu_r6_ab.py <tag> [--batches 12288,16384] [--mode packed|features] [--org 0] [--seconds 3] [--ring 0] [--sched 0]
 """
 import argparse
 import json
@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--no-power", action="store_true")
     ap.add_argument("--crc-modes", default="wg3")
     ap.add_argument("--ring", type=int, default=0, help="nvw_set_ring_in_lds mode of the timed launches (1: as many short-dilation layers as fit)")
+    ap.add_argument("--sched", type=int, default=0, help="nvw_set_compiled_schedule mode of the timed launches (0: the compiled dilation schedule where eligible, -1: never)")
     args = ap.parse_args()
     import torch
     import bench
@@ -56,10 +57,11 @@ def main():
         e, N, keep = bench.steady_engine(w, B, n, 11, None if args.mode == "packed" else args.mode, organisation=args.org)
         e.setClockProbe(True)
         e.setRingInLds(args.ring)
+        e.setCompiledSchedule(args.sched)
         ms = min(bench.time_range(e, bench.STEADY_FROM, n, N, B) for _ in range(3))
         ghz = e.lastLaunchClockGHz()
         info = e.kernelInfo(B, False)
-        rec = dict(tag=args.tag, ring=args.ring, lib=os.environ.get("NVW_LIB", "shipped"), B=B, mode=args.mode, us_per_sample=round(1e3 * ms / n, 3), khz=round(n / ms, 3),
+        rec = dict(tag=args.tag, ring=args.ring, sched=args.sched, lib=os.environ.get("NVW_LIB", "shipped"), B=B, mode=args.mode, us_per_sample=round(1e3 * ms / n, 3), khz=round(n / ms, 3),
                    msamples_per_s=round(B * n / ms / 1e3, 1), clock_ghz=round(ghz, 3), cycles_per_sample=round(1e3 * ms / n * ghz * 1e3), kernel=info, crc=crc)
         if not args.no_power:
             stream = torch.cuda.current_stream().cuda_stream
