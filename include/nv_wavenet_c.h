@@ -448,6 +448,40 @@ int nvw_set_temperatures(nvw_engine* e, const float* T, int n);
 int nvw_slot_set_temperature(nvw_engine* e, int slot, float T);
 float nvw_slot_temperature(nvw_engine* e, int slot);
 
+/* PROBABILITY FLOOR (MIN-P) PER UTTERANCE, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  The second sampling control: a column
+ * with floor p draws from its TEMPERED distribution (temperature first, then floor) without the bins whose probability is below p
+ * times that of the most probable bin, renormalised.  In the kernel: after e = exp2(x c - m c) -- which is prob / max prob up to the
+ * rounding of m c -- a bin with e < p gets e = 0 before the sum, the scan and the row search; nothing else changes.  p is finite and in
+ * [0, 0.5]; p = 0 keeps every bin and is bit-identical to a run without these calls; 0.5 is where the guarantee ends that the most
+ * probable bin survives the rounding of m c.  A forced sample (a prime) stays forced.  nvw_get_p reports the floored, renormalised
+ * probabilities (dropped bins read exactly 0), nvw_get_za the raw logits.  Scoring (nvw_score_*) is NOT changed: it stays the model's
+ * own distribution.  Top-k and top-p are not offered (they need a sort in the sample loop); greedy decoding is still not offered:
+ * ties at the maximum are drawn between.  A launch with no floor in force executes the same instructions per logit as before; one
+ * with a floor in force adds a compare and a select per logit.
+ * This extends the contract of slot mode once more: an utterance's samples depend on its features (or frames), its uid, the seed,
+ * the model, the temperature AND THE FLOOR IN FORCE AT EACH LOCAL SAMPLE -- and on nothing else.
+ *   nvw_set_min_p       lockstep: column b < n at floor p[b] (host array, 1 <= n <= batch) in the runs that follow; columns past n,
+ *                       and every column with p == NULL, at 0.  In force across nvw_set_features, nvw_set_mel, nvw_reset_history
+ *                       and between nvw_run_partial / nvw_run_range chunks until the next call; a call between two chunks takes
+ *                       effect at the next chunk.  Independent of nvw_set_temperatures: neither call resets the other's values.
+ *                       While any column's floor is not 0, a run on packed or in-place conditioning or on a multi-CU (chain) engine
+ *                       not on the features path prints one line and returns 0.  Synchronises.  0 when refused (in slot mode, n out
+ *                       of range, a bad value); nothing changes.
+ *   nvw_slot_set_min_p  slot mode: the utterance of column `slot` draws with floor p from the next step on, from that step's first
+ *                       sample.  nvw_slot_start / _start_mel put the column back to 0, so the order is start, then set;
+ *                       nvw_slots_begin and nvw_slots_end put every column back to 0.  nvw_slot_move, the saves and the resumes
+ *                       carry the value: a blob holds it in word 11 of its header as the bits of the float, all-zero bits for 0, so
+ *                       blobs of utterances at floor 0 are byte for byte what they were; a resume refuses a header whose word 11 is
+ *                       neither zero nor a valid floor.  The blobs that nvw_prefill_* and the scoring chunks write leave word 11
+ *                       zero: set the floor after resuming from one.  The step's one small launch that writes changed temperatures
+ *                       writes the changed floors as well.  0 when refused (not in slot mode, slot out of range, a column without
+ *                       an utterance or a pending start or resume, a bad value); nothing changes.
+ *   nvw_slot_min_p      the value in force for column `slot` (host state); -1 when the column holds no utterance (0 is a valid
+ *                       floor). */
+int nvw_set_min_p(nvw_engine* e, const float* p, int n);
+int nvw_slot_set_min_p(nvw_engine* e, int slot, float p);
+float nvw_slot_min_p(nvw_engine* e, int slot);
+
 /* PRIMED GENERATION: FORCED SAMPLE PREFIXES, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  An utterance may carry a prime, n
  * sample indices y[0 .. n) in 0 .. A-1: its local sample k < n IS y[k] -- written to the outputs (samples, PCM, ragged pieces) like
  * any other, fed back into the history and through the embeddings, so the rings evolve exactly as if it had been drawn --, and its

@@ -104,6 +104,9 @@ SIGNATURES = {
     "nvw_set_temperatures": (C.c_int, [C.c_void_p, _fp, C.c_int]),
     "nvw_slot_set_temperature": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "nvw_slot_temperature": (C.c_float, [C.c_void_p, C.c_int]),
+    "nvw_set_min_p": (C.c_int, [C.c_void_p, _fp, C.c_int]),
+    "nvw_slot_set_min_p": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "nvw_slot_min_p": (C.c_float, [C.c_void_p, C.c_int]),
     "nvw_set_prime": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_longlong]),
     "nvw_slot_prime": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
     "nvw_slot_primed": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1245,14 +1245,36 @@ public:
                 if (!wn::temperature_ok(T[b])) return false;
         }
         gpuErrChk(hipDeviceSynchronize());
-        m_temps.reset(false);
-        if (T == NULL) return true;
-        for (int b = 0; b < n; b++) m_temps.set(b, T[b]);
+        m_temps.resetT();
+        for (int b = 0; T != NULL && b < n; b++) m_temps.set(b, T[b]);
         m_temps.upload();
         return true;
     }
     // the temperature in force for column b (1 when none was ever set)
     float temperature(int b) const { return m_temps.get(b); }
+
+    // ---- probability floor, min-p (beyond the reference; slots_sampler.hpp) ----------------------------------------
+    // Column b of the runs that follow draws from its tempered distribution WITHOUT the bins whose probability is below minP[b] times
+    // that of the most probable bin, renormalised; b < n; the columns past n, and all of them with minP == NULL, from the whole
+    // distribution as before.  minP: a host array, 1 <= n <= maxBatch, every value finite and in [0, 0.5].  Everything else as
+    // setTemperatures: in force until the next call, a call between two chunks takes effect at the next chunk, only the features
+    // path honours it and the other paths refuse while any floor is not 0; floor 0 is bit-identical to never having called this.
+    // Synchronises.  false (nothing changes): in slot mode (slotSetMinP is the call there), n outside the batch, or a bad value.
+    bool setMinP(const float* minP, int n) {
+        if (m_slots->active()) return false;
+        if (minP != NULL) {
+            if (n < 1 || n > m_maxBatch) return false;
+            for (int b = 0; b < n; b++)
+                if (!wn::min_p_ok(minP[b])) return false;
+        }
+        gpuErrChk(hipDeviceSynchronize());
+        m_temps.resetP();
+        for (int b = 0; minP != NULL && b < n; b++) m_temps.setP(b, minP[b]);
+        m_temps.upload();
+        return true;
+    }
+    // the floor in force for column b (0 when none was ever set)
+    float minP(int b) const { return m_temps.getP(b); }
 
     // ---- primed generation (beyond the reference; slots_prime.hpp) -------------------------------------------------
     // Column b < batch of the runs that follow starts with the forced samples y[b * stride + k], k < n[b] (0 <= n[b] <= maxN <=
@@ -1602,6 +1624,12 @@ public:
             return false;
         }
 
+        if (m_temps.nonZero > 0 && !m_featPtr) {
+            fprintf(stderr, "nvWavenetInfer: %d columns have a probability floor (min-p) other than 0, which packed or in-place "
+                    "conditioning and multi-CU launches cannot honour: use the features path, or setMinP(NULL, 0)\n", m_temps.nonZero);
+            return false;
+        }
+
         if (m_prime.any() && !m_featPtr) {
             fprintf(stderr, "nvWavenetInfer: %d columns carry a prime, which packed or in-place conditioning and multi-CU launches cannot "
                     "honour: use the features path, or setPrime(NULL, ..)\n", m_prime.primed);
@@ -1639,6 +1667,7 @@ public:
         p.dump = dumpActivations ? 1 : 0;
         p.useRng = m_useRng ? 1 : 0;
         p.softScale = m_featPtr ? m_temps.softScale : NULL;
+        p.floorOn = (m_featPtr && m_temps.nonZero > 0) ? 1 : 0;      // (a floor other than 0 has made the table)
         m_lastStride = num_samples;
         if (p.count <= 0) return true;
         bool primeOk = true;
@@ -1789,6 +1818,7 @@ protected:
         p.dump = 0;
         p.useRng = 0;
         p.softScale = m_temps.softScale;
+        p.floorOn = m_temps.nonZero > 0 ? 1 : 0;      // (a floor other than 0 has made the table)
         p.forced = forced ? 1 : 0;
         return launchWg(p, tiles, stream);
     }
@@ -1818,6 +1848,7 @@ protected:
         p.tanhEmbed = m_tanhEmbed ? 1 : 0;
         p.embLds = 0;
         p.forced = 0;
+        p.floorOn = 0;
         p.rngKey0 = (unsigned)m_rngSeed;
         p.rngKey1 = (unsigned)(m_rngSeed >> 32);
         p.clk = m_clkOn ? m_clk : NULL;

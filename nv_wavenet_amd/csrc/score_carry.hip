@@ -231,9 +231,10 @@ char* blobTarget(const void* p, size_t bytes, bool* pinned) {
 }
 
 bool headerFits(const ScoreModel& m, const SlotStateHeader& h) {
-    float T;      // (word 10: zero, or the bits of a valid temperature)
+    float T, P;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid probability floor)
     return h.magic == kSlotStateMagic && h.version == kSlotStateVersion && h.precision == (m.f16 ? 16 : 32) && h.R == m.R &&
-           h.numLayers == m.numLayers && h.maxDilation == m.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T);
+           h.numLayers == m.numLayers && h.maxDilation == m.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T) &&
+           min_p_of_word(h.pad[1], P);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
-// slots_sampler.hip -- the kernel that writes the changed columns' softmax scales into the engine's table (slots_sampler.hpp).
-// Compiled once, both precisions.  At most maxBatch entries of 8 bytes per step: one thread per entry.
+// slots_sampler.hip -- the kernel that writes the changed columns' softmax scales and probability floors into the engine's table
+// (slots_sampler.hpp).  Compiled once, both precisions.  At most 2 maxBatch entries of 8 bytes per step: one thread per entry.
 #include "slots_sampler.hpp"
 
 #include "gpu_check.hpp"
@@ -9,23 +9,34 @@ namespace wn {
 TemperatureTable::~TemperatureTable() {
     if (softScale) gpuErrChk(hipFree(softScale));
 }
+void TemperatureTable::make() {
+    std::vector<float> unit(2 * (size_t)columns, 0.0f);
+    for (int b = 0; b < columns; b++) unit[b] = kSoftScaleUnit;
+    gpuErrChk(hipMalloc(&softScale, unit.size() * sizeof(float)));
+    gpuErrChk(hipMemcpy(softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+}
 void TemperatureTable::set(int b, float t) {
     if (T.empty()) {
         if (t == 1.0f) return;
         T.assign(columns, 1.0f);
     }
-    if (t != 1.0f && !softScale) {
-        std::vector<float> unit(columns, kSoftScaleUnit);
-        gpuErrChk(hipMalloc(&softScale, unit.size() * sizeof(float)));
-        gpuErrChk(hipMemcpy(softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if (t != 1.0f && !softScale) make();
     nonUnit += (t != 1.0f) - (T[b] != 1.0f);
     T[b] = t;
 }
+void TemperatureTable::setP(int b, float p) {
+    if (P.empty()) {
+        if (p == 0.0f) return;
+        P.assign(columns, 0.0f);
+    }
+    if (p != 0.0f && !softScale) make();
+    nonZero += (p != 0.0f) - (P[b] != 0.0f);
+    P[b] = p;
+}
 void TemperatureTable::reset(bool deviceBehind) {
-    const bool rewrite = softScale && (nonUnit > 0 || deviceBehind);
-    T.clear();
-    nonUnit = 0;
+    const bool rewrite = softScale && (nonUnit > 0 || nonZero > 0 || deviceBehind);
+    resetT();
+    resetP();
     if (rewrite) {
         gpuErrChk(hipDeviceSynchronize());
         upload();
@@ -33,8 +44,11 @@ void TemperatureTable::reset(bool deviceBehind) {
 }
 void TemperatureTable::upload() {
     if (!softScale) return;
-    std::vector<float> c(columns);
-    for (int b = 0; b < columns; b++) c[b] = temperature_scale(get(b));      // (T is empty when every value is 1)
+    std::vector<float> c(2 * (size_t)columns);
+    for (int b = 0; b < columns; b++) {
+        c[b] = temperature_scale(get(b));      // (T is empty when every value is 1, P when every floor is 0)
+        c[columns + b] = getP(b);
+    }
     gpuErrChk(hipMemcpy(softScale, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 

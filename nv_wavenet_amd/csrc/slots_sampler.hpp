@@ -1,10 +1,13 @@
-// slots_sampler.hpp -- the sampling temperature of every column.
+// slots_sampler.hpp -- the sampling temperature and the probability floor (min-p, §6m) of every column.
 //
 // The generation kernel's softmax computes exp2(x c - m c) with c = log2(e) / T (softmax_pick; Params::softScale, [maxBatch] floats
 // on the device, read by wavenet_wg<.., RAW = 3>).  The host keeps T per column and is the authority; the device table follows it:
 // a lockstep caller uploads it whole (setTemperatures), a slot-mode step whose columns changed -- starts, sets, moves, resumes --
 // scatters {column, c} pairs into it with one small launch ahead of the generation launch.  T = 1 gives c = log2(e) exactly, and
 // for T a power of two c and m c are exact scalings: the samples are those of the same model with Wza / T and Bza / T.
+// The floor tau of a column drops the bins whose tempered probability is below tau times that of the most probable bin: the kernel
+// zeroes e = exp2(x c - m c) < tau before the sum (softmax_pick).  The floors are the second half of the same table,
+// softScale[columns + b], read only by a launch whose Params::floorOn is set; they travel exactly as the scales do.
 // The kernel (slots_sampler.hip) is compiled once for both precisions.
 #pragma once
 
@@ -37,9 +40,27 @@ inline bool temperature_of_word(int w, float& T) {
     return temperature_ok(T);
 }
 
+// The probability floor: finite and within [0, 0.5] (a NaN fails both comparisons).  0.5 is where the guarantee ends that the most
+// probable bin survives: its e is 2^(rounding error of m c), at least 2^-0.5 while |m c| < 2^23.
+constexpr float kMinPMax = 0.5f;
+inline bool min_p_ok(float p) { return p >= 0.0f && p <= kMinPMax; }
+// The word that carries the floor in a state blob (SlotStateHeader::pad[1]): the bits of the float; 0 (and -0) is all-zero bits.
+inline int min_p_word(float p) {
+    int w = 0;
+    if (p != 0.0f) memcpy(&w, &p, sizeof(w));
+    return w;
+}
+// false: the word is neither zero nor a valid floor (the bits of -0 among them: min_p_word never writes them)
+inline bool min_p_of_word(int w, float& p) {
+    p = 0.0f;
+    if (w == 0) return true;
+    memcpy(&p, &w, sizeof(p));
+    return min_p_ok(p) && p != 0.0f;
+}
+
 // The table itself, lockstep and slot mode: the host's values are the authority, the device table follows them.  Nothing is
-// allocated, and Params::softScale stays NULL, until a temperature other than 1 has been set: an engine that never uses the
-// feature launches what it launched before.
+// allocated, and Params::softScale stays NULL, until a temperature other than 1 or a floor other than 0 has been set: an engine that
+// uses neither launches what it launched before.  The device table is [2][columns]: the scales, then the floors.
 struct TemperatureTable {
     explicit TemperatureTable(int columns) : columns(columns) {}
     ~TemperatureTable();
@@ -48,27 +69,38 @@ struct TemperatureTable {
     float get(int b) const { return (b >= 0 && b < (int)T.size()) ? T[b] : 1.0f; }
     // the host's value of column b; the first value other than 1 makes the device table (filled with log2(e); synchronises)
     void set(int b, float t);
-    // every column back to T = 1, on the host and in the table (synchronises when the table has to be rewritten: a value other
-    // than 1 is in force, or deviceBehind -- the table holds values the host has since taken back)
+    // the floor in force for column b (0 when none was ever set); the first value other than 0 makes the device table likewise
+    float getP(int b) const { return (b >= 0 && b < (int)P.size()) ? P[b] : 0.0f; }
+    void setP(int b, float p);
+    // every column back to T = 1 and floor 0, on the host and in the table (synchronises when the table has to be rewritten: a
+    // value other than these is in force, or deviceBehind -- the table holds values the host has since taken back)
     void reset(bool deviceBehind);
+    // the host's temperatures / floors alone back to 1 / 0 (the caller uploads)
+    void resetT() { T.clear(), nonUnit = 0; }
+    void resetP() { P.clear(), nonZero = 0; }
     // the whole table from the host's values, when it exists (blocking copy)
     void upload();
 
     const int columns;
     std::vector<float> T;                   // [columns] T per column (empty: 1 everywhere)
     int nonUnit = 0;                        // columns with T != 1
-    float* softScale = NULL;                // [columns] log2(e) / T on the device, made at the first use and filled with log2(e)
+    std::vector<float> P;                   // [columns] floor per column (empty: 0 everywhere)
+    int nonZero = 0;                        // columns with a floor != 0
+    float* softScale = NULL;                // [2][columns] on the device, made at the first use: log2(e) / T, filled with log2(e); then
+                                            // the floors, filled with 0
+private:
+    void make();
 };
 
-// one changed column of a step
+// one changed table entry of a step
 struct SlotScale {
-    int column;
-    float scale;             // log2(e) / T
+    int column;              // the entry: b for the scale of column b, columns + b for its floor
+    float scale;             // log2(e) / T, or the floor
 };
 static_assert(sizeof(SlotScale) == 8, "SlotScale layout");
 
-// table[upd[i].column] = upd[i].scale for the n entries (device memory; columns pairwise distinct, each below `columns`; an entry
-// outside the table is skipped).  Asynchronous.
+// table[upd[i].column] = upd[i].scale for the n entries (device memory; entries pairwise distinct, each below `columns`, the
+// length of the table -- twice the engine's batch; an entry outside the table is skipped).  Asynchronous.
 bool slots_set_scales(hipStream_t stream, float* table, int columns, const SlotScale* upd, int n);
 
 }  // namespace wn

@@ -39,9 +39,10 @@ SlotStateHeader headerCommon(const SlotFacts& f) {
     return h;
 }
 bool headerOk(const SlotFacts& f, const SlotStateHeader& h) {
-    float T;      // (word 10: zero, or the bits of a valid temperature)
+    float T, P;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid floor)
     return h.magic == kSlotStateMagic && h.version == kSlotStateVersion && h.precision == (f.f16 ? 16 : 32) && h.R == f.R &&
-           h.numLayers == f.numLayers && h.maxDilation == f.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T);
+           h.numLayers == f.numLayers && h.maxDilation == f.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T) &&
+           min_p_of_word(h.pad[1], P);
 }
 }  // namespace
 
@@ -98,7 +99,7 @@ bool SlotSession::begin(int window) {
     m_slotResume.assign(f.maxBatch, NULL);
     m_slotResumeDone.assign(f.maxBatch, 0);
     m_slotMoveEnd.assign(f.maxBatch, 0);
-    m_temps.reset(false);      // (every column at T = 1, a lockstep run's values included)
+    m_temps.reset(false);      // (every column at T = 1 and floor 0, a lockstep run's values included)
     m_primeY.clear();
     m_primeN.clear();
     m_primeListed.clear();
@@ -132,6 +133,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     d.active = 1;
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
+    slotMinPSet(slot, 0.0f);
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -142,6 +144,7 @@ bool SlotSession::stop(int slot) {
     m_slotHost[slot].active = 0;
     slotMarkPending(slot, 2);
     slotPrimeSet(slot, NULL, 0);
+    slotMinPSet(slot, 0.0f);      // (an idle column holds no floor: the launches go back to Params::floorOn = 0 with the last floored utterance)
     return true;
 }
 bool SlotSession::startMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
@@ -163,6 +166,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
+    slotMinPSet(slot, 0.0f);
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -178,6 +182,11 @@ bool SlotSession::melFrames(int slot, int frames, int final) {
 bool SlotSession::setTemperature(int slot, float T) {
     if (!inBatch(slot) || !slotHolds(slot) || !temperature_ok(T)) return false;
     slotTempSet(slot, T);
+    return true;
+}
+bool SlotSession::setMinP(int slot, float p) {
+    if (!inBatch(slot) || !slotHolds(slot) || !min_p_ok(p)) return false;
+    slotMinPSet(slot, p);
     return true;
 }
 bool SlotSession::prime(int slot, const int* y, int n) {
@@ -204,6 +213,8 @@ bool SlotSession::move(int from, int to) {
     m_slotMoveEnd[to] = 2;
     m_slotMoves.push_back(SlotMove{from, to});
     slotTempSet(to, m_temps.get(from));
+    slotMinPSet(to, m_temps.getP(from));
+    slotMinPSet(from, 0.0f);      // (as stop())
     if (primed(from)) {
         slotPrimeSet(to, m_primeY[from], m_primeN[from]);
         slotPrimeSet(from, NULL, 0);
@@ -221,6 +232,7 @@ int SlotSession::save(int slot, void* dst, hipStream_t stream) {
     h.done = (int)done;
     h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
     h.pad[0] = temperature_word(m_temps.get(slot));
+    h.pad[1] = min_p_word(m_temps.getP(slot));
     if (!slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), f.ring, f.ringSlots, f.ringFragsPerSlot, f.yInPrev, f.yInCur))
         return -1;
     return (int)done;
@@ -268,7 +280,7 @@ int SlotSession::saveList(const int* slots, int n, void* dst, long long stride, 
         const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
         const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
         const int done = (int)(m_slotCounter - start);
-        stage[i] = SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, temperature_word(m_temps.get(b)), 0};
+        stage[i] = SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, temperature_word(m_temps.get(b)), min_p_word(m_temps.getP(b))};
         saved[i] = SlotSaved{b, uid, done, mel ? 1 : 0};
     }
     gpuErrChk(hipMemcpyAsync(dev, stage, (size_t)n * sizeof(SlotSave), hipMemcpyHostToDevice, stream));
@@ -661,16 +673,25 @@ void SlotSession::slotTempSet(int slot, float T) {
     if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
     m_tempDirty[slot] = 1;
 }
+// ... and the probability floor: the same list, a changed column's two table entries are written together
+void SlotSession::slotMinPSet(int slot, float p) {
+    if (m_temps.getP(slot) == p) return;
+    m_temps.setP(slot, p);
+    if (m_tempDirty.empty()) m_tempDirty.assign(f.maxBatch, 0);
+    if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
+    m_tempDirty[slot] = 1;
+}
 // the pending start of column `slot` resumes from the blob `state`, whose (checked) header is h
 void SlotSession::slotSetResume(int slot, const void* state, const SlotStateHeader& h) {
     slotLayers();
     m_slotResume[slot] = state;
     m_slotResumeDone[slot] = h.done;
-    float T = 1.0f;
-    const bool ok = temperature_of_word(h.pad[0], T);      // (headerOk has checked it)
+    float T = 1.0f, P = 0.0f;
+    const bool ok = temperature_of_word(h.pad[0], T) && min_p_of_word(h.pad[1], P);      // (headerOk has checked them)
     assert(ok);
     (void)ok;
     slotTempSet(slot, T);
+    slotMinPSet(slot, P);
 }
 // the changed columns -> pinned staging -> device, then one slot_scale_kernel launch (staging halves as slotApplyPending, made
 // by the first step that needs them)
@@ -681,19 +702,20 @@ bool SlotSession::slotApplyTemperatures(hipStream_t stream) {
         return true;
     }
     if (!m_scaleDev) {
-        gpuErrChk(hipMalloc((void**)&m_scaleDev, (size_t)f.maxBatch * sizeof(SlotScale)));
-        m_scaleStage.make(2, (size_t)f.maxBatch * sizeof(SlotScale));
+        gpuErrChk(hipMalloc((void**)&m_scaleDev, 2 * (size_t)f.maxBatch * sizeof(SlotScale)));      // (a column's scale and its floor)
+        m_scaleStage.make(2, 2 * (size_t)f.maxBatch * sizeof(SlotScale));
     }
     SlotScale* const stage = (SlotScale*)m_scaleStage.acquire();
     int n = 0;
     for (int b : m_tempDirtyList) {
         stage[n++] = SlotScale{b, temperature_scale(m_temps.get(b))};
+        stage[n++] = SlotScale{f.maxBatch + b, m_temps.getP(b)};
         m_tempDirty[b] = 0;
     }
     m_tempDirtyList.clear();
     gpuErrChk(hipMemcpyAsync(m_scaleDev, stage, (size_t)n * sizeof(SlotScale), hipMemcpyHostToDevice, stream));
     m_scaleStage.release(stream);
-    return slots_set_scales(stream, m_temps.softScale, f.maxBatch, m_scaleDev, n);
+    return slots_set_scales(stream, m_temps.softScale, 2 * f.maxBatch, m_scaleDev, n);
 }
 // ---- primed generation (slots_prime.hpp) ----
 void SlotSession::slotPrimeSet(int slot, const int* y, int n) {

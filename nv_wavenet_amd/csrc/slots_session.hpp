@@ -122,6 +122,13 @@ public:
     bool setTemperature(int slot, float T);
     // the host's value for column `slot`; 0 when it holds no utterance (or outside slot mode, or outside the batch)
     float temperature(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot) : 0.f; }
+    // The utterance of column `slot` draws without the bins whose tempered probability is below p times that of the most probable
+    // bin (min-p), from the next step on, from that step's first sample; p as for setMinP.  Everything else as
+    // setTemperature: starts put the column back to 0, moves, saves and resumes carry the value (SlotStateHeader::pad[1]), and the
+    // step's one small launch writes the changed floors with the changed scales.  false (nothing changes): as setTemperature.
+    bool setMinP(int slot, float p);
+    // the host's value for column `slot`; -1 when it holds no utterance (0 is a valid floor)
+    float minP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getP(slot) : -1.f; }
     // ---- primed generation (slots_prime.hpp) ----
     // The utterance whose start or resume is pending on column `slot` carries the prime y[0 .. n) (device memory, int32; kept alive and
     // unchanged until local sample n has been generated): its local samples k < n are y[k], clamped into the alphabet, delivered and
@@ -270,7 +277,7 @@ private:
     // ... and the sampling temperatures (slots_sampler.hpp)
     std::vector<char> m_tempDirty;          // the columns whose table entry the next step writes
     std::vector<int> m_tempDirtyList;
-    SlotScale* m_scaleDev = NULL;           // [maxBatch] on the device: a step's changed entries (made by the first step that needs it)
+    SlotScale* m_scaleDev = NULL;           // [2 maxBatch] on the device: a step's changed entries (made by the first step that needs it)
     StageRing m_scaleStage;                 // ... their pinned host staging: two halves
     // ... and the primes (slots_prime.hpp)
     std::vector<const int*> m_primeY;       // per column: the prime in force (made by the first prime of a session) ...
@@ -317,6 +324,7 @@ private:
     void slotMarkPending(int slot, int what);
     bool slotApplyPending(hipStream_t stream);
     void slotTempSet(int slot, float T);
+    void slotMinPSet(int slot, float p);
     void slotSetResume(int slot, const void* state, const SlotStateHeader& h);
     bool slotApplyTemperatures(hipStream_t stream);
     void slotPrimeSet(int slot, const int* y, int n);

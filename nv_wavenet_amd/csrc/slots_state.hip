@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void slot_save_kernel(uintx4* __restrict__ blo
 }
 
 // Column save for a list: slot_save_kernel per entry, blockIdx.y striding over the entries (the grid of slot_load_kernel).  The common
-// header fields are one argument, done, uid and the temperature word come from the entry; every destination is device memory or the device-side address
+// header fields are one argument, done, uid, the temperature word and the floor word come from the entry; every destination is device memory or the device-side address
 // of mapped pinned host memory -- the blob side stays contiguous 16-byte stores either way.
 __global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __restrict__ saves, int nSaves, SlotStateHeader hdr,
                                                              const SlotLayer* __restrict__ layers, const uintx4* __restrict__ ring,
@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __r
             h.done = sv.done;
             h.uid = sv.uid;
             h.pad[0] = sv.temp;
+            h.pad[1] = sv.minp;
             h.yInPrev = yInPrev[sv.column];
             h.yInCur = yInCur[sv.column];
             *(SlotStateHeader*)sv.dst = h;

@@ -30,7 +30,8 @@ struct SlotStateHeader {
     unsigned uid;
     int yInPrev, yInCur;     // the column's sample history
     int pad[6];              // pad[0]: the sampling temperature as the bits of the float, all-zero bits for T = 1 (slots_sampler.hpp:
-                             // blobs of utterances at T = 1 are what they were before temperatures existed); the rest zero
+                             // blobs of utterances at T = 1 are what they were before temperatures existed); pad[1]: the probability floor likewise,
+                             // all-zero bits for floor 0; the rest zero
 };
 static_assert(sizeof(SlotStateHeader) == 64, "SlotStateHeader layout");
 
@@ -60,7 +61,7 @@ struct SlotSave {
     int done;
     unsigned uid;
     int temp;                // header word 10 (pad[0]): the bits of the column's sampling temperature, 0 for T = 1 (slots_sampler.hpp)
-    int pad;
+    int minp;                // header word 11 (pad[1]): the bits of the column's probability floor, 0 for floor 0
 };
 static_assert(sizeof(SlotSave) == 32, "SlotSave layout");
 

@@ -375,6 +375,20 @@ int nvw_slot_set_temperature(nvw_engine* e, int slot, float T) {
     return 0;
 }
 float nvw_slot_temperature(nvw_engine* e, int slot) { return e->slots().temperature(slot); }
+// ---- probability floor (min-p) per utterance, lockstep and in slot mode (additive within ABI 7) -----------------------------------
+int nvw_set_min_p(nvw_engine* e, const float* p, int n) {
+    if (e->setMinP(p, n)) return 1;
+    fprintf(stderr, "nvw_set_min_p: refused, nothing changed (not in slot mode; %d values for %d columns; every value finite and in "
+            "[0, 0.5])\n", n, e->maxBatch());
+    return 0;
+}
+int nvw_slot_set_min_p(nvw_engine* e, int slot, float p) {
+    if (e->slots().setMinP(slot, p)) return 1;
+    fprintf(stderr, "nvw_slot_set_min_p: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
+            "a pending start or resume; p = %g finite and in [0, 0.5])\n", slot, e->maxBatch(), (double)p);
+    return 0;
+}
+float nvw_slot_min_p(nvw_engine* e, int slot) { return e->slots().minP(slot); }
 // ---- primed generation: forced sample prefixes, lockstep and in slot mode (additive within ABI 7) -----------------------------------
 int nvw_set_prime(nvw_engine* e, const int* y, const int* n, int batch, int max_n, long long stride) {
     if (e->setPrime(y, n, batch, max_n, stride)) return 1;

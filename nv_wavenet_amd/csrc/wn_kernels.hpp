@@ -347,7 +347,14 @@ struct Params {
     int forced;              // RAW = 3 only, launch-uniform: != 0: a selector <= -1 is a forced sample, -(1 + y) stands for "the sample is
                              // y" (slots_prime.hpp: only its two kernels write such values); 0: every selector is a draw, as before.
                              // Behind softScale, for the same reason.
+    int floorOn;             // RAW = 3 only, launch-uniform: != 0: some column's probability floor (min-p) is not 0, and the floors are the
+                             // second half of the table softScale points to, softScale[maxBatch + b] (read only then); 0: no floor in
+                             // force, the launch executes the instructions it did before floors existed.  In the four bytes of padding
+                             // behind `forced`: the struct did not grow.
 };
+static_assert(sizeof(Params) == 1816 && offsetof(Params, forced) == 1808 && offsetof(Params, floorOn) == 1812,
+              "Params::floorOn lives in the padding behind Params::forced: the struct is the 1816 bytes it was before, and no kernel's "
+              "argument block moved");
 
 // ------------------------------------------------------------------------------------------
 // math helpers
@@ -775,9 +782,16 @@ template <int LPU> WN_DEV int group_min_i(int v) {
 }
 
 // `scale`: log2(e) / T of the utterance's sampling temperature T (Params::softScale); the default is T = 1.
+// `floor`, read only when FLOOR: the utterance's probability floor tau (min-p; finite, in [0, 0.5]): a logit whose
+// e = p / p_max (tempered) is below tau leaves the distribution -- its e becomes 0 before the sum, the scan, the target and the row
+// search see it, and in the probability dump.  The maximum's e is 2^(rounding error of m c) >= 2^-0.5 > 0.5 >= tau: it always stays,
+// and the total is never zero.  FLOOR = false (the default): off, the function is what it was -- the choice is a template argument
+// so that the compiler sees the old body; callers choose between the two forms under a launch-uniform flag.
 constexpr float kLog2e = 1.44269504088896340736f;
-template <int A, int LPU, int RPL>
-WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total, float scale = kLog2e) {
+template <int A, int LPU, int RPL, bool FLOOR = false>
+WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total, float scale = kLog2e,
+                        float floor = 0.f) {
+    (void)floor;
     (void)lane;
 #pragma unroll
     for (int i = 0; i < RPL / 4; i++) {
@@ -796,6 +810,7 @@ WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&
 #pragma unroll
         for (int i = 0; i < RPL; i++) {
             e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], scale, mneg));
+            if constexpr (FLOOR) e[i] = (e[i] >= floor) ? e[i] : 0.f;
             lsum += e[i];
         }
     }
@@ -1290,6 +1305,16 @@ WN_DEV void wavenet_wg_body(const Params& p) {
             int sb = (tile0 + bt) * 16 + su;
             sb = sb < p.batch ? sb : p.batch - 1;
             sscale[bt] = p.softScale != nullptr ? p.softScale[sb] : kLog2e;
+        }
+    }
+    // ... and its probability floor (Params::floorOn: the second half of the same table), likewise
+    float sfloor[FEAT ? BT : 1];
+    if constexpr (FEAT) {
+#pragma unroll
+        for (int bt = 0; bt < BT; bt++) {
+            int sb = (tile0 + bt) * 16 + su;
+            sb = sb < p.batch ? sb : p.batch - 1;
+            sfloor[bt] = p.floorOn ? p.softScale[p.maxBatch + sb] : 0.f;
         }
     }
     const int tEnd = p.initSample + p.count;
@@ -1844,7 +1869,9 @@ WN_DEV void wavenet_wg_body(const Params& p) {
                 const float* lrow = lgbuf + (bl * 16 + su) * C::LROW + sq * C::RPL;
                 int pick;
                 if constexpr (FEAT) {
-                    pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
+                    // (floorOn is launch-uniform: a launch with no floor in force runs the call it ran before)
+                    if (p.floorOn) pick = softmax_pick<A, C::LPU, C::RPL, true>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt]);
+                    else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
                     // a forced sample (Params::forced): the selector names it; e and total stay the model's
                     if (p.forced) pick = selv[bt] <= -1.0f ? (int)(-selv[bt]) - 1 : pick;
                 } else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total);

@@ -621,6 +621,31 @@ class WavenetEngine:
         """The temperature in force for column `slot` (host state); 0.0 when the column holds no utterance."""
         return float(lib.nvw_slot_temperature(self._h, int(slot)))
 
+    # ---- probability floor (min-p) per utterance (include/nv_wavenet_c.h, "PROBABILITY FLOOR"; DESIGN.md §6m) ----
+    def setMinP(self, p=None):
+        """Lockstep: column b of the features-path runs that follow draws from its tempered distribution without the bins whose
+        probability is below p[b] times that of the most probable bin.  p: None (every column at 0), a float (every column), or a
+        sequence of 1..maxBatch floats (the columns past it at 0), each finite and in [0, 0.5].  In force until the next call; a
+        call between two chunks takes effect at the next chunk.  While any column's floor is not 0, runs on packed or in-place
+        conditioning and on chain engines return False.  ValueError when refused (nothing changes)."""
+        if p is None:
+            ok = lib.nvw_set_min_p(self._h, None, 0)
+        else:
+            t = np.ascontiguousarray(np.full(self.maxBatch, p, dtype=np.float32) if np.isscalar(p) else np.asarray(p, dtype=np.float32).reshape(-1))
+            ok = lib.nvw_set_min_p(self._h, t.ctypes.data, int(t.size))
+        if not ok:
+            raise ValueError("nvw_set_min_p refused %r" % (p,))
+
+    def slotSetMinP(self, slot, p):
+        """Slot mode: the utterance of column `slot` draws with floor p from the next step on (after slotStart / slotResume, which
+        put the column back to 0 / to the blob's value).  ValueError when refused (nothing changes)."""
+        if not lib.nvw_slot_set_min_p(self._h, int(slot), float(p)):
+            raise ValueError("nvw_slot_set_min_p refused slot %d, p = %r" % (slot, p))
+
+    def slotMinP(self, slot):
+        """The floor in force for column `slot` (host state); -1.0 when the column holds no utterance (0 is a valid floor)."""
+        return float(lib.nvw_slot_min_p(self._h, int(slot)))
+
     # ---- primed generation: forced sample prefixes (include/nv_wavenet_c.h, "PRIMED GENERATION"; DESIGN.md §6h) ----
     def setPrime(self, y=None, lengths=None):
         """Lockstep: column b of the features-path runs that follow starts with the forced samples y[b][:lengths[b]] and draws from

@@ -422,7 +422,7 @@ class NVWaveNetEngine(NVWaveNet):
         return self._engine(batch_size, sample_count, implementation).condTiles()
 
     def infer(self, cond_input, implementation=Impl.AUTO, seed=None, return_audio=False, layout="CBLN",
-              generator=None, batch_size=None, temperature=None, prime=None):
+              generator=None, batch_size=None, temperature=None, prime=None, min_p=None):
         """cond_input: 2R x batch x layers x samples (layout "CBLN", the reference's: converted to the engine's fragment order
         by the one permuting copy any layout change needs), [samples][layers][batch][2R] contiguous (layout "NLBC", read in
         place), or the engine's own fragment order
@@ -432,7 +432,11 @@ class NVWaveNetEngine(NVWaveNet):
         Returns int32 [batch][samples] (and int16 audio [batch][samples] when return_audio).
         temperature: not here -- only the kernels that compute the conditioning from the features sample at a temperature
         (infer_features); anything but None raises ValueError.
-        prime: not here either, for the same reason (infer_features(..., prime=)); anything but None raises ValueError."""
+        prime: not here either, for the same reason (infer_features(..., prime=)); anything but None raises ValueError.
+        min_p: nor a probability floor (infer_features(..., min_p=)); anything but None raises ValueError."""
+        if min_p is not None:
+            raise ValueError("infer() runs on a conditioning tensor, whose kernels draw from the whole distribution only: use "
+                             "infer_features(x, cond_weight, cond_bias, min_p=...)")
         if prime is not None:
             raise ValueError("infer() runs on a conditioning tensor, whose kernels cannot force samples: use "
                              "infer_features(x, cond_weight, cond_bias, prime=...)")
@@ -472,7 +476,7 @@ class NVWaveNetEngine(NVWaveNet):
         return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
 
     def infer_features(self, x, cond_weight, cond_bias, implementation=Impl.AUTO, seed=None, return_audio=False, generator=None,
-                       temperature=None, prime=None, prime_lengths=None):
+                       temperature=None, prime=None, prime_lengths=None, min_p=None):
         """Generation with the conditioning convolution INSIDE the kernel (round 5): x = the upsampled features [batch][n_cond][samples]
         on the GPU (upsample_features(...) / the model's self.upsample output, trimmed), cond_weight / cond_bias = the model's
         cond_layers.weight / .bias.  Equivalent to infer(model.get_cond_input(features)) without ever building the
@@ -482,8 +486,17 @@ class NVWaveNetEngine(NVWaveNet):
         prime: None, or a [batch][n] integer tensor (n <= samples, values in 0..A-1) -- utterance b starts with the forced samples
         prime[b][:prime_lengths[b]] (prime_lengths None: all n) and is drawn from there on; the forced samples are part of the
         result.  The continuation of existing audio: infer_features(x, .., seed=s, prime=y[:, :n]) of a run y with the same x and
-        seed returns y.  ValueError for a bad shape, length or value."""
+        seed returns y.  ValueError for a bad shape, length or value.
+        min_p: None (0), a float, or a sequence of `batch` floats -- utterance b is drawn from its tempered distribution without
+        the bins whose probability is below min_p[b] times that of the most probable bin; each finite and in
+        [0, 0.5] (ValueError otherwise)."""
         batch_size, sample_count = x.size(0), x.size(2)
+        if min_p is not None and (isinstance(min_p, (int, float)) or getattr(min_p, "ndim", None) == 0):
+            min_p = float(min_p)      # (a Python or numpy scalar, a 0-d array or tensor: every column)
+        elif min_p is not None:
+            min_p = [float(p) for p in min_p]
+            if len(min_p) != batch_size:
+                raise ValueError("%d probability floors for a batch of %d" % (len(min_p), batch_size))
         if prime is not None:
             if prime.dim() != 2 or prime.size(0) != batch_size or not 0 < prime.size(1) <= sample_count or prime.is_floating_point():
                 raise ValueError("prime: an integer tensor [batch = %d][1 .. %d], got %s" % (batch_size, sample_count, tuple(prime.shape)))
@@ -510,12 +523,16 @@ class NVWaveNetEngine(NVWaveNet):
         e.setFeatures(x, sample_count)
         e.setTemperatures(temperature)
         try:
+            if min_p is not None:
+                e.setMinP(min_p)
             if prime is not None:
                 e.setPrime(prime.to(device=dev, dtype=torch.int32).contiguous(), prime_lengths)
             return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
         finally:
             if temperature is not None:
                 e.setTemperatures(None)      # (the engine is shared with infer(), whose kernels refuse to run at another temperature)
+            if min_p is not None:
+                e.setMinP(None)              # (... or with a floor)
             if prime is not None:
                 e.setPrime(None)             # (... or while a column is primed)
 

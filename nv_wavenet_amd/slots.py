@@ -52,6 +52,13 @@ resume, compact and to_bytes / from_bytes keep it (a blob holds it in word 10 of
     h = stream.submit(features, temperature=0.8)
     stream.set_temperature(h, 1.1)                      # waiting or running: the samples of the steps that follow
 
+A request may carry a probability floor as well (min-p; nvw_slot_set_min_p): the bins whose tempered probability is
+below min_p times that of the most probable bin are not drawn.  It travels as the temperature does (word 11 of a blob's header).
+min_p_rows() gives a scoring user the log-probabilities of the distribution such a request was drawn from.
+
+    h = stream.submit(features, temperature=0.8, min_p=0.05)
+    stream.set_min_p(h, 0.1)
+
 A request may carry a prime (nvw_slot_prime): its first n samples are given -- the tail of the previous sentence,
 the samples a lost stream had already delivered -- and it is drawn from sample n on.  The forced samples are delivered like the
 others.  suspend, drain, resume, compact and to_bytes / from_bytes keep what is left of it.
@@ -107,6 +114,45 @@ def check_temperature(T):
     return t
 
 
+def check_min_p(p):
+    """p as the engine takes it (a float32 value, finite, in [0, 0.5]); ValueError otherwise."""
+    try:
+        t = float(np.float32(p))
+    except (TypeError, ValueError):
+        raise ValueError("min_p %r is not a number" % (p,))
+    if not (0.0 <= t <= 0.5):      # (a NaN fails both comparisons)
+        raise ValueError("min_p %r: finite and in [0, 0.5]" % (p,))
+    return t + 0.0                 # (-0.0 is 0.0)
+
+
+def min_p_rows(rows, min_p):
+    """The log-probabilities of the floored, renormalised distribution: rows = log-probabilities [n][A] (or [A]) from any scoring
+    entry (WavenetEngine.scoreSamples(rows=True), at the temperature the samples were drawn at), min_p = the floor, a float or [n]
+    values.  A bin stays when rows[t][a] - max_a rows[t][a] >= log(min_p); the others read -inf, and the kept ones are
+    renormalised by the log of their summed probability (float64 inside; the result has the dtype of rows).  min_p = 0 returns
+    the rows renormalised by their own sum.  numpy in, numpy out; a torch tensor in, a torch tensor on the same device out.
+    This is the distribution a request with that floor was drawn from, EXCEPT for bins within rounding of the floor: the kernel
+    compares exp2(fma(z, c, -(m c))) in float32, whose exponent carries the rounding of m c, of the fma and -- here -- of the
+    scoring pass's own subtraction and scaling: a bin whose rows[t][a] - max differs from log(min_p) by less than a few float32
+    ulps of (c max|Za| + max|rows|) -- about 1e-5 at the shipped shapes -- may be kept by one and dropped by the other."""
+    torch_in = not isinstance(rows, np.ndarray) and hasattr(rows, "detach")
+    r = rows.detach().cpu().numpy() if torch_in else np.asarray(rows)
+    r64 = np.atleast_2d(r.astype(np.float64))
+    tau = np.asarray(min_p, dtype=np.float64).reshape(-1)
+    if tau.size not in (1, r64.shape[0]) or not np.all((tau >= 0.0) & (tau <= 0.5)):
+        raise ValueError("min_p: one value or one per row, each in [0, 0.5]")
+    rel = r64 - r64.max(axis=1, keepdims=True)
+    with np.errstate(divide="ignore"):
+        keep = rel >= np.log(tau)[:, None]
+        kept = np.where(keep, np.exp(rel), 0.0)
+        out = np.where(keep, rel - np.log(kept.sum(axis=1, keepdims=True)), -np.inf)
+    out = out.reshape(r.shape).astype(r.dtype if r.dtype.kind == "f" else np.float64)
+    if torch_in:
+        import torch
+        return torch.from_numpy(out).to(rows.device)
+    return out
+
+
 def check_prime(prime, length=None):
     """prime as the engine takes it: a 1-D integer tensor of 1..length values, returned as contiguous int32 (None stays None);
     ValueError otherwise.  The values are clamped into the alphabet by the engine."""
@@ -134,7 +180,8 @@ class SlotState:
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
     frames, final = of a mel request (frames written so far, no more to come); temperature = its sampling temperature (the one in
     the blob's header, word 10; a resume goes on at this attribute's value); prime = its prime (an int32 tensor [n], None: none; a
-    resume applies it again when done < n)."""
+    resume applies it again when done < n); min_p = its probability floor (word 11 of the blob's header where the engine saved
+    the blob; the blobs that prefill and scoring write leave the word zero, and the stream sets the floor after resuming)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -142,12 +189,15 @@ class SlotState:
     RECORD_MAGIC, RECORD_VERSION = b"NWSS", 1
     BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid,
     TEMPERATURE_WORD = 10                    # word 10 the temperature as the bits of the float (zero: 1.0)
+    MIN_P_WORD = 11                          # word 11 the probability floor likewise (zero: 0.0)
     # to_bytes() of a state with done < n of its prime: behind the blob this record, then the n - done values y[done .. n) (int32)
     PRIME = struct.Struct("<4sII")           # magic, first (= done), count (= n - done)
     PRIME_MAGIC = b"NWSP"
 
-    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None):
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0):
         self.prime = check_prime(prime)
+        self.min_p = check_min_p(min_p)
+        self._blob_min_p = self.min_p if blob is not None else 0.0                  # (word 11 of the blob as the engine will read it)
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
         self.temperature = check_temperature(temperature)
         self._blob_temperature = self.temperature if blob is not None else 1.0      # (what the engine reads from the header on resume)
@@ -159,14 +209,19 @@ class SlotState:
         """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
         tensor is not included.  A blob on the GPU is copied to the host here -- a synchronising copy --, and for a pinned blob
         the call waits for the device to have written it.  A request that had not started has no blob; with a temperature other
-        than 1 it carries the 64 bytes of a header alone (magic, uid, done = 0 and word 10), so that the value survives.  A state
+        than 1 or a floor other than 0 it carries the 64 bytes of a header alone (magic, uid, done = 0 and words 10 and 11), so
+        that the values survive; a blob whose word 11 is not the state's floor (a prefilled state) is written with it.  A state
         still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
         what they were before primes existed."""
         blob = b""
-        if self.blob is None and self.temperature != 1.0:
+        min_p = check_min_p(self.min_p)
+        floor_word = np.array([min_p], dtype="<f4").view("<u4")[0] if min_p != 0.0 else 0
+        if self.blob is None and (self.temperature != 1.0 or min_p != 0.0):
             hdr = np.zeros(16, dtype="<u4")
             hdr[0], hdr[1], hdr[7] = self.BLOB_MAGIC, 1, int(self.uid) & 0xFFFFFFFF
-            hdr[self.TEMPERATURE_WORD] = np.array([self.temperature], dtype="<f4").view("<u4")[0]
+            if self.temperature != 1.0:
+                hdr[self.TEMPERATURE_WORD] = np.array([self.temperature], dtype="<f4").view("<u4")[0]
+            hdr[self.MIN_P_WORD] = floor_word
             blob = hdr.tobytes()
         if self.blob is not None:
             if getattr(self.blob, "is_cuda", False):
@@ -176,6 +231,10 @@ class SlotState:
                     import torch
                     torch.cuda.synchronize()
                 blob = self.blob.numpy().tobytes()
+            if min_p != self._blob_min_p:
+                words = np.frombuffer(blob, dtype="<u4").copy()
+                words[self.MIN_P_WORD] = floor_word
+                blob = words.tobytes()
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
                                 1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob + self._prime_bytes()
@@ -209,20 +268,22 @@ class SlotState:
         if tail != 0 or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
-        temperature = 1.0
+        temperature, min_p = 1.0, 0.0
         if nblob:
             words = np.frombuffer(data, dtype="<u4", count=16, offset=cls.RECORD_BYTES)
             if int(words[0]) != cls.BLOB_MAGIC or int(words[6]) != done or int(words[7]) != uid:
                 raise ValueError("the blob's header does not belong to the record (magic %#x, done %d, uid %d)" % tuple(words[[0, 6, 7]]))
             if int(words[cls.TEMPERATURE_WORD]):
                 temperature = check_temperature(words[cls.TEMPERATURE_WORD:cls.TEMPERATURE_WORD + 1].view("<f4")[0])
+            if int(words[cls.MIN_P_WORD]):
+                min_p = check_min_p(words[cls.MIN_P_WORD:cls.MIN_P_WORD + 1].view("<f4")[0])
         if nblob > 64 or (nblob and done):      # (64 bytes with done = 0: the header alone of a request that had not started)
             host = torch.empty((1, nblob), dtype=torch.uint8, pin_memory=bool(pinned))
             host[0].numpy()[:] = np.frombuffer(data, dtype=np.uint8, count=nblob, offset=cls.RECORD_BYTES)
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   temperature, prime)
+                   temperature, prime, min_p)
 
 
 class StepOutput:
@@ -308,6 +369,7 @@ class SlotStream:
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
         self._prime = {}                               # handle -> prime (int32 tensor) of the requests (queued or running) that carry one
+        self._minp = {}                                # handle -> probability floor of the requests (queued or running) whose floor is not 0
         self._temp = {}                                # handle -> sampling temperature of the requests (queued or running) whose T is not 1
         # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
         # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
@@ -396,6 +458,7 @@ class SlotStream:
         prime = state.prime if state.prime is not None and state.prime.numel() > done + y.numel() else None
         after = SlotState(blobs[0], state.source, int(state.uid), done + int(y.numel()), state.kind, frames=state.frames if mel else None,
                           final=state.final if mel else None, buffer=blobs, row=0, temperature=temperature, prime=prime)
+        after.min_p = state.min_p                      # (the pass leaves word 11 of the blob zero: the stream sets the floor after the resume)
         after._prefilled_from = (y, blob)              # (read by the pass in stream order: kept with the state)
         return logp[0], after
 
@@ -444,7 +507,7 @@ class SlotStream:
             raise ValueError("score needs samples")
         return self.engine.scoreSamplesMel([(y if y.is_cuda else y.cuda(), mel, temperature, n)])[0]
 
-    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None):
+    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None, min_p=0.0):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
         run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
@@ -454,18 +517,22 @@ class SlotStream:
         with a prime of n < samples values makes the state behind the prime at once (prefill()) and queues the request as a resume
         at sample n -- its delivery starts there, the forced samples are not delivered again, and the samples from n on are bit
         for bit those of prefill=False; ValueError for a prime that covers the whole utterance.  Without a prime it changes
-        nothing."""
+        nothing.  min_p: its samples are drawn without the bins whose tempered probability is below min_p times that of the most
+        probable bin (ValueError unless finite and in [0, 0.5]); forced samples stay forced."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
         temperature = check_temperature(temperature)
+        min_p = check_min_p(min_p)
         prime = check_prime(prime, features.size(1))
         if (self._prefill if prefill is None else prefill) and prime is not None:
             if prime.numel() >= features.size(1):
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), features.size(1)))
             state = self.prefill(features, prime, uid, temperature)
+            state.min_p = min_p      # (the pass leaves word 11 of the blob zero: set after the resume, at admission)
             handle = self._next_handle
             self._next_handle += 1
             self._queue.append((handle, features, int(state.uid), None, state))
             self._note_temperature(handle, temperature)
+            self._note_min_p(handle, min_p)
             return handle
         handle = self._next_handle
         self._next_handle += 1
@@ -474,19 +541,21 @@ class SlotStream:
         self._next_uid = max(self._next_uid, int(uid) + 1)
         self._queue.append((handle, features, int(uid), None))
         self._note_temperature(handle, temperature)
+        self._note_min_p(handle, min_p)
         if prime is not None:
             self._prime[handle] = prime
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=None):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=None, min_p=0.0):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
-        final: no more will come); returns its handle.  uid, temperature and prime as for submit; the prime of a request that is
+        final: no more will come); returns its handle.  uid, temperature, min_p and prime as for submit; the prime of a request that is
         not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one).
         prefill (None: the stream's default): True with a prime of n values makes the state behind the prime at once
         (prefill_mel()) and queues the request as a mel resume at sample n -- its delivery starts there, the samples from n on are
         bit for bit those of prefill=False, and extend_mel works as for any queued mel request.  ValueError, before anything is
         queued or counted: the engine has no upsampling table, the frames written so far do not cover the prime, a final
         request's prime covers the whole utterance.  Without a prime it changes nothing."""
+        min_p = check_min_p(min_p)
         if (self._prefill if prefill is None else prefill) and prime is not None:
             stride = getattr(self.engine, "upStride", 0)
             if not stride or not self.engine.upsampleRowElems():
@@ -499,11 +568,13 @@ class SlotStream:
             if final and prime.numel() >= n * stride:
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), n * stride))
             state = self.prefill_mel(mel, prime, uid, temperature, n, final)
+            state.min_p = min_p      # (as in submit)
             handle = self._next_handle
             self._next_handle += 1
             req = self._mel[handle] = [n, bool(final), None, int(state.done)]
             self._queue.append((handle, mel, int(state.uid), req, state))
             self._note_temperature(handle, temperature)
+            self._note_min_p(handle, min_p)
             return handle
         n = self._mel_frames(mel, frames, final)
         temperature = check_temperature(temperature)
@@ -517,6 +588,7 @@ class SlotStream:
         self._mel[handle] = req
         self._queue.append((handle, mel, int(uid), req))
         self._note_temperature(handle, temperature)
+        self._note_min_p(handle, min_p)
         if prime is not None:
             self._prime[handle] = prime
         return handle
@@ -545,6 +617,31 @@ class SlotStream:
         if handle not in self.running() and not any(item[0] == handle for item in self._queue):
             raise KeyError(handle)
         return self._temp.get(handle, 1.0)
+
+    def _note_min_p(self, handle, p):
+        if p != 0.0:
+            self._minp[handle] = p
+        else:
+            self._minp.pop(handle, None)
+
+    def set_min_p(self, handle, min_p):
+        """Request `handle` draws with the probability floor `min_p` from the next step on: a running one through the engine at once
+        (its column's value changes with that step's first sample), a waiting one when it is admitted.  KeyError for a handle the
+        stream does not hold, ValueError for a bad value -- nothing changes."""
+        p = check_min_p(min_p)
+        col = self.running().get(handle)
+        if col is None:
+            if not any(item[0] == handle for item in self._queue):
+                raise KeyError(handle)
+        else:
+            self.engine.slotSetMinP(col, p)
+        self._note_min_p(handle, p)
+
+    def min_p(self, handle):
+        """The probability floor request `handle` (queued or running) is drawn with."""
+        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        return self._minp.get(handle, 0.0)
 
     def extend_mel(self, handle, frames, final=False):
         """The first `frames` frames of mel request `handle` are written (queued or running); final: no more will come."""
@@ -613,17 +710,19 @@ class SlotStream:
         """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
         handle, req = item[0], item[3]
         T = self._temp.pop(handle, 1.0)
+        P = self._minp.pop(handle, 0.0)
         prime = self._prime.pop(handle, None)
         if req is not None:
             del self._mel[handle]
         if len(item) > 4:
             if req is not None:
                 item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
-            item[4].temperature = T                                 # (... or given another temperature)
+            item[4].temperature = T                                 # (... or given another temperature
+            item[4].min_p = P                                       # or floor)
             return item[4]
         if req is None:
-            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime)
-        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime)
+            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime, min_p=P)
+        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime, min_p=P)
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
@@ -631,17 +730,18 @@ class SlotStream:
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
         T = self._temp.pop(handle, 1.0)      # (the engine has written the same value into the blob's header)
+        P = self._minp.pop(handle, 0.0)      # (likewise)
         prime = self._prime.pop(handle, None)
         heapq.heappush(self._free, col)
         self._ch[col] = -1
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime)
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime, min_p=P)
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime)
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime, P)
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -712,6 +812,7 @@ class SlotStream:
             req = self._mel[handle] = [int(state.frames), bool(state.final), None, int(state.done)]
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
         self._note_temperature(handle, check_temperature(state.temperature))
+        self._note_min_p(handle, check_min_p(state.min_p))
         if state.prime is not None and state.done < state.prime.numel():      # (still inside it: applied again when it is admitted)
             self._prime[handle] = state.prime
         return handle
@@ -737,6 +838,7 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
+        floored = []     # (column, floor) likewise: a start leaves 0, a resume word 11 of the blob (zero in a prefilled or scored one)
         tempered = []    # (column, temperature) of the admitted requests whose temperature is not what their start leaves the column at
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
@@ -752,6 +854,9 @@ class SlotStream:
             T = self._temp.get(handle, 1.0)
             if T != (state._blob_temperature if blob is not None else 1.0):      # (a start leaves 1, a resume the header's value)
                 tempered.append((col, T))
+            P = self._minp.get(handle, 0.0)
+            if P != (state._blob_min_p if blob is not None else 0.0):
+                floored.append((col, P))
             if req is None:
                 if blob is None:
                     self.engine.slotStart(col, x, uid)
@@ -777,6 +882,8 @@ class SlotStream:
             self._resume_listed(listed)
         for col, T in tempered:      # (start, then set: the engine applies both at the step that follows)
             self.engine.slotSetTemperature(col, T)
+        for col, P in floored:
+            self.engine.slotSetMinP(col, P)
         for col, handle in primed:   # (start or resume, then prime)
             self.engine.slotPrime(col, self._prime[handle])
 
@@ -837,6 +944,7 @@ class SlotStream:
                 del self._running[col]
                 del self._src[rec[0]]
                 self._temp.pop(rec[0], None)
+                self._minp.pop(rec[0], None)
                 self._prime.pop(rec[0], None)
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
@@ -848,6 +956,7 @@ class SlotStream:
         handle = self._running.pop(col)[0]
         self._mel.pop(handle, None)
         self._temp.pop(handle, None)
+        self._minp.pop(handle, None)
         self._prime.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1

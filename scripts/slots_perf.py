@@ -57,6 +57,10 @@ the host spends inside the calls is recorded beside the time of a step (host_us_
 --temperature is the same comparison for what the per-column sampling temperature costs a step: the parent's plain
 step, this commit's with every T = 1 (no table, the kernel argument NULL) and with mixed T (0.7, 0.85, 1, 1.2 cycling over the
 columns: the table and its scatter launch); a parent that has the temperature entries is simply run at T = 1.
+--min-p is that comparison for the probability floor: the parent's plain step, this commit's with every floor 0
+(set explicitly: no table, Params::floorOn = 0 -- the launches the parent issues) and with mixed floors (0, 0.05, 0.1, 0.25, 0.5
+cycling over the columns: the table, its scatter launch and a compare and a select per logit).  The verdict is about the all-zero
+case -- not above the parent by more than twice the parent's own spread --; the mixed case is reported beside it, not barred.
 --prime is that comparison for primed generation: the parent's plain step, this commit's with no prime anywhere
 (Params::forced = 0: the launches the parent issues) and with every column inside a prime for the whole measurement (one
 slot_prime_kernel launch per step and the select behind softmax_pick in every sample).  The verdict is about the case without a
@@ -98,6 +102,7 @@ results of the paths are checked to be equal bytes.  One JSON line each: median 
     python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
+    python scripts/slots_perf.py --min-p --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --prime --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
@@ -135,7 +140,8 @@ def main():
     ap.add_argument("--prefill-mel", action="store_true", help="time nvw_prefill_states_mel against nvw_prefill_states on rows upsampled beforehand and against mel columns of the parent")
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
-    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --prime: a libwavenet_infer.so built from the parent commit")
+    ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
+    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --min-p, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
     import torch
     import bench
@@ -167,7 +173,7 @@ def main():
         if not args.parent_lib:
             return
         args.parent = True
-    if args.temperature or args.parent or args.prime:
+    if args.temperature or args.parent or args.prime or args.min_p:
         assert args.parent_lib or not args.parent, "--parent needs --parent-lib"
         for chunk in [int(c) for c in args.chunks.split(",")]:
             print(json.dumps(time_against_parent(args, w, Wc, bc, chunk)), flush=True)
@@ -265,7 +271,7 @@ def main():
 
 
 def time_against_parent(args, w, Wc, bc, chunk):
-    """The --parent / --temperature / --prime measurement (module docstring) for steps of `chunk` samples.  A case is (library,
+    """The --parent / --temperature / --min-p / --prime measurement (module docstring) for steps of `chunk` samples.  A case is (library,
     temperatures or primes, kind of step); the cases of one library and setting share an engine."""
     import ctypes as C
     import torch
@@ -291,8 +297,10 @@ def time_against_parent(args, w, Wc, bc, chunk):
     here = load(_lib.LIB_PATH)
     here.nvw_slot_set_temperature.restype, here.nvw_slot_set_temperature.argtypes = ci, [vp, ci, C.c_float]
     here.nvw_slot_prime.restype, here.nvw_slot_prime.argtypes = ci, [vp, ci, vp, ci]
-    libs = {"unit": here, "mixed": here} if args.temperature else {"noprime": here, "primed": here} if args.prime else {"here": here}
-    single = args.temperature or args.prime      # (one kind of step, several settings of this commit)
+    here.nvw_slot_set_min_p.restype, here.nvw_slot_set_min_p.argtypes = ci, [vp, ci, C.c_float]
+    libs = ({"unit": here, "mixed": here} if args.temperature else {"zero": here, "floored": here} if args.min_p else
+            {"noprime": here, "primed": here} if args.prime else {"here": here})
+    single = args.temperature or args.prime or args.min_p      # (one kind of step, several settings of this commit)
     if args.parent_lib:
         libs = dict({"parent": load(args.parent_lib)}, **libs)
     kinds = ("step",) if single else ("step", "ragged")
@@ -305,6 +313,7 @@ def time_against_parent(args, w, Wc, bc, chunk):
     rng = np.random.default_rng(3)
     offs = rng.integers(0, 4096, size=B)
     mixed = (0.7, 0.85, 1.0, 1.2)
+    floors = (0.0, 0.05, 0.1, 0.25, 0.5)
     forced = torch.randint(0, sh.A, (need,), device="cuda", generator=g, dtype=torch.int32)      # one prime for every column, as long as the run
     a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
     engines, info = {}, {}
@@ -323,6 +332,8 @@ def time_against_parent(args, w, Wc, bc, chunk):
             assert h.nvw_slot_start(e, b, x.data_ptr(), 16, x.stride(0), x.stride(1), need, b)
             if case == "mixed":
                 assert h.nvw_slot_set_temperature(e, b, mixed[b % len(mixed)])
+            if case in ("zero", "floored"):
+                assert h.nvw_slot_set_min_p(e, b, floors[b % len(floors)] if case == "floored" else 0.0)
             if case == "primed":
                 assert h.nvw_slot_prime(e, b, forced.data_ptr(), need)
         buf = C.create_string_buffer(256)
@@ -371,9 +382,11 @@ def time_against_parent(args, w, Wc, bc, chunk):
     res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
            "ms_per_step": {name(k): [round(v, 4) for v in vs] for k, vs in ms.items()}, "median_ms_per_step": {name(k): round(v, 4) for k, v in med.items()},
            "host_us_per_call": {name(k): [round(v, 2) for v in vs] for k, vs in host_us.items()},
-           "kernel": info["unit" if args.temperature else "noprime" if args.prime else "here"], "device": torch.cuda.get_device_name(0)}
+           "kernel": info["unit" if args.temperature else "zero" if args.min_p else "noprime" if args.prime else "here"], "device": torch.cuda.get_device_name(0)}
     if args.temperature:
         res["mixed_temperatures"] = mixed
+    if args.min_p:
+        res["mixed_floors"] = floors
     if "parent" not in libs:
         res["parent"] = "not measured (no --parent-lib)"
         return res
@@ -384,7 +397,7 @@ def time_against_parent(args, w, Wc, bc, chunk):
             m = {k: float(np.median(x)) for k, x in v.items()}
             spread = (max(v[p]) - min(v[p])) / m[p]
             ratios = {case: m[(case, kind)] / m[p] for case in libs if case != "parent"}
-            barred = [r for case, r in ratios.items() if case != "primed"]      # (--prime: the primed case is reported, not barred)
+            barred = [r for case, r in ratios.items() if case not in ("primed", "floored")]      # (--prime, --min-p: the primed and the floored case are reported, not barred)
             res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
                                      "within_twice_the_parent_spread": bool(max(barred) <= 1.0 + 2.0 * spread)},
                                     **{case + "_vs_parent": round(r, 4) for case, r in ratios.items()})
