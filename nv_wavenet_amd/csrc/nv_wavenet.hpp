@@ -1317,39 +1317,11 @@ public:
     // precision, pointer, alignment or stride.
     int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported) return 0;
-        wn::PrefillModel m = prefillModel();
+        wn::TimeModel m = timeModel();
         if (m_featDirty) buildFeatStream(stream);
         m.wblob = m_wblobF;
         m.bias = m_biasF;
         return m_prefill.run(m, reqs, count, dst, stride, stream) ? count : 0;
-    }
-    // (without the weight stream and the bias table: buildFeatStream may still replace them)
-    wn::PrefillModel prefillModel() const {
-        const int L = m_numLayers;
-        wn::PrefillModel m;
-        m.f16 = F16;
-        m.R = R;
-        m.A = A;
-        m.numLayers = L;
-        m.maxDilation = m_maxDilation;
-        m.ringSlots = m_ringSlots;
-        m.nCond = m_nCond;
-        m.tanhEmbed = m_tanhEmbed ? 1 : 0;
-        m.wblob = NULL;
-        m.waveStreamFrags = CF::waveStreamFrags(L);
-        m.bias = NULL;
-        m.biasL = C::BIAS_L;
-        m.embPrev = m_embedPrev;
-        m.embCur = m_embedCur;
-        for (int l = 0, d = 1, off = 0; l < L; l++) {
-            int dN = d << 1;
-            if (dN > m_maxDilation) dN = 1;
-            m.layers[l] = wn::PrefillLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
-                                           (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L), l, d, dN, off + d};
-            off += d;
-            d = dN;
-        }
-        return m;
     }
     // ---- scoring: per-sample log-likelihoods from a time-parallel pass (beyond the reference; score.hpp) ---------------
     // the largest sum of n, each rounded up to 16, that one scoreSamples call accepts (its scratch stays under wn::kScoreScratchCap);
@@ -1364,7 +1336,7 @@ public:
     // pointer, a misaligned or unreachable output, a total over scoreMaxSamples().
     int scoreSamples(const wn::ScoreReq* reqs, int count, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported) return 0;
-        wn::ScoreModel m = scoreModel();
+        wn::TimeModel m = timeModel();
         // (checked before anything is queued: a refused call launches nothing, the stream rebuild included)
         if (!wn::Score::acceptable(m, reqs, count)) return 0;
         if (m_featDirty) buildFeatStream(stream);
@@ -1372,14 +1344,18 @@ public:
         m.bias = m_biasF;
         return m_score.run(m, reqs, count, stream) ? count : 0;
     }
-    wn::ScoreModel scoreModel() const {
+    // the model as prefill, scoring and scoring with carried state see it (time_pass.hpp), without the weight stream and the bias
+    // table: buildFeatStream may still replace them
+    wn::TimeModel timeModel() const {
         const int L = m_numLayers;
-        wn::ScoreModel m;
+        wn::TimeModel m;
         m.f16 = F16;
         m.R = R;
         m.S = S;
         m.A = A;
         m.numLayers = L;
+        m.maxDilation = m_maxDilation;
+        m.ringSlots = m_ringSlots;
         m.nCond = m_nCond;
         m.tanhEmbed = m_tanhEmbed ? 1 : 0;
         m.wblob = NULL;
@@ -1390,14 +1366,14 @@ public:
         m.biasL = C::BIAS_L;
         m.embPrev = m_embedPrev;
         m.embCur = m_embedCur;
-        m.maxDilation = m_maxDilation;
-        m.ringSlots = m_ringSlots;
-        for (int l = 0, d = 1; l < L; l++) {
-            m.layers[l] = wn::ScoreLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
-                                         (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L),
-                                         (unsigned)CF::streamPos(l, CF::O_SKIP, L), d};
-            d <<= 1;
-            if (d > m_maxDilation) d = 1;
+        for (int l = 0, d = 1, off = 0; l < L; l++) {
+            int dN = d << 1;
+            if (dN > m_maxDilation) dN = 1;
+            m.layers[l] = wn::TimeLayer{(unsigned)CF::streamPos(l, CF::O_COND, L), (unsigned)CF::streamPos(l, CF::O_PREV, L),
+                                        (unsigned)CF::streamPos(l, CF::O_CUR, L), (unsigned)CF::streamPos(l, CF::O_RES, L),
+                                        (unsigned)CF::streamPos(l, CF::O_SKIP, L), d, off, dN, off + d};
+            off += d;
+            d = dN;
         }
         return m;
     }
@@ -1416,11 +1392,10 @@ public:
         return m_melTime.run(melTimeModel(), reqs, count, stream) ? count : 0;
     }
     // prefillStates from frames: samples [t0, n) of every request are upsampled into the engine's own rows, and the prefill launches
-    // read those -- each job's base is the address row t0 would have if the rows started at sample 0, since the kernels index by
-    // the absolute sample.  The blob is byte for byte the one slotStartMel, slotPrime(y, n), steps to n and slotSave produce.
+    // read those.  The blob is byte for byte the one slotStartMel, slotPrime(y, n), steps to n and slotSave produce.
     int prefillStatesMel(const wn::PrefillMelReq* reqs, int count, void* dst, long long stride, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
-        wn::PrefillModel pm = prefillModel();
+        wn::TimeModel pm = timeModel();
         const wn::MelTimeModel mm = melTimeModel();
         const int W = wn::prefill_window(m_ringSlots);
         const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
@@ -1442,7 +1417,7 @@ public:
         char* const rows = m_melTime.rows(bytes);
         for (int i = 0; i < count; i++) {
             ur[i].dst = rows + at[i];
-            pr[i].x = (const void*)((uintptr_t)(rows + at[i]) - (uintptr_t)ur[i].first * rowB);
+            pr[i].x = rows + at[i];
         }
         if (m_featDirty) buildFeatStream(stream);
         pm.wblob = m_wblobF;
@@ -1455,7 +1430,7 @@ public:
     // launches read those.  Accepts what scoreMaxSamples() accepts.
     int scoreSamplesMel(const wn::ScoreMelReq* reqs, int count, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
-        wn::ScoreModel sm = scoreModel();
+        wn::TimeModel sm = timeModel();
         const wn::MelTimeModel mm = melTimeModel();
         const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
         std::vector<wn::MelTimeReq> ur(count);
@@ -1493,7 +1468,7 @@ public:
     // unreachable state, done + n beyond INT_MAX - 16, a stateOut that overlaps a state or another stateOut of the call.
     int scoreChunks(const wn::ScoreChunkReq* reqs, int count, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported) return 0;
-        wn::ScoreModel m = scoreModel();
+        wn::TimeModel m = timeModel();
         std::vector<wn::ScoreChunkIn> in;
         if (!wn::Score::chunksCheck(m, reqs, count, false, in)) return 0;
         if (m_featDirty) buildFeatStream(stream);
@@ -1505,7 +1480,7 @@ public:
     // into the engine's own rows (which start at the chunk), and the chunk pass reads those.
     int scoreChunksMel(const wn::ScoreChunkMelReq* reqs, int count, hipStream_t stream = 0) {
         if (m_nCond <= 0 || !m_supported || m_upStride <= 0 || reqs == NULL || count < 1 || count > 65535) return 0;
-        wn::ScoreModel sm = scoreModel();
+        wn::TimeModel sm = timeModel();
         const wn::MelTimeModel mm = melTimeModel();
         const size_t rowB = (size_t)wn::mel_time_row(m_nCond) * sizeof(elem);
         std::vector<wn::MelTimeReq> ur(count);

@@ -1,144 +1,12 @@
-// score.hip -- the kernels and the host side of wn::Score (score.hpp).  Compiled once: the (R, S) and (S, A) of the built shapes, both precisions.
+// score.hip -- the head kernel and the host side of wn::Score (score.hpp): the (S, A) of the built shapes, both precisions.  The
+// layer kernels are score_carry.hip's.
 #include "score.hpp"
-
-#include <string.h>
-
-#include <vector>
 
 #include "time_tiles.hpp"
 
 namespace wn {
 
 namespace {
-
-// x_0[t] = embPrev[y[t-2]] + embCur[y[t-1]] (history 128 before the start), tanh when the model says so: as prefill_embed_kernel.
-// blockIdx.y: request, x: time tile.  Rows at and past n (the padding of the last tile) are zero.
-template <bool F16>
-__global__ __launch_bounds__(256) void score_embed_kernel(const ScoreJob* __restrict__ jobs, int R, int A, const void* __restrict__ embPrevV,
-                                                          const void* __restrict__ embCurV, int tanhEmbed, float* __restrict__ xf,
-                                                          char* __restrict__ xd) {
-    using elem = typename Prec<F16>::elem;
-    using quad = typename Prec<F16>::quad;
-    const ScoreJob jb = jobs[blockIdx.y];
-    const int tile0 = blockIdx.x;
-    if (tile0 >= jb.tiles) return;
-    const elem* const embPrev = (const elem*)embPrevV;
-    const elem* const embCur = (const elem*)embCurV;
-    const int rowB = R * (int)sizeof(elem), quads = R / 4;
-    for (int it = threadIdx.x; it < 16 * quads; it += blockDim.x) {
-        const int q = it % quads, k = tile0 * 16 + it / quads;
-        const int tile = q >> 2, g = q & 3;
-        floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
-        if (k < jb.n) {
-            const int yc = k >= 1 ? clamp_sample(jb.y[k - 1], A) : 128, yp = k >= 2 ? clamp_sample(jb.y[k - 2], A) : 128;
-            const floatx4 ep = quad_to_f32(*(const quad*)(embPrev + (size_t)yp * R + q * 4));
-            const floatx4 ec = quad_to_f32(*(const quad*)(embCur + (size_t)yc * R + q * 4));
-            v = ep + ec;
-            if (tanhEmbed) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) v[e] = tanh_t<F16>(v[e]);
-            }
-        }
-        const size_t row = (size_t)jb.row0 + k;
-        *(floatx4*)(xf + row * R + q * 4) = v;
-        put_quad<F16>(xd + row * rowB + quad_off<F16>(tile, g), v);
-    }
-}
-
-// One layer over one time tile of one request: gate pre-activation (bias, conditioning, dilated tap, current tap), gate, residual --
-// prefill_layer_kernel's, operand for operand --, then the skip GEMM on the h fragments: skip[t] (+)= Wskip_l h, fp32, read and
-// written by the same lane.  first: the sum starts here (from zero); last: no residual.  blockIdx.y: request, x: time tile.
-template <bool F16, int R, int S>
-__global__ __launch_bounds__((PCfg<F16, R>::THREADS)) void score_layer_kernel(const ScoreJob* __restrict__ jobs, const ScoreLayer ly, int first, int last,
-                                                                              const char* __restrict__ wblob, size_t waveBytes,
-                                                                              const float* __restrict__ bl, int nCond, float* __restrict__ xf,
-                                                                              const char* __restrict__ xdIn, char* __restrict__ xdOut,
-                                                                              float* __restrict__ skf) {
-    using C = PCfg<F16, R>;
-    using P = Prec<F16>;
-    using frag = typename P::frag;
-    constexpr int NW = C::NW, HTW = C::HTW, KF_R = C::KF_R, KFC = C::KFC, RT = C::RT, ROWB = C::ROWB;
-    constexpr int STW = S / 16 / NW;
-    static_assert((S / 16) % NW == 0, "skip tiles must split evenly over the waves");
-    __shared__ __attribute__((aligned(16))) char hbuf[KF_R * 1024];
-
-    const ScoreJob jb = jobs[blockIdx.y];
-    if ((int)blockIdx.x >= jb.tiles) return;      // (uniform over the workgroup)
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, j = lane & 15;
-    const int r = blockIdx.x * 16 + j;            // this lane's column: the sample
-    const unsigned laneOff = (unsigned)lane * 16u;
-    const char* const wbase = wblob + (size_t)w * waveBytes;
-    const size_t jobRow = (size_t)jb.row0;
-
-    // gate bias
-    floatx4 acc[1][2 * HTW];
-#pragma unroll
-    for (int i = 0; i < HTW; i++) {
-        acc[0][2 * i] = *(const floatx4*)(bl + (w + NW * i) * 16 + g * 4);
-        acc[0][2 * i + 1] = *(const floatx4*)(bl + (w + NW * i + RT) * 16 + g * 4);
-    }
-    // + Wcond c: feature column t; columns past n - 1 (the padding of the last tile) repeat the last sample
-    {
-        frag cf[1][KFC];
-        feature_frags<F16, KFC>(jb.x, jb.precision, jb.cStride, jb.tStride, r < jb.n ? r : jb.n - 1, nCond, g, cf[0]);
-        gemm_direct<F16, 1, 2 * HTW, KFC>(wbase + (size_t)ly.cond * 1024, laneOff, acc, cf);
-    }
-    // + Wprev x_l[t - d]: zero before the start, as at a start from silence
-    const char* const inJob = xdIn + jobRow * ROWB;
-    {
-        frag xp[1][KF_R];
-        const int rp = r - ly.d;
-#pragma unroll
-        for (int kf = 0; kf < KF_R; kf++) {
-            frag v = {};
-            if (rp >= 0) v = *(const frag*)(inJob + (size_t)rp * ROWB + (kf * 4 + g) * 16);
-            xp[0][kf] = v;
-        }
-        gemm_direct<F16, 1, 2 * HTW, KF_R>(wbase + (size_t)ly.prev * 1024, laneOff, acc, xp);
-    }
-    // + Wcur x_l[t]
-    {
-        frag xb[1][KF_R];
-#pragma unroll
-        for (int kf = 0; kf < KF_R; kf++) xb[0][kf] = *(const frag*)(inJob + (size_t)r * ROWB + (kf * 4 + g) * 16);
-        gemm_direct<F16, 1, 2 * HTW, KF_R>(wbase + (size_t)ly.cur * 1024, laneOff, acc, xb);
-    }
-    // gate -> h as B fragments
-#pragma unroll
-    for (int i = 0; i < HTW; i++) lds_put_tile<F16>(hbuf, w + NW * i, lane, gate4<F16>(acc[0][2 * i], acc[0][2 * i + 1]));
-    __syncthreads();
-    frag hb[1][KF_R];
-    lds_get_frags<F16, KF_R>(hbuf, lane, hb[0]);
-    // residual: (Bres + x) + Wres h -> x_{l+1}[t], the running residual in fp32 (read again by this lane only) and the operand in T_data
-    if (!last) {
-        float* const xrow = xf + (jobRow + r) * R;
-        floatx4 xa[1][HTW];
-#pragma unroll
-        for (int i = 0; i < HTW; i++)
-            xa[0][i] = *(const floatx4*)(bl + 2 * R + (w + NW * i) * 16 + g * 4) + *(const floatx4*)(xrow + (w + NW * i) * 16 + g * 4);
-        gemm_direct<F16, 1, HTW, KF_R>(wbase + (size_t)ly.res * 1024, laneOff, xa, hb);
-        char* const orow = xdOut + (jobRow + r) * ROWB;
-#pragma unroll
-        for (int i = 0; i < HTW; i++) {
-            const int tile = w + NW * i;
-            *(floatx4*)(xrow + tile * 16 + g * 4) = xa[0][i];
-            put_quad<F16>(orow + quad_off<F16>(tile, g), xa[0][i]);
-        }
-    }
-    // skip[t] (+)= Wskip_l h: the engine's accumulator, kept in memory between the layers (fp32: nothing is rounded on the way)
-    float* const srow = skf + (jobRow + r) * S;
-    floatx4 sk[1][STW];
-#pragma unroll
-    for (int i = 0; i < STW; i++) {
-        floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
-        if (!first) v = *(const floatx4*)(srow + (w + NW * i) * 16 + g * 4);
-        sk[0][i] = v;
-    }
-    gemm_direct<F16, 1, STW, KF_R>(wbase + (size_t)ly.skip * 1024, laneOff, sk, hb);
-#pragma unroll
-    for (int i = 0; i < STW; i++) *(floatx4*)(srow + (w + NW * i) * 16 + g * 4) = sk[0][i];
-}
 
 // ---- head ------------------------------------------------------------------------------------------------------------------
 constexpr int kScoreLdsMax = 80 * 1024;      // two head workgroups share a CU's 160 KiB
@@ -192,7 +60,7 @@ WN_DEV float log_softmax1(float z, float scale, float mneg, float l2sum) { retur
 // The head over TT time tiles of one request: relu(skip + sum of the skip biases) -> Zs = relu(Bzs + Wzs .) -> Za = Bza + Wza . ->
 // log softmax(Za / T), the picked row's to logp and (when asked for) all of them to rows.  blockIdx.y: request, x: group of TT tiles.
 template <bool F16, int NW, int S, int A, int TT>
-__global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head_kernel(const ScoreJob* __restrict__ jobs, const char* __restrict__ wblob,
+__global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head_kernel(const TimeJob* __restrict__ jobs, const char* __restrict__ wblob,
                                                                                         size_t waveBytes, unsigned headZs, unsigned headZa,
                                                                                         const float* __restrict__ bias, int biasL, int skipBiasAt,
                                                                                         int L, const float* __restrict__ skf) {
@@ -204,7 +72,7 @@ __global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head
     char* const zsbuf = lds + H::SKBUF;
     float* const lgbuf = (float*)lds;
 
-    const ScoreJob jb = jobs[blockIdx.y];
+    const TimeJob jb = jobs[blockIdx.y];
     const int tile0 = blockIdx.x * TT;
     if (tile0 >= jb.tiles) return;      // (uniform over the workgroup)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -325,7 +193,7 @@ __global__ __launch_bounds__((HCfg<F16, NW, S, A, TT>::THREADS)) void score_head
 constexpr int score_nw(int R) { return R / 16 >= 4 ? 4 : R / 16; }
 
 template <bool F16, int R, int S, int A>
-bool launchHead(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
+bool launchHead(const TimeModel& m, const TimeJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
     constexpr int NW = score_nw(R), TT = score_head_tiles<F16, NW, S, A>();
     using H = HCfg<F16, NW, S, A, TT>;
     static_assert(H::FITS, "the head does not fit a CU");
@@ -337,134 +205,9 @@ bool launchHead(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTil
     return hipGetLastError() == hipSuccess;
 }
 
-template <bool F16, int R, int S, int A>
-bool launchScore(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, float* xf, char* xd0, char* xd1, float* skf,
-                 hipStream_t stream) {
-    using C = PCfg<F16, R>;
-    // (named here first, as it always was: the kernels of the object keep their order, and with it the object its bytes)
-    const auto head = score_head_kernel<F16, score_nw(R), S, A, score_head_tiles<F16, score_nw(R), S, A>()>;
-    (void)head;
-    hipLaunchKernelGGL((score_embed_kernel<F16>), dim3(maxTiles, count), dim3(256), 0, stream, jobs, R, A, m.embPrev, m.embCur, m.tanhEmbed, xf, xd0);
-    if (hipGetLastError() != hipSuccess) return false;
-    char* in = xd0;
-    char* out = xd1;
-    const int L = m.numLayers;
-    for (int l = 0; l < L; l++) {
-        hipLaunchKernelGGL((score_layer_kernel<F16, R, S>), dim3(maxTiles, count), dim3(C::THREADS), 0, stream, jobs, m.layers[l], l == 0 ? 1 : 0,
-                           l == L - 1 ? 1 : 0, (const char*)m.wblob, m.waveStreamFrags * 1024, m.bias + (size_t)l * m.biasL, m.nCond, xf,
-                           (const char*)in, out, skf);
-        if (hipGetLastError() != hipSuccess) return false;
-        char* const t = in;
-        in = out;
-        out = t;
-    }
-    return launchHead<F16, R, S, A>(m, jobs, count, maxTiles, skf, stream);
-}
-
-long long paddedSamples(int n) { return ((long long)n + 15) & ~15LL; }
-
 }  // namespace
 
-Score::~Score() {
-    if (m_scratch) gpuErrChk(hipFree(m_scratch));
-    if (m_jobs) gpuErrChk(hipFree(m_jobs));
-    if (m_chunkJobs) gpuErrChk(hipFree(m_chunkJobs));
-}
-
-char* Score::scratch(size_t need) {
-    if (need > m_scratchBytes) {
-        gpuErrChk(hipDeviceSynchronize());      // (an earlier call may still be using what is replaced)
-        if (m_scratch) gpuErrChk(hipFree(m_scratch));
-        m_scratch = NULL;
-        m_scratchBytes = 0;
-        gpuErrChk(hipMalloc((void**)&m_scratch, need));
-        m_scratchBytes = need;
-    }
-    return m_scratch;
-}
-
-bool Score::acceptable(const ScoreModel& m, const ScoreReq* reqs, int count, bool ownX) {
-    if (m.nCond <= 0 || reqs == NULL || count < 1 || count > 65535) return false;
-    bool shape = false;
-#define WN_SCORE_IS(RR, SS, AA) shape = shape || (m.R == RR && m.S == SS && m.A == AA);
-    WN_SCORE_SHAPES(WN_SCORE_IS)
-#undef WN_SCORE_IS
-    if (!shape) return false;
-    long long total = 0;
-    for (int i = 0; i < count; i++) {
-        const ScoreReq& q = reqs[i];
-        if (q.n < 1 || q.y == NULL || (q.precision != 32 && q.precision != 16) || q.cStride <= 0 || q.tStride <= 0 ||
-            !temperature_ok(q.temperature) || !is_device_ptr(q.y))
-            return false;
-        if (!ownX && (q.x == NULL || !is_device_ptr(q.x))) return false;
-        if (q.logp == NULL || ((size_t)q.logp & 3) != 0) return false;
-        char* const lp = (char*)store_target(q.logp);
-        const size_t span = (size_t)(q.n - 1) * sizeof(float);
-        if (lp == NULL || (char*)store_target((char*)q.logp + span) != lp + span) return false;
-        if (q.rows != NULL && (((size_t)q.rows & 15) != 0 || !is_device_ptr(q.rows) || !is_device_ptr(q.rows + (size_t)q.n * m.A - 1))) return false;
-        total += paddedSamples(q.n);
-        if (total > score_max_samples(m.f16, m.R, m.S)) return false;
-    }
-    return true;
-}
-
-bool Score::run(const ScoreModel& m, const ScoreReq* reqs, int count, hipStream_t stream, bool ownX) {
-    if (!acceptable(m, reqs, count, ownX)) return false;
-    std::vector<ScoreJob> jobs(count);
-    int maxTiles = 0;
-    long long total = 0;
-    for (int i = 0; i < count; i++) {
-        const ScoreReq& q = reqs[i];
-        ScoreJob& jb = jobs[i];
-        memset(&jb, 0, sizeof(jb));
-        jb.y = q.y;
-        jb.x = q.x;
-        jb.cStride = q.cStride;
-        jb.tStride = q.tStride;
-        jb.logp = (float*)store_target(q.logp);
-        jb.rows = q.rows;
-        jb.row0 = total;
-        jb.n = q.n;
-        jb.tiles = (int)(paddedSamples(q.n) / 16);
-        jb.precision = q.precision;
-        jb.scale = temperature_scale(q.temperature);
-        total += paddedSamples(q.n);
-        if (jb.tiles > maxTiles) maxTiles = jb.tiles;
-    }
-    // scratch, [total padded samples] each: the fp32 running residual, two T_data images of x, the fp32 skip sum
-    const int rowB = m.R * (m.f16 ? 2 : 4);
-    const size_t cells = (size_t)total, need = cells * score_row_bytes(m.f16, m.R, m.S);
-    scratch(need);
-    if (count > m_jobCap) {
-        gpuErrChk(hipDeviceSynchronize());      // (an earlier call may still be using what is replaced)
-        if (m_jobs) gpuErrChk(hipFree(m_jobs));
-        gpuErrChk(hipMalloc((void**)&m_jobs, 2 * (size_t)count * sizeof(ScoreJob)));
-        m_stage.make(2, (size_t)count * sizeof(ScoreJob));
-        m_jobCap = count;
-    }
-    float* const xf = (float*)m_scratch;
-    char* const xd0 = m_scratch + cells * m.R * 4;
-    char* const xd1 = xd0 + cells * rowB;
-    float* const skf = (float*)(xd1 + cells * rowB);
-    // the requests through pinned staging, two halves used by alternate calls (as prefill stages its requests)
-    ScoreJob* const dev = m_jobs + (size_t)m_stage.at() * m_jobCap;
-    void* const host = m_stage.acquire();
-    memcpy(host, jobs.data(), (size_t)count * sizeof(ScoreJob));
-    gpuErrChk(hipMemcpyAsync(dev, host, (size_t)count * sizeof(ScoreJob), hipMemcpyHostToDevice, stream));
-    m_stage.release(stream);
-
-    bool ok = false;
-#define WN_SCORE_CASE(RR, SS, AA)                                                                                              \
-    if (m.R == RR && m.S == SS && m.A == AA)                                                                                   \
-        ok = m.f16 ? launchScore<true, RR, SS, AA>(m, dev, count, maxTiles, xf, xd0, xd1, skf, stream)                         \
-                   : launchScore<false, RR, SS, AA>(m, dev, count, maxTiles, xf, xd0, xd1, skf, stream);
-    WN_SCORE_SHAPES(WN_SCORE_CASE)
-#undef WN_SCORE_CASE
-    return ok;
-}
-
-// (defined behind Score::run, so that the kernels are instantiated in the order they always were)
-bool score_launch_head(const ScoreModel& m, const ScoreJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
+bool score_launch_head(const TimeModel& m, const TimeJob* jobs, int count, int maxTiles, const float* skf, hipStream_t stream) {
     bool ok = false;
 #define WN_SCORE_HEAD(RR, SS, AA)                                                                                              \
     if (m.R == RR && m.S == SS && m.A == AA)                                                                                   \
@@ -473,6 +216,57 @@ bool score_launch_head(const ScoreModel& m, const ScoreJob* jobs, int count, int
     WN_SCORE_SHAPES(WN_SCORE_HEAD)
 #undef WN_SCORE_HEAD
     return ok;
+}
+
+bool Score::acceptable(const TimeModel& m, const ScoreReq* reqs, int count, bool ownX) {
+    if (!time_call_ok(m, reqs, count)) return false;
+    bool shape = false;
+#define WN_SCORE_IS(RR, SS, AA) shape = shape || (m.R == RR && m.S == SS && m.A == AA);
+    WN_SCORE_SHAPES(WN_SCORE_IS)
+#undef WN_SCORE_IS
+    if (!shape) return false;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        const ScoreReq& q = reqs[i];
+        if (!time_inputs_ok(q.y, q.n, q.x, q.precision, q.cStride, q.tStride, q.temperature, ownX)) return false;
+        if (q.logp == NULL || ((size_t)q.logp & 3) != 0) return false;
+        char* const lp = (char*)store_target(q.logp);
+        const size_t span = (size_t)(q.n - 1) * sizeof(float);
+        if (lp == NULL || (char*)store_target((char*)q.logp + span) != lp + span) return false;
+        if (q.rows != NULL && (((size_t)q.rows & 15) != 0 || !is_device_ptr(q.rows) || !is_device_ptr(q.rows + (size_t)q.n * m.A - 1))) return false;
+        total += padded_samples(q.n);
+        if (total > score_max_samples(m.f16, m.R, m.S)) return false;
+    }
+    return true;
+}
+
+bool Score::run(const TimeModel& m, const ScoreReq* reqs, int count, hipStream_t stream, bool ownX) {
+    if (!acceptable(m, reqs, count, ownX)) return false;
+    TimeJob* const jobs = m_jobs.begin(count);
+    int maxTiles = 0;
+    long long total = 0;
+    for (int i = 0; i < count; i++) {
+        const ScoreReq& q = reqs[i];
+        TimeJob& jb = jobs[i];
+        jb.y = q.y;
+        jb.x = q.x;
+        jb.cStride = q.cStride;
+        jb.tStride = q.tStride;
+        jb.logp = (float*)store_target(q.logp);
+        jb.rows = q.rows;
+        jb.row0 = total;
+        jb.n = q.n;
+        jb.tiles = (int)(padded_samples(q.n) / 16);
+        jb.precision = q.precision;
+        jb.yInPrev = jb.yInCur = 128;
+        jb.scale = temperature_scale(q.temperature);
+        total += padded_samples(q.n);
+        if (jb.tiles > maxTiles) maxTiles = jb.tiles;
+    }
+    const TimeScratch sc = time_carve(m_scratch.atLeast((size_t)total * time_scratch_bytes(m.f16, m.R, m.S)), (size_t)total, m);
+    const TimeJob* const dev = m_jobs.send(jobs, count, stream);
+
+    return launchLayers(m, dev, count, maxTiles, false, sc, stream) && score_launch_head(m, dev, count, maxTiles, sc.skf, stream);
 }
 
 }  // namespace wn

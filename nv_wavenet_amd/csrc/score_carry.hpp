@@ -8,14 +8,15 @@
 // the order of the whole pass, and one column of an MFMA's result does not depend on the other fifteen: logp and rows are bit for bit
 // those of score.hpp's pass over [0, k0 + n), and the out-state is byte for byte the blob of prefill.hpp at n' = k0 + n.
 //
-// Tiles are relative to the chunk: lane column r = 16 * tile + j is local sample k = k0 + r; k0 need not be a multiple of 16.
-//   * embedding: score_embed_kernel's arithmetic; y(k0 - 1), y(k0 - 2) from the in-state's header (128 from silence);
-//   * layer l: score_layer_kernel's body, operand for operand, except that the dilated tap of a column with r - d_l < 0 is read from
-//     the in-state's slot off_l + ((k0 + r - d_l) mod d_l) -- a zero operand where k0 + r - d_l < 0 or there is no in-state --, and
-//     that, with an out-state, x_{l+1} of the chunk's last min(n, d_{l+1}) samples also goes to the out blob's slots by ABSOLUTE k;
+// This is the time-parallel pass (time_pass.hpp) with everything on: tiles are relative to the chunk, lane column r = 16 * tile + j is
+// local sample k = k0 + r, and k0 need not be a multiple of 16.
+//   * embedding: y(k0 - 1), y(k0 - 2) from the in-state's header (128 from silence);
+//   * layer l: the dilated tap of a column with r - d_l < 0 is read from the in-state's slot off_l + ((k0 + r - d_l) mod d_l) -- a
+//     zero operand where k0 + r - d_l < 0 or there is no in-state --, and, with an out-state, x_{l+1} of the chunk's last
+//     min(n, d_{l+1}) samples also goes to the out blob's slots by ABSOLUTE k;
 //   * finish (only when some request has an out-state): the slots of every layer with d_l > n that no sample of the chunk maps to
 //     keep the in-state's bytes (zero from silence), and the header;
-//   * head: score.hip's score_head_kernel, launched through score_launch_head on a ScoreJob array staged beside the chunk jobs.
+//   * head: score.hip's score_head_kernel, launched through score_launch_head on the same jobs.
 // One launch per layer, ordered by the stream: no grid-wide barrier, no flag, nothing that waits for another workgroup.  In-states
 // are read only, and several requests may share one; an out-state overlaps no in-state and no other out-state of the call (a layer's
 // launch overwrites slots the next layer's launch still reads from the in-state).  The scratch is wn::Score's: one allocation, one cap.
@@ -65,26 +66,6 @@ struct ScoreChunkIn {
     int k0;                  // done of the in-state, 0 from silence
     unsigned uid;
     int yInPrev, yInCur;     // 128, 128 from silence
-};
-// ... as the kernels see a request
-struct CarryJob {
-    const int* y;
-    const void* x;
-    long long cStride, tStride;
-    const char* in;
-    char* out;
-    long long row0;          // first scratch row of the request
-    int n, tiles, precision, k0;
-    unsigned uid;
-    int temp;                // header word 10 of the out-state
-    int yInPrev, yInCur;
-};
-static_assert(sizeof(CarryJob) == 88, "CarryJob layout");
-// one layer's launch: ScoreLayer, the layer's first blob slot, and the ring of the layer it produces the input of
-struct CarryLayer {
-    unsigned cond, prev, cur, res, skip;
-    int d, off;
-    int dOut, offOut;
 };
 
 }  // namespace wn

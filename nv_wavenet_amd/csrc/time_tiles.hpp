@@ -1,8 +1,7 @@
-// time_tiles.hpp -- what the time-parallel passes share (prefill.hip, score.hip): 16 consecutive samples of one utterance in the
-// MFMA N dimension, x of a sample as a scratch row laid out like a blob slot.  Device code only; included behind wn_kernels.hpp.
+// time_tiles.hpp -- the device functions of the time-parallel passes (time_kernels.hpp, mel_time.hip): 16 consecutive samples of one
+// utterance in the MFMA N dimension, x of a sample as a scratch row laid out like a blob slot.
 #pragma once
 
-#include "gpu_check.hpp"
 #include "wn_kernels.hpp"
 
 namespace wn {
@@ -28,8 +27,7 @@ template <bool F16> WN_DEV void put_quad(char* at, floatx4 v) {
 WN_DEV int clamp_sample(int y, int A) { return y < 0 ? 0 : y >= A ? A - 1 : y; }
 
 // B fragments of the features of this lane's sample (column kk of the caller's tensor, channels 4g .. of every 16), converted as
-// the window feed converts them (slot_feed_kernel) -- the loop of prefill_layer_kernel, which keeps its own copy so that its
-// compiled code stays what it was
+// the window feed converts them (slot_feed_kernel)
 template <bool F16, int KFC>
 WN_DEV void feature_frags(const void* x, int precision, long long cStride, long long tStride, long long kk, int nCond, int g,
                           typename Prec<F16>::frag (&cf)[KFC]) {
@@ -47,19 +45,6 @@ WN_DEV void feature_frags(const void* x, int precision, long long cStride, long 
             }
             cf[kf][e] = (elem)v;
         }
-}
-
-// device memory (-> p) or mapped pinned host memory (-> its device-side address); NULL for anything else
-inline void* store_target(void* p) {
-    const int type = pointer_type(p);
-    if (type == hipMemoryTypeDevice || type == hipMemoryTypeManaged) return p;
-    if (type != hipMemoryTypeHost) return NULL;
-    void* d = NULL;
-    if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        return NULL;
-    }
-    return d;
 }
 
 }  // namespace wn

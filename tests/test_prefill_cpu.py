@@ -111,8 +111,13 @@ def test_the_prefill_kernels_use_no_scratch_and_spill_nothing():
     obj = os.path.join(BUILD, "prefill.o")
     if not os.path.exists(obj):
         pytest.skip("build the library first (__graft_entry__.build())")
-    rows = [r for r in kernel_table("prefill.o") if "prefill_" in r[0]]
-    layer = [r for r in rows if "prefill_layer_kernel<" in r[0]]
-    assert len(layer) == 8 and len(rows) == 11, [r[0] for r in rows]                       # R in {32, 64, 128, 256} x two precisions
+    rows = [r for r in kernel_table("prefill.o") if "::time_" in r[0]]
+    layer = [r for r in rows if "time_layer_kernel<" in r[0]]
+    embed = [r for r in rows if "time_embed_kernel<" in r[0]]
+    finish = [r for r in rows if "time_finish_kernel<" in r[0]]
+    # R in {32, 64, 128, 256} x two precisions, all without the skip path (S = 0) and the in-state taps; two embedding and two
+    # finish kernels
+    assert len(layer) == 8 and len(embed) == 2 and len(finish) == 2 and len(rows) == 12, [r[0] for r in rows]
+    assert all(re.search(r"time_layer_kernel<(true|false), \d+, 0, false>", r[0]) for r in layer), [r[0] for r in layer]
     for name, vgpr, agpr, sgpr, scratch, spill in rows:
         assert scratch == 0 and spill == 0 and vgpr <= 512 and agpr <= 256, (name, vgpr, agpr, scratch, spill)

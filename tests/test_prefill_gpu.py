@@ -155,6 +155,20 @@ def test_blob_equality_over_a_long_window(precision):
     e.close()
 
 
+def test_blob_equality_at_windows_that_start_past_sample_0():
+    """The prime shape (R 64, 8 layers, dilations 1 .. 16, W = 40) at n = 56, 57 and 90: the pass starts at t0 = 16, 16 and 48, so
+    the kernels index y and x from the window's first sample and the embedding reads its two history words from the prime itself,
+    in front of the window.  Both precisions."""
+    lengths = (56, 57, 90)
+    assert [PF.first_tile_sample(n, 8, 16) for n in lengths] == [16, 16, 48]
+    for precision in (16, 32):
+        case, e, xg, p = _shape_engine((64, 256, 256), 915, precision, N=96)
+        assert e.prefillWindow() == 40
+        jobs = [(b, b, _dev(p, b, n), 1.0) for b, n in enumerate(lengths)]
+        _check_equal(e, xg, jobs, case.shape.maxD, "windows past 0, fp%d" % precision)
+        e.close()
+
+
 # ---- 4. what follows a resume ------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("precision,mode", EQUALITY_RUNS)

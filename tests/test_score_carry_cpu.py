@@ -217,12 +217,14 @@ def test_the_carry_kernels_are_the_expected_ones_use_no_scratch_and_spill_nothin
     obj = os.path.join(BUILD, "score_carry.o")
     if not os.path.exists(obj):
         pytest.skip("build the library first (__graft_entry__.build())")
-    rows = [r for r in kernel_table("score_carry.o") if "score_carry_" in r[0]]
-    layer = [r for r in rows if "score_carry_layer_kernel<" in r[0]]
-    embed = [r for r in rows if "score_carry_embed_kernel<" in r[0]]
-    finish = [r for r in rows if "score_carry_finish_kernel" in r[0]]
-    # the six (R, S) of the eight built shapes in two precisions, two embedding kernels, one finish kernel; the head is score.o's
-    assert len(layer) == 12 and len(embed) == 2 and len(finish) == 1 and len(rows) == 15, [r[0] for r in rows]
+    rows = [r for r in kernel_table("score_carry.o") if "::time_" in r[0]]
+    layer = [r for r in rows if "time_layer_kernel<" in r[0]]
+    embed = [r for r in rows if "time_embed_kernel<" in r[0]]
+    finish = [r for r in rows if "time_finish_kernel<" in r[0]]
+    # the six (R, S) of the eight built shapes in two precisions, with the in-state taps -- the whole pass runs them too --; two
+    # embedding and two finish kernels; the head is score.o's
+    assert len(layer) == 12 and len(embed) == 2 and len(finish) == 2 and len(rows) == 16, [r[0] for r in rows]
+    assert all(re.search(r"time_layer_kernel<(true|false), \d+, (128|256), true>", r[0]) for r in layer), [r[0] for r in layer]
     assert not [r for r in kernel_table("score_carry.o") if "score_head_kernel" in r[0]], "a second copy of the head"
     for name, vgpr, agpr, sgpr, scratch, spill in rows:
         assert scratch == 0 and spill == 0 and vgpr <= 512 and agpr <= 256, (name, vgpr, agpr, scratch, spill)

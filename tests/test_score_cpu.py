@@ -120,10 +120,10 @@ def test_the_score_kernels_use_no_scratch_and_spill_nothing():
     obj = os.path.join(BUILD, "score.o")
     if not os.path.exists(obj):
         pytest.skip("build the library first (__graft_entry__.build())")
-    rows = [r for r in kernel_table("score.o") if "score_" in r[0]]
-    layer = [r for r in rows if "score_layer_kernel<" in r[0]]
+    rows = [r for r in kernel_table("score.o") if "score_" in r[0] or "::time_" in r[0]]
     head = [r for r in rows if "score_head_kernel<" in r[0]]
-    # (R, S) and (waves, S, A) of the eight built shapes, two precisions; two embedding kernels
-    assert len(layer) == 12 and len(head) == 12 and len(rows) == 26, [r[0] for r in rows]
+    # (waves, S, A) of the eight built shapes, two precisions; the layer kernels of the (R, S) are score_carry.o's, for the whole
+    # pass and the chunks, and are counted there (tests/test_score_carry_cpu.py)
+    assert len(head) == 12 and len(rows) == 12, [r[0] for r in rows]
     for name, vgpr, agpr, sgpr, scratch, spill in rows:
         assert scratch == 0 and spill == 0 and vgpr <= 512 and agpr <= 256, (name, vgpr, agpr, scratch, spill)
