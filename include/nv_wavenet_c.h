@@ -455,9 +455,8 @@ float nvw_slot_temperature(nvw_engine* e, int slot);
  * [0, 0.5]; p = 0 keeps every bin and is bit-identical to a run without these calls; 0.5 is where the guarantee ends that the most
  * probable bin survives the rounding of m c.  A forced sample (a prime) stays forced.  nvw_get_p reports the floored, renormalised
  * probabilities (dropped bins read exactly 0), nvw_get_za the raw logits.  Scoring (nvw_score_*) is NOT changed: it stays the model's
- * own distribution.  Top-k and top-p are not offered (they need a sort in the sample loop); greedy decoding is still not offered:
- * ties at the maximum are drawn between.  A launch with no floor in force executes the same instructions per logit as before; one
- * with a floor in force adds a compare and a select per logit.
+ * own distribution.  Top-k and top-p are the next section.  A launch with no floor in force executes the same instructions per logit
+ * as before; one with a floor in force adds a compare and a select per logit.
  * This extends the contract of slot mode once more: an utterance's samples depend on its features (or frames), its uid, the seed,
  * the model, the temperature AND THE FLOOR IN FORCE AT EACH LOCAL SAMPLE -- and on nothing else.
  *   nvw_set_min_p       lockstep: column b < n at floor p[b] (host array, 1 <= n <= batch) in the runs that follow; columns past n,
@@ -481,6 +480,46 @@ float nvw_slot_temperature(nvw_engine* e, int slot);
 int nvw_set_min_p(nvw_engine* e, const float* p, int n);
 int nvw_slot_set_min_p(nvw_engine* e, int slot, float p);
 float nvw_slot_min_p(nvw_engine* e, int slot);
+
+/* TAIL CUTS (TOP-K, TOP-P) PER UTTERANCE, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  Two more sampling controls, both
+ * thresholds on the quantity the floor compares, e = exp2(x c - m c) = prob / max prob of the TEMPERED distribution:
+ *   top-k = k  keeps the bins with e >= theta_k, theta_k the k-th largest e: the k most probable bins, and every bin that ties with
+ *              the k-th.  k is an integer in [0, A]; 0 is off (and k = A keeps every bin: bit-identical to off).
+ *   top-p = p  keeps the bins with e >= theta_p, theta_p the largest threshold whose kept mass (summed in float32, as the kernel sums)
+ *              still reaches p times the whole mass: the smallest set of most probable bins whose mass reaches p, ties at its edge
+ *              included.  p is finite and in (0, 1]; 1 is off.
+ * The kernel finds both thresholds by a bisection over the bit patterns of e -- no sort --, floors at max(theta_k, theta_p, min-p)
+ * and goes on as for the floor: the kept set is the INTERSECTION of the three cuts, each defined on the full tempered distribution
+ * (not the sequential "top-p of the renormalised top-k" some samplers apply).  The most probable bin always stays.  top-k = 1 is
+ * greedy decoding: the argmax, with only exact ties in e drawn between.  A forced sample stays forced; nvw_get_p reports the cut,
+ * renormalised probabilities (dropped bins read exactly 0), nvw_get_za the raw logits; scoring (nvw_score_*) is NOT changed.  A
+ * launch with every column off executes what it executed before these calls existed; one with a cut in force adds the search: 31
+ * steps, each with one compare per logit that serves both cuts, an add-with-carry (the count), a select and an add (the mass) --
+ * about a third of a sample at the headline shape, in every column of the launch, whatever the values.
+ * An utterance's samples depend on its features (or frames), its uid, the seed, the model, the temperature, the floor AND THE CUTS IN
+ * FORCE AT EACH LOCAL SAMPLE -- and on nothing else.
+ *   nvw_set_top_k, nvw_set_top_p            lockstep, as nvw_set_min_p: column b < n at k[b] / p[b] (host arrays, 1 <= n <= batch),
+ *                       columns past n, and every column with a NULL array, off.  None of nvw_set_temperatures, nvw_set_min_p and
+ *                       these two resets another's values.  While any column has a cut, a run on packed or in-place conditioning or
+ *                       on a multi-CU (chain) engine not on the features path prints one line and returns 0.  Synchronises.  0 when
+ *                       refused (in slot mode, n out of range, a bad value); nothing changes.
+ *   nvw_slot_set_top_k, nvw_slot_set_top_p  slot mode, as nvw_slot_set_min_p: from the next step on.  Starts put the column back to
+ *                       off; nvw_slot_move, the saves and the resumes carry the values: a blob holds top-k in word 12 of its header
+ *                       as the integer, top-p in word 13 as the bits of the float, all-zero bits for 1, so blobs of utterances
+ *                       without a cut are byte for byte what they were; a resume refuses a header whose word 12 is outside [0, A] or
+ *                       whose word 13 is neither zero nor a valid p.  The blobs that nvw_prefill_* and the scoring chunks write leave
+ *                       both words zero.  nvw_slot_stop and the source of a move go back to off.  0 when refused; nothing changes.
+ *   nvw_slot_top_k, nvw_slot_top_p          the value in force for column `slot` (host state); -1 when it holds no utterance.
+ *   nvw_sampler_mask    what the next features-path launch pays for (host state): bit 0, some column's floor is not 0 (a compare and
+ *                       a select per logit); bit 1, some column has a cut (the search).  0: the launches of an engine that never
+ *                       heard of floors and cuts.  A session whose floored and cutting utterances have all ended reads 0 again. */
+int nvw_set_top_k(nvw_engine* e, const int* k, int n);
+int nvw_set_top_p(nvw_engine* e, const float* p, int n);
+int nvw_slot_set_top_k(nvw_engine* e, int slot, int k);
+int nvw_slot_set_top_p(nvw_engine* e, int slot, float p);
+int nvw_slot_top_k(nvw_engine* e, int slot);
+float nvw_slot_top_p(nvw_engine* e, int slot);
+int nvw_sampler_mask(nvw_engine* e);
 
 /* PRIMED GENERATION: FORCED SAMPLE PREFIXES, LOCKSTEP AND IN SLOT MODE (additive within ABI 7).  An utterance may carry a prime, n
  * sample indices y[0 .. n) in 0 .. A-1: its local sample k < n IS y[k] -- written to the outputs (samples, PCM, ragged pieces) like

@@ -107,6 +107,13 @@ SIGNATURES = {
     "nvw_set_min_p": (C.c_int, [C.c_void_p, _fp, C.c_int]),
     "nvw_slot_set_min_p": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "nvw_slot_min_p": (C.c_float, [C.c_void_p, C.c_int]),
+    "nvw_set_top_k": (C.c_int, [C.c_void_p, _fp, C.c_int]),
+    "nvw_set_top_p": (C.c_int, [C.c_void_p, _fp, C.c_int]),
+    "nvw_slot_set_top_k": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "nvw_slot_set_top_p": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "nvw_slot_top_k": (C.c_int, [C.c_void_p, C.c_int]),
+    "nvw_slot_top_p": (C.c_float, [C.c_void_p, C.c_int]),
+    "nvw_sampler_mask": (C.c_int, [C.c_void_p]),
     "nvw_set_prime": (C.c_int, [C.c_void_p, _fp, _fp, C.c_int, C.c_int, C.c_longlong]),
     "nvw_slot_prime": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
     "nvw_slot_primed": (C.c_int, [C.c_void_p, C.c_int]),

@@ -61,6 +61,9 @@ struct nvw_engine {
     virtual void getYOut(int*, int, int, hipStream_t) = 0;
     virtual bool setTemperatures(const float*, int) = 0;
     virtual bool setMinP(const float*, int) = 0;
+    virtual bool setTopK(const int*, int) = 0;
+    virtual bool setTopP(const float*, int) = 0;
+    virtual int samplerMask() = 0;
     virtual bool setPrime(const int*, const int*, int, int, long long) = 0;
     virtual int prefillWindow() = 0;
     virtual int prefillStates(const wn::PrefillReq*, int, void*, long long, hipStream_t) = 0;
@@ -236,6 +239,9 @@ struct EngineImpl : nvw_engine {
     void getYOut(int* y, int off, int size, hipStream_t s) override { eng.getYOut(y, off, size, s); }
     bool setTemperatures(const float* T, int n) override { return eng.setTemperatures(T, n); }
     bool setMinP(const float* p, int n) override { return eng.setMinP(p, n); }
+    bool setTopK(const int* k, int n) override { return eng.setTopK(k, n); }
+    bool setTopP(const float* p, int n) override { return eng.setTopP(p, n); }
+    int samplerMask() override { return eng.floorMask(); }
     bool setPrime(const int* y, const int* n, int batch, int maxN, long long stride) override { return eng.setPrime(y, n, batch, maxN, stride); }
     int prefillWindow() override { return eng.prefillWindow(); }
     int prefillStates(const wn::PrefillReq* reqs, int count, void* dst, long long stride, hipStream_t s) override {

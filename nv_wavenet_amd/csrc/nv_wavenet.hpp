@@ -1252,6 +1252,8 @@ public:
     }
     // the temperature in force for column b (1 when none was ever set)
     float temperature(int b) const { return m_temps.get(b); }
+    // Params::floorOn of a features-path launch: bit 0, a floor other than 0 is in force; bit 1, a tail cut (either has made the table)
+    int floorMask() const { return (m_temps.nonZero > 0 ? 1 : 0) | (m_temps.cutting() > 0 ? 2 : 0); }
 
     // ---- probability floor, min-p (beyond the reference; slots_sampler.hpp) ----------------------------------------
     // Column b of the runs that follow draws from its tempered distribution WITHOUT the bins whose probability is below minP[b] times
@@ -1275,6 +1277,44 @@ public:
     }
     // the floor in force for column b (0 when none was ever set)
     float minP(int b) const { return m_temps.getP(b); }
+
+    // ---- tail cuts, top-k and top-p (beyond the reference; slots_sampler.hpp) ---------------------------------------
+    // Column b of the runs that follow draws from the topK[b] most probable bins of its tempered distribution (0: off), and from the
+    // smallest set of most probable bins whose mass reaches topP[b] (1: off), ties at either boundary included; the cuts and the
+    // floor intersect, each defined on the full tempered distribution.  b < n; the columns past n, and all of them with a NULL
+    // array, are off.  Host arrays, 1 <= n <= maxBatch; topK in [0, A]; topP finite and in (0, 1].  Everything else as setMinP, and
+    // none of the three calls resets another's values; with every column off the runs are bit-identical to never having called
+    // these.  Synchronises.  false (nothing changes): in slot mode (slotSetTopK / slotSetTopP are the calls there), n outside the
+    // batch, or a bad value.
+    bool setTopK(const int* topK, int n) {
+        if (m_slots->active()) return false;
+        if (topK != NULL) {
+            if (n < 1 || n > m_maxBatch) return false;
+            for (int b = 0; b < n; b++)
+                if (!wn::top_k_ok(topK[b], A)) return false;
+        }
+        gpuErrChk(hipDeviceSynchronize());
+        m_temps.resetK();
+        for (int b = 0; topK != NULL && b < n; b++) m_temps.setK(b, topK[b]);
+        m_temps.upload();
+        return true;
+    }
+    bool setTopP(const float* topP, int n) {
+        if (m_slots->active()) return false;
+        if (topP != NULL) {
+            if (n < 1 || n > m_maxBatch) return false;
+            for (int b = 0; b < n; b++)
+                if (!wn::top_p_ok(topP[b])) return false;
+        }
+        gpuErrChk(hipDeviceSynchronize());
+        m_temps.resetTopP();
+        for (int b = 0; topP != NULL && b < n; b++) m_temps.setTopP(b, topP[b]);
+        m_temps.upload();
+        return true;
+    }
+    // the cuts in force for column b (0 and 1 when none was ever set)
+    int topK(int b) const { return m_temps.getK(b); }
+    float topP(int b) const { return m_temps.getTopP(b); }
 
     // ---- primed generation (beyond the reference; slots_prime.hpp) -------------------------------------------------
     // Column b < batch of the runs that follow starts with the forced samples y[b * stride + k], k < n[b] (0 <= n[b] <= maxN <=
@@ -1605,6 +1645,13 @@ public:
             return false;
         }
 
+        if (m_temps.cutting() > 0 && !m_featPtr) {
+            fprintf(stderr, "nvWavenetInfer: some columns have a tail cut (%d top-k, %d top-p), which packed or in-place conditioning "
+                    "and multi-CU launches cannot honour: use the features path, or setTopK(NULL, 0) and setTopP(NULL, 0)\n",
+                    m_temps.nonOffK, m_temps.nonOffP);
+            return false;
+        }
+
         if (m_prime.any() && !m_featPtr) {
             fprintf(stderr, "nvWavenetInfer: %d columns carry a prime, which packed or in-place conditioning and multi-CU launches cannot "
                     "honour: use the features path, or setPrime(NULL, ..)\n", m_prime.primed);
@@ -1642,7 +1689,7 @@ public:
         p.dump = dumpActivations ? 1 : 0;
         p.useRng = m_useRng ? 1 : 0;
         p.softScale = m_featPtr ? m_temps.softScale : NULL;
-        p.floorOn = (m_featPtr && m_temps.nonZero > 0) ? 1 : 0;      // (a floor other than 0 has made the table)
+        p.floorOn = m_featPtr ? floorMask() : 0;
         m_lastStride = num_samples;
         if (p.count <= 0) return true;
         bool primeOk = true;
@@ -1793,7 +1840,7 @@ protected:
         p.dump = 0;
         p.useRng = 0;
         p.softScale = m_temps.softScale;
-        p.floorOn = m_temps.nonZero > 0 ? 1 : 0;      // (a floor other than 0 has made the table)
+        p.floorOn = floorMask();
         p.forced = forced ? 1 : 0;
         return launchWg(p, tiles, stream);
     }

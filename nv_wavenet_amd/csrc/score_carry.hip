@@ -29,10 +29,11 @@ char* blobTarget(const void* p, size_t bytes, bool* pinned) {
 }
 
 bool headerFits(const TimeModel& m, const SlotStateHeader& h) {
-    float T, P;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid probability floor)
+    float T, P, Q;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid probability floor;
+    int K;              // word 12: top-k within the alphabet; word 13: zero, or the bits of a valid top-p -- checked, then ignored)
     return h.magic == kSlotStateMagic && h.version == kSlotStateVersion && h.precision == (m.f16 ? 16 : 32) && h.R == m.R &&
            h.numLayers == m.numLayers && h.maxDilation == m.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T) &&
-           min_p_of_word(h.pad[1], P);
+           min_p_of_word(h.pad[1], P) && top_k_of_word(h.pad[2], m.A, K) && top_p_of_word(h.pad[3], Q);
 }
 
 }  // namespace

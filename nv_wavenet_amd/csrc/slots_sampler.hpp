@@ -8,6 +8,9 @@
 // The floor tau of a column drops the bins whose tempered probability is below tau times that of the most probable bin: the kernel
 // zeroes e = exp2(x c - m c) < tau before the sum (softmax_pick).  The floors are the second half of the same table,
 // softScale[columns + b], read only by a launch whose Params::floorOn is set; they travel exactly as the scales do.
+// The tail cuts of a column (top-k and top-p, §6n) are two more thresholds on the same e: the kernel finds them by a bisection over
+// the bit patterns of e (cut_threshold) and floors at the largest of the three.  Top-k (an integer, as its bits) and top-p are the
+// third and fourth quarter of the table, read only by a launch whose Params::floorOn has bit 1 set.
 // The kernel (slots_sampler.hip) is compiled once for both precisions.
 #pragma once
 
@@ -58,9 +61,43 @@ inline bool min_p_of_word(int w, float& p) {
     return min_p_ok(p) && p != 0.0f;
 }
 
+// Top-k: an integer in [0, A]; 0 is off (every bin stays), and so in effect is A.
+inline bool top_k_ok(int k, int A) { return k >= 0 && k <= A; }
+// The word that carries top-k in a state blob (SlotStateHeader::pad[2]): the integer itself.
+inline int top_k_word(int k) { return k; }
+// false: the word is outside [0, A]
+inline bool top_k_of_word(int w, int A, int& k) {
+    k = 0;
+    if (!top_k_ok(w, A)) return false;
+    k = w;
+    return true;
+}
+// Top-p (nucleus): finite and within (0, 1] (a NaN fails both comparisons); 1 is off.
+inline bool top_p_ok(float p) { return p > 0.0f && p <= 1.0f; }
+// The word that carries top-p in a state blob (SlotStateHeader::pad[3]): the bits of the float, all-zero bits for 1.
+inline int top_p_word(float p) {
+    int w = 0;
+    if (p != 1.0f) memcpy(&w, &p, sizeof(w));
+    return w;
+}
+// false: the word is neither zero nor a valid top-p (the bits of 1.0 among them: top_p_word never writes them)
+inline bool top_p_of_word(int w, float& p) {
+    p = 1.0f;
+    if (w == 0) return true;
+    memcpy(&p, &w, sizeof(p));
+    return top_p_ok(p) && p != 1.0f;
+}
+// a table entry that holds top-k: the integer's bits in the float's place
+inline float top_k_entry(int k) {
+    float f;
+    memcpy(&f, &k, sizeof(f));
+    return f;
+}
+
 // The table itself, lockstep and slot mode: the host's values are the authority, the device table follows them.  Nothing is
-// allocated, and Params::softScale stays NULL, until a temperature other than 1 or a floor other than 0 has been set: an engine that
-// uses neither launches what it launched before.  The device table is [2][columns]: the scales, then the floors.
+// allocated, and Params::softScale stays NULL, until a temperature other than 1, a floor other than 0 or a cut has been set: an
+// engine that uses none of them launches what it launched before.  The device table is [4][columns]: the scales, the floors, top-k
+// (integers) and top-p.
 struct TemperatureTable {
     explicit TemperatureTable(int columns) : columns(columns) {}
     ~TemperatureTable();
@@ -72,12 +109,21 @@ struct TemperatureTable {
     // the floor in force for column b (0 when none was ever set); the first value other than 0 makes the device table likewise
     float getP(int b) const { return (b >= 0 && b < (int)P.size()) ? P[b] : 0.0f; }
     void setP(int b, float p);
-    // every column back to T = 1 and floor 0, on the host and in the table (synchronises when the table has to be rewritten: a
+    // top-k and top-p in force for column b (0 and 1, off, when none was ever set); the first value that is not off makes the table
+    int getK(int b) const { return (b >= 0 && b < (int)K.size()) ? K[b] : 0; }
+    void setK(int b, int k);
+    float getTopP(int b) const { return (b >= 0 && b < (int)Q.size()) ? Q[b] : 1.0f; }
+    void setTopP(int b, float p);
+    // columns with a cut in force
+    int cutting() const { return nonOffK + nonOffP; }
+    // every column back to T = 1, floor 0 and no cut, on the host and in the table (synchronises when the table has to be rewritten: a
     // value other than these is in force, or deviceBehind -- the table holds values the host has since taken back)
     void reset(bool deviceBehind);
     // the host's temperatures / floors alone back to 1 / 0 (the caller uploads)
     void resetT() { T.clear(), nonUnit = 0; }
     void resetP() { P.clear(), nonZero = 0; }
+    void resetK() { K.clear(), nonOffK = 0; }
+    void resetTopP() { Q.clear(), nonOffP = 0; }
     // the whole table from the host's values, when it exists (blocking copy)
     void upload();
 
@@ -86,21 +132,26 @@ struct TemperatureTable {
     int nonUnit = 0;                        // columns with T != 1
     std::vector<float> P;                   // [columns] floor per column (empty: 0 everywhere)
     int nonZero = 0;                        // columns with a floor != 0
-    float* softScale = NULL;                // [2][columns] on the device, made at the first use: log2(e) / T, filled with log2(e); then
-                                            // the floors, filled with 0
+    std::vector<int> K;                     // [columns] top-k per column (empty: 0, off, everywhere)
+    int nonOffK = 0;                        // columns with top-k != 0
+    std::vector<float> Q;                   // [columns] top-p per column (empty: 1, off, everywhere)
+    int nonOffP = 0;                        // columns with top-p != 1
+    float* softScale = NULL;                // [4][columns] on the device, made at the first use: log2(e) / T, filled with log2(e); then
+                                            // the floors, filled with 0; top-k as integers, filled with 0; top-p, filled with 1
 private:
     void make();
 };
 
 // one changed table entry of a step
 struct SlotScale {
-    int column;              // the entry: b for the scale of column b, columns + b for its floor
-    float scale;             // log2(e) / T, or the floor
+    int column;              // the entry: b for the scale of column b, columns + b for its floor, 2 columns + b for its top-k,
+                             // 3 columns + b for its top-p
+    float scale;             // log2(e) / T, the floor, top-k (top_k_entry) or top-p
 };
 static_assert(sizeof(SlotScale) == 8, "SlotScale layout");
 
 // table[upd[i].column] = upd[i].scale for the n entries (device memory; entries pairwise distinct, each below `columns`, the
-// length of the table -- twice the engine's batch; an entry outside the table is skipped).  Asynchronous.
+// length of the table -- four times the engine's batch; an entry outside the table is skipped).  Asynchronous.
 bool slots_set_scales(hipStream_t stream, float* table, int columns, const SlotScale* upd, int n);
 
 }  // namespace wn

@@ -39,10 +39,11 @@ SlotStateHeader headerCommon(const SlotFacts& f) {
     return h;
 }
 bool headerOk(const SlotFacts& f, const SlotStateHeader& h) {
-    float T, P;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid floor)
+    float T, P, Q;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid floor; word 12: top-k,
+    int K;              // within the alphabet; word 13: zero, or the bits of a valid top-p)
     return h.magic == kSlotStateMagic && h.version == kSlotStateVersion && h.precision == (f.f16 ? 16 : 32) && h.R == f.R &&
            h.numLayers == f.numLayers && h.maxDilation == f.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T) &&
-           min_p_of_word(h.pad[1], P);
+           min_p_of_word(h.pad[1], P) && top_k_of_word(h.pad[2], f.A, K) && top_p_of_word(h.pad[3], Q);
 }
 }  // namespace
 
@@ -99,7 +100,7 @@ bool SlotSession::begin(int window) {
     m_slotResume.assign(f.maxBatch, NULL);
     m_slotResumeDone.assign(f.maxBatch, 0);
     m_slotMoveEnd.assign(f.maxBatch, 0);
-    m_temps.reset(false);      // (every column at T = 1 and floor 0, a lockstep run's values included)
+    m_temps.reset(false);      // (every column at T = 1, floor 0 and no cut, a lockstep run's values included)
     m_primeY.clear();
     m_primeN.clear();
     m_primeListed.clear();
@@ -134,6 +135,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
     slotMinPSet(slot, 0.0f);
+    slotCutSet(slot, 0, 1.0f);
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -145,6 +147,7 @@ bool SlotSession::stop(int slot) {
     slotMarkPending(slot, 2);
     slotPrimeSet(slot, NULL, 0);
     slotMinPSet(slot, 0.0f);      // (an idle column holds no floor: the launches go back to Params::floorOn = 0 with the last floored utterance)
+    slotCutSet(slot, 0, 1.0f);
     return true;
 }
 bool SlotSession::startMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
@@ -167,6 +170,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     slotMarkPending(slot, 1);
     slotTempSet(slot, 1.0f);
     slotMinPSet(slot, 0.0f);
+    slotCutSet(slot, 0, 1.0f);
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -187,6 +191,16 @@ bool SlotSession::setTemperature(int slot, float T) {
 bool SlotSession::setMinP(int slot, float p) {
     if (!inBatch(slot) || !slotHolds(slot) || !min_p_ok(p)) return false;
     slotMinPSet(slot, p);
+    return true;
+}
+bool SlotSession::setTopK(int slot, int k) {
+    if (!inBatch(slot) || !slotHolds(slot) || !top_k_ok(k, f.A)) return false;
+    slotCutSet(slot, k, m_temps.getTopP(slot));
+    return true;
+}
+bool SlotSession::setTopP(int slot, float p) {
+    if (!inBatch(slot) || !slotHolds(slot) || !top_p_ok(p)) return false;
+    slotCutSet(slot, m_temps.getK(slot), p);
     return true;
 }
 bool SlotSession::prime(int slot, const int* y, int n) {
@@ -215,6 +229,8 @@ bool SlotSession::move(int from, int to) {
     slotTempSet(to, m_temps.get(from));
     slotMinPSet(to, m_temps.getP(from));
     slotMinPSet(from, 0.0f);      // (as stop())
+    slotCutSet(to, m_temps.getK(from), m_temps.getTopP(from));
+    slotCutSet(from, 0, 1.0f);
     if (primed(from)) {
         slotPrimeSet(to, m_primeY[from], m_primeN[from]);
         slotPrimeSet(from, NULL, 0);
@@ -233,6 +249,8 @@ int SlotSession::save(int slot, void* dst, hipStream_t stream) {
     h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
     h.pad[0] = temperature_word(m_temps.get(slot));
     h.pad[1] = min_p_word(m_temps.getP(slot));
+    h.pad[2] = top_k_word(m_temps.getK(slot));
+    h.pad[3] = top_p_word(m_temps.getTopP(slot));
     if (!slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), f.ring, f.ringSlots, f.ringFragsPerSlot, f.yInPrev, f.yInCur))
         return -1;
     return (int)done;
@@ -267,13 +285,17 @@ int SlotSession::saveList(const int* slots, int n, void* dst, long long stride, 
         const long long done = m_slotCounter - (mel ? m_melHost[b].start : m_slotHost[b].start);
         if (done < 0 || done > 0x7fffffffLL) return -1;
     }
+    // (a half of the staging and of the device buffer: maxBatch entries, then their maxBatch pairs of cut words)
+    const size_t saveHalf = (size_t)f.maxBatch * (sizeof(SlotSave) + sizeof(SlotSaveCut));
     if (!m_saveDev) {
-        gpuErrChk(hipMalloc((void**)&m_saveDev, 2 * (size_t)f.maxBatch * sizeof(SlotSave)));
-        m_saveStage.make(2, (size_t)f.maxBatch * sizeof(SlotSave));
+        gpuErrChk(hipMalloc((void**)&m_saveDev, 2 * saveHalf));
+        m_saveStage.make(2, saveHalf);
     }
     const SlotLayer* const layers = slotLayers();
-    SlotSave* const dev = m_saveDev + (size_t)m_saveStage.at() * f.maxBatch;
+    SlotSave* const dev = (SlotSave*)((char*)m_saveDev + (size_t)m_saveStage.at() * saveHalf);
     SlotSave* const stage = (SlotSave*)m_saveStage.acquire();
+    SlotSaveCut* const cutStage = (SlotSaveCut*)(stage + f.maxBatch);
+    bool anyCut = false;
     for (int i = 0; i < n; i++) {
         const int b = slots[i];
         const bool mel = m_melHost[b].state != 0;
@@ -281,10 +303,14 @@ int SlotSession::saveList(const int* slots, int n, void* dst, long long stride, 
         const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
         const int done = (int)(m_slotCounter - start);
         stage[i] = SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, temperature_word(m_temps.get(b)), min_p_word(m_temps.getP(b))};
+        cutStage[i] = SlotSaveCut{top_k_word(m_temps.getK(b)), top_p_word(m_temps.getTopP(b))};
+        anyCut = anyCut || cutStage[i].x != 0 || cutStage[i].y != 0;
         saved[i] = SlotSaved{b, uid, done, mel ? 1 : 0};
     }
     gpuErrChk(hipMemcpyAsync(dev, stage, (size_t)n * sizeof(SlotSave), hipMemcpyHostToDevice, stream));
-    const bool ok = slots_save_list(stream, dev, n, headerCommon(f), layers, f.ring, f.ringSlots, f.ringFragsPerSlot, f.yInPrev, f.yInCur);
+    SlotSaveCut* const cutDev = (SlotSaveCut*)(dev + f.maxBatch);
+    if (anyCut) gpuErrChk(hipMemcpyAsync(cutDev, cutStage, (size_t)n * sizeof(SlotSaveCut), hipMemcpyHostToDevice, stream));
+    const bool ok = slots_save_list(stream, dev, anyCut ? cutDev : NULL, n, headerCommon(f), layers, f.ring, f.ringSlots, f.ringFragsPerSlot, f.yInPrev, f.yInCur);
     m_saveStage.release(stream);
     return ok ? n : -1;
 }
@@ -681,17 +707,29 @@ void SlotSession::slotMinPSet(int slot, float p) {
     if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
     m_tempDirty[slot] = 1;
 }
+// ... and the tail cuts (top-k, top-p): the same list, a changed column's four table entries are written together
+void SlotSession::slotCutSet(int slot, int k, float p) {
+    if (m_temps.getK(slot) == k && m_temps.getTopP(slot) == p) return;
+    m_temps.setK(slot, k);
+    m_temps.setTopP(slot, p);
+    if (m_tempDirty.empty()) m_tempDirty.assign(f.maxBatch, 0);
+    if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
+    m_tempDirty[slot] = 1;
+}
 // the pending start of column `slot` resumes from the blob `state`, whose (checked) header is h
 void SlotSession::slotSetResume(int slot, const void* state, const SlotStateHeader& h) {
     slotLayers();
     m_slotResume[slot] = state;
     m_slotResumeDone[slot] = h.done;
-    float T = 1.0f, P = 0.0f;
-    const bool ok = temperature_of_word(h.pad[0], T) && min_p_of_word(h.pad[1], P);      // (headerOk has checked them)
+    float T = 1.0f, P = 0.0f, Q = 1.0f;
+    int K = 0;
+    const bool ok = temperature_of_word(h.pad[0], T) && min_p_of_word(h.pad[1], P) && top_k_of_word(h.pad[2], f.A, K) &&
+                    top_p_of_word(h.pad[3], Q);      // (headerOk has checked them)
     assert(ok);
     (void)ok;
     slotTempSet(slot, T);
     slotMinPSet(slot, P);
+    slotCutSet(slot, K, Q);
 }
 // the changed columns -> pinned staging -> device, then one slot_scale_kernel launch (staging halves as slotApplyPending, made
 // by the first step that needs them)
@@ -702,20 +740,22 @@ bool SlotSession::slotApplyTemperatures(hipStream_t stream) {
         return true;
     }
     if (!m_scaleDev) {
-        gpuErrChk(hipMalloc((void**)&m_scaleDev, 2 * (size_t)f.maxBatch * sizeof(SlotScale)));      // (a column's scale and its floor)
-        m_scaleStage.make(2, 2 * (size_t)f.maxBatch * sizeof(SlotScale));
+        gpuErrChk(hipMalloc((void**)&m_scaleDev, 4 * (size_t)f.maxBatch * sizeof(SlotScale)));      // (a column's scale, floor, top-k and top-p)
+        m_scaleStage.make(2, 4 * (size_t)f.maxBatch * sizeof(SlotScale));
     }
     SlotScale* const stage = (SlotScale*)m_scaleStage.acquire();
     int n = 0;
     for (int b : m_tempDirtyList) {
         stage[n++] = SlotScale{b, temperature_scale(m_temps.get(b))};
         stage[n++] = SlotScale{f.maxBatch + b, m_temps.getP(b)};
+        stage[n++] = SlotScale{2 * f.maxBatch + b, top_k_entry(m_temps.getK(b))};
+        stage[n++] = SlotScale{3 * f.maxBatch + b, m_temps.getTopP(b)};
         m_tempDirty[b] = 0;
     }
     m_tempDirtyList.clear();
     gpuErrChk(hipMemcpyAsync(m_scaleDev, stage, (size_t)n * sizeof(SlotScale), hipMemcpyHostToDevice, stream));
     m_scaleStage.release(stream);
-    return slots_set_scales(stream, m_temps.softScale, 2 * f.maxBatch, m_scaleDev, n);
+    return slots_set_scales(stream, m_temps.softScale, 4 * f.maxBatch, m_scaleDev, n);
 }
 // ---- primed generation (slots_prime.hpp) ----
 void SlotSession::slotPrimeSet(int slot, const int* y, int n) {

@@ -129,6 +129,16 @@ public:
     bool setMinP(int slot, float p);
     // the host's value for column `slot`; -1 when it holds no utterance (0 is a valid floor)
     float minP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getP(slot) : -1.f; }
+    // The utterance of column `slot` draws from the k most probable bins of its tempered distribution (top-k; 0: off), or from the
+    // smallest set of most probable bins whose mass reaches p (top-p; 1: off), ties at either boundary included, from
+    // the next step on; the cuts and the floor intersect.  Everything else as setMinP: starts put the column back to off, moves, saves
+    // and resumes carry the values (SlotStateHeader::pad[2], pad[3]), the step's one small launch writes them.  false (nothing
+    // changes): as setTemperature; k outside [0, A]; p not finite or outside (0, 1].
+    bool setTopK(int slot, int k);
+    bool setTopP(int slot, float p);
+    // the host's values for column `slot`; -1 when it holds no utterance
+    int topK(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getK(slot) : -1; }
+    float topP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getTopP(slot) : -1.f; }
     // ---- primed generation (slots_prime.hpp) ----
     // The utterance whose start or resume is pending on column `slot` carries the prime y[0 .. n) (device memory, int32; kept alive and
     // unchanged until local sample n has been generated): its local samples k < n are y[k], clamped into the alphabet, delivered and
@@ -266,7 +276,7 @@ private:
     std::vector<SlotMove> m_slotMoves;      // the pending moves
     SlotLayer* m_slotLayers = NULL;         // the schedule per ring slot on the device (built by the first save or resume, kept)
     // ... and lists of columns saved in one launch: the entries' staging, made by the first list save
-    SlotSave* m_saveDev = NULL;             // [2][maxBatch] on the device, used by alternate list saves ...
+    SlotSave* m_saveDev = NULL;             // [2] x ([maxBatch] entries, then [maxBatch] SlotSaveCut) on the device, used by alternate list saves ...
     StageRing m_saveStage;                  // ... their pinned host staging: two halves
     std::vector<int> m_listMark;            // scratch of the list calls: per column, the index + 1 of the entry that names it
     // ... and ragged delivery (slots_deliver.hpp): a step's valid samples piece by piece, completion by ticket
@@ -277,7 +287,7 @@ private:
     // ... and the sampling temperatures (slots_sampler.hpp)
     std::vector<char> m_tempDirty;          // the columns whose table entry the next step writes
     std::vector<int> m_tempDirtyList;
-    SlotScale* m_scaleDev = NULL;           // [2 maxBatch] on the device: a step's changed entries (made by the first step that needs it)
+    SlotScale* m_scaleDev = NULL;           // [4 maxBatch] on the device: a step's changed entries (made by the first step that needs it)
     StageRing m_scaleStage;                 // ... their pinned host staging: two halves
     // ... and the primes (slots_prime.hpp)
     std::vector<const int*> m_primeY;       // per column: the prime in force (made by the first prime of a session) ...
@@ -325,6 +335,7 @@ private:
     bool slotApplyPending(hipStream_t stream);
     void slotTempSet(int slot, float T);
     void slotMinPSet(int slot, float p);
+    void slotCutSet(int slot, int k, float p);
     void slotSetResume(int slot, const void* state, const SlotStateHeader& h);
     bool slotApplyTemperatures(hipStream_t stream);
     void slotPrimeSet(int slot, const int* y, int n);

@@ -73,9 +73,10 @@ __global__ __launch_bounds__(256) void slot_save_kernel(uintx4* __restrict__ blo
 }
 
 // Column save for a list: slot_save_kernel per entry, blockIdx.y striding over the entries (the grid of slot_load_kernel).  The common
-// header fields are one argument, done, uid, the temperature word and the floor word come from the entry; every destination is device memory or the device-side address
+// header fields are one argument, done, uid, the temperature word and the floor word come from the entry, the cut words from the array beside them (NULL: zero); every destination is device memory or the device-side address
 // of mapped pinned host memory -- the blob side stays contiguous 16-byte stores either way.
-__global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __restrict__ saves, int nSaves, SlotStateHeader hdr,
+__global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __restrict__ saves, const SlotSaveCut* __restrict__ cuts,
+                                                             int nSaves, SlotStateHeader hdr,
                                                              const SlotLayer* __restrict__ layers, const uintx4* __restrict__ ring,
                                                              int ringSlots, int pshift, const int* __restrict__ yInPrev,
                                                              const int* __restrict__ yInCur) {
@@ -95,6 +96,11 @@ __global__ __launch_bounds__(256) void slot_save_list_kernel(const SlotSave* __r
             h.uid = sv.uid;
             h.pad[0] = sv.temp;
             h.pad[1] = sv.minp;
+            if (cuts != nullptr) {
+                const SlotSaveCut cut = cuts[c];
+                h.pad[2] = cut.x;
+                h.pad[3] = cut.y;
+            }
             h.yInPrev = yInPrev[sv.column];
             h.yInCur = yInCur[sv.column];
             *(SlotStateHeader*)sv.dst = h;
@@ -154,13 +160,13 @@ bool slots_save(hipStream_t stream, void* dst, SlotStateHeader hdr, int column, 
     return hipGetLastError() == hipSuccess;
 }
 
-bool slots_save_list(hipStream_t stream, const SlotSave* saves, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
+bool slots_save_list(hipStream_t stream, const SlotSave* saves, const SlotSaveCut* cuts, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
                      int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur) {
     const int pshift = pieceShift(fragsPerSlot);
     if (pshift < 0) return false;
     if (nSaves <= 0) return true;
     hipLaunchKernelGGL(slot_save_list_kernel, dim3(gridOf(ringSlots << pshift, 64), nSaves > 1024 ? 1024 : nSaves), dim3(256), 0, stream, saves,
-                       nSaves, hdr, layers, (const uintx4*)ring, ringSlots, pshift, yInPrev, yInCur);
+                       cuts, nSaves, hdr, layers, (const uintx4*)ring, ringSlots, pshift, yInPrev, yInCur);
     return hipGetLastError() == hipSuccess;
 }
 

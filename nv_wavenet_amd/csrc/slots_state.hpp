@@ -31,7 +31,8 @@ struct SlotStateHeader {
     int yInPrev, yInCur;     // the column's sample history
     int pad[6];              // pad[0]: the sampling temperature as the bits of the float, all-zero bits for T = 1 (slots_sampler.hpp:
                              // blobs of utterances at T = 1 are what they were before temperatures existed); pad[1]: the probability floor likewise,
-                             // all-zero bits for floor 0; the rest zero
+                             // all-zero bits for floor 0; pad[2]: top-k, the integer (0: off); pad[3]: top-p as the bits of the float, all-zero
+                             // bits for 1 (off); the rest zero
 };
 static_assert(sizeof(SlotStateHeader) == 64, "SlotStateHeader layout");
 
@@ -64,6 +65,9 @@ struct SlotSave {
     int minp;                // header word 11 (pad[1]): the bits of the column's probability floor, 0 for floor 0
 };
 static_assert(sizeof(SlotSave) == 32, "SlotSave layout");
+// ... and its tail cuts, in an array beside the entries (SlotSave is full): x = header word 12 (pad[2]), top-k; y = header word 13
+// (pad[3]), the top-p word
+typedef int2 SlotSaveCut;
 
 // what the host reports per column of a list save, and one request of a list resume (nvw_slot_saved, nvw_slot_resume_req)
 struct SlotSaved {
@@ -92,8 +96,9 @@ bool slots_move(hipStream_t stream, const SlotMove* moves, int nMoves, void* rin
 bool slots_save(hipStream_t stream, void* dst, SlotStateHeader hdr, int column, int rot, const SlotLayer* layers, const void* ring,
                 int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur);
 // slots_save for nSaves columns in one launch: entry i's column into entry i's dst, hdr = the fields every blob shares (done, uid and
-// the history are filled per entry).  The destinations are pairwise disjoint.  Asynchronous.
-bool slots_save_list(hipStream_t stream, const SlotSave* saves, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
+// the history are filled per entry; cuts: entry i's words 12 and 13, NULL when no saved column has a cut -- both words zero).  The
+// destinations are pairwise disjoint.  Asynchronous.
+bool slots_save_list(hipStream_t stream, const SlotSave* saves, const SlotSaveCut* cuts, int nSaves, SlotStateHeader hdr, const SlotLayer* layers, const void* ring,
                      int ringSlots, int fragsPerSlot, const int* yInPrev, const int* yInCur);
 // The nLoads blobs into their columns with the inverse rotation; the history from their headers.  Asynchronous.
 bool slots_load(hipStream_t stream, const SlotLoad* loads, int nLoads, const SlotLayer* layers, void* ring, int ringSlots,

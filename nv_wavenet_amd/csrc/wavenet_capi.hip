@@ -389,6 +389,34 @@ int nvw_slot_set_min_p(nvw_engine* e, int slot, float p) {
     return 0;
 }
 float nvw_slot_min_p(nvw_engine* e, int slot) { return e->slots().minP(slot); }
+// ---- tail cuts (top-k, top-p) per utterance, lockstep and in slot mode (additive within ABI 7) -------------------------------------
+int nvw_set_top_k(nvw_engine* e, const int* k, int n) {
+    if (e->setTopK(k, n)) return 1;
+    fprintf(stderr, "nvw_set_top_k: refused, nothing changed (not in slot mode; %d values for %d columns; every value in [0, A])\n", n,
+            e->maxBatch());
+    return 0;
+}
+int nvw_set_top_p(nvw_engine* e, const float* p, int n) {
+    if (e->setTopP(p, n)) return 1;
+    fprintf(stderr, "nvw_set_top_p: refused, nothing changed (not in slot mode; %d values for %d columns; every value finite and in "
+            "(0, 1])\n", n, e->maxBatch());
+    return 0;
+}
+int nvw_slot_set_top_k(nvw_engine* e, int slot, int k) {
+    if (e->slots().setTopK(slot, k)) return 1;
+    fprintf(stderr, "nvw_slot_set_top_k: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
+            "a pending start or resume; k = %d in [0, A])\n", slot, e->maxBatch(), k);
+    return 0;
+}
+int nvw_slot_set_top_p(nvw_engine* e, int slot, float p) {
+    if (e->slots().setTopP(slot, p)) return 1;
+    fprintf(stderr, "nvw_slot_set_top_p: refused, nothing changed (nvw_slots_begin first; slot %d of %d: a column with an utterance or "
+            "a pending start or resume; p = %g finite and in (0, 1])\n", slot, e->maxBatch(), (double)p);
+    return 0;
+}
+int nvw_slot_top_k(nvw_engine* e, int slot) { return e->slots().topK(slot); }
+float nvw_slot_top_p(nvw_engine* e, int slot) { return e->slots().topP(slot); }
+int nvw_sampler_mask(nvw_engine* e) { return e->samplerMask(); }
 // ---- primed generation: forced sample prefixes, lockstep and in slot mode (additive within ABI 7) -----------------------------------
 int nvw_set_prime(nvw_engine* e, const int* y, const int* n, int batch, int max_n, long long stride) {
     if (e->setPrime(y, n, batch, max_n, stride)) return 1;

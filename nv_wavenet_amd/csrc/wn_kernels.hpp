@@ -347,10 +347,12 @@ struct Params {
     int forced;              // RAW = 3 only, launch-uniform: != 0: a selector <= -1 is a forced sample, -(1 + y) stands for "the sample is
                              // y" (slots_prime.hpp: only its two kernels write such values); 0: every selector is a draw, as before.
                              // Behind softScale, for the same reason.
-    int floorOn;             // RAW = 3 only, launch-uniform: != 0: some column's probability floor (min-p) is not 0, and the floors are the
-                             // second half of the table softScale points to, softScale[maxBatch + b] (read only then); 0: no floor in
-                             // force, the launch executes the instructions it did before floors existed.  In the four bytes of padding
-                             // behind `forced`: the struct did not grow.
+    int floorOn;             // RAW = 3 only, launch-uniform, a bit mask.  Bit 0: some column's probability floor (min-p) is not 0.  Bit 1:
+                             // some column has a tail cut (top-k or top-p).  != 0: the table softScale points to is
+                             // [4][maxBatch] -- scales, floors, top-k (integers), top-p -- and the floors, softScale[maxBatch + b], are
+                             // read; the cuts, softScale[2 maxBatch + b] and [3 maxBatch + b], only with bit 1.  0: nothing in force,
+                             // the launch executes the instructions it did before floors existed; bit 1 clear: those it did before
+                             // cuts existed.  In the four bytes of padding behind `forced`: the struct did not grow.
 };
 static_assert(sizeof(Params) == 1816 && offsetof(Params, forced) == 1808 && offsetof(Params, floorOn) == 1812,
               "Params::floorOn lives in the padding behind Params::forced: the struct is the 1816 bytes it was before, and no kernel's "
@@ -788,10 +790,122 @@ template <int LPU> WN_DEV int group_min_i(int v) {
 // and the total is never zero.  FLOOR = false (the default): off, the function is what it was -- the choice is a template argument
 // so that the compiler sees the old body; callers choose between the two forms under a launch-uniform flag.
 constexpr float kLog2e = 1.44269504088896340736f;
-template <int A, int LPU, int RPL, bool FLOOR = false>
+
+// The threshold of a column's tail cuts (top-k and top-p) on its e[] = exp2(x c - m c), the same quantity the floor
+// compares.  theta_k is the largest float with #{e >= theta} >= k (the k-th largest e, ties stay); theta_p the largest float with
+// S(theta) >= p S(0), S(theta) the float32 sum of the e >= theta: each lane its RPL values in row order, the lanes by
+// group_reduce_f with + (both partners of a butterfly or mirror step add the same two operands, so every lane of the group holds
+// the same sum and takes the same branch of the search).  Both predicates fall monotonically in theta -- float addition is
+// monotone in each operand --: one holds on [0, theta_k], the other on [0, theta_p], and their disjunction on [0, max of the two].
+// So ONE bisection over the bit patterns of the non-negative floats, which order as the floats do, finds max(theta_k, theta_p),
+// with one compare per logit serving the count and the mass: lo = 0 is never evaluated, hi is the pattern just above the largest
+// e, where both predicates fail.  31 steps bring any interval of non-negative float patterns down to hi - lo = 1, and a step at
+// that length changes nothing: the trip count is fixed, the same for every group of a wave.  k = 0 and p >= 1 are off by a select
+// on the predicate's bound (a count no group reaches, a mass no sum reaches): an off cut never holds, and with both off lo stays
+// 0.  Returns max(theta_k, theta_p) in every lane of the group.
+// (One case where the mass predicate does not fail at hi: a p so small that p S(0) rounds to 0 -- a denormal p -- holds at every
+// threshold, S being >= 0.  The search then ends at hi - 1, the pattern of the largest e: that column keeps its most probable bin
+// alone, which is what so small a p asks for.)
+template <int LPU> WN_DEV int group_sum_i(int v) {
+    v += dpp_i<DPP_XOR1>(v);
+    v += dpp_i<DPP_XOR2>(v);
+    if (LPU >= 8) v += dpp_i<DPP_HALF_MIRROR>(v);
+    if (LPU >= 16) v += dpp_i<DPP_MIRROR>(v);
+    return v;
+}
+template <int LPU, int RPL> WN_DEV float cut_threshold(const float (&e)[RPL], int k, float topP) {
+    const auto add = [](float a, float b) { return a + b; };
+    float emax = e[0], s0 = 0.f;
+#pragma unroll
+    for (int i = 0; i < RPL; i++) {
+        emax = __builtin_fmaxf(emax, e[i]);
+        s0 += e[i];
+    }
+    emax = group_reduce_f<LPU>(emax, [](float a, float b) { return __builtin_fmaxf(a, b); });
+    s0 = group_reduce_f<LPU>(s0, add);
+    const float need = topP < 1.0f ? topP * s0 : __builtin_inff();
+    const int kneed = k > 0 ? k : 0x7fffffff;
+    unsigned lo = 0u, hi = __float_as_uint(emax) + 1u;
+#pragma unroll 1
+    for (int step = 0; step < 31; step++) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        const float t = __uint_as_float(mid);
+        int cnt = 0;
+        float mass = 0.f;
+#pragma unroll
+        for (int i = 0; i < RPL; i++) {
+            const bool in = e[i] >= t;
+            cnt += in ? 1 : 0;
+            mass += in ? e[i] : 0.f;
+        }
+        cnt = group_sum_i<LPU>(cnt);
+        mass = group_reduce_f<LPU>(mass, add);
+        const bool holds = (cnt >= kneed) | (mass >= need);
+        lo = holds ? mid : lo;
+        hi = holds ? hi : mid;
+    }
+    return __uint_as_float(lo);
+}
+
+// The same threshold for the activation-dump kernels (DUMP = true), which stand at the register limit and whose speed is nobody's
+// concern: inlined, cut_threshold made the three-tile dump kernels of R 64, S 128, A 256 spill that had been spill-free.  This form
+// holds no e[] across the search and is kept OUT OF LINE -- its arguments are five scalars and a pointer, so nothing goes through
+// memory.  lrow points at the lane's RPL logits in lgbuf, which holds them until the next barrier, and every step computes
+// exp2(fma(x, scale, mneg)) again: the same instruction on the same operands, so the same e bit for bit, the same sums in the same
+// order and the same threshold.  The search sets the 31 bits of the pattern from the top -- lo | step is kept where the
+// disjunction holds, step = 2^30 .. 1: the bisection of [0, 2^31) -- because an upper bound just above the largest e would cost
+// another pass over the logits.  None is needed: above the largest e no bin passes the compare (nor against the patterns of inf
+// and NaN) and the count is 0; the mass predicate is taken only with a count above 0, so that a bound p S(0) that rounds to 0 ends
+// at the largest e here too.  The empty asm keeps the compiler from hoisting the RPL loads and exp2 out of the loop again.
+template <int LPU, int RPL>
+__device__ __attribute__((noinline)) float cut_threshold_dump(const float* lrow, int k, float topP, float scale, float mneg) {
+    const auto add = [](float a, float b) { return a + b; };
+    const auto value = [&](const float* src, int i) { return __builtin_amdgcn_exp2f(__builtin_fmaf(src[i], scale, mneg)); };
+    float s0 = 0.f;
+    {
+        const float* src = lrow;
+        asm volatile("" : "+v"(src));
+#pragma unroll
+        for (int i = 0; i < RPL; i++) s0 += value(src, i);
+    }
+    s0 = group_reduce_f<LPU>(s0, add);
+    const float need = topP < 1.0f ? topP * s0 : __builtin_inff();
+    const int kneed = k > 0 ? k : 0x7fffffff;
+    unsigned lo = 0u;
+#pragma unroll 1
+    for (unsigned step = 1u << 30; step != 0u; step >>= 1) {
+        const unsigned mid = lo | step;
+        const float t = __uint_as_float(mid);
+        int cnt = 0;
+        float mass = 0.f;
+        const float* src = lrow;
+        asm volatile("" : "+v"(src));
+#pragma unroll
+        for (int i = 0; i < RPL; i++) {
+            const float ei = value(src, i);
+            const bool in = ei >= t;
+            cnt += in ? 1 : 0;
+            mass += in ? ei : 0.f;
+        }
+        cnt = group_sum_i<LPU>(cnt);
+        mass = group_reduce_f<LPU>(mass, add);
+        const bool holds = (cnt >= kneed) | ((mass >= need) & (cnt > 0));
+        lo = holds ? mid : lo;
+    }
+    return __uint_as_float(lo);
+}
+
+// FLOOR: 0 (the default) off, 1 the floor, 2 the floor and the tail cuts: between the exp2 loop and the flooring cut_threshold
+// finds the cuts' threshold from topK and topP (read only then), the column floors at the largest of the three, and from there on
+// the function is the FLOOR = 1 path.  0 and 1 compile to the bodies they had.  3 is 2 for the activation-dump kernels: the threshold
+// comes from cut_threshold_dump, and the logits are read again behind it, so that no e[] lives across the search; the same
+// threshold and the same e, bit for bit.
+template <int A, int LPU, int RPL, int FLOOR = 0>
 WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total, float scale = kLog2e,
-                        float floor = 0.f) {
+                        float floor = 0.f, int topK = 0, float topP = 1.0f) {
     (void)floor;
+    (void)topK;
+    (void)topP;
     (void)lane;
 #pragma unroll
     for (int i = 0; i < RPL / 4; i++) {
@@ -807,11 +921,32 @@ WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&
     {
         // exp((x - m) / T) = 2^(x c - m c), c = log2 e / T: one fma in front of the v_exp_f32 instead of a subtraction and a multiplication
         const float mneg = -m * scale;
+        if constexpr (FLOOR == 2) {
 #pragma unroll
-        for (int i = 0; i < RPL; i++) {
-            e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], scale, mneg));
-            if constexpr (FLOOR) e[i] = (e[i] >= floor) ? e[i] : 0.f;
-            lsum += e[i];
+            for (int i = 0; i < RPL; i++) e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], scale, mneg));
+            const float thr = __builtin_fmaxf(cut_threshold<LPU, RPL>(e, topK, topP), floor);
+#pragma unroll
+            for (int i = 0; i < RPL; i++) {
+                e[i] = (e[i] >= thr) ? e[i] : 0.f;
+                lsum += e[i];
+            }
+        } else if constexpr (FLOOR == 3) {
+            const float thr = __builtin_fmaxf(cut_threshold_dump<LPU, RPL>(lrow, topK, topP, scale, mneg), floor);
+            const float* src = lrow;
+            asm volatile("" : "+v"(src));      // (read again: the values loaded for the maximum are not kept across the search)
+#pragma unroll
+            for (int i = 0; i < RPL; i++) {
+                e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(src[i], scale, mneg));
+                e[i] = (e[i] >= thr) ? e[i] : 0.f;
+                lsum += e[i];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < RPL; i++) {
+                e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], scale, mneg));
+                if constexpr (FLOOR == 1) e[i] = (e[i] >= floor) ? e[i] : 0.f;
+                lsum += e[i];
+            }
         }
     }
     // inclusive scan of the lane sums over the LPU lanes of this utterance (row_shr:o reads lane - o of the row)
@@ -1315,6 +1450,18 @@ WN_DEV void wavenet_wg_body(const Params& p) {
             int sb = (tile0 + bt) * 16 + su;
             sb = sb < p.batch ? sb : p.batch - 1;
             sfloor[bt] = p.floorOn ? p.softScale[p.maxBatch + sb] : 0.f;
+        }
+    }
+    // ... and its tail cuts (Params::floorOn bit 1: the third and fourth quarter of the table), likewise
+    int stopk[FEAT ? BT : 1];
+    float stopp[FEAT ? BT : 1];
+    if constexpr (FEAT) {
+#pragma unroll
+        for (int bt = 0; bt < BT; bt++) {
+            int sb = (tile0 + bt) * 16 + su;
+            sb = sb < p.batch ? sb : p.batch - 1;
+            stopk[bt] = (p.floorOn & 2) ? __float_as_int(p.softScale[2 * p.maxBatch + sb]) : 0;
+            stopp[bt] = (p.floorOn & 2) ? p.softScale[3 * p.maxBatch + sb] : 1.0f;
         }
     }
     const int tEnd = p.initSample + p.count;
@@ -1869,8 +2016,11 @@ WN_DEV void wavenet_wg_body(const Params& p) {
                 const float* lrow = lgbuf + (bl * 16 + su) * C::LROW + sq * C::RPL;
                 int pick;
                 if constexpr (FEAT) {
-                    // (floorOn is launch-uniform: a launch with no floor in force runs the call it ran before)
-                    if (p.floorOn) pick = softmax_pick<A, C::LPU, C::RPL, true>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt]);
+                    // (floorOn is launch-uniform: a launch with no cut in force runs one of the two calls it ran before, and one with
+                    // no floor either the one it ran before that)
+                    if (p.floorOn & 2)
+                        pick = softmax_pick<A, C::LPU, C::RPL, (DUMP ? 3 : 2)>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt], stopk[bt], stopp[bt]);
+                    else if (p.floorOn & 1) pick = softmax_pick<A, C::LPU, C::RPL, 1>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt]);
                     else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
                     // a forced sample (Params::forced): the selector names it; e and total stay the model's
                     if (p.forced) pick = selv[bt] <= -1.0f ? (int)(-selv[bt]) - 1 : pick;

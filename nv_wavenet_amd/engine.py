@@ -646,6 +646,62 @@ class WavenetEngine:
         """The floor in force for column `slot` (host state); -1.0 when the column holds no utterance (0 is a valid floor)."""
         return float(lib.nvw_slot_min_p(self._h, int(slot)))
 
+    # ---- tail cuts, top-k and top-p, per utterance (include/nv_wavenet_c.h, "TAIL CUTS"; DESIGN.md §6n) ----
+    def setTopK(self, k=None):
+        """Lockstep: column b of the features-path runs that follow draws from the k[b] most probable bins of its tempered
+        distribution, ties with the k-th included.  k: None (every column off), an int (every column), or a sequence of
+        1..maxBatch ints (the columns past it off), each in [0, A]; 0 is off, 1 is greedy decoding.  In force until the next call,
+        independent of setTemperatures, setMinP and setTopP; the kept set is the intersection of the cuts and the floor.  While any
+        column has a cut, runs on packed or in-place conditioning and on chain engines return False.  ValueError when refused
+        (nothing changes)."""
+        if k is None:
+            ok = lib.nvw_set_top_k(self._h, None, 0)
+        else:
+            a = np.asarray(k)
+            if a.dtype.kind not in "iu" or np.any(a != a.astype(np.int32)):
+                raise ValueError("nvw_set_top_k refused %r" % (k,))
+            t = np.ascontiguousarray(np.full(self.maxBatch, int(a), dtype=np.int32) if a.ndim == 0 else a.astype(np.int32).reshape(-1))
+            ok = lib.nvw_set_top_k(self._h, t.ctypes.data, int(t.size))
+        if not ok:
+            raise ValueError("nvw_set_top_k refused %r" % (k,))
+
+    def setTopP(self, p=None):
+        """Lockstep: column b draws from the smallest set of most probable bins of its tempered distribution whose mass reaches
+        p[b], ties at its edge included.  p: None (every column off), a float (every column), or a sequence of 1..maxBatch floats
+        (the columns past it off), each finite and in (0, 1]; 1 is off.  Everything else as setTopK."""
+        if p is None:
+            ok = lib.nvw_set_top_p(self._h, None, 0)
+        else:
+            a = np.asarray(p, dtype=np.float32)      # (a scalar of any kind, a 0-d array or tensor: every column)
+            t = np.ascontiguousarray(np.full(self.maxBatch, a, dtype=np.float32) if a.ndim == 0 else a.reshape(-1))
+            ok = lib.nvw_set_top_p(self._h, t.ctypes.data, int(t.size))
+        if not ok:
+            raise ValueError("nvw_set_top_p refused %r" % (p,))
+
+    def slotSetTopK(self, slot, k):
+        """Slot mode: the utterance of column `slot` draws with top-k = k from the next step on (after slotStart / slotResume, which
+        put the column back to off / to the blob's value).  ValueError when refused (nothing changes)."""
+        if int(k) != k or not -2**31 <= int(k) < 2**31 or not lib.nvw_slot_set_top_k(self._h, int(slot), int(k)):
+            raise ValueError("nvw_slot_set_top_k refused slot %d, k = %r" % (slot, k))
+
+    def slotSetTopP(self, slot, p):
+        """Slot mode: likewise with top-p = p."""
+        if not lib.nvw_slot_set_top_p(self._h, int(slot), float(p)):
+            raise ValueError("nvw_slot_set_top_p refused slot %d, p = %r" % (slot, p))
+
+    def slotTopK(self, slot):
+        """Top-k in force for column `slot` (host state); -1 when the column holds no utterance."""
+        return int(lib.nvw_slot_top_k(self._h, int(slot)))
+
+    def slotTopP(self, slot):
+        """Top-p in force for column `slot` (host state); -1.0 when the column holds no utterance."""
+        return float(lib.nvw_slot_top_p(self._h, int(slot)))
+
+    def samplerMask(self):
+        """What the next features-path launch pays for (host state): bit 0, some column's floor is not 0; bit 1, some column has a
+        cut (the threshold search, in every column of the launch).  0: the launches of an engine without floors and cuts."""
+        return int(lib.nvw_sampler_mask(self._h))
+
     # ---- primed generation: forced sample prefixes (include/nv_wavenet_c.h, "PRIMED GENERATION"; DESIGN.md §6h) ----
     def setPrime(self, y=None, lengths=None):
         """Lockstep: column b of the features-path runs that follow starts with the forced samples y[b][:lengths[b]] and draws from

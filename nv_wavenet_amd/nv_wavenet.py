@@ -422,7 +422,7 @@ class NVWaveNetEngine(NVWaveNet):
         return self._engine(batch_size, sample_count, implementation).condTiles()
 
     def infer(self, cond_input, implementation=Impl.AUTO, seed=None, return_audio=False, layout="CBLN",
-              generator=None, batch_size=None, temperature=None, prime=None, min_p=None):
+              generator=None, batch_size=None, temperature=None, prime=None, min_p=None, top_k=None, top_p=None):
         """cond_input: 2R x batch x layers x samples (layout "CBLN", the reference's: converted to the engine's fragment order
         by the one permuting copy any layout change needs), [samples][layers][batch][2R] contiguous (layout "NLBC", read in
         place), or the engine's own fragment order
@@ -433,7 +433,11 @@ class NVWaveNetEngine(NVWaveNet):
         temperature: not here -- only the kernels that compute the conditioning from the features sample at a temperature
         (infer_features); anything but None raises ValueError.
         prime: not here either, for the same reason (infer_features(..., prime=)); anything but None raises ValueError.
-        min_p: nor a probability floor (infer_features(..., min_p=)); anything but None raises ValueError."""
+        min_p: nor a probability floor (infer_features(..., min_p=)); anything but None raises ValueError.
+        top_k, top_p: nor a tail cut (infer_features(..., top_k=, top_p=)); anything but None raises ValueError."""
+        if top_k is not None or top_p is not None:
+            raise ValueError("infer() runs on a conditioning tensor, whose kernels draw from the whole distribution only: use "
+                             "infer_features(x, cond_weight, cond_bias, top_k=..., top_p=...)")
         if min_p is not None:
             raise ValueError("infer() runs on a conditioning tensor, whose kernels draw from the whole distribution only: use "
                              "infer_features(x, cond_weight, cond_bias, min_p=...)")
@@ -476,7 +480,7 @@ class NVWaveNetEngine(NVWaveNet):
         return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
 
     def infer_features(self, x, cond_weight, cond_bias, implementation=Impl.AUTO, seed=None, return_audio=False, generator=None,
-                       temperature=None, prime=None, prime_lengths=None, min_p=None):
+                       temperature=None, prime=None, prime_lengths=None, min_p=None, top_k=None, top_p=None):
         """Generation with the conditioning convolution INSIDE the kernel (round 5): x = the upsampled features [batch][n_cond][samples]
         on the GPU (upsample_features(...) / the model's self.upsample output, trimmed), cond_weight / cond_bias = the model's
         cond_layers.weight / .bias.  Equivalent to infer(model.get_cond_input(features)) without ever building the
@@ -489,8 +493,22 @@ class NVWaveNetEngine(NVWaveNet):
         seed returns y.  ValueError for a bad shape, length or value.
         min_p: None (0), a float, or a sequence of `batch` floats -- utterance b is drawn from its tempered distribution without
         the bins whose probability is below min_p[b] times that of the most probable bin; each finite and in
-        [0, 0.5] (ValueError otherwise)."""
+        [0, 0.5] (ValueError otherwise).
+        top_k: None (off), an int, or a sequence of `batch` ints in [0, A] -- utterance b is drawn from its top_k[b] most probable
+        bins (0: off; 1: greedy); top_p: None (off), a float, or a sequence of `batch` floats, finite and in (0, 1] -- from the
+        smallest set of most probable bins whose mass reaches top_p[b] (ValueError otherwise).  The cuts and the
+        floor intersect; each is defined on the tempered distribution."""
         batch_size, sample_count = x.size(0), x.size(2)
+        if top_k is not None and not (isinstance(top_k, (int, float)) or getattr(top_k, "ndim", None) == 0):      # (a scalar: every column)
+            top_k = list(top_k)
+            if len(top_k) != batch_size:
+                raise ValueError("%d top-k values for a batch of %d" % (len(top_k), batch_size))
+        if top_p is not None and (isinstance(top_p, (int, float)) or getattr(top_p, "ndim", None) == 0):
+            top_p = float(top_p)
+        elif top_p is not None:
+            top_p = [float(p) for p in top_p]
+            if len(top_p) != batch_size:
+                raise ValueError("%d top-p values for a batch of %d" % (len(top_p), batch_size))
         if min_p is not None and (isinstance(min_p, (int, float)) or getattr(min_p, "ndim", None) == 0):
             min_p = float(min_p)      # (a Python or numpy scalar, a 0-d array or tensor: every column)
         elif min_p is not None:
@@ -525,6 +543,10 @@ class NVWaveNetEngine(NVWaveNet):
         try:
             if min_p is not None:
                 e.setMinP(min_p)
+            if top_k is not None:
+                e.setTopK(top_k)
+            if top_p is not None:
+                e.setTopP(top_p)
             if prime is not None:
                 e.setPrime(prime.to(device=dev, dtype=torch.int32).contiguous(), prime_lengths)
             return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
@@ -533,6 +555,10 @@ class NVWaveNetEngine(NVWaveNet):
                 e.setTemperatures(None)      # (the engine is shared with infer(), whose kernels refuse to run at another temperature)
             if min_p is not None:
                 e.setMinP(None)              # (... or with a floor)
+            if top_k is not None:
+                e.setTopK(None)              # (... or with a cut)
+            if top_p is not None:
+                e.setTopP(None)
             if prime is not None:
                 e.setPrime(None)             # (... or while a column is primed)
 

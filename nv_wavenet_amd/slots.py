@@ -59,6 +59,14 @@ min_p_rows() gives a scoring user the log-probabilities of the distribution such
     h = stream.submit(features, temperature=0.8, min_p=0.05)
     stream.set_min_p(h, 0.1)
 
+A request may carry tail cuts (top-k, top-p; nvw_slot_set_top_k, nvw_slot_set_top_p): it is drawn from its top_k most
+probable bins, and from the smallest set of most probable bins whose mass reaches top_p; the cuts and the floor intersect.  They
+travel as the floor does (words 12 and 13 of a blob's header).  cut_rows() gives a scoring user the log-probabilities of the
+distribution such a request was drawn from.
+
+    h = stream.submit(features, top_k=50, top_p=0.9)
+    stream.set_top_k(h, 1)                              # greedy from the next step on
+
 A request may carry a prime (nvw_slot_prime): its first n samples are given -- the tail of the previous sentence,
 the samples a lost stream had already delivered -- and it is drawn from sample n on.  The forced samples are delivered like the
 others.  suspend, drain, resume, compact and to_bytes / from_bytes keep what is left of it.
@@ -125,6 +133,80 @@ def check_min_p(p):
     return t + 0.0                 # (-0.0 is 0.0)
 
 
+def check_top_k(k, A=None):
+    """k as the engine takes it (an integer, 0 <= k, and k <= A where the alphabet is known); ValueError otherwise."""
+    try:
+        t = int(k)
+        whole = t == k
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("top_k %r is not an integer" % (k,))
+    if not whole or t < 0 or t >= 2**31 or (A is not None and t > A):
+        raise ValueError("top_k %r: an integer in [0, A]" % (k,))
+    return t
+
+
+def check_top_p(p):
+    """p as the engine takes it (a float32 value, finite, in (0, 1]); ValueError otherwise."""
+    try:
+        t = float(np.float32(p))
+    except (TypeError, ValueError):
+        raise ValueError("top_p %r is not a number" % (p,))
+    if not (0.0 < t <= 1.0):      # (a NaN fails both comparisons)
+        raise ValueError("top_p %r: finite and in (0, 1]" % (p,))
+    return t
+
+
+def cut_rows(rows, top_k=0, top_p=1.0, min_p=0.0):
+    """The log-probabilities of the cut, renormalised distribution: rows = log-probabilities [n][A] (or [A]) from any scoring entry
+    (at the temperature the samples were drawn at); top_k, top_p, min_p = a value or [n] values each.  With q = exp(rows - max):
+    top_k keeps q >= the k-th largest q (ties stay; 0: off), top_p keeps q >= theta, theta the largest value of q whose kept mass
+    still reaches top_p times the whole mass (the smallest set of most probable bins whose mass reaches top_p, ties included; 1:
+    off), min_p keeps q >= min_p.  The kept set is the intersection -- each cut is defined on the full distribution of the row, not
+    on what the others left --; dropped bins read -inf and the kept ones are renormalised by the log of their summed probability
+    (float64 inside; the result has the dtype of rows).  numpy in, numpy out; a torch tensor in, a torch tensor on the same device
+    out.  This is the distribution a request with those values was drawn from, EXCEPT at boundaries within rounding: the kernel
+    compares and sums exp2(fma(z, c, -(m c))) in float32 (see min_p_rows), so a bin whose q is within about 1e-5 (relative) of a
+    threshold, or a prefix mass within about 1e-5 of top_p, may fall on the other side there."""
+    torch_in = not isinstance(rows, np.ndarray) and hasattr(rows, "detach")
+    r = rows.detach().cpu().numpy() if torch_in else np.asarray(rows)
+    r64 = np.atleast_2d(r.astype(np.float64))
+    n, A = r64.shape
+    k = np.asarray(top_k).reshape(-1)
+    p = np.asarray(top_p, dtype=np.float64).reshape(-1)
+    tau = np.asarray(min_p, dtype=np.float64).reshape(-1)
+    if k.size not in (1, n) or k.dtype.kind not in "iu" or not np.all((k >= 0) & (k <= A)):
+        raise ValueError("top_k: one integer or one per row, each in [0, %d]" % A)
+    if p.size not in (1, n) or not np.all((p > 0.0) & (p <= 1.0)):
+        raise ValueError("top_p: one value or one per row, each in (0, 1]")
+    if tau.size not in (1, n) or not np.all((tau >= 0.0) & (tau <= 0.5)):
+        raise ValueError("min_p: one value or one per row, each in [0, 0.5]")
+    k, p, tau = np.broadcast_to(k, (n,)), np.broadcast_to(p, (n,)), np.broadcast_to(tau, (n,))
+    rel = r64 - r64.max(axis=1, keepdims=True)
+    q = np.exp(rel)
+    desc = -np.sort(-q, axis=1)
+    rows_i = np.arange(n)
+    theta_k = np.where(k > 0, desc[rows_i, np.maximum(k, 1) - 1], 0.0)
+    # the mass of the bins >= each distinct value, at every position of the sorted row: the prefix sum up to the LAST bin of a tie
+    cum = np.cumsum(desc, axis=1)
+    last = np.empty_like(cum)
+    last[:, -1] = cum[:, -1]
+    for j in range(A - 2, -1, -1):
+        last[:, j] = np.where(desc[:, j] == desc[:, j + 1], last[:, j + 1], cum[:, j])
+    reach = last >= (p * cum[:, -1])[:, None]
+    reach[:, -1] = True
+    theta_p = np.where(p < 1.0, desc[rows_i, np.argmax(reach, axis=1)], 0.0)
+    thr = np.maximum(np.maximum(theta_k, theta_p), tau)
+    keep = q >= thr[:, None]
+    with np.errstate(divide="ignore"):
+        kept = np.where(keep, q, 0.0)
+        out = np.where(keep, rel - np.log(kept.sum(axis=1, keepdims=True)), -np.inf)
+    out = out.reshape(r.shape).astype(r.dtype if r.dtype.kind == "f" else np.float64)
+    if torch_in:
+        import torch
+        return torch.from_numpy(out).to(rows.device)
+    return out
+
+
 def min_p_rows(rows, min_p):
     """The log-probabilities of the floored, renormalised distribution: rows = log-probabilities [n][A] (or [A]) from any scoring
     entry (WavenetEngine.scoreSamples(rows=True), at the temperature the samples were drawn at), min_p = the floor, a float or [n]
@@ -181,7 +263,8 @@ class SlotState:
     frames, final = of a mel request (frames written so far, no more to come); temperature = its sampling temperature (the one in
     the blob's header, word 10; a resume goes on at this attribute's value); prime = its prime (an int32 tensor [n], None: none; a
     resume applies it again when done < n); min_p = its probability floor (word 11 of the blob's header where the engine saved
-    the blob; the blobs that prefill and scoring write leave the word zero, and the stream sets the floor after resuming)."""
+    the blob; the blobs that prefill and scoring write leave the word zero, and the stream sets the floor after resuming); top_k,
+    top_p = its tail cuts (words 12 and 13, likewise)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -190,13 +273,18 @@ class SlotState:
     BLOB_MAGIC = 0x5453574E                  # the first word of a blob ("NWST"); its words 6 and 7 are done and uid,
     TEMPERATURE_WORD = 10                    # word 10 the temperature as the bits of the float (zero: 1.0)
     MIN_P_WORD = 11                          # word 11 the probability floor likewise (zero: 0.0)
+    TOP_K_WORD = 12                          # word 12 top-k, the integer (zero: off)
+    TOP_P_WORD = 13                          # word 13 top-p as the bits of the float (zero: 1.0, off)
     # to_bytes() of a state with done < n of its prime: behind the blob this record, then the n - done values y[done .. n) (int32)
     PRIME = struct.Struct("<4sII")           # magic, first (= done), count (= n - done)
     PRIME_MAGIC = b"NWSP"
 
-    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0):
+    def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0,
+                 top_k=0, top_p=1.0):
         self.prime = check_prime(prime)
         self.min_p = check_min_p(min_p)
+        self.top_k, self.top_p = check_top_k(top_k), check_top_p(top_p)
+        self._blob_cut = (self.top_k, self.top_p) if blob is not None else (0, 1.0)      # (words 12 and 13 as the engine will read them)
         self._blob_min_p = self.min_p if blob is not None else 0.0                  # (word 11 of the blob as the engine will read it)
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
         self.temperature = check_temperature(temperature)
@@ -209,19 +297,23 @@ class SlotState:
         """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
         tensor is not included.  A blob on the GPU is copied to the host here -- a synchronising copy --, and for a pinned blob
         the call waits for the device to have written it.  A request that had not started has no blob; with a temperature other
-        than 1 or a floor other than 0 it carries the 64 bytes of a header alone (magic, uid, done = 0 and words 10 and 11), so
-        that the values survive; a blob whose word 11 is not the state's floor (a prefilled state) is written with it.  A state
+        than 1, a floor other than 0 or a cut it carries the 64 bytes of a header alone (magic, uid, done = 0 and words 10 to 13),
+        so that the values survive; a blob whose words 11 to 13 are not the state's floor and cuts (a prefilled state) is written
+        with them.  A state
         still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
         what they were before primes existed."""
         blob = b""
         min_p = check_min_p(self.min_p)
         floor_word = np.array([min_p], dtype="<f4").view("<u4")[0] if min_p != 0.0 else 0
-        if self.blob is None and (self.temperature != 1.0 or min_p != 0.0):
+        top_k, top_p = check_top_k(self.top_k), check_top_p(self.top_p)
+        top_p_word = np.array([top_p], dtype="<f4").view("<u4")[0] if top_p != 1.0 else 0
+        if self.blob is None and (self.temperature != 1.0 or min_p != 0.0 or top_k != 0 or top_p != 1.0):
             hdr = np.zeros(16, dtype="<u4")
             hdr[0], hdr[1], hdr[7] = self.BLOB_MAGIC, 1, int(self.uid) & 0xFFFFFFFF
             if self.temperature != 1.0:
                 hdr[self.TEMPERATURE_WORD] = np.array([self.temperature], dtype="<f4").view("<u4")[0]
             hdr[self.MIN_P_WORD] = floor_word
+            hdr[self.TOP_K_WORD], hdr[self.TOP_P_WORD] = top_k, top_p_word
             blob = hdr.tobytes()
         if self.blob is not None:
             if getattr(self.blob, "is_cuda", False):
@@ -231,9 +323,10 @@ class SlotState:
                     import torch
                     torch.cuda.synchronize()
                 blob = self.blob.numpy().tobytes()
-            if min_p != self._blob_min_p:
+            if min_p != self._blob_min_p or (top_k, top_p) != self._blob_cut:
                 words = np.frombuffer(blob, dtype="<u4").copy()
                 words[self.MIN_P_WORD] = floor_word
+                words[self.TOP_K_WORD], words[self.TOP_P_WORD] = top_k, top_p_word
                 blob = words.tobytes()
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
@@ -268,7 +361,7 @@ class SlotState:
         if tail != 0 or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
-        temperature, min_p = 1.0, 0.0
+        temperature, min_p, top_k, top_p = 1.0, 0.0, 0, 1.0
         if nblob:
             words = np.frombuffer(data, dtype="<u4", count=16, offset=cls.RECORD_BYTES)
             if int(words[0]) != cls.BLOB_MAGIC or int(words[6]) != done or int(words[7]) != uid:
@@ -277,13 +370,18 @@ class SlotState:
                 temperature = check_temperature(words[cls.TEMPERATURE_WORD:cls.TEMPERATURE_WORD + 1].view("<f4")[0])
             if int(words[cls.MIN_P_WORD]):
                 min_p = check_min_p(words[cls.MIN_P_WORD:cls.MIN_P_WORD + 1].view("<f4")[0])
+            top_k = check_top_k(int(words[cls.TOP_K_WORD]))
+            if int(words[cls.TOP_P_WORD]):
+                top_p = check_top_p(words[cls.TOP_P_WORD:cls.TOP_P_WORD + 1].view("<f4")[0])
+                if top_p == 1.0:
+                    raise ValueError("word 13 of the blob's header holds the bits of 1.0, which stand for no top-p as zero")
         if nblob > 64 or (nblob and done):      # (64 bytes with done = 0: the header alone of a request that had not started)
             host = torch.empty((1, nblob), dtype=torch.uint8, pin_memory=bool(pinned))
             host[0].numpy()[:] = np.frombuffer(data, dtype=np.uint8, count=nblob, offset=cls.RECORD_BYTES)
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   temperature, prime, min_p)
+                   temperature, prime, min_p, top_k, top_p)
 
 
 class StepOutput:
@@ -370,6 +468,7 @@ class SlotStream:
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
         self._prime = {}                               # handle -> prime (int32 tensor) of the requests (queued or running) that carry one
         self._minp = {}                                # handle -> probability floor of the requests (queued or running) whose floor is not 0
+        self._cut = {}                                 # handle -> (top_k, top_p) of the requests (queued or running) with a cut
         self._temp = {}                                # handle -> sampling temperature of the requests (queued or running) whose T is not 1
         # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
         # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
@@ -459,6 +558,7 @@ class SlotStream:
         after = SlotState(blobs[0], state.source, int(state.uid), done + int(y.numel()), state.kind, frames=state.frames if mel else None,
                           final=state.final if mel else None, buffer=blobs, row=0, temperature=temperature, prime=prime)
         after.min_p = state.min_p                      # (the pass leaves word 11 of the blob zero: the stream sets the floor after the resume)
+        after.top_k, after.top_p = state.top_k, state.top_p      # (... and words 12 and 13)
         after._prefilled_from = (y, blob)              # (read by the pass in stream order: kept with the state)
         return logp[0], after
 
@@ -507,7 +607,7 @@ class SlotStream:
             raise ValueError("score needs samples")
         return self.engine.scoreSamplesMel([(y if y.is_cuda else y.cuda(), mel, temperature, n)])[0]
 
-    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None, min_p=0.0):
+    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None, min_p=0.0, top_k=0, top_p=1.0):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
         run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
@@ -518,21 +618,27 @@ class SlotStream:
         at sample n -- its delivery starts there, the forced samples are not delivered again, and the samples from n on are bit
         for bit those of prefill=False; ValueError for a prime that covers the whole utterance.  Without a prime it changes
         nothing.  min_p: its samples are drawn without the bins whose tempered probability is below min_p times that of the most
-        probable bin (ValueError unless finite and in [0, 0.5]); forced samples stay forced."""
+        probable bin (ValueError unless finite and in [0, 0.5]); forced samples stay forced.  top_k, top_p: its samples are drawn
+        from its top_k most probable bins (0: off; 1: greedy) and from the smallest set of most probable bins whose mass reaches
+        top_p (1: off), on the tempered distribution, intersected with each other and with the floor (ValueError unless top_k is
+        an integer in [0, A] and top_p finite and in (0, 1])."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
         temperature = check_temperature(temperature)
         min_p = check_min_p(min_p)
+        cut = self._check_cut(top_k, top_p)
         prime = check_prime(prime, features.size(1))
         if (self._prefill if prefill is None else prefill) and prime is not None:
             if prime.numel() >= features.size(1):
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), features.size(1)))
             state = self.prefill(features, prime, uid, temperature)
             state.min_p = min_p      # (the pass leaves word 11 of the blob zero: set after the resume, at admission)
+            state.top_k, state.top_p = cut
             handle = self._next_handle
             self._next_handle += 1
             self._queue.append((handle, features, int(state.uid), None, state))
             self._note_temperature(handle, temperature)
             self._note_min_p(handle, min_p)
+            self._note_cut(handle, cut)
             return handle
         handle = self._next_handle
         self._next_handle += 1
@@ -542,13 +648,14 @@ class SlotStream:
         self._queue.append((handle, features, int(uid), None))
         self._note_temperature(handle, temperature)
         self._note_min_p(handle, min_p)
+        self._note_cut(handle, cut)
         if prime is not None:
             self._prime[handle] = prime
         return handle
 
-    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=None, min_p=0.0):
+    def submit_mel(self, mel, uid=None, frames=None, final=True, temperature=1.0, prime=None, prefill=None, min_p=0.0, top_k=0, top_p=1.0):
         """Queues one mel utterance (mel [n_cond][capacity], CUDA, float32 or float16, its first `frames` -- default all -- written;
-        final: no more will come); returns its handle.  uid, temperature, min_p and prime as for submit; the prime of a request that is
+        final: no more will come); returns its handle.  uid, temperature, min_p, top_k, top_p and prime as for submit; the prime of a request that is
         not final is not bounded by the frames written so far (a forced sample still waits for its frames, as a drawn one).
         prefill (None: the stream's default): True with a prime of n values makes the state behind the prime at once
         (prefill_mel()) and queues the request as a mel resume at sample n -- its delivery starts there, the samples from n on are
@@ -556,6 +663,7 @@ class SlotStream:
         queued or counted: the engine has no upsampling table, the frames written so far do not cover the prime, a final
         request's prime covers the whole utterance.  Without a prime it changes nothing."""
         min_p = check_min_p(min_p)
+        cut = self._check_cut(top_k, top_p)
         if (self._prefill if prefill is None else prefill) and prime is not None:
             stride = getattr(self.engine, "upStride", 0)
             if not stride or not self.engine.upsampleRowElems():
@@ -569,12 +677,14 @@ class SlotStream:
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), n * stride))
             state = self.prefill_mel(mel, prime, uid, temperature, n, final)
             state.min_p = min_p      # (as in submit)
+            state.top_k, state.top_p = cut
             handle = self._next_handle
             self._next_handle += 1
             req = self._mel[handle] = [n, bool(final), None, int(state.done)]
             self._queue.append((handle, mel, int(state.uid), req, state))
             self._note_temperature(handle, temperature)
             self._note_min_p(handle, min_p)
+            self._note_cut(handle, cut)
             return handle
         n = self._mel_frames(mel, frames, final)
         temperature = check_temperature(temperature)
@@ -589,6 +699,7 @@ class SlotStream:
         self._queue.append((handle, mel, int(uid), req))
         self._note_temperature(handle, temperature)
         self._note_min_p(handle, min_p)
+        self._note_cut(handle, cut)
         if prime is not None:
             self._prime[handle] = prime
         return handle
@@ -642,6 +753,52 @@ class SlotStream:
         if handle not in self.running() and not any(item[0] == handle for item in self._queue):
             raise KeyError(handle)
         return self._minp.get(handle, 0.0)
+
+    def _check_cut(self, top_k, top_p):
+        return check_top_k(top_k, getattr(self.engine, "A", None)), check_top_p(top_p)
+
+    def _note_cut(self, handle, cut):
+        if cut != (0, 1.0):
+            self._cut[handle] = cut
+        else:
+            self._cut.pop(handle, None)
+
+    def _set_cut(self, handle, top_k=None, top_p=None):
+        col = self.running().get(handle)
+        if col is None and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        k, p = self._cut.get(handle, (0, 1.0))
+        if top_k is not None:
+            k = top_k
+            if col is not None:
+                self.engine.slotSetTopK(col, k)
+        else:
+            p = top_p
+            if col is not None:
+                self.engine.slotSetTopP(col, p)
+        self._note_cut(handle, (k, p))
+
+    def set_top_k(self, handle, top_k):
+        """Request `handle` draws from its `top_k` most probable bins from the next step on (0: off): a running one through the
+        engine at once, a waiting one when it is admitted.  KeyError for a handle the stream does not hold, ValueError for a bad
+        value -- nothing changes."""
+        self._set_cut(handle, top_k=self._check_cut(top_k, 1.0)[0])
+
+    def set_top_p(self, handle, top_p):
+        """Likewise with the nucleus mass `top_p` (1: off)."""
+        self._set_cut(handle, top_p=check_top_p(top_p))
+
+    def top_k(self, handle):
+        """Top-k request `handle` (queued or running) is drawn with."""
+        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        return self._cut.get(handle, (0, 1.0))[0]
+
+    def top_p(self, handle):
+        """Top-p request `handle` (queued or running) is drawn with."""
+        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        return self._cut.get(handle, (0, 1.0))[1]
 
     def extend_mel(self, handle, frames, final=False):
         """The first `frames` frames of mel request `handle` are written (queued or running); final: no more will come."""
@@ -711,6 +868,7 @@ class SlotStream:
         handle, req = item[0], item[3]
         T = self._temp.pop(handle, 1.0)
         P = self._minp.pop(handle, 0.0)
+        K, Q = self._cut.pop(handle, (0, 1.0))
         prime = self._prime.pop(handle, None)
         if req is not None:
             del self._mel[handle]
@@ -718,11 +876,12 @@ class SlotStream:
             if req is not None:
                 item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
             item[4].temperature = T                                 # (... or given another temperature
-            item[4].min_p = P                                       # or floor)
+            item[4].min_p = P                                       # or floor
+            item[4].top_k, item[4].top_p = K, Q                     # or cuts)
             return item[4]
         if req is None:
-            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime, min_p=P)
-        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime, min_p=P)
+            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
+        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
@@ -731,17 +890,18 @@ class SlotStream:
         x, uid = self._src.pop(handle)
         T = self._temp.pop(handle, 1.0)      # (the engine has written the same value into the blob's header)
         P = self._minp.pop(handle, 0.0)      # (likewise)
+        K, Q = self._cut.pop(handle, (0, 1.0))
         prime = self._prime.pop(handle, None)
         heapq.heappush(self._free, col)
         self._ch[col] = -1
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime, min_p=P)
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime, P)
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime, P, K, Q)
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -804,6 +964,7 @@ class SlotStream:
         list and can be drained)."""
         if hasattr(state.blob, "numel") and state.blob.numel() != self.engine.slotStateBytes():
             raise ValueError("a state of %d bytes, this engine's are %d: another shape or precision" % (state.blob.numel(), self.engine.slotStateBytes()))
+        cut = self._check_cut(state.top_k, state.top_p)      # (against this engine's alphabet, before anything is queued)
         handle = self._next_handle
         self._next_handle += 1
         self._next_uid = max(self._next_uid, int(state.uid) + 1)
@@ -813,6 +974,7 @@ class SlotStream:
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
         self._note_temperature(handle, check_temperature(state.temperature))
         self._note_min_p(handle, check_min_p(state.min_p))
+        self._note_cut(handle, cut)
         if state.prime is not None and state.done < state.prime.numel():      # (still inside it: applied again when it is admitted)
             self._prime[handle] = state.prime
         return handle
@@ -838,6 +1000,7 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
+        cuts = []        # (column, (top_k, top_p), what the start or the resume leaves) likewise: words 12 and 13
         floored = []     # (column, floor) likewise: a start leaves 0, a resume word 11 of the blob (zero in a prefilled or scored one)
         tempered = []    # (column, temperature) of the admitted requests whose temperature is not what their start leaves the column at
         while self._queue and self._free and self._ready(self._queue[0], count):
@@ -857,6 +1020,9 @@ class SlotStream:
             P = self._minp.get(handle, 0.0)
             if P != (state._blob_min_p if blob is not None else 0.0):
                 floored.append((col, P))
+            cut, had = self._cut.get(handle, (0, 1.0)), (state._blob_cut if blob is not None else (0, 1.0))
+            if cut != had:
+                cuts.append((col, cut, had))
             if req is None:
                 if blob is None:
                     self.engine.slotStart(col, x, uid)
@@ -884,6 +1050,11 @@ class SlotStream:
             self.engine.slotSetTemperature(col, T)
         for col, P in floored:
             self.engine.slotSetMinP(col, P)
+        for col, cut, had in cuts:
+            if cut[0] != had[0]:
+                self.engine.slotSetTopK(col, cut[0])
+            if cut[1] != had[1]:
+                self.engine.slotSetTopP(col, cut[1])
         for col, handle in primed:   # (start or resume, then prime)
             self.engine.slotPrime(col, self._prime[handle])
 
@@ -945,6 +1116,7 @@ class SlotStream:
                 del self._src[rec[0]]
                 self._temp.pop(rec[0], None)
                 self._minp.pop(rec[0], None)
+                self._cut.pop(rec[0], None)
                 self._prime.pop(rec[0], None)
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
@@ -957,6 +1129,7 @@ class SlotStream:
         self._mel.pop(handle, None)
         self._temp.pop(handle, None)
         self._minp.pop(handle, None)
+        self._cut.pop(handle, None)
         self._prime.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1

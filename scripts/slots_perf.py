@@ -61,6 +61,12 @@ columns: the table and its scatter launch); a parent that has the temperature en
 (set explicitly: no table, Params::floorOn = 0 -- the launches the parent issues) and with mixed floors (0, 0.05, 0.1, 0.25, 0.5
 cycling over the columns: the table, its scatter launch and a compare and a select per logit).  The verdict is about the all-zero
 case -- not above the parent by more than twice the parent's own spread --; the mixed case is reported beside it, not barred.
+--cut is that comparison for the tail cuts (top-k and top-p), seven cases: the parent's plain step and its step with
+mixed floors; this commit's with every control off (set explicitly: no table, Params::floorOn = 0), with the same mixed floors only
+(floorOn = 1: the launches the parent issues for them), with top-k only (0, 1, 4, 32, A cycling over the columns), with top-p only
+(1, 0.5, 0.8, 0.9 cycling) and with both (floorOn bit 1: the search, 31 steps of one compare per logit with an add-with-carry, a select and an add).  The
+verdict: the all-off case not above the parent's plain step, and the floors-only case not above the parent's floors-only step, each
+by more than twice the spread of the parent's case it is held to; the three cutting cases are reported, not barred.
 --prime is that comparison for primed generation: the parent's plain step, this commit's with no prime anywhere
 (Params::forced = 0: the launches the parent issues) and with every column inside a prime for the whole measurement (one
 slot_prime_kernel launch per step and the select behind softmax_pick in every sample).  The verdict is about the case without a
@@ -103,6 +109,7 @@ results of the paths are checked to be equal bytes.  One JSON line each: median 
     python scripts/slots_perf.py --parent --parent-lib PATH [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --temperature --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --min-p --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
+    python scripts/slots_perf.py --cut --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --prime --parent-lib PATH [--batch 12288] [--chunks 256,2048] [--rounds 5]
     python scripts/slots_perf.py --compact [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --serve [--batch 12288] [--chunks 256,2048] [--rounds 5]
@@ -141,7 +148,8 @@ def main():
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
-    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --min-p, --prime: a libwavenet_infer.so built from the parent commit")
+    ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
+    ap.add_argument("--parent-lib", default=None, help="--parent, --temperature, --min-p, --cut, --prime: a libwavenet_infer.so built from the parent commit")
     args = ap.parse_args()
     import torch
     import bench
@@ -173,8 +181,8 @@ def main():
         if not args.parent_lib:
             return
         args.parent = True
-    if args.temperature or args.parent or args.prime or args.min_p:
-        assert args.parent_lib or not args.parent, "--parent needs --parent-lib"
+    if args.temperature or args.parent or args.prime or args.min_p or args.cut:
+        assert args.parent_lib or not (args.parent or args.cut), "--parent and --cut need --parent-lib"
         for chunk in [int(c) for c in args.chunks.split(",")]:
             print(json.dumps(time_against_parent(args, w, Wc, bc, chunk)), flush=True)
         return
@@ -271,7 +279,7 @@ def main():
 
 
 def time_against_parent(args, w, Wc, bc, chunk):
-    """The --parent / --temperature / --min-p / --prime measurement (module docstring) for steps of `chunk` samples.  A case is (library,
+    """The --parent / --temperature / --min-p / --cut / --prime measurement (module docstring) for steps of `chunk` samples.  A case is (library,
     temperatures or primes, kind of step); the cases of one library and setting share an engine."""
     import ctypes as C
     import torch
@@ -298,11 +306,18 @@ def time_against_parent(args, w, Wc, bc, chunk):
     here.nvw_slot_set_temperature.restype, here.nvw_slot_set_temperature.argtypes = ci, [vp, ci, C.c_float]
     here.nvw_slot_prime.restype, here.nvw_slot_prime.argtypes = ci, [vp, ci, vp, ci]
     here.nvw_slot_set_min_p.restype, here.nvw_slot_set_min_p.argtypes = ci, [vp, ci, C.c_float]
+    here.nvw_slot_set_top_k.restype, here.nvw_slot_set_top_k.argtypes = ci, [vp, ci, ci]
+    here.nvw_slot_set_top_p.restype, here.nvw_slot_set_top_p.argtypes = ci, [vp, ci, C.c_float]
     libs = ({"unit": here, "mixed": here} if args.temperature else {"zero": here, "floored": here} if args.min_p else
+            {"off": here, "floors": here, "top_k": here, "top_p": here, "both": here} if args.cut else
             {"noprime": here, "primed": here} if args.prime else {"here": here})
-    single = args.temperature or args.prime or args.min_p      # (one kind of step, several settings of this commit)
+    single = args.temperature or args.prime or args.min_p or args.cut      # (one kind of step, several settings of this commit)
     if args.parent_lib:
-        libs = dict({"parent": load(args.parent_lib)}, **libs)
+        parent = load(args.parent_lib)
+        libs = dict({"parent": parent}, **libs)
+        if args.cut:      # (the parent has the floors: its own floors-only step is what this commit's is held to)
+            parent.nvw_slot_set_min_p.restype, parent.nvw_slot_set_min_p.argtypes = ci, [vp, ci, C.c_float]
+            libs = dict({"parent": parent, "parent_floors": parent}, **{k: v for k, v in libs.items() if k != "parent"})
     kinds = ("step",) if single else ("step", "ragged")
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
@@ -314,6 +329,7 @@ def time_against_parent(args, w, Wc, bc, chunk):
     offs = rng.integers(0, 4096, size=B)
     mixed = (0.7, 0.85, 1.0, 1.2)
     floors = (0.0, 0.05, 0.1, 0.25, 0.5)
+    top_ks, top_ps = (0, 1, 4, 32, sh.A), (1.0, 0.5, 0.8, 0.9)
     forced = torch.randint(0, sh.A, (need,), device="cuda", generator=g, dtype=torch.int32)      # one prime for every column, as long as the run
     a = lambda x: np.ascontiguousarray(x, dtype=np.float32).ctypes.data
     engines, info = {}, {}
@@ -334,6 +350,14 @@ def time_against_parent(args, w, Wc, bc, chunk):
                 assert h.nvw_slot_set_temperature(e, b, mixed[b % len(mixed)])
             if case in ("zero", "floored"):
                 assert h.nvw_slot_set_min_p(e, b, floors[b % len(floors)] if case == "floored" else 0.0)
+            if case in ("parent_floors", "floors"):
+                assert h.nvw_slot_set_min_p(e, b, floors[b % len(floors)])
+            if case == "off":
+                assert h.nvw_slot_set_min_p(e, b, 0.0) and h.nvw_slot_set_top_k(e, b, 0) and h.nvw_slot_set_top_p(e, b, 1.0)
+            if case in ("top_k", "both"):
+                assert h.nvw_slot_set_top_k(e, b, top_ks[b % len(top_ks)])
+            if case in ("top_p", "both"):
+                assert h.nvw_slot_set_top_p(e, b, top_ps[b % len(top_ps)])
             if case == "primed":
                 assert h.nvw_slot_prime(e, b, forced.data_ptr(), need)
         buf = C.create_string_buffer(256)
@@ -382,11 +406,13 @@ def time_against_parent(args, w, Wc, bc, chunk):
     res = {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
            "ms_per_step": {name(k): [round(v, 4) for v in vs] for k, vs in ms.items()}, "median_ms_per_step": {name(k): round(v, 4) for k, v in med.items()},
            "host_us_per_call": {name(k): [round(v, 2) for v in vs] for k, vs in host_us.items()},
-           "kernel": info["unit" if args.temperature else "zero" if args.min_p else "noprime" if args.prime else "here"], "device": torch.cuda.get_device_name(0)}
+           "kernel": info["unit" if args.temperature else "zero" if args.min_p else "off" if args.cut else "noprime" if args.prime else "here"], "device": torch.cuda.get_device_name(0)}
     if args.temperature:
         res["mixed_temperatures"] = mixed
-    if args.min_p:
+    if args.min_p or args.cut:
         res["mixed_floors"] = floors
+    if args.cut:
+        res["top_ks"], res["top_ps"] = top_ks, top_ps
     if "parent" not in libs:
         res["parent"] = "not measured (no --parent-lib)"
         return res
@@ -397,6 +423,17 @@ def time_against_parent(args, w, Wc, bc, chunk):
             m = {k: float(np.median(x)) for k, x in v.items()}
             spread = (max(v[p]) - min(v[p])) / m[p]
             ratios = {case: m[(case, kind)] / m[p] for case in libs if case != "parent"}
+            if args.cut:      # (off against the parent's plain step, floors against the parent's floors-only step; the cutting cases are reported)
+                pf = ("parent_floors", kind)
+                spread_f = (max(v[pf]) - min(v[pf])) / m[pf]
+                floors_ratio = m[("floors", kind)] / m[pf]
+                res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
+                                         "parent_floors_median": round(m[pf], 4), "parent_floors_spread": round(spread_f, 4),
+                                         "floors_vs_parent_floors": round(floors_ratio, 4),
+                                         "within_twice_the_parent_spread": bool(ratios["off"] <= 1.0 + 2.0 * spread and
+                                                                                floors_ratio <= 1.0 + 2.0 * spread_f)},
+                                        **{case + "_vs_parent": round(r, 4) for case, r in ratios.items()})
+                continue
             barred = [r for case, r in ratios.items() if case not in ("primed", "floored")]      # (--prime, --min-p: the primed and the floored case are reported, not barred)
             res[what + kind] = dict({"parent_median": round(m[p], 4), "parent_spread": round(spread, 4),
                                      "within_twice_the_parent_spread": bool(max(barred) <= 1.0 + 2.0 * spread)},
