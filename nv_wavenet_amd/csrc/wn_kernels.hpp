@@ -899,7 +899,7 @@ __device__ __attribute__((noinline)) float cut_threshold_dump(const float* lrow,
 // finds the cuts' threshold from topK and topP (read only then), the column floors at the largest of the three, and from there on
 // the function is the FLOOR = 1 path.  0 and 1 compile to the bodies they had.  3 is 2 for the activation-dump kernels: the threshold
 // comes from cut_threshold_dump, and the logits are read again behind it, so that no e[] lives across the search; the same
-// threshold and the same e, bit for bit.
+// threshold and the same e, bit for bit.  FLOOR >= 1 never returns a dropped bin (nor the plain form's 128): see the end of the function.
 template <int A, int LPU, int RPL, int FLOOR = 0>
 WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&e)[RPL], float& total, float scale = kLog2e,
                         float floor = 0.f, int topK = 0, float topP = 1.0f) {
@@ -972,14 +972,37 @@ WN_DEV int softmax_pick(const float* lrow, int sq, int lane, float sel, float (&
     // The running sums of non-negative terms never decrease, so the rows whose sum does NOT exceed the target form a prefix:
     // its length is the first row that does (compare + add-with-carry per row instead of two compares and a select).
     float cum = incl - lsum;   // exclusive prefix of this lane
-    int first = 0;
+    int first = 0, lastKept = -1;
 #pragma unroll
     for (int i = 0; i < RPL; i++) {
         cum += e[i];
         first += (cum <= target) ? 1 : 0;
+        if constexpr (FLOOR >= 1) lastKept = (e[i] > 0.f) ? i : lastKept;   // (for the answer below; see there)
     }
     int pick = first < RPL ? sq * RPL + first : 0x7fffffff;
-    pick = group_min_i<LPU>(pick);
+    if constexpr (FLOOR >= 1) {
+        // Under a floor or a cut the draw has to be a kept bin, and the scan alone does not promise that.  `incl - lsum` is the lane's
+        // exclusive prefix only up to rounding: the last kept lane's running sum can end an ulp or two under `total`, so that at the
+        // selectors next to 1 no row exceeds the target (the scan falls off the end), or only a later lane does, whose sum STARTS above
+        // the target -- and whose first row is a bin the cut dropped.  Inside a lane a row that stops the scan behind one that did not
+        // has raised the sum, so its e > 0: a dropped bin can stop the scan only as a lane's first row.  That case travels through the
+        // minimum as bit 0 (the fall-off's 0x7fffffff has it set too), and both get the same answer: the highest kept row below the
+        // row the scan stopped on -- the last kept bin of the column when it fell off.  Every other draw is the row it was.
+        // (lastKept is found in the scan's loop, a compare and a select per row: a loop of its own over e[] inside the rare branch
+        // made hipcc 7.2 fail on the fp32 kernels of R 64, S 128, A 256 with "Operand has incorrect register class".)
+        const bool dropped = (first == 0) & (e[0] == 0.f);
+        int enc = first < RPL ? 2 * pick + (dropped ? 1 : 0) : 0x7fffffff;
+        enc = group_min_i<LPU>(enc);
+        pick = enc >> 1;
+        if (enc & 1) {                     // (the same in every lane of the group: its DPP steps run with the whole group)
+            int last = lastKept >= 0 ? sq * RPL + lastKept : -1;
+            last = last < pick ? last : -1;
+            last = -group_min_i<LPU>(-last);
+            pick = last >= 0 ? last : pick;   // (nothing kept below: a target below zero, the selector of a forced sample)
+        }
+    } else {
+        pick = group_min_i<LPU>(pick);
+    }
     if (pick >= A) pick = 128;             // scan fell off the end (softmax.cuh:154-155)
     return pick;
 }
@@ -2018,9 +2041,12 @@ WN_DEV void wavenet_wg_body(const Params& p) {
                 if constexpr (FEAT) {
                     // (floorOn is launch-uniform: a launch with no cut in force runs one of the two calls it ran before, and one with
                     // no floor either the one it ran before that)
-                    if (p.floorOn & 2)
+                    // (The activation-dump kernels take their cutting form for a floor alone as well -- k = 0 and p = 1 are loaded
+                    // then, the search ends at 0 and the threshold is the floor: the same e and the same draw, bit for bit --: a third
+                    // softmax body made the three-tile dump kernel of R 64, S 128, A 256 spill.)
+                    if (p.floorOn & (DUMP ? 3 : 2))
                         pick = softmax_pick<A, C::LPU, C::RPL, (DUMP ? 3 : 2)>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt], stopk[bt], stopp[bt]);
-                    else if (p.floorOn & 1) pick = softmax_pick<A, C::LPU, C::RPL, 1>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt]);
+                    else if (!DUMP && (p.floorOn & 1)) pick = softmax_pick<A, C::LPU, C::RPL, 1>(lrow, sq, lane, selv[bt], e, total, sscale[bt], sfloor[bt]);
                     else pick = softmax_pick<A, C::LPU, C::RPL>(lrow, sq, lane, selv[bt], e, total, sscale[bt]);
                     // a forced sample (Params::forced): the selector names it; e and total stay the model's
                     if (p.forced) pick = selv[bt] <= -1.0f ? (int)(-selv[bt]) - 1 : pick;

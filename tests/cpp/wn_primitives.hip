@@ -3,6 +3,9 @@
 //   wnp_gemm          pack_weight_kernel -> per-wave fragment streams -> take()/gemm() over one tile of 16 columns
 //                     (the MFMA fragment packing, the K permutation, the gated tile pairing, the prefetch ring)
 //   wnp_softmax_pick  wn::softmax_pick (max / sum / scan / inverse-CDF pick over LPU lanes per utterance)
+//   wnp_softmax_pick_form   the same in each of its forms (plain, floor, floor + tail cuts, the dump kernels' search), per-utterance
+//                     scale, floor, top-k and top-p; the raw e[] and the total come back
+//   wnp_cut_threshold wn::cut_threshold / wn::cut_threshold_dump alone, on e formed as softmax_pick forms it
 //   wnp_handoff       wn::send_tiles / recv_tiles_fast between two workgroups (tagged granules, both store scopes)
 //   wnp_stream_walk   pack_layer_kernel + Cfg::streamPos -> the per-wave weight stream walked exactly like wavenet_wg walks
 //                     it (buffer-resource ring: gemm_b / take_group / refill_group / skip_frags, the wrap behind the head)
@@ -129,6 +132,126 @@ template <int A, int NW> static int run_softmax(const float* logits, const float
     CK(hipFree(ds));
     CK(hipFree(dp));
     CK(hipFree(dk));
+    return 0;
+}
+
+// softmax_pick in each of its forms (FORM = the FLOOR template argument: 0 plain, 1 the floor, 2 the floor and the tail cuts, 3 the
+// same with the dump kernels' search), every argument per utterance; the raw e[] (not divided) and the total come back.  lg stays
+// as it is across the call, as lgbuf does in the engine: FORM 3 reads the logits again behind its search.
+template <int A, int NW, int FORM>
+__global__ __launch_bounds__(NW * 64) void softmax_form_kernel(const float* logits, const float* sel, const float* scale, const float* floor,
+                                                               const int* topk, const float* topp, int* picks, float* eout, float* totals) {
+    constexpr int LPU = 4 * NW, RPL = A / LPU, LROW = A + 4;
+    __shared__ __attribute__((aligned(16))) float lg[16 * LROW];
+    for (int i = threadIdx.x; i < 16 * A; i += NW * 64) lg[(i / A) * LROW + i % A] = logits[i];
+    __syncthreads();
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int su = tid / LPU, sq = tid % LPU;
+    const float* lrow = lg + su * LROW + sq * RPL;
+    float e[RPL];
+    float total;
+    int pick;
+    if constexpr (FORM == 0) pick = softmax_pick<A, LPU, RPL>(lrow, sq, lane, sel[su], e, total, scale[su]);
+    else if constexpr (FORM == 1) pick = softmax_pick<A, LPU, RPL, 1>(lrow, sq, lane, sel[su], e, total, scale[su], floor[su]);
+    else pick = softmax_pick<A, LPU, RPL, FORM>(lrow, sq, lane, sel[su], e, total, scale[su], floor[su], topk[su], topp[su]);
+    if (sq == 0) {
+        picks[su] = pick;
+        totals[su] = total;
+    }
+    for (int i = 0; i < RPL; i++) eout[su * A + sq * RPL + i] = e[i];
+}
+
+// the threshold of the tail cuts alone, on e formed as softmax_pick forms it (the same loads, maximum, fma and exp2 on
+// mneg = -m * scale); DUMP: cut_threshold_dump instead of cut_threshold
+template <int A, int NW, bool DUMP>
+__global__ __launch_bounds__(NW * 64) void cut_threshold_kernel(const float* logits, const float* scale, const int* topk, const float* topp,
+                                                                float* thr) {
+    constexpr int LPU = 4 * NW, RPL = A / LPU, LROW = A + 4;
+    __shared__ __attribute__((aligned(16))) float lg[16 * LROW];
+    for (int i = threadIdx.x; i < 16 * A; i += NW * 64) lg[(i / A) * LROW + i % A] = logits[i];
+    __syncthreads();
+    const int tid = threadIdx.x;
+    const int su = tid / LPU, sq = tid % LPU;
+    const float* lrow = lg + su * LROW + sq * RPL;
+    float e[RPL];
+#pragma unroll
+    for (int i = 0; i < RPL / 4; i++) {
+        floatx4 v = *(const floatx4*)(lrow + i * 4);
+#pragma unroll
+        for (int r = 0; r < 4; r++) e[i * 4 + r] = v[r];
+    }
+    float m = e[0];
+#pragma unroll
+    for (int i = 1; i < RPL; i++) m = __builtin_fmaxf(m, e[i]);
+    m = group_reduce_f<LPU>(m, [](float a, float b) { return __builtin_fmaxf(a, b); });
+    const float sc = scale[su], mneg = -m * sc;
+    float t;
+    if constexpr (DUMP) {
+        t = cut_threshold_dump<LPU, RPL>(lrow, topk[su], topp[su], sc, mneg);
+    } else {
+#pragma unroll
+        for (int i = 0; i < RPL; i++) e[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(e[i], sc, mneg));
+        t = cut_threshold<LPU, RPL>(e, topk[su], topp[su]);
+    }
+    if (sq == 0) thr[su] = t;
+}
+
+// host side of the two: 16 utterances of A logits, per-utterance arguments in arrays of 16
+struct SamplerArgs {
+    const float *logits, *sel, *scale, *floor, *topp;
+    const int* topk;
+};
+template <int A, int NW> static int run_softmax_form(int form, const SamplerArgs& a, int* picks, float* e, float* total) {
+    float *dl, *df, *de;      // df: sel | scale | floor | topp | total, 16 each
+    int* di;                  // topk | picks
+    CK(hipMalloc(&dl, sizeof(float) * 16 * A));
+    CK(hipMalloc(&de, sizeof(float) * 16 * A));
+    CK(hipMalloc(&df, sizeof(float) * 16 * 5));
+    CK(hipMalloc(&di, sizeof(int) * 16 * 2));
+    CK(hipMemcpy(dl, a.logits, sizeof(float) * 16 * A, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df, a.sel, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df + 16, a.scale, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df + 32, a.floor, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df + 48, a.topp, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(di, a.topk, sizeof(int) * 16, hipMemcpyHostToDevice));
+    CK(hipMemset(de, 0xff, sizeof(float) * 16 * A));
+    CK(hipMemset(df + 64, 0xff, sizeof(float) * 16));
+    CK(hipMemset(di + 16, 0xff, sizeof(int) * 16));
+#define FORM_LAUNCH(f) \
+    hipLaunchKernelGGL((softmax_form_kernel<A, NW, f>), dim3(1), dim3(NW * 64), 0, 0, dl, df, df + 16, df + 32, di, df + 48, di + 16, de, df + 64)
+    if (form == 0) FORM_LAUNCH(0);
+    else if (form == 1) FORM_LAUNCH(1);
+    else if (form == 2) FORM_LAUNCH(2);
+    else FORM_LAUNCH(3);
+#undef FORM_LAUNCH
+    CK(hipGetLastError());
+    CK(hipMemcpy(picks, di + 16, sizeof(int) * 16, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(e, de, sizeof(float) * 16 * A, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(total, df + 64, sizeof(float) * 16, hipMemcpyDeviceToHost));
+    CK(hipFree(dl));
+    CK(hipFree(de));
+    CK(hipFree(df));
+    CK(hipFree(di));
+    return 0;
+}
+template <int A, int NW> static int run_cut_threshold(int dump, const SamplerArgs& a, float* thr) {
+    float *dl, *df;           // df: scale | topp | thr
+    int* di;
+    CK(hipMalloc(&dl, sizeof(float) * 16 * A));
+    CK(hipMalloc(&df, sizeof(float) * 16 * 3));
+    CK(hipMalloc(&di, sizeof(int) * 16));
+    CK(hipMemcpy(dl, a.logits, sizeof(float) * 16 * A, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df, a.scale, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(df + 16, a.topp, sizeof(float) * 16, hipMemcpyHostToDevice));
+    CK(hipMemcpy(di, a.topk, sizeof(int) * 16, hipMemcpyHostToDevice));
+    CK(hipMemset(df + 32, 0xff, sizeof(float) * 16));
+    if (dump) hipLaunchKernelGGL((cut_threshold_kernel<A, NW, true>), dim3(1), dim3(NW * 64), 0, 0, dl, df, di, df + 16, df + 32);
+    else hipLaunchKernelGGL((cut_threshold_kernel<A, NW, false>), dim3(1), dim3(NW * 64), 0, 0, dl, df, di, df + 16, df + 32);
+    CK(hipGetLastError());
+    CK(hipMemcpy(thr, df + 32, sizeof(float) * 16, hipMemcpyDeviceToHost));
+    CK(hipFree(dl));
+    CK(hipFree(df));
+    CK(hipFree(di));
     return 0;
 }
 
@@ -462,6 +585,33 @@ int wnp_softmax_pick(int A, int nw, const float* logits, const float* sel, int* 
     if (A == 256 && nw == 2) return run_softmax<256, 2>(logits, sel, picks, probs);
     if (A == 512 && nw == 4) return run_softmax<512, 4>(logits, sel, picks, probs);
     if (A == 1024 && nw == 4) return run_softmax<1024, 4>(logits, sel, picks, probs);
+    return -2;
+}
+
+// the (A, nw) pairs of wnp_softmax_pick: every softmax lane layout a RAW = 3 kernel is built with
+#define SAMPLER_PAIRS(RUN) \
+    if (A == 256 && nw == 4) return RUN(256, 4);  \
+    if (A == 256 && nw == 2) return RUN(256, 2);  \
+    if (A == 512 && nw == 4) return RUN(512, 4);  \
+    if (A == 1024 && nw == 4) return RUN(1024, 4);
+
+// softmax_pick<A, 4 nw, A / (4 nw), form> of 16 utterances, form 0 .. 3; every argument per utterance; e [16][A] the raw e[]
+int wnp_softmax_pick_form(int A, int nw, int form, const float* logits, const float* sel, const float* scale, const float* floor,
+                          const int* topk, const float* topp, int* picks, float* e, float* total) {
+    if (form < 0 || form > 3) return -2;
+    const SamplerArgs a{logits, sel, scale, floor, topp, topk};
+#define RUN(a_, n_) run_softmax_form<a_, n_>(form, a, picks, e, total)
+    SAMPLER_PAIRS(RUN)
+#undef RUN
+    return -2;
+}
+
+// cut_threshold (dump = 0) or cut_threshold_dump (dump = 1) of 16 utterances
+int wnp_cut_threshold(int A, int nw, int dump, const float* logits, const float* scale, const int* topk, const float* topp, float* thr) {
+    const SamplerArgs a{logits, nullptr, scale, nullptr, topp, topk};
+#define RUN(a_, n_) run_cut_threshold<a_, n_>(dump, a, thr)
+    SAMPLER_PAIRS(RUN)
+#undef RUN
     return -2;
 }
 

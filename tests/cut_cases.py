@@ -171,12 +171,14 @@ def rows_of_mask(rows, mask):
 
 
 def pick(rows, u, mask):
-    """the inverse-CDF pick of the rule from rows [n][A] restricted to mask: the first bin whose cumulative sum exceeds u * total"""
+    """the inverse-CDF pick of the rule from rows [n][A] restricted to mask: the first bin whose cumulative sum exceeds u * total
+    (the last kept bin when the scan falls off the end: under a cut the kernel never answers a dropped bin)"""
     r = np.asarray(rows, dtype=np.float64)
     e = np.where(mask, np.exp(r - r.max(axis=1, keepdims=True)), 0.0)
     cum = np.cumsum(e, axis=1)
     first = (cum <= (np.asarray(u, dtype=np.float64) * cum[:, -1])[:, None]).sum(axis=1)
-    return np.where(first < r.shape[1], first, 128).astype(np.int64)
+    last = r.shape[1] - 1 - np.argmax((e > 0)[:, ::-1], axis=1)
+    return np.where(first < r.shape[1], first, last).astype(np.int64)
 
 
 def pick_cut(rows, u, k, p, tau):

@@ -62,15 +62,16 @@ def kept(rows, tau):
 
 def pick_min_p(rows, u, tau):
     """The numpy mirror of the rule on log-probabilities rows [n][A] (float64; already at the column's temperature), draws u [n]:
-    e = p / p_max, e < tau -> 0, the pick is the first row whose cumulative sum exceeds u * total (128 when the scan falls off the
-    end).  Returns y [n]."""
+    e = p / p_max, e < tau -> 0, the pick is the first row whose cumulative sum exceeds u * total (the last kept bin when the scan
+    falls off the end: under a floor the kernel never answers a dropped bin).  Returns y [n]."""
     r = np.asarray(rows, dtype=np.float64)
     e = np.exp(r - r.max(axis=1, keepdims=True))
     e = np.where(e >= float(tau), e, 0.0)
     cum = np.cumsum(e, axis=1)
     target = np.asarray(u, dtype=np.float64) * cum[:, -1]
     first = (cum <= target[:, None]).sum(axis=1)
-    return np.where(first < r.shape[1], first, 128).astype(np.int64)
+    last = r.shape[1] - 1 - np.argmax((e > 0)[:, ::-1], axis=1)
+    return np.where(first < r.shape[1], first, last).astype(np.int64)
 
 
 def check_column(rows, y, u, tau, eps, min_p_rows):
