@@ -61,9 +61,10 @@ def log_softmax(Za, T=1.0):
 MUTATIONS = ("no_skip_bias", "drop_last_skip", "restart_skip", "shift_y", "swap_history", "ignore_T", "feature_prev")
 
 
-def reference(t, shape, y, Lh, T=1.0, mutate=None):
+def reference(t, shape, y, Lh, T=1.0, mutate=None, tanh_embed=True):
     """(Za [n][A], logp [n]) in float64 of the network t teacher-forced on y [n] from silence, conditioning Lh [>= n][L][2R].
-    shape: anything with R, S, A, L, maxD.  mutate: one of MUTATIONS, a deliberately broken model (negative controls)."""
+    shape: anything with R, S, A, L, maxD.  mutate: one of MUTATIONS, a deliberately broken model (negative controls).
+    tanh_embed=False: the embedding sum enters layer 0 as it is (WavenetEngine(tanhEmbed=False), the oracle's set_tanh_embed(False))."""
     assert mutate is None or mutate in MUTATIONS
     R, S, A, L, maxD = shape.R, shape.S, shape.A, shape.L, shape.maxD
     f = lambda a: np.asarray(a, dtype=np.float64)
@@ -74,7 +75,9 @@ def reference(t, shape, y, Lh, T=1.0, mutate=None):
     old = np.concatenate([[128, 128], fed[:-2]])[:n]                             # y[t-2]
     if mutate == "swap_history":
         cur, old = old, cur
-    x = np.tanh(f(t.embP)[old] + f(t.embC)[cur])
+    x = f(t.embP)[old] + f(t.embC)[cur]
+    if tanh_embed:
+        x = np.tanh(x)
     lh = f(Lh)[:n]
     if mutate == "feature_prev":
         lh = np.concatenate([lh[:1], lh[:-1]])

@@ -39,7 +39,8 @@ def _sequential_blobs(e, xg, jobs, window, lead=5):
     e.slotsBegin(window)
     if lead:
         e.slotStart(e.maxBatch - 1, xg[0], 0)
-        assert e.slotsStep(lead)
+        for at in range(0, lead, window):          # (a step is at most the window: 1 where every layer has d = 1)
+            assert e.slotsStep(min(window, lead - at))
         e.slotStop(e.maxBatch - 1)
     for col, uid, y, T in jobs:
         e.slotStart(col, xg[uid], uid)

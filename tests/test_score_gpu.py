@@ -20,10 +20,10 @@ SEED = 0x5C02E0000000011
 _nets, _refs = {}, {}
 
 
-def _engine(case, t, precision, w, b, columns=16, weights=True):
+def _engine(case, t, precision, w, b, columns=16, weights=True, tanh_embed=True):
     s = case.shape
-    e = WavenetEngine(s.R, s.S, s.A, s.L, s.maxD, columns, max(s.N, 64), impl=1 if s.S <= 4 * s.R else 3, tanhEmbed=True, precision=precision,
-                      organisation=util.MODE_ORG["wg"])
+    e = WavenetEngine(s.R, s.S, s.A, s.L, s.maxD, columns, max(s.N, 64), impl=1 if s.S <= 4 * s.R else 3, tanhEmbed=tanh_embed,
+                      precision=precision, organisation=util.MODE_ORG["wg"])
     e.setEmbeddings(t.embP, t.embC)
     for l in range(s.L):
         e.setLayerWeights(l, t.Wprev[l], t.Wcur[l], t.Bh[l], t.Wres[l], t.Bres[l], t.Wskip[l], t.Bskip[l])

@@ -50,9 +50,9 @@ def _plan(n_utt, columns, N, seed, sizes=COUNTS, lo=5):
     return plan, counts
 
 
-def _engine(case, t, precision, mode, w, cond_b, columns):
+def _engine(case, t, precision, mode, w, cond_b, columns, tanh_embed=True):
     s = case.shape
-    e = WavenetEngine(s.R, s.S, s.A, s.L, s.maxD, columns, s.N, impl=1 if s.S <= 4 * s.R else 3, tanhEmbed=True, precision=precision,
+    e = WavenetEngine(s.R, s.S, s.A, s.L, s.maxD, columns, s.N, impl=1 if s.S <= 4 * s.R else 3, tanhEmbed=tanh_embed, precision=precision,
                       organisation=util.MODE_ORG[mode])
     e.setEmbeddings(t.embP, t.embC)
     for l in range(s.L):
