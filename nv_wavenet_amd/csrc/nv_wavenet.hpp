@@ -275,6 +275,10 @@ protected:
     // Returns LD for a launch whose ring plan keeps d <= ringD on chip, 0 for a launch that reads its schedule at run time.  (More may
     // fit than LD = 2 holds: placing fewer layers than fit is always legal; the caller caps the plan to 2^(LD-1).)
     static constexpr int kCycle = 10;
+    // ... and, for a model of exactly kStraight cycles, the layer count compiled in as well (wavenet_wg_sl: the sample's layers as
+    // straight-line code, no join with loads in flight); other whole numbers of cycles keep the cycle loop
+    static constexpr int kStraight = 2;
+    bool straightLine() const { return m_numLayers == kStraight * kCycle; }
     static constexpr bool schedBuilt(int bt, bool dump, int raw) { return F16 && WG3 && bt == 3 && !dump && raw == 0; }
     int compiledSchedule(int bt, bool dump, int raw, int ringD) const {
         if (!schedBuilt(bt, dump, raw) || m_schedMode < 0) return 0;
@@ -303,7 +307,10 @@ protected:
                 const int ld = compiledSchedule(BT, DUMP, RAW, p.ldsRingD);
                 if (ld > 0) {
                     capLdsRing(p, 1 << (ld - 1));      // (the LDS of the plan stays: no smaller than what the capped one needs)
-                    if (ld == 2) hipLaunchKernelGGL((wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 2>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
+                    if (straightLine()) {
+                        if (ld == 2) hipLaunchKernelGGL((wn::wavenet_wg_sl<F16, R, S, A, BT, EMB, kCycle, kStraight, 2>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
+                        else hipLaunchKernelGGL((wn::wavenet_wg_sl<F16, R, S, A, BT, EMB, kCycle, kStraight, 1>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
+                    } else if (ld == 2) hipLaunchKernelGGL((wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 2>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
                     else hipLaunchKernelGGL((wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 1>), dim3(grid), dim3(CB::THREADS), need + ringBytes, stream, p);
                     return hipGetLastError() == hipSuccess;
                 }
@@ -367,6 +374,10 @@ protected:
                 gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 1>,
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_cs<F16, R, S, A, BT, EMB, kCycle, 2>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+                gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_sl<F16, R, S, A, BT, EMB, kCycle, kStraight, 1>,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+                gpuErrChk(hipFuncSetAttribute((const void*)wn::wavenet_wg_sl<F16, R, S, A, BT, EMB, kCycle, kStraight, 2>,
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
             }
         }
@@ -1200,7 +1211,7 @@ public:
         const int ld = compiledSchedule(bt, dump, raw, ringD);
         if (ld > 0) ringD = 1 << (ld - 1);
         char ring[64] = "";
-        if (ringD > 0) snprintf(ring, sizeof(ring), " ring_in_lds=d<=%d%s", ringD, ld > 0 ? " sched=cycle10" : "");
+        if (ringD > 0) snprintf(ring, sizeof(ring), " ring_in_lds=d<=%d%s", ringD, ld > 0 ? (straightLine() ? " cycles=2 sched=cycle10" : " sched=cycle10") : "");
         snprintf(buf, n, "wn::wavenet_wg<%s,%d,%d,%d,BT=%d,EMBLDS=%d,DUMP=%d,RAW=%d%s> tiles/wg=%d wgs=%d lds=%zu%s",
                  F16 ? "fp16" : "fp32", R, S, A, bt, nEmb, dump ? 1 : 0, raw, ringD > 0 ? ",LR=1" : "", bt, (tiles + bt - 1) / bt, lds, ring);
     }

@@ -1111,7 +1111,12 @@ template <bool F16> WN_DEV void cond_add(floatx4* a, typename Prec<F16>::frag c,
 // placement (LDS or HBM) of its own and the next two layers' slots and its register-set parity as constants.  0: the schedule is read at
 // run time (Dil entries travelling with a layer-pair loop).  One body for both: `layer` below takes its schedule entries as Dil or as DilC.
 // Same barriers, same stream order, same refill and request points, same summation order: samples and ring are bit-identical.
-template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP, int RAW, bool LR, int CYC, int LD>
+// NC (wavenet_wg_sl): with CYC > 0, the number of cycles as a constant as well (L = NC * CYC; 0: read at run time).  The sample's layers then
+// are straight-line code, layer 0 without its skip GEMM and layers 1 .. L-1 one behind the other: the cycle's bases, the layer number, the
+// weight-stream positions and the wrap of the last two layers onto sample t+1 are constants, only the slot index t & (d - 1) is left to run
+// time -- and no control-flow join stands between a sample's requests and their readers.  (A join with loads in flight is where the
+// compiler's wait counts fall back to vmcnt(0), which waits for the youngest weight refill and for the tap requested two layers ahead.)
+template <bool F16, int R, int S, int A, int BT, bool EMBLDS, bool DUMP, int RAW, bool LR, int CYC, int LD, int NC = 0>
 WN_DEV void wavenet_wg_body(const Params& p) {
     constexpr bool FEAT = RAW == 3;
     constexpr int KFC = FEAT ? feat_kfc<F16>() : 0;
@@ -1136,13 +1141,14 @@ WN_DEV void wavenet_wg_body(const Params& p) {
 
     static_assert(RAW == 0 || RAW == 1 || (RAW == 2 && F16) || RAW == 3, "RAW: 0 packed, 1 fp32 in place, 2 fp16 in place (fp16 engine), 3 features");
     static_assert(CYC == 0 || (LR && !DUMP && LD >= 1 && LD <= CYC - 2 && CYC % 2 == 0), "compiled schedule: an LR kernel with an even cycle, its first LD layers' slots in LDS");
+    static_assert(NC == 0 || CYC > 0, "a compiled number of cycles needs the compiled cycle");
     if (p.gate != nullptr && __builtin_nontemporal_load(p.gate) == 0u) return;   // (a fallback launch that is not needed)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, j = lane & 15;
-    const int L = p.numLayers;
+    const int L = NC > 0 ? NC * CYC : p.numLayers;
     const int tile0 = p.tileBase + blockIdx.x * BT;
     if (p.clk != nullptr && blockIdx.x == 0 && tid == 0) {
         p.clk[0] = __builtin_amdgcn_s_memtime();
@@ -1203,12 +1209,17 @@ WN_DEV void wavenet_wg_body(const Params& p) {
         const floatx4* s0 = (const floatx4*)p.embCur;
         const floatx4* s1 = (const floatx4*)p.embPrev;
         constexpr int CH = (int)(A * R * sizeof(elem) / 16);
+        // The straight-line kernel (NC > 0) gathers the older tap's rows from memory wherever the launch has room for their table: a
+        // table in LDS or in memory by a run-time test makes the gather a FLAT load, and while one is in flight the compiler cannot count
+        // the queue -- every wait up to the row's reader, a whole sample later, becomes vmcnt(0) (two per sample: in front of layer 0's
+        // first MFMA and in the middle of its refills).  The gather is a sample ahead of its use: its latency is on nobody's path.
+        const bool prevInLds = NC == 0 && p.embLds > 1;
         for (int i = tid; i < CH; i += C::THREADS) {
             ((floatx4*)embLds)[i] = s0[i];
-            if (p.embLds > 1) ((floatx4*)embLds)[CH + i] = s1[i];
+            if (prevInLds) ((floatx4*)embLds)[CH + i] = s1[i];
         }
         embCur = embLds;
-        if (p.embLds > 1) embPrev = embLds + A * R;
+        if (prevInLds) embPrev = embLds + A * R;
         __syncthreads();   // the tables are complete before the first gather below
     }
 
@@ -1826,7 +1837,26 @@ WN_DEV void wavenet_wg_body(const Params& p) {
             __builtin_amdgcn_sched_barrier(0);
             gemm_b<F16, PF, 0, BT, 2 * HTW, KF_R>(ws, rsW, C::P_PREV - PB, wl, 0, laneOff, acc, xp);
         };
-        if constexpr (CYC > 0) {
+        if constexpr (CYC > 0 && NC > 0) {
+            // Compiled schedule and layer count: the L = NC * CYC layers one behind the other.  Entries L, L+1 are layers 0, 1 of sample t+1.
+            constexpr int SLOTS = (1 << CYC) - 1, LSLOTS = (1 << LD) - 1;      // ring slots of a cycle: all of them, those in LDS
+            static_for<NC * CYC>([&](auto LI) {
+                constexpr int l = decltype(LI)::value;
+                auto entry = [&](auto J) {
+                    constexpr int q = decltype(J)::value % (NC * CYC);
+                    return DilC<q % CYC, LD>((q / CYC) * SLOTS, (q / CYC) * LSLOTS);
+                };
+                auto wraps = [&](auto J) { return std::integral_constant<bool, (decltype(J)::value >= NC * CYC)>{}; };
+                const auto dl = entry(LI);
+                const auto dN = entry(std::integral_constant<int, l + 1>{});
+                const auto dl2 = entry(std::integral_constant<int, l + 2>{});
+                const auto wrapN = wraps(std::integral_constant<int, l + 1>{});
+                const auto wrap2 = wraps(std::integral_constant<int, l + 2>{});
+                constexpr std::integral_constant<bool, (l > 0)> withSkip{};
+                if constexpr (l % 2 == 0) layer(withSkip, l, wrapN, wrap2, dl, dN, dl2, xpA, cdA, xpB, cdB);
+                else layer(withSkip, l, wrapN, wrap2, dl, dN, dl2, xpB, cdB, xpA, cdA);
+            });
+        } else if constexpr (CYC > 0) {
             // Compiled schedule: a run-time loop over the L / CYC dilation cycles, its body the CYC layers one behind the other.  Layer i
             // of a cycle knows its dilation, its slots' places inside the cycle, which of layers i .. i+2 have their slots in LDS and its
             // register-set parity (CYC is even); per cycle only the bases advance.  Run-time, each at one place of the cycle: layer 0 of
@@ -2108,6 +2138,11 @@ __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_w
 template <bool F16, int R, int S, int A, int BT, bool EMBLDS, int CYC, int LD>
 __global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_wg_cs(const Params p) {
     wavenet_wg_body<F16, R, S, A, BT, EMBLDS, false, 0, true, CYC, LD>(p);
+}
+// ... and with the number of cycles compiled in as well (NC above): the sample's layers as straight-line code.  Again a kernel of its own name.
+template <bool F16, int R, int S, int A, int BT, bool EMBLDS, int CYC, int NC, int LD>
+__global__ __launch_bounds__((Cfg<F16, R, S, A, BT>::THREADS), 1) void wavenet_wg_sl(const Params p) {
+    wavenet_wg_body<F16, R, S, A, BT, EMBLDS, false, 0, true, CYC, LD, NC>(p);
 }
 
 // mu-law expansion of the generated indices to int16 PCM (pytorch/utils.py:62-70 +

@@ -84,7 +84,29 @@ def classify(op):
     return "other"
 
 
-def mix(inst, sub):
+def is_full_drain(op, args):
+    """a wait for the whole vector-memory queue: the youngest request with it"""
+    return op == "s_waitcnt" and re.search(r"vmcnt\(0\)", args) is not None
+
+
+def is_copy(op):
+    """register-to-register copies, either file: what the compiler places at joins (and constants: v_mov of an immediate counts too)"""
+    return re.match(r"v_accvgpr_(mov|read|write)|v_mov_b(32|64)", op) is not None
+
+
+def sample_loop(inst, sub):
+    """(full drains, copies, instructions) of the per-sample loop -- the largest loop body -- of every kernel whose demangled name
+    contains `sub`, by short name"""
+    out = {}
+    for name, lines, loops in kernels_of(inst, sub):
+        lo, hi = sorted(loops, key=lambda l: l[0] - l[1])[0]
+        body = lines[lo:hi + 1]
+        out[name.replace(" ", "")] = (sum(is_full_drain(op, args) for _, op, args, _ in body), sum(is_copy(op) for _, op, _, _ in body), len(body))
+    return out
+
+
+def kernels_of(inst, sub):
+    """[(short name, [(address, opcode, operands, branch target or None)], [(first index, last index) of every backward branch])]"""
     co = code_object(inst)
     dis = subprocess.run([LLVM + "llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
     blocks = re.split(r"\n(?=[0-9a-f]+ <)", dis)
@@ -94,22 +116,31 @@ def mix(inst, sub):
         if m:
             syms.append((m.group(1), b))
     dm = demangle([s for s, _ in syms])
-    hits = [(s, b) for s, b in syms if sub in dm[s]]
-    if not hits:
-        sys.exit("no kernel matches %r" % sub)
-    for s, body in hits:
-        lines = []          # (address, opcode, operands, branch target or None)
+    out = []
+    for s, body in syms:
+        if sub.replace(" ", "") not in dm[s].replace(" ", ""):
+            continue
+        lines = []
         for ln in body.split("\n")[1:]:
             m = re.match(r"\s+(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):\s*[0-9A-Fa-f ]+(?:<[^>+]+\+0x([0-9a-f]+)>)?", ln)
             if m:
                 lines.append((int(m.group(3), 16), m.group(1), m.group(2), int(m.group(4), 16) if m.group(4) else None))
         base = lines[0][0]
         addr_to_idx = {a: i for i, (a, _, _, _) in enumerate(lines)}
-        loops = []          # (first index, last index) of every backward branch
+        loops = []
         for i, (a, op, args, off) in enumerate(lines):
             if (op.startswith("s_cbranch") or op == "s_branch") and off is not None and base + off <= a and base + off in addr_to_idx:
                 loops.append((addr_to_idx[base + off], i))
-        print("== %s" % short(dm[s]))
+        out.append((short(dm[s]), lines, loops))
+    return out
+
+
+def mix(inst, sub):
+    hits = kernels_of(inst, sub)
+    if not hits:
+        sys.exit("no kernel matches %r" % sub)
+    for name, lines, loops in hits:
+        print("== %s" % name)
 
         def report(title, lo, hi, excl=(), scalar=False):
             idx = [i for i in range(lo, hi + 1) if not any(a <= i <= b for a, b in excl)]
@@ -118,6 +149,8 @@ def mix(inst, sub):
             valu = sum(v for k, v in cnt.items() if k in ("v_pk_f32", "v_pk_other", "trans", "accvgpr", "cndmask", "v_cvt", "dpp/perm", "valu_other"))
             print("  %s: %d instructions, VALU %d, MFMA %d, VALU:MFMA %.2f" % (title, tot, valu, cnt["mfma"], valu / max(1, cnt["mfma"])))
             print("   " + "  ".join("%s %d" % (k, cnt[k]) for k, _ in CLASSES if cnt[k]))
+            print("   full drains (s_waitcnt vmcnt(0)) %d  copies (v_accvgpr_mov/read/write, v_mov_b32/_b64) %d" %
+                  (sum(is_full_drain(lines[i][1], lines[i][2]) for i in idx), sum(is_copy(lines[i][1]) for i in idx)))
             if scalar:          # the scalar side by opcode (waits, s_nop and barriers are classes of their own above)
                 ops = collections.Counter(lines[i][1] for i in idx if lines[i][1].startswith("s_") and lines[i][1] not in ("s_waitcnt", "s_nop", "s_barrier"))
                 br = sum(v for k, v in ops.items() if "branch" in k)
