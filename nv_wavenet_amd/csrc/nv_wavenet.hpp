@@ -148,7 +148,7 @@ protected:
     bool m_clkOn;
 
     // sampling temperature per column (slots_sampler.hpp), lockstep and slot mode
-    wn::TemperatureTable m_temps;
+    wn::SamplingTable m_temps;
     wn::PrimeTable m_prime;           // the lockstep primes (slots_prime.hpp)
     wn::Score m_score;                // scratch and staging of scoreSamples (score.hpp), nothing until the first call
     wn::MelTime m_melTime;            // staging and feature rows of upsampleRequests / prefillStatesMel / scoreSamplesMel (mel_time.hpp), nothing until the first call
@@ -1248,23 +1248,11 @@ public:
     // offered: T = 2^-10 approaches it, but still draws between logits that tie at the maximum.  Synchronises.
     // false (nothing changes): in slot mode (slotSetTemperature is the call there), n outside the batch with a non-NULL T, or a
     // bad value.
-    bool setTemperatures(const float* T, int n) {
-        if (m_slots->active()) return false;
-        if (T != NULL) {
-            if (n < 1 || n > m_maxBatch) return false;
-            for (int b = 0; b < n; b++)
-                if (!wn::temperature_ok(T[b])) return false;
-        }
-        gpuErrChk(hipDeviceSynchronize());
-        m_temps.resetT();
-        for (int b = 0; T != NULL && b < n; b++) m_temps.set(b, T[b]);
-        m_temps.upload();
-        return true;
-    }
+    bool setTemperatures(const float* T, int n) { return setSampling(&wn::Sampling::temperature, T, n, wn::temperature_ok); }
     // the temperature in force for column b (1 when none was ever set)
-    float temperature(int b) const { return m_temps.get(b); }
+    float temperature(int b) const { return m_temps.get(b).temperature; }
     // Params::floorOn of a features-path launch: bit 0, a floor other than 0 is in force; bit 1, a tail cut (either has made the table)
-    int floorMask() const { return (m_temps.nonZero > 0 ? 1 : 0) | (m_temps.cutting() > 0 ? 2 : 0); }
+    int floorMask() const { return (m_temps.on[wn::kMinP] > 0 ? 1 : 0) | (m_temps.cutting() > 0 ? 2 : 0); }
 
     // ---- probability floor, min-p (beyond the reference; slots_sampler.hpp) ----------------------------------------
     // Column b of the runs that follow draws from its tempered distribution WITHOUT the bins whose probability is below minP[b] times
@@ -1273,21 +1261,9 @@ public:
     // setTemperatures: in force until the next call, a call between two chunks takes effect at the next chunk, only the features
     // path honours it and the other paths refuse while any floor is not 0; floor 0 is bit-identical to never having called this.
     // Synchronises.  false (nothing changes): in slot mode (slotSetMinP is the call there), n outside the batch, or a bad value.
-    bool setMinP(const float* minP, int n) {
-        if (m_slots->active()) return false;
-        if (minP != NULL) {
-            if (n < 1 || n > m_maxBatch) return false;
-            for (int b = 0; b < n; b++)
-                if (!wn::min_p_ok(minP[b])) return false;
-        }
-        gpuErrChk(hipDeviceSynchronize());
-        m_temps.resetP();
-        for (int b = 0; minP != NULL && b < n; b++) m_temps.setP(b, minP[b]);
-        m_temps.upload();
-        return true;
-    }
+    bool setMinP(const float* minP, int n) { return setSampling(&wn::Sampling::minP, minP, n, wn::min_p_ok); }
     // the floor in force for column b (0 when none was ever set)
-    float minP(int b) const { return m_temps.getP(b); }
+    float minP(int b) const { return m_temps.get(b).minP; }
 
     // ---- tail cuts, top-k and top-p (beyond the reference; slots_sampler.hpp) ---------------------------------------
     // Column b of the runs that follow draws from the topK[b] most probable bins of its tempered distribution (0: off), and from the
@@ -1298,34 +1274,33 @@ public:
     // these.  Synchronises.  false (nothing changes): in slot mode (slotSetTopK / slotSetTopP are the calls there), n outside the
     // batch, or a bad value.
     bool setTopK(const int* topK, int n) {
-        if (m_slots->active()) return false;
-        if (topK != NULL) {
-            if (n < 1 || n > m_maxBatch) return false;
-            for (int b = 0; b < n; b++)
-                if (!wn::top_k_ok(topK[b], A)) return false;
-        }
-        gpuErrChk(hipDeviceSynchronize());
-        m_temps.resetK();
-        for (int b = 0; topK != NULL && b < n; b++) m_temps.setK(b, topK[b]);
-        m_temps.upload();
-        return true;
+        return setSampling(&wn::Sampling::topK, topK, n, [](int k) { return wn::top_k_ok(k, A); });
     }
-    bool setTopP(const float* topP, int n) {
-        if (m_slots->active()) return false;
-        if (topP != NULL) {
-            if (n < 1 || n > m_maxBatch) return false;
-            for (int b = 0; b < n; b++)
-                if (!wn::top_p_ok(topP[b])) return false;
-        }
-        gpuErrChk(hipDeviceSynchronize());
-        m_temps.resetTopP();
-        for (int b = 0; topP != NULL && b < n; b++) m_temps.setTopP(b, topP[b]);
-        m_temps.upload();
-        return true;
-    }
+    bool setTopP(const float* topP, int n) { return setSampling(&wn::Sampling::topP, topP, n, wn::top_p_ok); }
     // the cuts in force for column b (0 and 1 when none was ever set)
-    int topK(int b) const { return m_temps.getK(b); }
-    float topP(int b) const { return m_temps.getTopP(b); }
+    int topK(int b) const { return m_temps.get(b).topK; }
+    float topP(int b) const { return m_temps.get(b).topP; }
+private:
+    // The four lockstep setters: every value is checked before anything changes, the other three kinds stay as they are.
+    template <class V, class Ok>
+    bool setSampling(V wn::Sampling::*field, const V* v, int n, Ok ok) {
+        if (m_slots->active()) return false;
+        if (v != NULL) {
+            if (n < 1 || n > m_maxBatch) return false;
+            for (int b = 0; b < n; b++)
+                if (!ok(v[b])) return false;
+        }
+        gpuErrChk(hipDeviceSynchronize());
+        m_temps.resetKind(field);
+        for (int b = 0; v != NULL && b < n; b++) {
+            wn::Sampling s = m_temps.get(b);
+            s.*field = v[b];
+            m_temps.set(b, s);
+        }
+        m_temps.upload();
+        return true;
+    }
+public:
 
     // ---- primed generation (beyond the reference; slots_prime.hpp) -------------------------------------------------
     // Column b < batch of the runs that follow starts with the forced samples y[b * stride + k], k < n[b] (0 <= n[b] <= maxN <=
@@ -1642,24 +1617,20 @@ public:
         assert(m_pcmUser == NULL || m_pcmUserElems == 0 || m_pcmUserElems >= (size_t)batch_size * num_samples);
         if (m_implementation == SINGLE_BLOCK) assert(S <= 4 * R);
         if (!m_supported) return false;
-        if (m_temps.nonUnit > 0 && !m_featPtr) {
-            // only the kernels that compute the conditioning from the features read the temperatures: nothing is generated rather than
-            // generated at T = 1
-            fprintf(stderr, "nvWavenetInfer: %d columns have a sampling temperature other than 1, which packed or in-place conditioning "
-                    "and multi-CU launches cannot honour: use the features path, or setTemperatures(NULL, 0)\n", m_temps.nonUnit);
-            return false;
-        }
-
-        if (m_temps.nonZero > 0 && !m_featPtr) {
-            fprintf(stderr, "nvWavenetInfer: %d columns have a probability floor (min-p) other than 0, which packed or in-place "
-                    "conditioning and multi-CU launches cannot honour: use the features path, or setMinP(NULL, 0)\n", m_temps.nonZero);
-            return false;
-        }
-
-        if (m_temps.cutting() > 0 && !m_featPtr) {
-            fprintf(stderr, "nvWavenetInfer: some columns have a tail cut (%d top-k, %d top-p), which packed or in-place conditioning "
-                    "and multi-CU launches cannot honour: use the features path, or setTopK(NULL, 0) and setTopP(NULL, 0)\n",
-                    m_temps.nonOffK, m_temps.nonOffP);
+        const int* const on = m_temps.on;
+        if (!m_featPtr && (on[wn::kTemperature] > 0 || on[wn::kMinP] > 0 || m_temps.cutting() > 0)) {
+            // only the kernels that compute the conditioning from the features read the table: nothing is generated rather than
+            // generated with the values off
+            if (on[wn::kTemperature] > 0)
+                fprintf(stderr, "nvWavenetInfer: %d columns have a sampling temperature other than 1, which packed or in-place conditioning "
+                        "and multi-CU launches cannot honour: use the features path, or setTemperatures(NULL, 0)\n", on[wn::kTemperature]);
+            else if (on[wn::kMinP] > 0)
+                fprintf(stderr, "nvWavenetInfer: %d columns have a probability floor (min-p) other than 0, which packed or in-place "
+                        "conditioning and multi-CU launches cannot honour: use the features path, or setMinP(NULL, 0)\n", on[wn::kMinP]);
+            else
+                fprintf(stderr, "nvWavenetInfer: some columns have a tail cut (%d top-k, %d top-p), which packed or in-place conditioning "
+                        "and multi-CU launches cannot honour: use the features path, or setTopK(NULL, 0) and setTopP(NULL, 0)\n",
+                        on[wn::kTopK], on[wn::kTopP]);
             return false;
         }
 

@@ -6,70 +6,42 @@
 
 namespace wn {
 
-TemperatureTable::~TemperatureTable() {
+SamplingTable::~SamplingTable() {
     if (softScale) gpuErrChk(hipFree(softScale));
 }
-void TemperatureTable::make() {
-    std::vector<float> unit(4 * (size_t)columns, 0.0f);
-    for (int b = 0; b < columns; b++) unit[b] = kSoftScaleUnit, unit[3 * (size_t)columns + b] = 1.0f;
-    gpuErrChk(hipMalloc(&softScale, unit.size() * sizeof(float)));
-    gpuErrChk(hipMemcpy(softScale, unit.data(), unit.size() * sizeof(float), hipMemcpyHostToDevice));
+void SamplingTable::make() {
+    gpuErrChk(hipMalloc(&softScale, kSamplingKinds * (size_t)columns * sizeof(float)));
+    upload();      // (the host's values before the one that makes the table: off in every column)
 }
-void TemperatureTable::set(int b, float t) {
-    if (T.empty()) {
-        if (t == 1.0f) return;
-        T.assign(columns, 1.0f);
+void SamplingTable::set(int b, const Sampling& s) {
+    const bool off = s == Sampling{};
+    if (rows.empty()) {
+        if (off) return;
+        rows.assign(columns, Sampling{});
     }
-    if (t != 1.0f && !softScale) make();
-    nonUnit += (t != 1.0f) - (T[b] != 1.0f);
-    T[b] = t;
+    if (!off && !softScale) make();
+    int now[kSamplingKinds], was[kSamplingKinds];
+    sampling_words(s, now);
+    sampling_words(rows[b], was);
+    for (int k = 0; k < kSamplingKinds; k++) on[k] += (now[k] != 0) - (was[k] != 0);
+    rows[b] = s;
 }
-void TemperatureTable::setP(int b, float p) {
-    if (P.empty()) {
-        if (p == 0.0f) return;
-        P.assign(columns, 0.0f);
-    }
-    if (p != 0.0f && !softScale) make();
-    nonZero += (p != 0.0f) - (P[b] != 0.0f);
-    P[b] = p;
-}
-void TemperatureTable::setK(int b, int k) {
-    if (K.empty()) {
-        if (k == 0) return;
-        K.assign(columns, 0);
-    }
-    if (k != 0 && !softScale) make();
-    nonOffK += (k != 0) - (K[b] != 0);
-    K[b] = k;
-}
-void TemperatureTable::setTopP(int b, float p) {
-    if (Q.empty()) {
-        if (p == 1.0f) return;
-        Q.assign(columns, 1.0f);
-    }
-    if (p != 1.0f && !softScale) make();
-    nonOffP += (p != 1.0f) - (Q[b] != 1.0f);
-    Q[b] = p;
-}
-void TemperatureTable::reset(bool deviceBehind) {
-    const bool rewrite = softScale && (nonUnit > 0 || nonZero > 0 || cutting() > 0 || deviceBehind);
-    resetT();
-    resetP();
-    resetK();
-    resetTopP();
+void SamplingTable::reset(bool deviceBehind) {
+    const bool rewrite = softScale && (on[kTemperature] > 0 || on[kMinP] > 0 || cutting() > 0 || deviceBehind);
+    rows.clear();
+    for (int& n : on) n = 0;
     if (rewrite) {
         gpuErrChk(hipDeviceSynchronize());
         upload();
     }
 }
-void TemperatureTable::upload() {
+void SamplingTable::upload() {
     if (!softScale) return;
-    std::vector<float> c(4 * (size_t)columns);
+    std::vector<float> c(kSamplingKinds * (size_t)columns);
     for (int b = 0; b < columns; b++) {
-        c[b] = temperature_scale(get(b));      // (T is empty when every value is 1, P when every floor is 0, K and Q when no cut)
-        c[columns + b] = getP(b);
-        c[2 * (size_t)columns + b] = top_k_entry(getK(b));
-        c[3 * (size_t)columns + b] = getTopP(b);
+        float entry[kSamplingKinds];
+        sampling_entries(get(b), entry);      // (rows is empty when every value is off)
+        for (int k = 0; k < kSamplingKinds; k++) c[k * (size_t)columns + b] = entry[k];
     }
     gpuErrChk(hipMemcpy(softScale, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
 }

@@ -94,48 +94,73 @@ inline float top_k_entry(int k) {
     return f;
 }
 
+// A column's sampling: the four values above, each off by default.  Their order here is the order of the kinds everywhere: kind i is
+// header word SlotStateHeader::pad[i] of a state blob and quarter i of the device table (entry i * columns + b for column b).
+struct Sampling {
+    float temperature = 1;
+    float minP = 0;
+    int topK = 0;
+    float topP = 1;
+};
+enum { kTemperature, kMinP, kTopK, kTopP, kSamplingKinds };
+inline bool operator==(const Sampling& a, const Sampling& b) {
+    return a.temperature == b.temperature && a.minP == b.minP && a.topK == b.topK && a.topP == b.topP;
+}
+inline bool sampling_ok(const Sampling& s, int A) {
+    return temperature_ok(s.temperature) && min_p_ok(s.minP) && top_k_ok(s.topK, A) && top_p_ok(s.topP);
+}
+// the four header words; a kind's word is zero exactly when the kind is off
+inline void sampling_words(const Sampling& s, int pad[4]) {
+    pad[kTemperature] = temperature_word(s.temperature);
+    pad[kMinP] = min_p_word(s.minP);
+    pad[kTopK] = top_k_word(s.topK);
+    pad[kTopP] = top_p_word(s.topP);
+}
+// false: one of the words is not valid (s holds what the valid ones say, off for the others)
+inline bool sampling_of_words(const int pad[4], int A, Sampling& s) {
+    const bool t = temperature_of_word(pad[kTemperature], s.temperature), p = min_p_of_word(pad[kMinP], s.minP);
+    const bool k = top_k_of_word(pad[kTopK], A, s.topK), q = top_p_of_word(pad[kTopP], s.topP);
+    return t && p && k && q;
+}
+// the four table entries
+inline void sampling_entries(const Sampling& s, float out[4]) {
+    out[kTemperature] = temperature_scale(s.temperature);
+    out[kMinP] = s.minP;
+    out[kTopK] = top_k_entry(s.topK);
+    out[kTopP] = s.topP;
+}
+
 // The table itself, lockstep and slot mode: the host's values are the authority, the device table follows them.  Nothing is
-// allocated, and Params::softScale stays NULL, until a temperature other than 1, a floor other than 0 or a cut has been set: an
-// engine that uses none of them launches what it launched before.  The device table is [4][columns]: the scales, the floors, top-k
-// (integers) and top-p.
-struct TemperatureTable {
-    explicit TemperatureTable(int columns) : columns(columns) {}
-    ~TemperatureTable();
-    TemperatureTable(const TemperatureTable&) = delete;      // (owns the device table)
-    // the temperature in force for column b (1 when none was ever set)
-    float get(int b) const { return (b >= 0 && b < (int)T.size()) ? T[b] : 1.0f; }
-    // the host's value of column b; the first value other than 1 makes the device table (filled with log2(e); synchronises)
-    void set(int b, float t);
-    // the floor in force for column b (0 when none was ever set); the first value other than 0 makes the device table likewise
-    float getP(int b) const { return (b >= 0 && b < (int)P.size()) ? P[b] : 0.0f; }
-    void setP(int b, float p);
-    // top-k and top-p in force for column b (0 and 1, off, when none was ever set); the first value that is not off makes the table
-    int getK(int b) const { return (b >= 0 && b < (int)K.size()) ? K[b] : 0; }
-    void setK(int b, int k);
-    float getTopP(int b) const { return (b >= 0 && b < (int)Q.size()) ? Q[b] : 1.0f; }
-    void setTopP(int b, float p);
+// allocated, and Params::softScale stays NULL, until a value that is not off has been set: an engine that uses none launches what
+// it launched before.  The device table is [4][columns]: the scales, the floors, top-k (integers) and top-p.
+struct SamplingTable {
+    explicit SamplingTable(int columns) : columns(columns) {}
+    ~SamplingTable();
+    SamplingTable(const SamplingTable&) = delete;      // (owns the device table)
+    // the values in force for column b (off when none was ever set)
+    Sampling get(int b) const { return (b >= 0 && b < (int)rows.size()) ? rows[b] : Sampling{}; }
+    // the host's values of column b; the first value that is not off makes the device table (filled with off; synchronises)
+    void set(int b, const Sampling& s);
     // columns with a cut in force
-    int cutting() const { return nonOffK + nonOffP; }
-    // every column back to T = 1, floor 0 and no cut, on the host and in the table (synchronises when the table has to be rewritten: a
-    // value other than these is in force, or deviceBehind -- the table holds values the host has since taken back)
+    int cutting() const { return on[kTopK] + on[kTopP]; }
+    // one value of every column back to off on the host (the caller uploads): the lockstep setters, each of which leaves the others' alone
+    template <class V>
+    void resetKind(V Sampling::*field) {
+        for (int b = 0; b < (int)rows.size(); b++) {
+            Sampling s = rows[b];
+            s.*field = Sampling{}.*field;
+            set(b, s);
+        }
+    }
+    // every column back to off, on the host and in the table (synchronises when the table has to be rewritten: a value that is not
+    // off is in force, or deviceBehind -- the table holds values the host has since taken back)
     void reset(bool deviceBehind);
-    // the host's temperatures / floors alone back to 1 / 0 (the caller uploads)
-    void resetT() { T.clear(), nonUnit = 0; }
-    void resetP() { P.clear(), nonZero = 0; }
-    void resetK() { K.clear(), nonOffK = 0; }
-    void resetTopP() { Q.clear(), nonOffP = 0; }
     // the whole table from the host's values, when it exists (blocking copy)
     void upload();
 
     const int columns;
-    std::vector<float> T;                   // [columns] T per column (empty: 1 everywhere)
-    int nonUnit = 0;                        // columns with T != 1
-    std::vector<float> P;                   // [columns] floor per column (empty: 0 everywhere)
-    int nonZero = 0;                        // columns with a floor != 0
-    std::vector<int> K;                     // [columns] top-k per column (empty: 0, off, everywhere)
-    int nonOffK = 0;                        // columns with top-k != 0
-    std::vector<float> Q;                   // [columns] top-p per column (empty: 1, off, everywhere)
-    int nonOffP = 0;                        // columns with top-p != 1
+    std::vector<Sampling> rows;             // [columns] (empty: off everywhere)
+    int on[kSamplingKinds] = {};            // per kind, the columns whose value is not off
     float* softScale = NULL;                // [4][columns] on the device, made at the first use: log2(e) / T, filled with log2(e); then
                                             // the floors, filled with 0; top-k as integers, filled with 0; top-p, filled with 1
 private:

@@ -39,11 +39,10 @@ SlotStateHeader headerCommon(const SlotFacts& f) {
     return h;
 }
 bool headerOk(const SlotFacts& f, const SlotStateHeader& h) {
-    float T, P, Q;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid floor; word 12: top-k,
-    int K;              // within the alphabet; word 13: zero, or the bits of a valid top-p)
+    Sampling s;      // (word 10: zero, or the bits of a valid temperature; word 11: zero, or the bits of a valid floor; word 12: top-k,
+                     // within the alphabet; word 13: zero, or the bits of a valid top-p)
     return h.magic == kSlotStateMagic && h.version == kSlotStateVersion && h.precision == (f.f16 ? 16 : 32) && h.R == f.R &&
-           h.numLayers == f.numLayers && h.maxDilation == f.maxDilation && h.done >= 0 && temperature_of_word(h.pad[0], T) &&
-           min_p_of_word(h.pad[1], P) && top_k_of_word(h.pad[2], f.A, K) && top_p_of_word(h.pad[3], Q);
+           h.numLayers == f.numLayers && h.maxDilation == f.maxDilation && h.done >= 0 && sampling_of_words(h.pad, f.A, s);
 }
 }  // namespace
 
@@ -77,7 +76,7 @@ void StageRing::release(hipStream_t stream) {
 }
 
 // ---- SlotSession ----
-SlotSession::SlotSession(const SlotFacts& facts, SlotHost& host, TemperatureTable& temps) : f(facts), m_host(host), m_temps(temps) {
+SlotSession::SlotSession(const SlotFacts& facts, SlotHost& host, SamplingTable& temps) : f(facts), m_host(host), m_temps(temps) {
     for (int l = 0, d = 1; l < f.numLayers; l++) {
         if (d > m_largestD) m_largestD = d;
         d <<= 1;
@@ -133,9 +132,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     d.precision = precision;
     d.active = 1;
     slotMarkPending(slot, 1);
-    slotTempSet(slot, 1.0f);
-    slotMinPSet(slot, 0.0f);
-    slotCutSet(slot, 0, 1.0f);
+    slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -146,8 +143,7 @@ bool SlotSession::stop(int slot) {
     m_slotHost[slot].active = 0;
     slotMarkPending(slot, 2);
     slotPrimeSet(slot, NULL, 0);
-    slotMinPSet(slot, 0.0f);      // (an idle column holds no floor: the launches go back to Params::floorOn = 0 with the last floored utterance)
-    slotCutSet(slot, 0, 1.0f);
+    slotSamplingSet(slot, Sampling{});      // (an idle column holds no value: the launches go back to Params::floorOn = 0 with the last floored or cutting utterance)
     return true;
 }
 bool SlotSession::startMel(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, unsigned uid) {
@@ -168,9 +164,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     m_melTilesDirty = true;
     m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
     slotMarkPending(slot, 1);
-    slotTempSet(slot, 1.0f);
-    slotMinPSet(slot, 0.0f);
-    slotCutSet(slot, 0, 1.0f);
+    slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
     return true;
 }
@@ -184,24 +178,24 @@ bool SlotSession::melFrames(int slot, int frames, int final) {
     return true;
 }
 bool SlotSession::setTemperature(int slot, float T) {
-    if (!inBatch(slot) || !slotHolds(slot) || !temperature_ok(T)) return false;
-    slotTempSet(slot, T);
-    return true;
+    Sampling s = m_temps.get(slot);
+    s.temperature = T;
+    return slotSamplingChange(slot, s);
 }
 bool SlotSession::setMinP(int slot, float p) {
-    if (!inBatch(slot) || !slotHolds(slot) || !min_p_ok(p)) return false;
-    slotMinPSet(slot, p);
-    return true;
+    Sampling s = m_temps.get(slot);
+    s.minP = p;
+    return slotSamplingChange(slot, s);
 }
 bool SlotSession::setTopK(int slot, int k) {
-    if (!inBatch(slot) || !slotHolds(slot) || !top_k_ok(k, f.A)) return false;
-    slotCutSet(slot, k, m_temps.getTopP(slot));
-    return true;
+    Sampling s = m_temps.get(slot);
+    s.topK = k;
+    return slotSamplingChange(slot, s);
 }
 bool SlotSession::setTopP(int slot, float p) {
-    if (!inBatch(slot) || !slotHolds(slot) || !top_p_ok(p)) return false;
-    slotCutSet(slot, m_temps.getK(slot), p);
-    return true;
+    Sampling s = m_temps.get(slot);
+    s.topP = p;
+    return slotSamplingChange(slot, s);
 }
 bool SlotSession::prime(int slot, const int* y, int n) {
     if (!inBatch(slot) || m_slotPending[slot] != 1 || y == NULL || n < 1 || !is_device_ptr(y)) return false;
@@ -226,11 +220,8 @@ bool SlotSession::move(int from, int to) {
     m_slotMoveEnd[from] = 1;
     m_slotMoveEnd[to] = 2;
     m_slotMoves.push_back(SlotMove{from, to});
-    slotTempSet(to, m_temps.get(from));
-    slotMinPSet(to, m_temps.getP(from));
-    slotMinPSet(from, 0.0f);      // (as stop())
-    slotCutSet(to, m_temps.getK(from), m_temps.getTopP(from));
-    slotCutSet(from, 0, 1.0f);
+    slotSamplingSet(to, m_temps.get(from));
+    slotSamplingSet(from, Sampling{});      // (as stop())
     if (primed(from)) {
         slotPrimeSet(to, m_primeY[from], m_primeN[from]);
         slotPrimeSet(from, NULL, 0);
@@ -247,10 +238,7 @@ int SlotSession::save(int slot, void* dst, hipStream_t stream) {
     SlotStateHeader h = headerCommon(f);
     h.done = (int)done;
     h.uid = mel ? m_melHost[slot].uid : m_slotHost[slot].uid;
-    h.pad[0] = temperature_word(m_temps.get(slot));
-    h.pad[1] = min_p_word(m_temps.getP(slot));
-    h.pad[2] = top_k_word(m_temps.getK(slot));
-    h.pad[3] = top_p_word(m_temps.getTopP(slot));
+    sampling_words(m_temps.get(slot), h.pad);
     if (!slots_save(stream, dst, h, slot, slotRotation(start), slotLayers(), f.ring, f.ringSlots, f.ringFragsPerSlot, f.yInPrev, f.yInCur))
         return -1;
     return (int)done;
@@ -302,8 +290,10 @@ int SlotSession::saveList(const int* slots, int n, void* dst, long long stride, 
         const long long start = mel ? m_melHost[b].start : m_slotHost[b].start;
         const unsigned uid = mel ? m_melHost[b].uid : m_slotHost[b].uid;
         const int done = (int)(m_slotCounter - start);
-        stage[i] = SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, temperature_word(m_temps.get(b)), min_p_word(m_temps.getP(b))};
-        cutStage[i] = SlotSaveCut{top_k_word(m_temps.getK(b)), top_p_word(m_temps.getTopP(b))};
+        int w[kSamplingKinds];
+        sampling_words(m_temps.get(b), w);
+        stage[i] = SlotSave{out + (size_t)i * (size_t)stride, b, slotRotation(start), done, uid, w[kTemperature], w[kMinP]};
+        cutStage[i] = SlotSaveCut{w[kTopK], w[kTopP]};
         anyCut = anyCut || cutStage[i].x != 0 || cutStage[i].y != 0;
         saved[i] = SlotSaved{b, uid, done, mel ? 1 : 0};
     }
@@ -691,27 +681,15 @@ bool SlotSession::slotApplyPending(hipStream_t stream) {
                         f.yInPrev, f.yInCur) && ok;
     return ok;
 }
-// ---- sampling temperature (slots_sampler.hpp): the next step writes the column's table entry when the value changes ----
-void SlotSession::slotTempSet(int slot, float T) {
-    if (m_temps.get(slot) == T) return;
-    m_temps.set(slot, T);
-    if (m_tempDirty.empty()) m_tempDirty.assign(f.maxBatch, 0);
-    if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
-    m_tempDirty[slot] = 1;
+// ---- a column's sampling (slots_sampler.hpp): the next step writes the column's four table entries when a value changes ----
+bool SlotSession::slotSamplingChange(int slot, const Sampling& s) {
+    if (!inBatch(slot) || !slotHolds(slot) || !sampling_ok(s, f.A)) return false;
+    slotSamplingSet(slot, s);
+    return true;
 }
-// ... and the probability floor: the same list, a changed column's two table entries are written together
-void SlotSession::slotMinPSet(int slot, float p) {
-    if (m_temps.getP(slot) == p) return;
-    m_temps.setP(slot, p);
-    if (m_tempDirty.empty()) m_tempDirty.assign(f.maxBatch, 0);
-    if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
-    m_tempDirty[slot] = 1;
-}
-// ... and the tail cuts (top-k, top-p): the same list, a changed column's four table entries are written together
-void SlotSession::slotCutSet(int slot, int k, float p) {
-    if (m_temps.getK(slot) == k && m_temps.getTopP(slot) == p) return;
-    m_temps.setK(slot, k);
-    m_temps.setTopP(slot, p);
+void SlotSession::slotSamplingSet(int slot, const Sampling& s) {
+    if (m_temps.get(slot) == s) return;
+    m_temps.set(slot, s);
     if (m_tempDirty.empty()) m_tempDirty.assign(f.maxBatch, 0);
     if (!m_tempDirty[slot]) m_tempDirtyList.push_back(slot);
     m_tempDirty[slot] = 1;
@@ -721,15 +699,11 @@ void SlotSession::slotSetResume(int slot, const void* state, const SlotStateHead
     slotLayers();
     m_slotResume[slot] = state;
     m_slotResumeDone[slot] = h.done;
-    float T = 1.0f, P = 0.0f, Q = 1.0f;
-    int K = 0;
-    const bool ok = temperature_of_word(h.pad[0], T) && min_p_of_word(h.pad[1], P) && top_k_of_word(h.pad[2], f.A, K) &&
-                    top_p_of_word(h.pad[3], Q);      // (headerOk has checked them)
+    Sampling s;
+    const bool ok = sampling_of_words(h.pad, f.A, s);      // (headerOk has checked them)
     assert(ok);
     (void)ok;
-    slotTempSet(slot, T);
-    slotMinPSet(slot, P);
-    slotCutSet(slot, K, Q);
+    slotSamplingSet(slot, s);
 }
 // the changed columns -> pinned staging -> device, then one slot_scale_kernel launch (staging halves as slotApplyPending, made
 // by the first step that needs them)
@@ -746,10 +720,9 @@ bool SlotSession::slotApplyTemperatures(hipStream_t stream) {
     SlotScale* const stage = (SlotScale*)m_scaleStage.acquire();
     int n = 0;
     for (int b : m_tempDirtyList) {
-        stage[n++] = SlotScale{b, temperature_scale(m_temps.get(b))};
-        stage[n++] = SlotScale{f.maxBatch + b, m_temps.getP(b)};
-        stage[n++] = SlotScale{2 * f.maxBatch + b, top_k_entry(m_temps.getK(b))};
-        stage[n++] = SlotScale{3 * f.maxBatch + b, m_temps.getTopP(b)};
+        float entry[kSamplingKinds];
+        sampling_entries(m_temps.get(b), entry);
+        for (int k = 0; k < kSamplingKinds; k++) stage[n++] = SlotScale{k * f.maxBatch + b, entry[k]};
         m_tempDirty[b] = 0;
     }
     m_tempDirtyList.clear();

@@ -78,7 +78,7 @@ private:
 
 class SlotSession {
 public:
-    SlotSession(const SlotFacts& facts, SlotHost& host, TemperatureTable& temps);
+    SlotSession(const SlotFacts& facts, SlotHost& host, SamplingTable& temps);
     ~SlotSession();
 
     // ---- slot mode: continuous batching (slots.hpp; DESIGN.md "Slot mode") ------------------------------------------------------
@@ -100,7 +100,7 @@ public:
     // non-positive strides or length; or the column is the destination of a pending move (the start would silently drop the
     // utterance on its way in: stop it, or step first).
     bool start(int slot, const void* x, int precision, long long cStride, long long tStride, int length, unsigned uid);
-    // Column `slot` goes idle at the next step (its features are no longer read from then on).
+    // Column `slot` goes idle at the next step (its features are no longer read from then on); its sampling values go back to off.
     bool stop(int slot);
     // Column `slot` takes a mel utterance at the next step: its frames mel[c * cStride + f * fStride] (device memory,
     // `precision`-bit floats, n_cond channels; kept alive while the column runs), `frames` of them available so far, final != 0: no
@@ -121,14 +121,14 @@ public:
     // utterance and has no pending start or resume, or a bad value.
     bool setTemperature(int slot, float T);
     // the host's value for column `slot`; 0 when it holds no utterance (or outside slot mode, or outside the batch)
-    float temperature(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot) : 0.f; }
+    float temperature(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot).temperature : 0.f; }
     // The utterance of column `slot` draws without the bins whose tempered probability is below p times that of the most probable
     // bin (min-p), from the next step on, from that step's first sample; p as for setMinP.  Everything else as
     // setTemperature: starts put the column back to 0, moves, saves and resumes carry the value (SlotStateHeader::pad[1]), and the
     // step's one small launch writes the changed floors with the changed scales.  false (nothing changes): as setTemperature.
     bool setMinP(int slot, float p);
     // the host's value for column `slot`; -1 when it holds no utterance (0 is a valid floor)
-    float minP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getP(slot) : -1.f; }
+    float minP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot).minP : -1.f; }
     // The utterance of column `slot` draws from the k most probable bins of its tempered distribution (top-k; 0: off), or from the
     // smallest set of most probable bins whose mass reaches p (top-p; 1: off), ties at either boundary included, from
     // the next step on; the cuts and the floor intersect.  Everything else as setMinP: starts put the column back to off, moves, saves
@@ -137,8 +137,8 @@ public:
     bool setTopK(int slot, int k);
     bool setTopP(int slot, float p);
     // the host's values for column `slot`; -1 when it holds no utterance
-    int topK(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getK(slot) : -1; }
-    float topP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.getTopP(slot) : -1.f; }
+    int topK(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot).topK : -1; }
+    float topP(int slot) const { return inBatch(slot) && slotHolds(slot) ? m_temps.get(slot).topP : -1.f; }
     // ---- primed generation (slots_prime.hpp) ----
     // The utterance whose start or resume is pending on column `slot` carries the prime y[0 .. n) (device memory, int32; kept alive and
     // unchanged until local sample n has been generated): its local samples k < n are y[k], clamped into the alphabet, delivered and
@@ -239,7 +239,7 @@ private:
     const SlotFacts f;
     SlotHost& m_host;
     int m_largestD = 1;
-    TemperatureTable& m_temps;              // the engine's (slots_sampler.hpp), shared with lockstep setTemperatures
+    SamplingTable& m_temps;                 // the engine's (slots_sampler.hpp), shared with lockstep setTemperatures
 
     int m_slotW = 0;                        // window (samples); 0: not in slot mode
     long long m_slotCounter = 0;            // samples generated since slotsBegin: window row of the next step = counter mod W
@@ -333,9 +333,8 @@ private:
     bool slotApplyMoves(hipStream_t stream);
     void slotMarkPending(int slot, int what);
     bool slotApplyPending(hipStream_t stream);
-    void slotTempSet(int slot, float T);
-    void slotMinPSet(int slot, float p);
-    void slotCutSet(int slot, int k, float p);
+    bool slotSamplingChange(int slot, const Sampling& s);      // (the public setters: checked)
+    void slotSamplingSet(int slot, const Sampling& s);
     void slotSetResume(int slot, const void* state, const SlotStateHeader& h);
     bool slotApplyTemperatures(hipStream_t stream);
     void slotPrimeSet(int slot, const int* y, int n);

@@ -596,6 +596,29 @@ class WavenetEngine:
         lib.nvw_slots_end(self._h)
         self._slot_keep = {}
 
+    # ---- a column's sampling: one helper behind the lockstep setters, one behind the slot setters, one behind the slot getters ----
+    def _set_sampling(self, symbol, values, integer=False):
+        """values: None (every column off), a scalar of any kind, a 0-d array or tensor (every column), or 1..maxBatch values (the
+        columns past them off); integer: whole numbers that fit 32 bits only.  ValueError when refused (nothing changes)."""
+        if values is None:
+            ok = getattr(lib, symbol)(self._h, None, 0)
+        else:
+            dtype = np.int32 if integer else np.float32
+            a = np.asarray(values, dtype=None if integer else dtype)
+            if integer and (a.dtype.kind not in "iu" or np.any(a != a.astype(dtype))):
+                raise ValueError("%s refused %r" % (symbol, values))
+            t = np.ascontiguousarray(np.full(self.maxBatch, a, dtype=dtype) if a.ndim == 0 else a.astype(dtype).reshape(-1))
+            ok = getattr(lib, symbol)(self._h, t.ctypes.data, int(t.size))
+        if not ok:
+            raise ValueError("%s refused %r" % (symbol, values))
+
+    def _slot_set_sampling(self, symbol, slot, value, name, cast=float):
+        if not getattr(lib, symbol)(self._h, int(slot), cast(value)):
+            raise ValueError("%s refused slot %d, %s = %r" % (symbol, slot, name, value))
+
+    def _slot_sampling(self, symbol, slot, cast=float):
+        return cast(getattr(lib, symbol)(self._h, int(slot)))
+
     # ---- sampling temperature per utterance (include/nv_wavenet_c.h, "SAMPLING TEMPERATURE"; DESIGN.md §6g) ----
     def setTemperatures(self, T=None):
         """Lockstep: column b of the features-path runs that follow samples from softmax(logits / T[b]).  T: None (every column at
@@ -603,23 +626,16 @@ class WavenetEngine:
         [2^-10, 2^10].  In force until the next call; a call between two chunks takes effect at the next chunk.  While any
         column's T is not 1, runs on packed or in-place conditioning and on chain engines return False.  ValueError when refused
         (nothing changes)."""
-        if T is None:
-            ok = lib.nvw_set_temperatures(self._h, None, 0)
-        else:
-            t = np.ascontiguousarray(np.full(self.maxBatch, T, dtype=np.float32) if np.isscalar(T) else np.asarray(T, dtype=np.float32).reshape(-1))
-            ok = lib.nvw_set_temperatures(self._h, t.ctypes.data, int(t.size))
-        if not ok:
-            raise ValueError("nvw_set_temperatures refused %r" % (T,))
+        self._set_sampling("nvw_set_temperatures", T)
 
     def slotSetTemperature(self, slot, T):
         """Slot mode: the utterance of column `slot` samples at temperature T from the next step on (after slotStart / slotResume,
         which put the column back to 1 / to the blob's value).  ValueError when refused (nothing changes)."""
-        if not lib.nvw_slot_set_temperature(self._h, int(slot), float(T)):
-            raise ValueError("nvw_slot_set_temperature refused slot %d, T = %r" % (slot, T))
+        self._slot_set_sampling("nvw_slot_set_temperature", slot, T, "T")
 
     def slotTemperature(self, slot):
         """The temperature in force for column `slot` (host state); 0.0 when the column holds no utterance."""
-        return float(lib.nvw_slot_temperature(self._h, int(slot)))
+        return self._slot_sampling("nvw_slot_temperature", slot)
 
     # ---- probability floor (min-p) per utterance (include/nv_wavenet_c.h, "PROBABILITY FLOOR"; DESIGN.md §6m) ----
     def setMinP(self, p=None):
@@ -628,23 +644,16 @@ class WavenetEngine:
         sequence of 1..maxBatch floats (the columns past it at 0), each finite and in [0, 0.5].  In force until the next call; a
         call between two chunks takes effect at the next chunk.  While any column's floor is not 0, runs on packed or in-place
         conditioning and on chain engines return False.  ValueError when refused (nothing changes)."""
-        if p is None:
-            ok = lib.nvw_set_min_p(self._h, None, 0)
-        else:
-            t = np.ascontiguousarray(np.full(self.maxBatch, p, dtype=np.float32) if np.isscalar(p) else np.asarray(p, dtype=np.float32).reshape(-1))
-            ok = lib.nvw_set_min_p(self._h, t.ctypes.data, int(t.size))
-        if not ok:
-            raise ValueError("nvw_set_min_p refused %r" % (p,))
+        self._set_sampling("nvw_set_min_p", p)
 
     def slotSetMinP(self, slot, p):
         """Slot mode: the utterance of column `slot` draws with floor p from the next step on (after slotStart / slotResume, which
         put the column back to 0 / to the blob's value).  ValueError when refused (nothing changes)."""
-        if not lib.nvw_slot_set_min_p(self._h, int(slot), float(p)):
-            raise ValueError("nvw_slot_set_min_p refused slot %d, p = %r" % (slot, p))
+        self._slot_set_sampling("nvw_slot_set_min_p", slot, p, "p")
 
     def slotMinP(self, slot):
         """The floor in force for column `slot` (host state); -1.0 when the column holds no utterance (0 is a valid floor)."""
-        return float(lib.nvw_slot_min_p(self._h, int(slot)))
+        return self._slot_sampling("nvw_slot_min_p", slot)
 
     # ---- tail cuts, top-k and top-p, per utterance (include/nv_wavenet_c.h, "TAIL CUTS"; DESIGN.md §6n) ----
     def setTopK(self, k=None):
@@ -654,48 +663,32 @@ class WavenetEngine:
         independent of setTemperatures, setMinP and setTopP; the kept set is the intersection of the cuts and the floor.  While any
         column has a cut, runs on packed or in-place conditioning and on chain engines return False.  ValueError when refused
         (nothing changes)."""
-        if k is None:
-            ok = lib.nvw_set_top_k(self._h, None, 0)
-        else:
-            a = np.asarray(k)
-            if a.dtype.kind not in "iu" or np.any(a != a.astype(np.int32)):
-                raise ValueError("nvw_set_top_k refused %r" % (k,))
-            t = np.ascontiguousarray(np.full(self.maxBatch, int(a), dtype=np.int32) if a.ndim == 0 else a.astype(np.int32).reshape(-1))
-            ok = lib.nvw_set_top_k(self._h, t.ctypes.data, int(t.size))
-        if not ok:
-            raise ValueError("nvw_set_top_k refused %r" % (k,))
+        self._set_sampling("nvw_set_top_k", k, integer=True)
 
     def setTopP(self, p=None):
         """Lockstep: column b draws from the smallest set of most probable bins of its tempered distribution whose mass reaches
         p[b], ties at its edge included.  p: None (every column off), a float (every column), or a sequence of 1..maxBatch floats
         (the columns past it off), each finite and in (0, 1]; 1 is off.  Everything else as setTopK."""
-        if p is None:
-            ok = lib.nvw_set_top_p(self._h, None, 0)
-        else:
-            a = np.asarray(p, dtype=np.float32)      # (a scalar of any kind, a 0-d array or tensor: every column)
-            t = np.ascontiguousarray(np.full(self.maxBatch, a, dtype=np.float32) if a.ndim == 0 else a.reshape(-1))
-            ok = lib.nvw_set_top_p(self._h, t.ctypes.data, int(t.size))
-        if not ok:
-            raise ValueError("nvw_set_top_p refused %r" % (p,))
+        self._set_sampling("nvw_set_top_p", p)
 
     def slotSetTopK(self, slot, k):
         """Slot mode: the utterance of column `slot` draws with top-k = k from the next step on (after slotStart / slotResume, which
         put the column back to off / to the blob's value).  ValueError when refused (nothing changes)."""
-        if int(k) != k or not -2**31 <= int(k) < 2**31 or not lib.nvw_slot_set_top_k(self._h, int(slot), int(k)):
+        if int(k) != k or not -2**31 <= int(k) < 2**31:
             raise ValueError("nvw_slot_set_top_k refused slot %d, k = %r" % (slot, k))
+        self._slot_set_sampling("nvw_slot_set_top_k", slot, k, "k", int)
 
     def slotSetTopP(self, slot, p):
         """Slot mode: likewise with top-p = p."""
-        if not lib.nvw_slot_set_top_p(self._h, int(slot), float(p)):
-            raise ValueError("nvw_slot_set_top_p refused slot %d, p = %r" % (slot, p))
+        self._slot_set_sampling("nvw_slot_set_top_p", slot, p, "p")
 
     def slotTopK(self, slot):
         """Top-k in force for column `slot` (host state); -1 when the column holds no utterance."""
-        return int(lib.nvw_slot_top_k(self._h, int(slot)))
+        return self._slot_sampling("nvw_slot_top_k", slot, int)
 
     def slotTopP(self, slot):
         """Top-p in force for column `slot` (host state); -1.0 when the column holds no utterance."""
-        return float(lib.nvw_slot_top_p(self._h, int(slot)))
+        return self._slot_sampling("nvw_slot_top_p", slot)
 
     def samplerMask(self):
         """What the next features-path launch pays for (host state): bit 0, some column's floor is not 0; bit 1, some column has a

@@ -499,22 +499,18 @@ class NVWaveNetEngine(NVWaveNet):
         smallest set of most probable bins whose mass reaches top_p[b] (ValueError otherwise).  The cuts and the
         floor intersect; each is defined on the tempered distribution."""
         batch_size, sample_count = x.size(0), x.size(2)
-        if top_k is not None and not (isinstance(top_k, (int, float)) or getattr(top_k, "ndim", None) == 0):      # (a scalar: every column)
-            top_k = list(top_k)
-            if len(top_k) != batch_size:
-                raise ValueError("%d top-k values for a batch of %d" % (len(top_k), batch_size))
-        if top_p is not None and (isinstance(top_p, (int, float)) or getattr(top_p, "ndim", None) == 0):
-            top_p = float(top_p)
-        elif top_p is not None:
-            top_p = [float(p) for p in top_p]
-            if len(top_p) != batch_size:
-                raise ValueError("%d top-p values for a batch of %d" % (len(top_p), batch_size))
-        if min_p is not None and (isinstance(min_p, (int, float)) or getattr(min_p, "ndim", None) == 0):
-            min_p = float(min_p)      # (a Python or numpy scalar, a 0-d array or tensor: every column)
-        elif min_p is not None:
-            min_p = [float(p) for p in min_p]
-            if len(min_p) != batch_size:
-                raise ValueError("%d probability floors for a batch of %d" % (len(min_p), batch_size))
+        def per_utterance(value, what, cast=float):
+            """None, a scalar (a Python or numpy scalar, a 0-d array or tensor: every column) or `batch` values"""
+            if value is None or isinstance(value, (int, float)) or getattr(value, "ndim", None) == 0:
+                return value if value is None else cast(value)
+            value = [cast(v) for v in value]
+            if len(value) != batch_size:
+                raise ValueError("%d %s for a batch of %d" % (len(value), what, batch_size))
+            return value
+
+        sampling = [("setTemperatures", per_utterance(temperature, "temperatures")), ("setMinP", per_utterance(min_p, "probability floors")),
+                    ("setTopK", per_utterance(top_k, "top-k values", lambda k: k)), ("setTopP", per_utterance(top_p, "top-p values"))]
+        sampling = [(setter, value) for setter, value in sampling if value is not None]
         if prime is not None:
             if prime.dim() != 2 or prime.size(0) != batch_size or not 0 < prime.size(1) <= sample_count or prime.is_floating_point():
                 raise ValueError("prime: an integer tensor [batch = %d][1 .. %d], got %s" % (batch_size, sample_count, tuple(prime.shape)))
@@ -526,10 +522,6 @@ class NVWaveNetEngine(NVWaveNet):
                 raise ValueError("prime: values in 0 .. %d" % (self.A - 1))
         elif prime_lengths is not None:
             raise ValueError("prime_lengths without a prime")
-        if temperature is not None and not isinstance(temperature, (int, float)):
-            temperature = [float(t) for t in temperature]
-            if len(temperature) != batch_size:
-                raise ValueError("%d temperatures for a batch of %d" % (len(temperature), batch_size))
         e = self._engine(batch_size, sample_count, implementation)
         dev = x.device
         key = (cond_weight.data_ptr(), cond_weight._version, cond_bias.data_ptr(), cond_bias._version)
@@ -539,26 +531,15 @@ class NVWaveNetEngine(NVWaveNet):
         stream = torch.cuda.current_stream(dev)
         stream.synchronize()
         e.setFeatures(x, sample_count)
-        e.setTemperatures(temperature)
         try:
-            if min_p is not None:
-                e.setMinP(min_p)
-            if top_k is not None:
-                e.setTopK(top_k)
-            if top_p is not None:
-                e.setTopP(top_p)
+            for setter, value in sampling:
+                getattr(e, setter)(value)
             if prime is not None:
                 e.setPrime(prime.to(device=dev, dtype=torch.int32).contiguous(), prime_lengths)
             return self._generate(e, dev, stream, sample_count, batch_size, seed, return_audio, generator)
         finally:
-            if temperature is not None:
-                e.setTemperatures(None)      # (the engine is shared with infer(), whose kernels refuse to run at another temperature)
-            if min_p is not None:
-                e.setMinP(None)              # (... or with a floor)
-            if top_k is not None:
-                e.setTopK(None)              # (... or with a cut)
-            if top_p is not None:
-                e.setTopP(None)
+            for setter, value in sampling:
+                getattr(e, setter)(None)     # (the engine is shared with infer(), whose kernels refuse to run with a value that is not off)
             if prime is not None:
                 e.setPrime(None)             # (... or while a column is primed)
 

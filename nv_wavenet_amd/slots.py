@@ -106,7 +106,7 @@ start or end in it.  Two steps may be pending: the GPU generates step k + 1 whil
 """
 import heapq
 import struct
-from collections import deque
+from collections import deque, namedtuple
 
 import numpy as np
 
@@ -154,6 +154,19 @@ def check_top_p(p):
     if not (0.0 < t <= 1.0):      # (a NaN fails both comparisons)
         raise ValueError("top_p %r: finite and in (0, 1]" % (p,))
     return t
+
+
+# A request's sampling: the four values, and what each is when it is off.  The order of the fields is the order of the kinds in the
+# engine: words 10 to 13 of a blob's header.
+Sampling = namedtuple("Sampling", "temperature min_p top_k top_p")
+OFF = Sampling(1.0, 0.0, 0, 1.0)
+_SLOT_SETTERS = Sampling("slotSetTemperature", "slotSetMinP", "slotSetTopK", "slotSetTopP")      # of WavenetEngine, per field
+
+
+def check_sampling(temperature=1.0, min_p=0.0, top_k=0, top_p=1.0, A=None):
+    """The four values as the engine takes them, as a Sampling (check_temperature, check_min_p, check_top_k, check_top_p); ValueError
+    otherwise."""
+    return Sampling(check_temperature(temperature), check_min_p(min_p), check_top_k(top_k, A), check_top_p(top_p))
 
 
 def cut_rows(rows, top_k=0, top_p=1.0, min_p=0.0):
@@ -275,6 +288,9 @@ class SlotState:
     MIN_P_WORD = 11                          # word 11 the probability floor likewise (zero: 0.0)
     TOP_K_WORD = 12                          # word 12 top-k, the integer (zero: off)
     TOP_P_WORD = 13                          # word 13 top-p as the bits of the float (zero: 1.0, off)
+    # per field of Sampling: (word, off value, the bits of a float32 or the integer itself)
+    SAMPLING_WORDS = Sampling((TEMPERATURE_WORD, OFF.temperature, True), (MIN_P_WORD, OFF.min_p, True), (TOP_K_WORD, OFF.top_k, False),
+                              (TOP_P_WORD, OFF.top_p, True))
     # to_bytes() of a state with done < n of its prime: behind the blob this record, then the n - done values y[done .. n) (int32)
     PRIME = struct.Struct("<4sII")           # magic, first (= done), count (= n - done)
     PRIME_MAGIC = b"NWSP"
@@ -282,16 +298,22 @@ class SlotState:
     def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0,
                  top_k=0, top_p=1.0):
         self.prime = check_prime(prime)
-        self.min_p = check_min_p(min_p)
-        self.top_k, self.top_p = check_top_k(top_k), check_top_p(top_p)
-        self._blob_cut = (self.top_k, self.top_p) if blob is not None else (0, 1.0)      # (words 12 and 13 as the engine will read them)
-        self._blob_min_p = self.min_p if blob is not None else 0.0                  # (word 11 of the blob as the engine will read it)
+        self.temperature, self.min_p, self.top_k, self.top_p = check_sampling(temperature, min_p, top_k, top_p)
+        self._blob_sampling = self.sampling() if blob is not None else OFF      # (what the engine reads from the header on resume)
         self.blob, self.source, self.uid, self.done, self.kind, self.frames, self.final = blob, source, uid, done, kind, frames, final
-        self.temperature = check_temperature(temperature)
-        self._blob_temperature = self.temperature if blob is not None else 1.0      # (what the engine reads from the header on resume)
         # the blob as a row of a buffer that SlotStream hands to slotsResumeList (suspend_many, drain, from_bytes(pinned=True));
         # None: a blob of its own -- a CUDA tensor of suspend(), resumed by slotResume, or a CPU tensor of from_bytes(), uploaded
         self.buffer, self.row = buffer, row
+
+    def sampling(self, A=None):
+        """The four attributes as a Sampling, checked (top_k against the alphabet A where it is known); ValueError otherwise."""
+        return check_sampling(self.temperature, self.min_p, self.top_k, self.top_p, A)
+
+    @classmethod
+    def _header_words(cls, s):
+        """(word, its value) for every field of the Sampling s: zero for a value that is off"""
+        return [(word, 0 if v == off else int(np.array([v], dtype="<f4").view("<u4")[0]) if is_float else v)
+                for (word, off, is_float), v in zip(cls.SAMPLING_WORDS, s)]
 
     def to_bytes(self):
         """The state as bytes: RECORD (kind, frames, final, uid, done, the blob's size or 0) followed by the blob.  The source
@@ -303,17 +325,12 @@ class SlotState:
         still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
         what they were before primes existed."""
         blob = b""
-        min_p = check_min_p(self.min_p)
-        floor_word = np.array([min_p], dtype="<f4").view("<u4")[0] if min_p != 0.0 else 0
-        top_k, top_p = check_top_k(self.top_k), check_top_p(self.top_p)
-        top_p_word = np.array([top_p], dtype="<f4").view("<u4")[0] if top_p != 1.0 else 0
-        if self.blob is None and (self.temperature != 1.0 or min_p != 0.0 or top_k != 0 or top_p != 1.0):
+        s = self.sampling()
+        if self.blob is None and s != OFF:
             hdr = np.zeros(16, dtype="<u4")
             hdr[0], hdr[1], hdr[7] = self.BLOB_MAGIC, 1, int(self.uid) & 0xFFFFFFFF
-            if self.temperature != 1.0:
-                hdr[self.TEMPERATURE_WORD] = np.array([self.temperature], dtype="<f4").view("<u4")[0]
-            hdr[self.MIN_P_WORD] = floor_word
-            hdr[self.TOP_K_WORD], hdr[self.TOP_P_WORD] = top_k, top_p_word
+            for word, value in self._header_words(s):
+                hdr[word] = value
             blob = hdr.tobytes()
         if self.blob is not None:
             if getattr(self.blob, "is_cuda", False):
@@ -323,10 +340,10 @@ class SlotState:
                     import torch
                     torch.cuda.synchronize()
                 blob = self.blob.numpy().tobytes()
-            if min_p != self._blob_min_p or (top_k, top_p) != self._blob_cut:
+            if s[1:] != self._blob_sampling[1:]:      # (word 10 is always the engine's or the pass's own)
                 words = np.frombuffer(blob, dtype="<u4").copy()
-                words[self.MIN_P_WORD] = floor_word
-                words[self.TOP_K_WORD], words[self.TOP_P_WORD] = top_k, top_p_word
+                for word, value in self._header_words(s)[1:]:
+                    words[word] = value
                 blob = words.tobytes()
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
@@ -361,27 +378,26 @@ class SlotState:
         if tail != 0 or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
-        temperature, min_p, top_k, top_p = 1.0, 0.0, 0, 1.0
+        values = list(OFF)
         if nblob:
             words = np.frombuffer(data, dtype="<u4", count=16, offset=cls.RECORD_BYTES)
             if int(words[0]) != cls.BLOB_MAGIC or int(words[6]) != done or int(words[7]) != uid:
                 raise ValueError("the blob's header does not belong to the record (magic %#x, done %d, uid %d)" % tuple(words[[0, 6, 7]]))
-            if int(words[cls.TEMPERATURE_WORD]):
-                temperature = check_temperature(words[cls.TEMPERATURE_WORD:cls.TEMPERATURE_WORD + 1].view("<f4")[0])
-            if int(words[cls.MIN_P_WORD]):
-                min_p = check_min_p(words[cls.MIN_P_WORD:cls.MIN_P_WORD + 1].view("<f4")[0])
-            top_k = check_top_k(int(words[cls.TOP_K_WORD]))
-            if int(words[cls.TOP_P_WORD]):
-                top_p = check_top_p(words[cls.TOP_P_WORD:cls.TOP_P_WORD + 1].view("<f4")[0])
-                if top_p == 1.0:
-                    raise ValueError("word 13 of the blob's header holds the bits of 1.0, which stand for no top-p as zero")
+            for i, (word, off, is_float) in enumerate(cls.SAMPLING_WORDS):
+                if not is_float:
+                    values[i] = int(words[word])
+                elif int(words[word]):
+                    values[i] = float(words[word:word + 1].view("<f4")[0])
+                    if values[i] == off and word != cls.TEMPERATURE_WORD:      # (the bits of 1.0 are a valid temperature word, as in the engine)
+                        raise ValueError("word %d of the blob's header holds the bits of %r, which zero stands for" % (word, values[i]))
+        s = check_sampling(*values)
         if nblob > 64 or (nblob and done):      # (64 bytes with done = 0: the header alone of a request that had not started)
             host = torch.empty((1, nblob), dtype=torch.uint8, pin_memory=bool(pinned))
             host[0].numpy()[:] = np.frombuffer(data, dtype=np.uint8, count=nblob, offset=cls.RECORD_BYTES)
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   temperature, prime, min_p, top_k, top_p)
+                   prime=prime, **s._asdict())
 
 
 class StepOutput:
@@ -467,9 +483,7 @@ class SlotStream:
         self._running = {}                             # column -> [handle, samples still to come (None: mel, see _mel)]
         self._mel = {}                                 # handle -> [frames, final, column or None, samples delivered] of mel requests
         self._prime = {}                               # handle -> prime (int32 tensor) of the requests (queued or running) that carry one
-        self._minp = {}                                # handle -> probability floor of the requests (queued or running) whose floor is not 0
-        self._cut = {}                                 # handle -> (top_k, top_p) of the requests (queued or running) with a cut
-        self._temp = {}                                # handle -> sampling temperature of the requests (queued or running) whose T is not 1
+        self._sampling = {}                            # handle -> Sampling of the requests (queued or running) that differ from OFF
         # step_async keeps the per-column counts in arrays instead (one numpy operation per step); _arrays says which of the two
         # forms is current, and the other is brought up to date when the caller changes between step() and step_async()
         self._arrays = False
@@ -623,22 +637,17 @@ class SlotStream:
         top_p (1: off), on the tempered distribution, intersected with each other and with the floor (ValueError unless top_k is
         an integer in [0, A] and top_p finite and in (0, 1])."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
-        temperature = check_temperature(temperature)
-        min_p = check_min_p(min_p)
-        cut = self._check_cut(top_k, top_p)
+        s = self._check(temperature, min_p, top_k, top_p)
         prime = check_prime(prime, features.size(1))
         if (self._prefill if prefill is None else prefill) and prime is not None:
             if prime.numel() >= features.size(1):
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), features.size(1)))
-            state = self.prefill(features, prime, uid, temperature)
-            state.min_p = min_p      # (the pass leaves word 11 of the blob zero: set after the resume, at admission)
-            state.top_k, state.top_p = cut
+            state = self.prefill(features, prime, uid, s.temperature)
+            state.min_p, state.top_k, state.top_p = s[1:]      # (the pass leaves words 11 to 13 of the blob zero: set after the resume, at admission)
             handle = self._next_handle
             self._next_handle += 1
             self._queue.append((handle, features, int(state.uid), None, state))
-            self._note_temperature(handle, temperature)
-            self._note_min_p(handle, min_p)
-            self._note_cut(handle, cut)
+            self._note(handle, s)
             return handle
         handle = self._next_handle
         self._next_handle += 1
@@ -646,9 +655,7 @@ class SlotStream:
             uid = self._next_uid
         self._next_uid = max(self._next_uid, int(uid) + 1)
         self._queue.append((handle, features, int(uid), None))
-        self._note_temperature(handle, temperature)
-        self._note_min_p(handle, min_p)
-        self._note_cut(handle, cut)
+        self._note(handle, s)
         if prime is not None:
             self._prime[handle] = prime
         return handle
@@ -662,32 +669,26 @@ class SlotStream:
         bit for bit those of prefill=False, and extend_mel works as for any queued mel request.  ValueError, before anything is
         queued or counted: the engine has no upsampling table, the frames written so far do not cover the prime, a final
         request's prime covers the whole utterance.  Without a prime it changes nothing."""
-        min_p = check_min_p(min_p)
-        cut = self._check_cut(top_k, top_p)
+        s = self._check(temperature, min_p, top_k, top_p)
         if (self._prefill if prefill is None else prefill) and prime is not None:
             stride = getattr(self.engine, "upStride", 0)
             if not stride or not self.engine.upsampleRowElems():
                 raise ValueError("prefill of a mel request needs the engine's upsampling table (setUpsampling)")
             n = self._mel_frames(mel, frames, final)
-            temperature = check_temperature(temperature)
             prime = check_prime(prime, n * stride if final else None)
             if prime.numel() > n * stride:
                 raise ValueError("prefill: a prime of %d samples, the %d frames written so far upsample to %d" % (prime.numel(), n, n * stride))
             if final and prime.numel() >= n * stride:
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), n * stride))
-            state = self.prefill_mel(mel, prime, uid, temperature, n, final)
-            state.min_p = min_p      # (as in submit)
-            state.top_k, state.top_p = cut
+            state = self.prefill_mel(mel, prime, uid, s.temperature, n, final)
+            state.min_p, state.top_k, state.top_p = s[1:]      # (as in submit)
             handle = self._next_handle
             self._next_handle += 1
             req = self._mel[handle] = [n, bool(final), None, int(state.done)]
             self._queue.append((handle, mel, int(state.uid), req, state))
-            self._note_temperature(handle, temperature)
-            self._note_min_p(handle, min_p)
-            self._note_cut(handle, cut)
+            self._note(handle, s)
             return handle
         n = self._mel_frames(mel, frames, final)
-        temperature = check_temperature(temperature)
         prime = check_prime(prime, n * self.engine.upStride if final else None)
         handle = self._next_handle
         self._next_handle += 1
@@ -697,108 +698,74 @@ class SlotStream:
         req = [n, bool(final), None, 0]
         self._mel[handle] = req
         self._queue.append((handle, mel, int(uid), req))
-        self._note_temperature(handle, temperature)
-        self._note_min_p(handle, min_p)
-        self._note_cut(handle, cut)
+        self._note(handle, s)
         if prime is not None:
             self._prime[handle] = prime
         return handle
 
-    def _note_temperature(self, handle, T):
-        if T != 1.0:
-            self._temp[handle] = T
+    def _check(self, temperature, min_p, top_k, top_p):
+        return check_sampling(temperature, min_p, top_k, top_p, getattr(self.engine, "A", None))
+
+    def _note(self, handle, s):
+        if s != OFF:
+            self._sampling[handle] = s
         else:
-            self._temp.pop(handle, None)
+            self._sampling.pop(handle, None)
+
+    def _column(self, handle):
+        """The column of a running request, None for a queued one; KeyError for a handle the stream does not hold."""
+        col = self.running().get(handle)
+        if col is None and not any(item[0] == handle for item in self._queue):
+            raise KeyError(handle)
+        return col
+
+    def _set(self, handle, field, value):
+        col = self._column(handle)
+        if col is not None:
+            getattr(self.engine, getattr(_SLOT_SETTERS, field))(col, value)
+        self._note(handle, self._sampling.get(handle, OFF)._replace(**{field: value}))
+
+    def _get(self, handle, field):
+        self._column(handle)
+        return getattr(self._sampling.get(handle, OFF), field)
 
     def set_temperature(self, handle, temperature):
         """Request `handle` samples at `temperature` from the next step on: a running one through the engine at once (its column's
         value changes with that step's first sample), a waiting one when it is admitted.  KeyError for a handle the stream does
         not hold, ValueError for a bad value -- nothing changes."""
-        T = check_temperature(temperature)
-        col = self.running().get(handle)
-        if col is None:
-            if not any(item[0] == handle for item in self._queue):
-                raise KeyError(handle)
-        else:
-            self.engine.slotSetTemperature(col, T)
-        self._note_temperature(handle, T)
+        self._set(handle, "temperature", check_temperature(temperature))
 
     def temperature(self, handle):
         """The temperature request `handle` (queued or running) samples at."""
-        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
-            raise KeyError(handle)
-        return self._temp.get(handle, 1.0)
-
-    def _note_min_p(self, handle, p):
-        if p != 0.0:
-            self._minp[handle] = p
-        else:
-            self._minp.pop(handle, None)
+        return self._get(handle, "temperature")
 
     def set_min_p(self, handle, min_p):
         """Request `handle` draws with the probability floor `min_p` from the next step on: a running one through the engine at once
         (its column's value changes with that step's first sample), a waiting one when it is admitted.  KeyError for a handle the
         stream does not hold, ValueError for a bad value -- nothing changes."""
-        p = check_min_p(min_p)
-        col = self.running().get(handle)
-        if col is None:
-            if not any(item[0] == handle for item in self._queue):
-                raise KeyError(handle)
-        else:
-            self.engine.slotSetMinP(col, p)
-        self._note_min_p(handle, p)
+        self._set(handle, "min_p", check_min_p(min_p))
 
     def min_p(self, handle):
         """The probability floor request `handle` (queued or running) is drawn with."""
-        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
-            raise KeyError(handle)
-        return self._minp.get(handle, 0.0)
-
-    def _check_cut(self, top_k, top_p):
-        return check_top_k(top_k, getattr(self.engine, "A", None)), check_top_p(top_p)
-
-    def _note_cut(self, handle, cut):
-        if cut != (0, 1.0):
-            self._cut[handle] = cut
-        else:
-            self._cut.pop(handle, None)
-
-    def _set_cut(self, handle, top_k=None, top_p=None):
-        col = self.running().get(handle)
-        if col is None and not any(item[0] == handle for item in self._queue):
-            raise KeyError(handle)
-        k, p = self._cut.get(handle, (0, 1.0))
-        if top_k is not None:
-            k = top_k
-            if col is not None:
-                self.engine.slotSetTopK(col, k)
-        else:
-            p = top_p
-            if col is not None:
-                self.engine.slotSetTopP(col, p)
-        self._note_cut(handle, (k, p))
+        return self._get(handle, "min_p")
 
     def set_top_k(self, handle, top_k):
         """Request `handle` draws from its `top_k` most probable bins from the next step on (0: off): a running one through the
         engine at once, a waiting one when it is admitted.  KeyError for a handle the stream does not hold, ValueError for a bad
         value -- nothing changes."""
-        self._set_cut(handle, top_k=self._check_cut(top_k, 1.0)[0])
+        self._set(handle, "top_k", check_top_k(top_k, getattr(self.engine, "A", None)))
 
     def set_top_p(self, handle, top_p):
         """Likewise with the nucleus mass `top_p` (1: off)."""
-        self._set_cut(handle, top_p=check_top_p(top_p))
+        self._set(handle, "top_p", check_top_p(top_p))
 
     def top_k(self, handle):
         """Top-k request `handle` (queued or running) is drawn with."""
-        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
-            raise KeyError(handle)
-        return self._cut.get(handle, (0, 1.0))[0]
+        return self._get(handle, "top_k")
 
     def top_p(self, handle):
         """Top-p request `handle` (queued or running) is drawn with."""
-        if handle not in self.running() and not any(item[0] == handle for item in self._queue):
-            raise KeyError(handle)
-        return self._cut.get(handle, (0, 1.0))[1]
+        return self._get(handle, "top_p")
 
     def extend_mel(self, handle, frames, final=False):
         """The first `frames` frames of mel request `handle` are written (queued or running); final: no more will come."""
@@ -866,42 +833,36 @@ class SlotStream:
     def _dequeued(self, item):
         """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
         handle, req = item[0], item[3]
-        T = self._temp.pop(handle, 1.0)
-        P = self._minp.pop(handle, 0.0)
-        K, Q = self._cut.pop(handle, (0, 1.0))
+        s = self._sampling.pop(handle, OFF)
         prime = self._prime.pop(handle, None)
         if req is not None:
             del self._mel[handle]
         if len(item) > 4:
             if req is not None:
                 item[4].frames, item[4].final = req[0], req[1]      # (it may have been extended while it waited)
-            item[4].temperature = T                                 # (... or given another temperature
-            item[4].min_p = P                                       # or floor
-            item[4].top_k, item[4].top_p = K, Q                     # or cuts)
+            item[4].temperature, item[4].min_p, item[4].top_k, item[4].top_p = s      # (... or given other values)
             return item[4]
         if req is None:
-            return SlotState(None, item[1], item[2], 0, "features", temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
-        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
+            return SlotState(None, item[1], item[2], 0, "features", prime=prime, **s._asdict())
+        return SlotState(None, item[1], item[2], 0, "mel", req[0], req[1], prime=prime, **s._asdict())
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
         self.engine.slotStop(col)
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
-        T = self._temp.pop(handle, 1.0)      # (the engine has written the same value into the blob's header)
-        P = self._minp.pop(handle, 0.0)      # (likewise)
-        K, Q = self._cut.pop(handle, (0, 1.0))
+        s = self._sampling.pop(handle, OFF)      # (the engine has written the same values into the blob's header)
         prime = self._prime.pop(handle, None)
         heapq.heappush(self._free, col)
         self._ch[col] = -1
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, temperature=T, prime=prime, min_p=P, top_k=K, top_p=Q)
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, prime=prime, **s._asdict())
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, T, prime, P, K, Q)
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, prime=prime, **s._asdict())
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -964,7 +925,7 @@ class SlotStream:
         list and can be drained)."""
         if hasattr(state.blob, "numel") and state.blob.numel() != self.engine.slotStateBytes():
             raise ValueError("a state of %d bytes, this engine's are %d: another shape or precision" % (state.blob.numel(), self.engine.slotStateBytes()))
-        cut = self._check_cut(state.top_k, state.top_p)      # (against this engine's alphabet, before anything is queued)
+        s = state.sampling(getattr(self.engine, "A", None))      # (against this engine's alphabet, before anything is queued)
         handle = self._next_handle
         self._next_handle += 1
         self._next_uid = max(self._next_uid, int(state.uid) + 1)
@@ -972,9 +933,7 @@ class SlotStream:
         if state.kind == "mel":
             req = self._mel[handle] = [int(state.frames), bool(state.final), None, int(state.done)]
         self._queue.appendleft((handle, state.source, int(state.uid), req, state))
-        self._note_temperature(handle, check_temperature(state.temperature))
-        self._note_min_p(handle, check_min_p(state.min_p))
-        self._note_cut(handle, cut)
+        self._note(handle, s)
         if state.prime is not None and state.done < state.prime.numel():      # (still inside it: applied again when it is admitted)
             self._prime[handle] = state.prime
         return handle
@@ -1000,9 +959,8 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
-        cuts = []        # (column, (top_k, top_p), what the start or the resume leaves) likewise: words 12 and 13
-        floored = []     # (column, floor) likewise: a start leaves 0, a resume word 11 of the blob (zero in a prefilled or scored one)
-        tempered = []    # (column, temperature) of the admitted requests whose temperature is not what their start leaves the column at
+        wanted = []      # (column, Sampling, what the start or the resume leaves) likewise, where the two differ: a start leaves OFF, a
+                         # resume words 10 to 13 of the blob (11 to 13 zero in a prefilled or scored one)
         while self._queue and self._free and self._ready(self._queue[0], count):
             col = heapq.heappop(self._free)
             item = self._queue.popleft()
@@ -1014,15 +972,9 @@ class SlotStream:
             self._src[handle] = (x, uid)
             if handle in self._prime:
                 primed.append((col, handle))
-            T = self._temp.get(handle, 1.0)
-            if T != (state._blob_temperature if blob is not None else 1.0):      # (a start leaves 1, a resume the header's value)
-                tempered.append((col, T))
-            P = self._minp.get(handle, 0.0)
-            if P != (state._blob_min_p if blob is not None else 0.0):
-                floored.append((col, P))
-            cut, had = self._cut.get(handle, (0, 1.0)), (state._blob_cut if blob is not None else (0, 1.0))
-            if cut != had:
-                cuts.append((col, cut, had))
+            s, had = self._sampling.get(handle, OFF), (state._blob_sampling if blob is not None else OFF)
+            if s != had:
+                wanted.append((col, s, had))
             if req is None:
                 if blob is None:
                     self.engine.slotStart(col, x, uid)
@@ -1046,15 +998,11 @@ class SlotStream:
                 self._deliv[col] = req[3] if req is not None else 0
         if listed:
             self._resume_listed(listed)
-        for col, T in tempered:      # (start, then set: the engine applies both at the step that follows)
-            self.engine.slotSetTemperature(col, T)
-        for col, P in floored:
-            self.engine.slotSetMinP(col, P)
-        for col, cut, had in cuts:
-            if cut[0] != had[0]:
-                self.engine.slotSetTopK(col, cut[0])
-            if cut[1] != had[1]:
-                self.engine.slotSetTopP(col, cut[1])
+        # start, then set (the engine applies both at the step that follows): every temperature, every floor, then the cuts by column
+        order = [(f, it) for f in ("temperature", "min_p") for it in wanted] + [(f, it) for it in wanted for f in ("top_k", "top_p")]
+        for field, (col, s, had) in order:
+            if getattr(s, field) != getattr(had, field):
+                getattr(self.engine, getattr(_SLOT_SETTERS, field))(col, getattr(s, field))
         for col, handle in primed:   # (start or resume, then prime)
             self.engine.slotPrime(col, self._prime[handle])
 
@@ -1114,9 +1062,7 @@ class SlotStream:
                     del self._mel[rec[0]]
                 del self._running[col]
                 del self._src[rec[0]]
-                self._temp.pop(rec[0], None)
-                self._minp.pop(rec[0], None)
-                self._cut.pop(rec[0], None)
+                self._sampling.pop(rec[0], None)
                 self._prime.pop(rec[0], None)
                 self.engine.slotStop(col)
                 heapq.heappush(self._free, col)
@@ -1127,9 +1073,7 @@ class SlotStream:
         """The request of column `col` has had its last sample issued: the column stops at the next step and is free."""
         handle = self._running.pop(col)[0]
         self._mel.pop(handle, None)
-        self._temp.pop(handle, None)
-        self._minp.pop(handle, None)
-        self._cut.pop(handle, None)
+        self._sampling.pop(handle, None)
         self._prime.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1

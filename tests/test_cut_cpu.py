@@ -97,6 +97,33 @@ int main() {
             memcpy(&e, &f, 4);
             printf("k %d A %d ok %d word %d word_ok %d back %d entry %d\n", k, A, (int)wn::top_k_ok(k, A), wn::top_k_word(k), (int)okw, back, e);
         }
+    // the record helpers beside the per-kind ones: off, each field alone at a valid value, all four, each field alone at a bad one
+    const wn::Sampling recs[] = {{}, {0.5f, 0.0f, 0, 1.0f}, {1.0f, 0.25f, 0, 1.0f}, {1.0f, 0.0f, 32, 1.0f}, {1.0f, 0.0f, 0, 0.9f},
+                                 {2.0f, 0.1f, 4, 0.8f}, {4096.0f, 0.0f, 0, 1.0f}, {1.0f, 0.6f, 0, 1.0f}, {1.0f, 0.0f, 257, 1.0f},
+                                 {1.0f, 0.0f, 0, 1.5f}};
+    for (const wn::Sampling& s : recs) {
+        const int A = 256;
+        int w[4];
+        wn::sampling_words(s, w);
+        const int pw[4] = {wn::temperature_word(s.temperature), wn::min_p_word(s.minP), wn::top_k_word(s.topK), wn::top_p_word(s.topP)};
+        wn::Sampling back{-7.0f, -7.0f, -7, -7.0f}, pb{-7.0f, -7.0f, -7, -7.0f};
+        const bool okb = wn::sampling_of_words(w, A, back);
+        const bool pokb[4] = {wn::temperature_of_word(pw[0], pb.temperature), wn::min_p_of_word(pw[1], pb.minP),
+                              wn::top_k_of_word(pw[2], A, pb.topK), wn::top_p_of_word(pw[3], pb.topP)};
+        float e[4];
+        wn::sampling_entries(s, e);
+        const float pe[4] = {wn::temperature_scale(s.temperature), s.minP, wn::top_k_entry(s.topK), s.topP};
+        printf("rec %x %x %x %x %x", (int)wn::sampling_ok(s, A), (int)wn::temperature_ok(s.temperature), (int)wn::min_p_ok(s.minP),
+               (int)wn::top_k_ok(s.topK, A), (int)wn::top_p_ok(s.topP));
+        for (int i = 0; i < 4; i++) printf(" %x", (unsigned)w[i]);
+        for (int i = 0; i < 4; i++) printf(" %x", (unsigned)pw[i]);
+        printf(" %x %x %x %x %x", (int)okb, (int)pokb[0], (int)pokb[1], (int)pokb[2], (int)pokb[3]);
+        printf(" %x %x %x %x", bits(back.temperature), bits(back.minP), (unsigned)back.topK, bits(back.topP));
+        printf(" %x %x %x %x", bits(pb.temperature), bits(pb.minP), (unsigned)pb.topK, bits(pb.topP));
+        for (int i = 0; i < 4; i++) printf(" %x", bits(e[i]));
+        for (int i = 0; i < 4; i++) printf(" %x", bits(pe[i]));
+        printf(" %x %x\n", (int)(s == wn::Sampling{}), (int)(back == s));
+    }
     return 0;
 }
 """
@@ -149,6 +176,33 @@ def test_the_word_helpers_accept_the_cuts_and_refuse_everything_else(helper_repo
             ok, word, word_ok, back, entry = ks[(k, A)]
             good = 0 <= k <= A
             assert (ok, word_ok) == (int(good), int(good)) and word == k and entry == k and back == (k if good else 0), (k, A)
+
+
+def test_the_record_helpers_are_the_per_kind_helpers_field_by_field(helper_report):
+    """wn::Sampling through sampling_ok, sampling_words, sampling_of_words and sampling_entries against temperature_*, min_p_*,
+    top_k_* and top_p_* on the same values (A = 256): off, each field alone at a valid value, all four, each field alone at a bad one."""
+    recs = [[int(x, 16) for x in ln.split()[1:]] for ln in helper_report if ln.startswith("rec ")]
+    values = [(1.0, 0.0, 0, 1.0), (0.5, 0.0, 0, 1.0), (1.0, 0.25, 0, 1.0), (1.0, 0.0, 32, 1.0), (1.0, 0.0, 0, 0.9), (2.0, 0.1, 4, 0.8),
+              (4096.0, 0.0, 0, 1.0), (1.0, 0.6, 0, 1.0), (1.0, 0.0, 257, 1.0), (1.0, 0.0, 0, 1.5)]
+    assert len(recs) == len(values)
+    for i, (f, v) in enumerate(zip(recs, values)):
+        ok, ok_kinds, words, kind_words = f[0], f[1:5], f[5:9], f[9:13]
+        back_ok, back_ok_kinds, back, kind_back = f[13], f[14:18], f[18:22], f[22:26]
+        entries, kind_entries, is_off, round_trip = f[26:30], f[30:34], f[34], f[35]
+        as_bits = [_bits(v[0]), _bits(v[1]), v[2], _bits(v[3])]
+        for kind in range(4):
+            assert words[kind] == kind_words[kind], (i, kind)
+            assert back[kind] == kind_back[kind], (i, kind)
+            assert entries[kind] == kind_entries[kind], (i, kind)
+        assert ok == int(all(ok_kinds)) and back_ok == int(all(back_ok_kinds)), i
+        assert is_off == int(i == 0)
+        if i < 6:                                       # valid: the words are the values' bits, zero where off, and come back as they went
+            assert ok == 1 and back_ok == 1 and round_trip == 1, i
+            assert words == [0 if v[k] == values[0][k] else as_bits[k] for k in range(4)] and back == as_bits, i
+        else:                                           # one bad field: that kind alone is refused, as a value and as a word
+            assert ok == 0 and back_ok == 0 and ok_kinds == back_ok_kinds == [int(k != i - 6) for k in range(4)], i
+    assert recs[0][5:9] == [0, 0, 0, 0]                 # off is four zero words: the blobs of before the values existed
+    assert recs[5][26:30] == [_bits(np.float32(1.4426950408889634) * (np.float32(1.0) / np.float32(2.0))), _bits(0.1), 4, _bits(0.8)]
 
 
 def test_check_top_k_and_check_top_p_are_the_engines_ranges():
@@ -436,15 +490,15 @@ def test_the_cuts_survive_to_bytes_and_from_bytes():
         assert data[R:] == blob.numpy().tobytes()
         back = SlotState.from_bytes(data, src)
         assert (back.top_k, back.top_p, back.min_p, back.temperature, back.kind, back.done) == (k, p, 0.0, 1.0, "mel", 13)
-        assert back._blob_cut == (k, p) and back.to_bytes() == data
+        assert back._blob_sampling[2:] == (k, p) and back.to_bytes() == data
     # a prefilled or scored state: the blob's words are zero, the state's cuts are not -- the bytes carry them
     st = SlotState(_synthetic_blob(5, 8, 13, 4), src, 4, 13, "features")
     st.top_k, st.top_p = 4, 0.5
-    assert st._blob_cut == (0, 1.0)
+    assert st._blob_sampling[2:] == (0, 1.0)
     words = np.frombuffer(st.to_bytes(), dtype="<u4", count=16, offset=R)
     assert (words[K_WORD], words[P_WORD], words[11]) == (4, CC.p_bits(0.5), 0)
     back = SlotState.from_bytes(st.to_bytes(), src)
-    assert (back.top_k, back.top_p) == (4, 0.5) and back._blob_cut == (4, 0.5)
+    assert (back.top_k, back.top_p) == (4, 0.5) and back._blob_sampling[2:] == (4, 0.5)
     # a request that had not started: the record alone without a cut (as before), the record and a bare header otherwise
     assert len(SlotState(None, src, 3, 0, "features").to_bytes()) == R
     data = SlotState(None, src, 3, 0, "features", top_k=7).to_bytes()
@@ -585,7 +639,7 @@ def test_submit_with_cuts_sets_them_after_the_start_and_before_the_step():
     assert _kinds(eng, before)[-4:] == ["start", "top_k", "top_p", "step"] and eng.cuts_at_step[3] == {3: (4, 0.5)}
     while st.busy():
         st.step(4)
-    assert st._cut == {}                                                 # nothing is kept of a finished request
+    assert st._sampling == {}                                                 # nothing is kept of a finished request
     st.close()
 
 
@@ -596,7 +650,7 @@ def test_resume_refuses_a_top_k_beyond_the_engines_alphabet_before_anything_is_q
     state = SlotState(None, torch.zeros(80, 12), 5, 0, "features", top_k=CutFakeEngine.A + 1)      # (a state does not know the alphabet)
     with pytest.raises(ValueError):
         st.resume(state)
-    assert not st.busy() and st._next_handle == 0 and st._cut == {} and _kinds(eng) == ["begin"]
+    assert not st.busy() and st._next_handle == 0 and st._sampling == {} and _kinds(eng) == ["begin"]
     state.top_k = CutFakeEngine.A
     h = st.resume(state)
     st.step(4)
@@ -640,6 +694,44 @@ def test_compact_suspend_and_resume_keep_the_cuts():
     h4 = st.resume(again)
     st.step(4)
     assert eng.cuts_at_step[-1][again.uid] == (1, float(np.float32(0.8))) and st.top_k(h4) == 1
-    assert other.suspend(h3).top_p == float(np.float32(0.9)) and other._cut == {}
+    assert other.suspend(h3).top_p == float(np.float32(0.9)) and other._sampling == {}
+    other.close()
+    st.close()
+
+
+def test_an_admission_sets_the_values_in_one_order_and_a_resume_only_those_that_differ_from_the_blob():
+    """Two requests that differ from what their start leaves in all four values, one of them primed, admitted by one step: the whole
+    call list -- the starts, every temperature, every floor, then top-k and top-p column by column, then the prime.  A suspended one
+    resumed elsewhere takes its values from the blob: only those changed on the state since are set again."""
+    from nv_wavenet_amd.slots import SlotStream
+
+    class PrimedCutFakeEngine(CutFakeEngine):
+        def slotPrime(self, col, y):
+            assert col in self.pending, "prime without a pending start or resume"
+            self.calls.append(("prime", col, y.numel()))
+
+    eng = PrimedCutFakeEngine(4)
+    st = SlotStream(eng, 64)
+    p9, p8 = float(np.float32(0.9)), float(np.float32(0.8))
+    a = st.submit(torch.zeros(80, 40), temperature=0.5, min_p=0.25, top_k=32, top_p=0.9, prime=torch.tensor([3, 1, 2]))
+    st.submit_mel(torch.zeros(80, 10), temperature=2.0, min_p=0.125, top_k=4, top_p=0.8)
+    st.step(4)
+    assert eng.calls == [("begin", 64), ("start", 0, 0), ("start_mel", 1, 1, 10, True),
+                         ("temperature", 0, 0.5), ("temperature", 1, 2.0), ("min_p", 0, 0.25), ("min_p", 1, 0.125),
+                         ("top_k", 0, 32), ("top_p", 0, p9), ("top_k", 1, 4), ("top_p", 1, p8), ("prime", 0, 3), ("step", 4, 1)]
+    state = st.suspend(a)
+    assert eng.calls[-2:] == [("save", 0, 4), ("stop", 0)] and state.blob == ("blob", 0, 4, 0.5, 0.25, (32, p9))
+    other_eng = PrimedCutFakeEngine(2)
+    other = SlotStream(other_eng, 64)
+    h = other.resume(state)                                              # as saved: the engine reads all four from the blob
+    other.step(4)
+    assert other_eng.calls == [("begin", 64), ("resume", 0, 0, 4), ("step", 4, 1)]
+    state = other.suspend(h)
+    state.min_p, state.top_k = 0.5, 1                                    # two of the four changed on the state
+    h = other.resume(state)
+    other.step(4)
+    assert other_eng.calls[3:] == [("save", 0, 8), ("stop", 0), ("resume", 0, 0, 8), ("min_p", 0, 0.5), ("top_k", 0, 1), ("step", 4, 1)]
+    assert (other.temperature(h), other.min_p(h), other.top_k(h), other.top_p(h)) == (0.5, 0.5, 1, p9)
+    assert (other_eng.temp[0], other_eng.minp[0], other_eng.cut[0]) == (0.5, 0.5, (1, p9))
     other.close()
     st.close()

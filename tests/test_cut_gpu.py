@@ -543,6 +543,56 @@ def test_a_session_whose_cutting_utterances_have_ended_launches_without_the_sear
     r.check(_uncut(CC.COND, precision, mode)["y"], "utterances without cuts in vacated columns", only=(2, 3, 4))
 
 
+def _bare(cc, precision, mode):
+    """the run of a fresh engine with nothing set, once"""
+    key = ("bare", cc.name, precision, mode)
+    if key not in _cache:
+        case, m, x, w, Lh, t = _inputs(cc, precision)
+        e = _seeded(case, t, precision, mode, m, x, w)
+        _cache[key] = _run(e, case)
+        e.close()
+    return _cache[key]
+
+
+def test_mode_changes_leave_no_value_behind():
+    """One engine: lockstep with all four values in every column; a slot session begun over them, whose utterances run with every
+    value off until theirs are set; the session ended while a set column still waits for its step; lockstep again with nothing set.
+    Each change of mode puts the host's values and the device table back to off."""
+    precision, mode = 16, "wg2"
+    case, m, x, w, Lh, t = _inputs(CC.COND, precision)
+    s = case.shape
+    ks, ps, taus, temps = _values(CC.COND)
+    xg = torch.from_numpy(x).cuda()
+    bare = _bare(CC.COND, precision, mode)
+    e = _seeded(case, t, precision, mode, m, x, w)
+    e.setTemperatures(temps), e.setMinP(taus), e.setTopK(ks), e.setTopP(ps)
+    assert e.samplerMask() == 3
+    assert np.array_equal(_run(e, case, dump=False)["y"], _mixed(CC.COND, precision, mode)["y"])
+    r = Run(e, xg, s.maxD)                                    # slotsBegin over the lockstep values
+    assert e.samplerMask() == 0
+    uids = (2, 7, 17, 0)                                      # (the first three: all four values on; their columns' lockstep T was not 1)
+    cols = [_column_of(b, s.B) for b in uids]
+    assert all(temps[c] != 1.0 for c in cols) and all(ks[b] and ps[b] != 1.0 and taus[b] and temps[b] != 1.0 for b in uids[:3])
+    for col, b in zip(cols, uids):
+        r.start(col, b)
+    assert e.samplerMask() == 0
+    r.step(5)
+    r.check(bare["y"], "begun over lockstep values, nothing set")
+    for col, b in zip(cols[:2], uids[:2]):
+        _set_all(e, col, b, ks, ps, taus, temps)
+    r.step(5)
+    r.check(bare["y"], "the columns nothing was set in", only=(2, 3))
+    _set_all(e, cols[2], uids[2], ks, ps, taus, temps)        # no step follows: the column is still to be written at the end
+    assert e.samplerMask() == 3
+    e.slotsEnd()
+    assert e.samplerMask() == 0
+    e.setFeatures(xg)
+    again = _run(e, case)
+    assert e.samplerMask() == 0
+    e.close()
+    assert np.array_equal(again["y"], bare["y"]) and np.array_equal(again["P"], bare["P"]) and np.array_equal(again["Za"], bare["Za"])
+
+
 @pytest.mark.parametrize("pinned", [False, True], ids=["device", "pinned"])
 def test_list_saves_and_list_resumes_carry_the_cuts(pinned):
     """SlotStream: submit(top_k=, top_p=), set_top_k / set_top_p, suspend_many -- one list save, the device writes words 12 and 13 of
@@ -625,7 +675,7 @@ def test_a_prefilled_state_resumed_with_cuts_continues_as_the_sequentially_prime
     seq = {b: st.submit(xg[b], **kw(b)) for b in uids}
     pre = {b: st.submit(xg[b], prefill=True, **kw(b)) for b in uids}
     state = st._queue[len(uids)][4]
-    assert (state.top_k, state.top_p) == (1, 0.5) and state._blob_cut == (0, 1.0) and _words(state.blob) == (0, 0)
+    assert (state.top_k, state.top_p) == (1, 0.5) and state._blob_sampling[2:] == (0, 1.0) and _words(state.blob) == (0, 0)
     got = {h: [] for h in list(seq.values()) + list(pre.values())}
     while st.busy():
         for h, (y, _) in st.step(7).items():

@@ -304,15 +304,15 @@ def test_the_floor_survives_to_bytes_and_from_bytes():
         assert data[R:] == blob.numpy().tobytes()
         back = SlotState.from_bytes(data, src)
         assert (back.min_p, back.temperature, back.kind, back.frames, back.final, back.done) == (p, 0.5, "mel", 9, False, 13)
-        assert back._blob_min_p == p and back.to_bytes() == data
+        assert back._blob_sampling.min_p == p and back.to_bytes() == data
     # a prefilled or scored state: the blob's word 11 is zero, the state's floor is not -- the bytes carry it
     st = SlotState(_synthetic_blob(5, 8, 13, 4), src, 4, 13, "features")
     st.min_p = 0.25
-    assert st._blob_min_p == 0.0
+    assert st._blob_sampling.min_p == 0.0
     data = st.to_bytes()
     assert np.frombuffer(data, dtype="<u4", count=16, offset=R)[WORD] == MP.bits(0.25)
     back = SlotState.from_bytes(data, src)
-    assert back.min_p == 0.25 and back._blob_min_p == 0.25
+    assert back.min_p == 0.25 and back._blob_sampling.min_p == 0.25
     # a request that had not started: the record alone at floor 0 (as before), the record and a bare header otherwise
     assert len(SlotState(None, src, 3, 0, "features").to_bytes()) == R
     data = SlotState(None, src, 3, 0, "features", min_p=0.1).to_bytes()
@@ -441,7 +441,7 @@ def test_submit_with_a_floor_sets_it_after_the_start_and_before_the_step():
     assert eng.floors_at_step[3] == {3: 0.5}
     while st.busy():
         st.step(4)
-    assert st._minp == {}                                                # nothing is kept of a finished request
+    assert st._sampling == {}                                                # nothing is kept of a finished request
     st.close()
 
 
@@ -480,6 +480,6 @@ def test_compact_suspend_and_resume_keep_the_floor():
     h4 = st.resume(again)
     st.step(4)
     assert eng.floors_at_step[-1][again.uid] == waiting.min_p and st.min_p(h4) == waiting.min_p
-    assert other.suspend(h3).min_p == 0.5 and other._minp == {}
+    assert other.suspend(h3).min_p == 0.5 and other._sampling == {}
     other.close()
     st.close()

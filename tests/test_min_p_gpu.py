@@ -526,7 +526,7 @@ def test_a_prefilled_state_resumed_with_a_floor_continues_as_the_sequentially_pr
     seq = {b: st.submit(xg[b], uid=b, temperature=temps[b], prime=prime[b], min_p=taus[b]) for b in uids}
     pre = {b: st.submit(xg[b], uid=b, temperature=temps[b], prime=prime[b], prefill=True, min_p=taus[b]) for b in uids}
     state = st._queue[len(uids)][4]
-    assert state.min_p == float(np.float32(taus[3])) and state._blob_min_p == 0.0 and _header(state.blob)[WORD] == 0
+    assert state.min_p == float(np.float32(taus[3])) and state._blob_sampling.min_p == 0.0 and _header(state.blob)[WORD] == 0
     got = {h: [] for h in list(seq.values()) + list(pre.values())}
     while st.busy():
         for h, (y, _) in st.step(7).items():

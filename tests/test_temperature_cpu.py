@@ -217,7 +217,7 @@ def test_submit_with_a_temperature_sets_it_after_the_start_and_before_the_step()
     assert eng.temps_at_step[3] == {3: 0.25}
     while st.busy():
         st.step(4)
-    assert st._temp == {}                                                # nothing is kept of a finished request
+    assert st._sampling == {}                                                # nothing is kept of a finished request
     st.close()
 
 
@@ -261,6 +261,6 @@ def test_compact_and_suspend_and_resume_keep_the_temperature():
     assert eng.temps_at_step[-1][again.uid] == 8.0 and st.temperature(h4) == 8.0
     states = [other.suspend(h) for h in (h3, w, w2)]
     assert [s.temperature for s in states] == [0.25, 0.5, 1.0]
-    assert other._temp == {}
+    assert other._sampling == {}
     other.close()
     st.close()
