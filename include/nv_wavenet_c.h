@@ -744,6 +744,36 @@ typedef struct {
 int nvw_score_chunks(nvw_engine* e, const nvw_score_chunk_req* reqs, int count, void* stream);
 int nvw_score_chunks_mel(nvw_engine* e, const nvw_score_chunk_mel_req* reqs, int count, void* stream);
 
+/* ANALYSIS FRONT END: PCM TO MU-LAW SAMPLES AND LOG-MEL FRAMES (additive within ABI 7).  Scoring and priming start from the sample
+ * indices y and the mel frames of existing audio; the engine ends at int16 PCM (nvw_generate_stream).  This pass goes the other way,
+ * batched, in one launch per call.  For PCM p[0 .. n) with x = p / 32768, reflect-padded by n_fft / 2 on both sides,
+ * frame f = padded samples [f * hop, f * hop + n_fft), f = 0 .. n / hop (the frames of torch.stft(center=True, pad_mode="reflect")):
+ *     X[k]      = sum_j w[j] x_f[j] e^{-2 pi i k j / n_fft},  k = 0 .. n_fft / 2,  w the periodic Hann window of length n_fft
+ *     mel[c][f] = log(max(sum_k M[c][k] |X[k]|, 1e-5))          (Tacotron-2's TacotronSTFT.mel_spectrogram, which the reference calls)
+ *     y[t]      = int((sign(x) log1p(mu |x|) / log1p(mu) + 1) / 2 * mu + 0.5),  mu = A - 1      (the reference's mu_law_encode)
+ * The spectrum is computed in fp32 (a GEMM of matrix instructions against a windowed DFT table built in float64); y is exact: the
+ * float64 formula on every int16 value.  The mel basis M [n_mel][n_fft / 2 + 1] is a weight of the caller's, as the upsampling is.
+ *   nvw_set_analysis     the geometry and M (host memory, copied).  Returns 1; 0 with the previous geometry kept: n_fft not a
+ *                        multiple of 4 in 64 .. 2048, hop outside 1 .. n_fft, n_mel outside 1 .. 128, or a geometry whose workgroup
+ *                        needs more than 160 KiB of LDS: 4 * (15 hop + J' + 4 ((15 hop + J') / hop + 1)) bytes of samples, 64 K' of
+ *                        magnitudes (J' = n_fft rounded up to 16, K' = n_fft / 2 + 1 rounded up to 16) and 2 A of thresholds.  1024 /
+ *                        256 takes 53 KiB, 800 / 200 42 KiB (A = 256); n_fft = 2048 fits up to hop = 1446 at A = 1024.  Synchronises.
+ *   nvw_analysis_frames  n / hop + 1; 0 when nvw_set_analysis has not been called or nvw_analyse refuses n.
+ *   nvw_analyse          `count` requests (1 .. 65535).  pcm: n int16 samples in device memory, n > n_fft / 2 (the reflection needs
+ *                        that many).  mel: NULL, or device memory written as mel[c * c_stride + f * f_stride], c < n_mel,
+ *                        f < nvw_analysis_frames(n), `precision`-bit floats (16 or 32), positive strides.  y: NULL, or n int32 in device
+ *                        memory.  Not both NULL.  Nothing else is written.  Asynchronous on `stream`: pcm and the outputs stay alive
+ *                        until it has run.  Works inside and outside slot mode, touches no ring, column or session.  Returns count, or
+ *                        0 with nothing written and nothing launched. */
+typedef struct {
+    const short* pcm; int n;
+    void* mel; int precision; long long c_stride, f_stride;
+    int* y;
+} nvw_analysis_req;
+int nvw_set_analysis(nvw_engine* e, int n_fft, int hop, int n_mel, const float* mel_basis);
+int nvw_analysis_frames(nvw_engine* e, int n);
+int nvw_analyse(nvw_engine* e, const nvw_analysis_req* reqs, int count, void* stream);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

@@ -3,6 +3,7 @@
 // big kernel templates compile in parallel.
 #pragma once
 #include "../../include/nv_wavenet_c.h"
+#include "analysis.hpp"
 #include "nv_wavenet.hpp"
 
 struct nvw_engine {
@@ -76,7 +77,17 @@ struct nvw_engine {
     virtual int scoreChunks(const wn::ScoreChunkReq*, int, hipStream_t) = 0;
     virtual int scoreChunksMel(const wn::ScoreChunkMelReq*, int, hipStream_t) = 0;
     virtual wn::SlotSession& slots() = 0;      // slot mode is the session's: the C functions call it directly
+    // the analysis front end (analysis.hpp) depends on no template argument but A (`levels`, set by nvw_create_ex) and on no state
+    // of the class: it lives here, and the C functions call it directly
+    wn::Analysis analysis;
+    int levels = 0;
 };
+static_assert(sizeof(nvw_analysis_req) == sizeof(wn::AnalysisReq) && offsetof(nvw_analysis_req, pcm) == offsetof(wn::AnalysisReq, pcm) &&
+              offsetof(nvw_analysis_req, n) == offsetof(wn::AnalysisReq, n) && offsetof(nvw_analysis_req, mel) == offsetof(wn::AnalysisReq, mel) &&
+              offsetof(nvw_analysis_req, precision) == offsetof(wn::AnalysisReq, precision) &&
+              offsetof(nvw_analysis_req, c_stride) == offsetof(wn::AnalysisReq, cStride) &&
+              offsetof(nvw_analysis_req, f_stride) == offsetof(wn::AnalysisReq, fStride) && offsetof(nvw_analysis_req, y) == offsetof(wn::AnalysisReq, y),
+              "nvw_analysis_req is wn::AnalysisReq");
 static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_slot_piece, slot) == offsetof(wn::SlotPiece, slot) &&
               offsetof(nvw_slot_piece, uid) == offsetof(wn::SlotPiece, uid) && offsetof(nvw_slot_piece, finished) == offsetof(wn::SlotPiece, finished) &&
               offsetof(nvw_slot_piece, first) == offsetof(wn::SlotPiece, first) &&

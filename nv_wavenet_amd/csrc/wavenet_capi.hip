@@ -64,6 +64,7 @@ nvw_engine* nvw_create_ex(int R, int S, int A, int precision, int num_layers, in
         return NULL;
     }
     nvw_engine* w = e->make(num_layers, max_dilation, batch_size, num_samples, implementation, tanh_embed, organisation);
+    if (w) w->levels = A;
     if (w && !w->supported()) {   // the shape does not fit a CU in this organisation (message already printed)
         delete w;
         return NULL;
@@ -496,6 +497,25 @@ int nvw_score_chunks_mel(nvw_engine* e, const nvw_score_chunk_mel_req* reqs, int
         fprintf(stderr, "nvw_score_chunks_mel: refused, nothing written (as nvw_score_samples_mel and nvw_score_chunks: %d requests, frames * "
                 "stride >= done + n, states and state_out of %zu bytes)\n", count, e->slots().stateBytes());
     return got;
+}
+// ---- analysis front end: PCM to mu-law samples and log-mel frames (additive within ABI 7) -------------------------------------------
+int nvw_set_analysis(nvw_engine* e, int n_fft, int hop, int n_mel, const float* mel_basis) {
+    if (!e->analysis.set(n_fft, hop, n_mel, mel_basis, e->levels)) {
+        fprintf(stderr, "nvw_set_analysis: refused (n_fft %d: a multiple of 4 in %d .. %d; hop %d: 1 .. n_fft; n_mel %d: 1 .. %d; a host mel "
+                "basis; %zu bytes of LDS per workgroup, at most %d)\n", n_fft, wn::kAnalysisFftMin, wn::kAnalysisFftMax, hop, n_mel,
+                wn::kAnalysisMelMax, n_fft > 0 && hop > 0 ? wn::Analysis::ldsBytes(n_fft, hop, e->levels) : (size_t)0, wn::kAnalysisLdsMax);
+        return 0;
+    }
+    return 1;
+}
+int nvw_analysis_frames(nvw_engine* e, int n) { return e->analysis.frames(n); }
+int nvw_analyse(nvw_engine* e, const nvw_analysis_req* reqs, int count, void* stream) {
+    if (!e->analysis.run((const wn::AnalysisReq*)reqs, count, (hipStream_t)stream)) {
+        fprintf(stderr, "nvw_analyse: refused, nothing written (nvw_set_analysis first; %d requests of 1 .. 65535; every n > n_fft / 2, pcm in "
+                "device memory; mel or y given, in device memory; precision 32 or 16, positive strides)\n", count);
+        return 0;
+    }
+    return count;
 }
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,

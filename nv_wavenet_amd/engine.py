@@ -46,6 +46,10 @@ SCORE_CHUNK_MEL_REQ = np.dtype({"names": ["state", "y", "n", "mel", "precision",
                                           "logp", "rows", "state_out"],
                                 "formats": ["<u8", "<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<i4", "<u4", "<f4", "<u8", "<u8", "<u8"],
                                 "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 60, 64, 72, 80, 88], "itemsize": 96})
+# ... nvw_analysis_req of nvw_analyse
+ANALYSIS_REQ = np.dtype({"names": ["pcm", "n", "mel", "precision", "c_stride", "f_stride", "y"],
+                         "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<u8"],
+                         "offsets": [0, 8, 16, 24, 32, 40, 48], "itemsize": 56})
 
 
 class Impl:
@@ -898,6 +902,46 @@ class WavenetEngine:
         if got != n or n == 0:
             raise ValueError("nvw_score_samples_mel refused %d requests" % n)
         return out
+
+    # ---- the analysis front end (include/nv_wavenet_c.h, "ANALYSIS FRONT END") ----
+    def setAnalysis(self, nFft, hop, melBasis):
+        """The geometry of analyse() and the mel basis [n_mel][nFft / 2 + 1] (numpy or torch, copied).  ValueError when refused (the
+        previous geometry stays): see nvw_set_analysis."""
+        basis = np.ascontiguousarray(melBasis.detach().cpu().numpy() if hasattr(melBasis, "detach") else melBasis, dtype=np.float32)
+        if basis.ndim != 2 or basis.shape[1] != int(nFft) // 2 + 1:
+            raise ValueError("the mel basis is [n_mel][nFft / 2 + 1], got %s" % (basis.shape,))
+        if not lib.nvw_set_analysis(self._h, int(nFft), int(hop), basis.shape[0], basis.ctypes.data):
+            raise ValueError("nvw_set_analysis refused nFft %d, hop %d, %d channels" % (nFft, hop, basis.shape[0]))
+        self.nMel = basis.shape[0]
+
+    def analysisFrames(self, n):
+        """Frames of n samples, n // hop + 1; 0 without setAnalysis, or for an n analyse() refuses (n <= nFft / 2)."""
+        return int(lib.nvw_analysis_frames(self._h, int(n)))
+
+    def analyse(self, requests, stream=None):
+        """PCM to mu-law samples and log-mel frames, one launch: requests = [(pcm, mel, y), ...] with pcm a contiguous 1-D int16 CUDA
+        tensor of n samples; mel None, or a CUDA tensor [n_mel][>= analysisFrames(n)], float32 or float16, any positive strides, of
+        which the first analysisFrames(n) frames are written; y None, or a contiguous 1-D int32 CUDA tensor of n values.
+        Asynchronous on `stream`.  ValueError when refused (nothing written): see nvw_analyse."""
+        import torch
+        requests = list(requests)
+        n = len(requests)
+        reqs = np.zeros(max(n, 1), dtype=ANALYSIS_REQ)
+        for i, (pcm, mel, y) in enumerate(requests):
+            if not hasattr(pcm, "data_ptr") or pcm.dim() != 1 or pcm.dtype != torch.int16 or not pcm.is_contiguous() or not pcm.is_cuda:
+                raise ValueError("audio is a contiguous 1-D int16 CUDA tensor")
+            bits, sc, sf = 0, 0, 0
+            if mel is not None:
+                bits = {torch.float32: 32, torch.float16: 16}.get(mel.dtype)
+                if not bits or not mel.is_cuda or mel.dim() != 2 or mel.size(0) != getattr(self, "nMel", 0) or \
+                        mel.size(1) < max(1, self.analysisFrames(pcm.numel())):
+                    raise ValueError("mel: a float32 or float16 CUDA tensor [n_mel][>= analysisFrames(n)]")
+                sc, sf = mel.stride(0), mel.stride(1)
+            if y is not None and (y.dim() != 1 or y.dtype != torch.int32 or not y.is_contiguous() or not y.is_cuda or y.numel() != pcm.numel()):
+                raise ValueError("y: a contiguous 1-D int32 CUDA tensor of n values")
+            reqs[i] = (pcm.data_ptr(), pcm.numel(), 0 if mel is None else mel.data_ptr(), bits, sc, sf, 0 if y is None else y.data_ptr())
+        if n == 0 or lib.nvw_analyse(self._h, reqs.ctypes.data, n, stream) != n:
+            raise ValueError("nvw_analyse refused %d requests" % n)
 
     # ---- scoring with carried state (include/nv_wavenet_c.h, "SCORING WITH CARRIED STATE"; DESIGN.md §6l) ----
     def _score_chunks(self, requests, mel, rows, states, pinned, stream, out=None):

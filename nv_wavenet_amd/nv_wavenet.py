@@ -574,6 +574,55 @@ class NVWaveNetEngine(NVWaveNet):
         return self._score(mel, mel.size(2) * int(upsample_stride), up, cond_weight, cond_bias, samples, lengths, temperature, return_rows,
                            chunk, return_state)
 
+    def set_analysis(self, n_fft, hop, mel_basis):
+        """The geometry of analyse() / score_audio(): Tacotron-2's mel_spectrogram with filter_length = win_length =
+        n_fft, hop_length = hop, and mel_basis [n_mel][n_fft / 2 + 1] (a weight of the caller's, as the upsampling is)."""
+        basis = mel_basis.detach().float().cpu().contiguous()
+        if basis.dim() != 2 or basis.size(1) != int(n_fft) // 2 + 1:
+            raise ValueError("mel_basis: [n_mel][n_fft / 2 + 1], got %s" % (tuple(basis.shape),))
+        self._analysis = (int(n_fft), int(hop), basis)
+
+    def analyse(self, pcm, lengths=None):
+        """Audio to what scoring and priming take (nvw_analyse): pcm = int16 [batch][n] on the GPU; lengths: None (all
+        n), or `batch` values in n_fft / 2 + 1 .. n.  Returns (mel [batch][n_mel][n // hop + 1] in the engine's precision, y
+        [batch][n] int32), on the GPU, in one launch for the whole batch: utterance b's first lengths[b] // hop + 1 frames and
+        lengths[b] samples, zero past them.  Needs set_analysis; ValueError for a bad shape or length."""
+        if getattr(self, "_analysis", None) is None:
+            raise ValueError("analyse needs set_analysis")
+        n_fft, hop, basis = self._analysis
+        if pcm.dim() != 2 or pcm.dtype != torch.int16 or not pcm.is_cuda:
+            raise ValueError("pcm: an int16 CUDA tensor [batch][n], got %s %s" % (pcm.dtype, tuple(pcm.shape)))
+        batch_size, n = pcm.shape
+        lengths = [n] * batch_size if lengths is None else [int(k) for k in lengths]
+        if len(lengths) != batch_size or not all(n_fft // 2 < k <= n for k in lengths):
+            raise ValueError("lengths: %d values in %d .. %d" % (batch_size, n_fft // 2 + 1, n))
+        capacity = -(-n // self.BUCKET) * self.BUCKET
+        kept = [k for k in self._engines if k[:2] == (batch_size, capacity)]
+        e = self._engine(batch_size, n, kept[-1][2] if kept else Impl.AUTO)
+        key = (n_fft, hop, basis.data_ptr(), basis._version)
+        if getattr(e, "_analysis_key", None) != key:
+            e.setAnalysis(n_fft, hop, basis)
+            e._analysis_key = key
+        pcm = pcm.contiguous()
+        mel = torch.zeros((batch_size, basis.size(0), n // hop + 1), dtype=torch.float16 if self.precision == 16 else torch.float32, device=pcm.device)
+        y = torch.zeros((batch_size, n), dtype=torch.int32, device=pcm.device)
+        e.analyse([(pcm[b, :lengths[b]], mel[b], y[b, :lengths[b]]) for b in range(batch_size)],
+                  stream=torch.cuda.current_stream(pcm.device).cuda_stream)
+        return mel, y
+
+    def score_audio(self, pcm, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, lengths=None, temperature=None,
+                    return_rows=False, chunk=None, return_state=False):
+        """score_mel() of a recording: analyse(pcm, lengths), then score_mel on its frames and samples, and nothing else.  The
+        analysis' hop must be the upsampling's stride and its n_mel the upsampling's input channels (ValueError otherwise)."""
+        if getattr(self, "_analysis", None) is None:
+            raise ValueError("score_audio needs set_analysis")
+        if self._analysis[1] != int(upsample_stride) or self._analysis[2].size(0) != upsample_weight.size(0):
+            raise ValueError("the analysis has hop %d and %d channels, the upsampling stride %d and %d" %
+                             (self._analysis[1], self._analysis[2].size(0), int(upsample_stride), upsample_weight.size(0)))
+        mel, y = self.analyse(pcm, lengths)
+        return self.score_mel(mel, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, y, lengths=lengths,
+                              temperature=temperature, return_rows=return_rows, chunk=chunk, return_state=return_state)
+
     def _score(self, x, sample_count, up, cond_weight, cond_bias, samples, lengths, temperature, return_rows, chunk=None, return_state=False):
         """score (up None: x holds features) and score_mel (up = upsampling weight, bias, stride: x holds frames)."""
         from .slots import check_temperature

@@ -100,9 +100,14 @@ nvw_upsample_requests alone; with --parent-lib the primes are also forced throug
 (nvw_slot_start_mel + nvw_slot_prime, steps of the window up to sample n), the only way the parent can prime from frames.  The
 results of the paths are checked to be equal bytes.  One JSON line each: median and min .. max of the rounds per path.
 
+--analyse times the analysis front end at n_fft 1024 / hop 256 / 80 channels: nvw_analyse for 1 and 256 requests of
+24 000 int16 samples (frames in fp16 and samples, one launch) beside nvw_score_samples_mel of the frames and samples it wrote -- the
+claim to confirm is only that analysing a recording is a small share of scoring it.
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
     python scripts/slots_perf.py --prefill-mel [--parent-lib PATH] [--rounds 5]
     python scripts/slots_perf.py --score-mel [--rounds 5]
+    python scripts/slots_perf.py --analyse [--rounds 5]
     python scripts/slots_perf.py --score-chunks [--parent-lib PATH] [--rounds 5]
     python scripts/slots_perf.py --score [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
     python scripts/slots_perf.py --prefill [--parent-lib PATH] [--batch 12288] [--chunks 256] [--rounds 5]
@@ -146,6 +151,7 @@ def main():
     ap.add_argument("--score-chunks", action="store_true", help="time nvw_score_chunks against the whole pass, a request past the cap, and candidates behind a shared prefix")
     ap.add_argument("--prefill-mel", action="store_true", help="time nvw_prefill_states_mel against nvw_prefill_states on rows upsampled beforehand and against mel columns of the parent")
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
+    ap.add_argument("--analyse", action="store_true", help="time nvw_analyse beside nvw_score_samples_mel of the same audio")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
     ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
@@ -158,6 +164,9 @@ def main():
     B, W = args.batch, args.window
     w = bench.make_weights()
     Wc, bc = bench.make_cond_layers()
+    if args.analyse:
+        print(json.dumps(time_analyse(args, w, Wc, bc)), flush=True)
+        return
     if args.prefill_mel or args.score_mel:
         if args.prefill_mel:
             print(json.dumps(time_prefill_mel(args, w, Wc, bc)), flush=True)
@@ -1016,6 +1025,64 @@ def time_score_mel(args, w, Wc, bc):
                                                    "upsampling_share": round((med["score_mel"] - med["score_rows"]) / med["score_mel"], 3),
                                                    "upsample_GB_per_s_written": round(count * n * row * 2 / (1e-3 * med["upsample"]) / 1e9, 1)}
             del rows
+        e.close()
+        torch.cuda.empty_cache()
+    return res
+
+
+def time_analyse(args, w, Wc, bc):
+    """The --analyse measurement: nvw_analyse for 1 and 256 requests of 24 000 samples (n_fft 1024 / hop 256, 80 channels, fp16 frames)
+    beside nvw_score_samples_mel of what it wrote, calls split at nvw_score_max_samples as --score-mel does."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import ANALYSIS_REQ, SCORE_MEL_REQ
+    sh = bench.HEAD
+    n_fft, hop, n = 1024, bench.UP_STRIDE, 24000
+    up_w, up_b = _up_weights()
+    basis = np.random.default_rng(29).random((bench.N_COND, n_fft // 2 + 1), dtype=np.float32) / 64
+    g = torch.Generator(device="cuda")
+    g.manual_seed(31)
+    s = torch.cuda.current_stream().cuda_stream
+    res = {"shape": "R%d S%d A%d L%d maxD%d fp16" % (sh.R, sh.S, sh.A, sh.L, sh.maxD), "analysis": "%d / %d / %d" % (n_fft, hop, bench.N_COND),
+           "n": n, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "cases": {}}
+    for count in (1, 256):
+        e = bench.build_engine(w, count, 4096)
+        e.setConditioningWeights(Wc, bc)
+        e.setUpsampling(up_w, up_b, hop)
+        e.setAnalysis(n_fft, hop, basis)
+        frames, cap = e.analysisFrames(n), e.scoreMaxSamples()
+        pcm = (8000 * torch.randn(count, n, device="cuda", generator=g)).clamp(-32768, 32767).to(torch.int16)
+        mel = torch.empty(count, bench.N_COND, frames, dtype=torch.float16, device="cuda")
+        ys = torch.empty(count, n, dtype=torch.int32, device="cuda")
+        logp = torch.empty(count, n, dtype=torch.float32, device="cuda")
+        ra = np.zeros(count, dtype=ANALYSIS_REQ)
+        for b in range(count):
+            ra[b] = (pcm[b].data_ptr(), n, mel[b].data_ptr(), 16, mel[b].stride(0), mel[b].stride(1), ys[b].data_ptr())
+        per_call = max(1, min(count, cap // (-(-n // 16) * 16)))
+        groups = []
+        for b0 in range(0, count, per_call):
+            k = min(per_call, count - b0)
+            rm = np.zeros(k, dtype=SCORE_MEL_REQ)
+            for i in range(k):
+                m = mel[b0 + i]
+                rm[i] = (ys[b0 + i].data_ptr(), n, m.data_ptr(), 16, m.stride(0), m.stride(1), frames, 1.0, logp[b0 + i].data_ptr(), 0)
+            groups.append((rm, k))
+
+        def analyse():
+            assert lib.nvw_analyse(e._h, ra.ctypes.data, count, s) == count
+
+        def score():
+            for rm, k in groups:
+                assert lib.nvw_score_samples_mel(e._h, rm.ctypes.data, k, s) == k
+
+        analyse()
+        ms = _timed_rounds([("analyse", analyse), ("score_mel", score)], args.rounds)
+        assert bool(torch.isfinite(logp).all()) and bool(torch.isfinite(mel.float()).all())
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        res["cases"]["%d x %d" % (count, n)] = {"score_calls": len(groups), "ms": {k: _stats(v) for k, v in ms.items()},
+                                               "analysis_share_of_scoring": round(med["analyse"] / med["score_mel"], 4),
+                                               "audio_seconds_per_second": round(count * n / 24000.0 / (1e-3 * med["analyse"]), 1)}
         e.close()
         torch.cuda.empty_cache()
     return res
