@@ -774,6 +774,47 @@ int nvw_set_analysis(nvw_engine* e, int n_fft, int hop, int n_mel, const float* 
 int nvw_analysis_frames(nvw_engine* e, int n);
 int nvw_analyse(nvw_engine* e, const nvw_analysis_req* reqs, int count, void* stream);
 
+/* SAMPLE-RATE CONVERSION: RECORDINGS IN, DELIVERED PCM OUT (additive within ABI 7).  Every other entry takes and gives audio at the
+ * model's own rate; recordings arrive at 44.1 / 48 / 16 kHz and a serving stack delivers at 8 / 16 / 44.1 / 48 kHz.  This pass converts
+ * by a rational factor up / down = L / M (coprime), batched, in one launch per call: a polyphase FIR run as a GEMM of fp32 matrix
+ * instructions.  The prototype taps h[0 .. T), T odd, centre c = (T - 1) / 2, are defined at rate L * rate_in with the
+ * gain of L folded in; they are a weight of the caller's, as the mel basis is.  A stream x[i] is indexed by its absolute sample index
+ * i >= 0; it is zero for i < 0 and, when the request says `last`, from its end on:
+ *     out[m] = sum_i x[i] h[c + m M - i L]        over the i with 0 <= c + m M - i L < T
+ * so out[m] needs the inputs i in [ceil((m M - c) / L), floor((m M + c) / L)], and a complete stream of n samples has ceil(n L / M)
+ * outputs.  Values are in PCM units throughout (nothing is divided by 32768) and accumulated in fp32; an fp32 output is the sum, an
+ * int16 output the sum rounded to nearest-even and saturated to [-32768, 32767].
+ *   nvw_set_resampler    slot 0 .. 3 (four independent resamplers per handle, typically one for input and one for output), the factors
+ *                        and the taps (host memory, float64, copied).  Builds the table in float64, rounds it to fp32, uploads it;
+ *                        synchronises.  Returns 1; 0 with the slot's previous contents kept: a slot outside 0 .. 3, up or down outside
+ *                        1 .. 640 or not coprime, n_taps even or < 1, no taps, or a geometry whose workgroup needs more than 160 KiB
+ *                        of LDS: 4 (S + s (S / hop + 1)) bytes with q the smallest number with L q >= 16 and q M >= 4, Q = L q,
+ *                        hop = q M, W' = floor(((Q - 1) M + c) / L) + floor(c / L) + 1 rounded up to 16, G = 4 when Q <= 48 and 1
+ *                        otherwise, S = (16 G - 1) hop + W' and s = (4 - hop) mod 8.  48 -> 24 kHz with the default design of the
+ *                        Python package (T = 65) takes 9 KiB, 24 -> 22.05 kHz (147 / 160, T = 5121) 10 KiB, 44.1 -> 8 kHz (80 / 441,
+ *                        T = 14113) 28 KiB.
+ *   nvw_resample_count   ceil(n up / down): the outputs of a complete stream of n samples; 0 when the slot is unset or n < 1.
+ *   nvw_resample         `count` requests (1 .. 65535) in one launch.  in: n_in samples in device memory, int16 (in_type 16) or fp32
+ *                        (32), the inputs of absolute index first .. first + n_in - 1; last: 1 when the stream ends at first + n_in.
+ *                        out: `count` samples in device memory, int16 or fp32 (out_type), the outputs m0 .. m0 + count - 1.  The range
+ *                        form is stateless, as nvw_upsample_requests is: a streaming caller keeps the tail of its input and asks for
+ *                        the outputs that have become computable, and gets bit for bit what the whole stream gives in one request.
+ *                        Nothing is written beyond out[count).  Asynchronous on `stream`: in and out stay alive until it has run.
+ *                        Works inside and outside slot mode, touches no ring, column or session.  Returns count, or 0 with nothing
+ *                        written and nothing launched: the slot is unset, count outside 1 .. 65535, a pointer not in device memory,
+ *                        a type other than 16 or 32, a non-positive n_in or count, a negative first or m0, a needed input with
+ *                        absolute index >= 0 below `first`, or a needed input at or beyond first + n_in when last is 0. */
+typedef struct {
+    const void* in; int in_type;
+    long long first; int n_in;
+    int last;
+    void* out; int out_type;
+    long long m0; int count;
+} nvw_resample_req;
+int nvw_set_resampler(nvw_engine* e, int slot, int up, int down, const double* taps, int n_taps);
+long long nvw_resample_count(nvw_engine* e, int slot, long long n);
+int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int count, void* stream);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

@@ -5,6 +5,7 @@
 #include "../../include/nv_wavenet_c.h"
 #include "analysis.hpp"
 #include "nv_wavenet.hpp"
+#include "resample.hpp"
 
 struct nvw_engine {
     virtual ~nvw_engine() {}
@@ -81,7 +82,16 @@ struct nvw_engine {
     // of the class: it lives here, and the C functions call it directly
     wn::Analysis analysis;
     int levels = 0;
+    // ... and so do the sample-rate converters (resample.hpp), four to a handle
+    wn::Resampler resamplers[4];
 };
+static_assert(sizeof(nvw_resample_req) == sizeof(wn::ResampleReq) && offsetof(nvw_resample_req, in) == offsetof(wn::ResampleReq, in) &&
+              offsetof(nvw_resample_req, in_type) == offsetof(wn::ResampleReq, inType) &&
+              offsetof(nvw_resample_req, first) == offsetof(wn::ResampleReq, first) && offsetof(nvw_resample_req, n_in) == offsetof(wn::ResampleReq, nIn) &&
+              offsetof(nvw_resample_req, last) == offsetof(wn::ResampleReq, last) && offsetof(nvw_resample_req, out) == offsetof(wn::ResampleReq, out) &&
+              offsetof(nvw_resample_req, out_type) == offsetof(wn::ResampleReq, outType) &&
+              offsetof(nvw_resample_req, m0) == offsetof(wn::ResampleReq, m0) && offsetof(nvw_resample_req, count) == offsetof(wn::ResampleReq, count),
+              "nvw_resample_req is wn::ResampleReq");
 static_assert(sizeof(nvw_analysis_req) == sizeof(wn::AnalysisReq) && offsetof(nvw_analysis_req, pcm) == offsetof(wn::AnalysisReq, pcm) &&
               offsetof(nvw_analysis_req, n) == offsetof(wn::AnalysisReq, n) && offsetof(nvw_analysis_req, mel) == offsetof(wn::AnalysisReq, mel) &&
               offsetof(nvw_analysis_req, precision) == offsetof(wn::AnalysisReq, precision) &&

@@ -517,6 +517,25 @@ int nvw_analyse(nvw_engine* e, const nvw_analysis_req* reqs, int count, void* st
     }
     return count;
 }
+// ---- sample-rate conversion: a polyphase FIR by request and output range (additive within ABI 7) ------------------------------------
+int nvw_set_resampler(nvw_engine* e, int slot, int up, int down, const double* taps, int n_taps) {
+    if (slot < 0 || slot > 3 || !e->resamplers[slot].set(up, down, taps, n_taps)) {
+        fprintf(stderr, "nvw_set_resampler: refused (slot %d: 0 .. 3; up %d and down %d: coprime, in 1 .. %d; %d taps: odd, in host memory; at "
+                "most %d bytes of LDS per workgroup)\n", slot, up, down, wn::kResampleFactorMax, n_taps, wn::kResampleLdsMax);
+        return 0;
+    }
+    return 1;
+}
+long long nvw_resample_count(nvw_engine* e, int slot, long long n) { return slot < 0 || slot > 3 ? 0 : e->resamplers[slot].count(n); }
+int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int count, void* stream) {
+    if (slot < 0 || slot > 3 || !e->resamplers[slot].run((const wn::ResampleReq*)reqs, count, (hipStream_t)stream)) {
+        fprintf(stderr, "nvw_resample: refused, nothing written (nvw_set_resampler on slot %d first; %d requests of 1 .. 65535; in and out in "
+                "device memory, types 16 or 32; n_in, count > 0, first, m0 >= 0; every needed input of index >= 0 within [first, first + "
+                "n_in), or past it with last = 1)\n", slot, count);
+        return 0;
+    }
+    return count;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

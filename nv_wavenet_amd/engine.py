@@ -50,6 +50,10 @@ SCORE_CHUNK_MEL_REQ = np.dtype({"names": ["state", "y", "n", "mel", "precision",
 ANALYSIS_REQ = np.dtype({"names": ["pcm", "n", "mel", "precision", "c_stride", "f_stride", "y"],
                          "formats": ["<u8", "<i4", "<u8", "<i4", "<i8", "<i8", "<u8"],
                          "offsets": [0, 8, 16, 24, 32, 40, 48], "itemsize": 56})
+# ... nvw_resample_req of nvw_resample
+RESAMPLE_REQ = np.dtype({"names": ["in", "in_type", "first", "n_in", "last", "out", "out_type", "m0", "count"],
+                         "formats": ["<u8", "<i4", "<i8", "<i4", "<i4", "<u8", "<i4", "<i8", "<i4"],
+                         "offsets": [0, 8, 16, 24, 28, 32, 40, 48, 56], "itemsize": 64})
 
 
 class Impl:
@@ -942,6 +946,37 @@ class WavenetEngine:
             reqs[i] = (pcm.data_ptr(), pcm.numel(), 0 if mel is None else mel.data_ptr(), bits, sc, sf, 0 if y is None else y.data_ptr())
         if n == 0 or lib.nvw_analyse(self._h, reqs.ctypes.data, n, stream) != n:
             raise ValueError("nvw_analyse refused %d requests" % n)
+
+    # ---- sample-rate conversion (include/nv_wavenet_c.h, "SAMPLE-RATE CONVERSION") ----
+    def setResampler(self, slot, up, down, taps):
+        """Resampler `slot` (0 .. 3) of this engine: the factors up / down (coprime, 1 .. 640) and the prototype taps (an odd number
+        of float64, numpy or torch, copied; nv_wavenet.resample_taps designs them).  ValueError when refused (the slot's previous
+        contents stay): see nvw_set_resampler."""
+        h = np.ascontiguousarray(taps.detach().cpu().numpy() if hasattr(taps, "detach") else taps, dtype=np.float64)
+        if h.ndim != 1 or not lib.nvw_set_resampler(self._h, int(slot), int(up), int(down), h.ctypes.data, h.size):
+            raise ValueError("nvw_set_resampler refused slot %d, %d / %d, taps %s" % (slot, up, down, h.shape))
+
+    def resampleCount(self, slot, n):
+        """Outputs of a complete stream of n samples, ceil(n up / down); 0 when the slot is unset."""
+        return int(lib.nvw_resample_count(self._h, int(slot), int(n)))
+
+    def resample(self, slot, requests, stream=None):
+        """Sample-rate conversion by resampler `slot`, one launch: requests = [(x, first, last, out, m0), ...] with x a contiguous
+        1-D int16 or float32 CUDA tensor, the inputs of absolute index first .. first + len(x) - 1 of its stream (last: the stream
+        ends there), and out a contiguous 1-D int16 or float32 CUDA tensor that receives the outputs m0 .. m0 + len(out) - 1.
+        Asynchronous on `stream`.  ValueError when refused (nothing written): see nvw_resample."""
+        import torch
+        bits = {torch.int16: 16, torch.float32: 32}
+        requests = list(requests)
+        n = len(requests)
+        reqs = np.zeros(max(n, 1), dtype=RESAMPLE_REQ)
+        for i, (x, first, last, out, m0) in enumerate(requests):
+            for t in (x, out):
+                if not hasattr(t, "data_ptr") or t.dim() != 1 or t.dtype not in bits or not t.is_contiguous() or not t.is_cuda:
+                    raise ValueError("samples are contiguous 1-D int16 or float32 CUDA tensors")
+            reqs[i] = (x.data_ptr(), bits[x.dtype], int(first), x.numel(), 1 if last else 0, out.data_ptr(), bits[out.dtype], int(m0), out.numel())
+        if n == 0 or lib.nvw_resample(self._h, int(slot), reqs.ctypes.data, n, stream) != n:
+            raise ValueError("nvw_resample refused %d requests" % n)
 
     # ---- scoring with carried state (include/nv_wavenet_c.h, "SCORING WITH CARRIED STATE"; DESIGN.md §6l) ----
     def _score_chunks(self, requests, mel, rows, states, pinned, stream, out=None):

@@ -341,6 +341,67 @@ def get_cond_input(features, upsample_weight, upsample_bias, upsample_stride, co
     return (x if dtype is None else x.to(dtype)).contiguous()
 
 
+def resample_taps(rate_in, rate_out, zeros=16, rolloff=0.945, beta=14.77):
+    """The default prototype filter of NVWaveNetEngine.resample: returns (L, M, taps) with L / M = rate_out / rate_in
+    in lowest terms and taps a float64 array of T = 2 zeros max(L, M) + 1 values at rate L rate_in -- a Kaiser-windowed sinc with
+    its cutoff at rolloff x 0.5 / max(L, M) of that rate (rolloff x the lower of the two Nyquist frequencies), symmetric about
+    its centre (T - 1) / 2, the gain L of the zero-stuffing folded in.  The defaults are settings, not measurements: rolloff and
+    beta are those of resampy's "kaiser_best" filter (0.9476, 14.7697), which torchaudio documents as its equivalent setting;
+    zeros = 16 zero crossings a side is a quarter of that filter's 64, a shorter filter for a wider transition band."""
+    import math
+    import numpy as np
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in < 1 or rate_out < 1 or int(zeros) < 1:
+        raise ValueError("rates and zeros are positive integers")
+    g = math.gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    big = max(L, M)
+    T = 2 * int(zeros) * big + 1
+    fc = float(rolloff) * 0.5 / big
+    k = np.arange(T, dtype=np.float64) - (T - 1) // 2
+    return L, M, L * 2 * fc * np.sinc(2 * fc * k) * np.kaiser(T, float(beta))
+
+
+class ResampleStream:
+    """Streaming side of NVWaveNetEngine.resample (resample_stream makes it): feed(chunk, last=False) takes the next samples
+    [batch][k] (or [k] for a batch of 1) of `batch` streams that advance together and returns the outputs that have become
+    computable, [batch][count] (count may be 0).  Holds the tail of the input that later outputs still need and the two absolute
+    counters; any chunking of a signal gives the outputs of the whole-signal call bit for bit."""
+
+    def __init__(self, model, rate_in, rate_out, batch, out_dtype, taps):
+        self._model, self._rates, self._taps = model, (rate_in, rate_out), taps
+        self.L, self.M, self._centre = model._resampler(rate_in, rate_out, taps)[2:]
+        self.batch, self.out_dtype = int(batch), out_dtype
+        self.fed = self.done = 0            # inputs taken, outputs given
+        self._tail, self._first = None, 0   # [batch][k]: the inputs of absolute index _first .. fed - 1
+        self.finished = False
+
+    def feed(self, chunk, last=False):
+        if self.finished:
+            raise ValueError("the stream has ended")
+        chunk = chunk.view(1, -1) if chunk.dim() == 1 else chunk
+        if chunk.dim() != 2 or chunk.size(0) != self.batch or not chunk.is_cuda or chunk.dtype not in (torch.int16, torch.float32):
+            raise ValueError("a chunk is an int16 or float32 CUDA tensor [batch = %d][k]" % self.batch)
+        buf = chunk if self._tail is None else torch.cat((self._tail, chunk), dim=1)
+        self.fed += chunk.size(1)
+        L, M, c = self.L, self.M, self._centre
+        # out[m] needs the inputs up to floor((m M + c) / L): computable while that is below `fed`, or all of them at the end
+        end = -(-self.fed * L // M) if last else max(0, (self.fed * L - c - 1) // M + 1)
+        count = max(0, end - self.done)
+        out = torch.zeros((self.batch, count), dtype=self.out_dtype, device=chunk.device)
+        if count and buf.size(1):
+            e, slot = self._model._resampler(*self._rates, self._taps)[:2]
+            buf = buf.contiguous()
+            e.resample(slot, [(buf[b], self._first, last, out[b], self.done) for b in range(self.batch)],
+                       stream=torch.cuda.current_stream(chunk.device).cuda_stream)
+            self.done = end
+        self.finished = bool(last)
+        # the next output needs the inputs from ceil((done M - c) / L) on
+        keep = min(self.fed, max(self._first, -((c - self.done * M) // L)))
+        self._tail, self._first = buf[:, keep - self._first:], keep
+        return out
+
+
 class NVWaveNetEngine(NVWaveNet):
     """The same wrapper with the engine kept alive: the reference rebuilds
     its nvWavenetInfer object and re-uploads every weight on each infer() (wavenet_infer.cu:124-143).
@@ -416,6 +477,53 @@ class NVWaveNetEngine(NVWaveNet):
         for e in self._engines.values():
             e.close()
         self._engines = {}
+        if getattr(self, "_resample_engine", None) is not None:
+            self._resample_engine.close()
+            self._resample_engine = None
+
+    def _resampler(self, rate_in, rate_out, taps=None):
+        """(engine, slot, L, M, centre) of a ratio and its taps (None: resample_taps' default design).  The conversions have a
+        small engine of their own, which no generation evicts; its four slots are cached per ratio, least recently used first out."""
+        L, M, design = resample_taps(rate_in, rate_out)
+        if taps is not None:
+            import numpy as np
+            design = np.ascontiguousarray(taps.detach().cpu().numpy() if hasattr(taps, "detach") else taps, dtype=np.float64)
+        key = (L, M, None if taps is None else design.tobytes())
+        if getattr(self, "_resample_engine", None) is None:
+            self._resample_engine, self._resample_slots = self._new_engine(1, 64, Impl.AUTO), {}
+        e, slots = self._resample_engine, self._resample_slots
+        slot = slots.pop(key, None)
+        if slot is None:
+            slot = next(s for s in range(4) if s not in slots.values()) if len(slots) < 4 else slots.pop(next(iter(slots)))
+            e.setResampler(slot, L, M, design)
+        slots[key] = slot                   # (re-)inserted last: most recently used
+        return e, slot, L, M, (len(design) - 1) // 2
+
+    def resample(self, pcm, rate_in, rate_out, lengths=None, out_dtype=torch.int16, taps=None):
+        """Sample-rate conversion on the GPU (nvw_resample): pcm = int16 or float32 [batch][n] on the GPU, in PCM
+        units; lengths: None (all n), or `batch` values in 1 .. n.  Returns [batch][ceil(n L / M)] of out_dtype (torch.int16:
+        rounded to nearest-even and saturated; torch.float32), L / M = rate_out / rate_in in lowest terms, in one launch for the
+        whole batch: utterance b's ceil(lengths[b] L / M) outputs, zero past them.  taps: None (resample_taps(rate_in, rate_out)),
+        or an odd number of float64 prototype taps at rate L rate_in.  ValueError for a bad shape, type, length or filter."""
+        if pcm.dim() != 2 or pcm.dtype not in (torch.int16, torch.float32) or not pcm.is_cuda or pcm.size(1) < 1 or \
+                out_dtype not in (torch.int16, torch.float32):
+            raise ValueError("pcm: an int16 or float32 CUDA tensor [batch][n], out_dtype torch.int16 or torch.float32")
+        batch_size, n = pcm.shape
+        lengths = [n] * batch_size if lengths is None else [int(k) for k in lengths]
+        if len(lengths) != batch_size or not all(0 < k <= n for k in lengths):
+            raise ValueError("lengths: %d values in 1 .. %d" % (batch_size, n))
+        e, slot, L, M, _ = self._resampler(rate_in, rate_out, taps)
+        pcm = pcm.contiguous()
+        out = torch.zeros((batch_size, -(-n * L // M)), dtype=out_dtype, device=pcm.device)
+        e.resample(slot, [(pcm[b, :lengths[b]], 0, True, out[b, :-(-lengths[b] * L // M)], 0) for b in range(batch_size)],
+                   stream=torch.cuda.current_stream(pcm.device).cuda_stream)
+        return out
+
+    def resample_stream(self, rate_in, rate_out, batch=1, out_dtype=torch.int16, taps=None):
+        """A ResampleStream: resample() step by step, for callers that convert delivered PCM as it arrives (slot mode).  Its
+        feed(chunk, last=False) returns the outputs that have become computable; the concatenation over any chunking is bit for
+        bit what resample() returns for the whole signal."""
+        return ResampleStream(self, rate_in, rate_out, batch, out_dtype, taps)
 
     def cond_tiles(self, batch_size, sample_count, implementation=Impl.AUTO):
         """condTiles() of the engine that infer() will use for this batch and utterance length (for layout "packed")."""
@@ -574,21 +682,37 @@ class NVWaveNetEngine(NVWaveNet):
         return self._score(mel, mel.size(2) * int(upsample_stride), up, cond_weight, cond_bias, samples, lengths, temperature, return_rows,
                            chunk, return_state)
 
-    def set_analysis(self, n_fft, hop, mel_basis):
+    def set_analysis(self, n_fft, hop, mel_basis, sample_rate=None):
         """The geometry of analyse() / score_audio(): Tacotron-2's mel_spectrogram with filter_length = win_length =
-        n_fft, hop_length = hop, and mel_basis [n_mel][n_fft / 2 + 1] (a weight of the caller's, as the upsampling is)."""
+        n_fft, hop_length = hop, and mel_basis [n_mel][n_fft / 2 + 1] (a weight of the caller's, as the upsampling is).
+        sample_rate: None, or the model's rate in Hz, which lets analyse() and score_audio() take recordings at another rate."""
         basis = mel_basis.detach().float().cpu().contiguous()
         if basis.dim() != 2 or basis.size(1) != int(n_fft) // 2 + 1:
             raise ValueError("mel_basis: [n_mel][n_fft / 2 + 1], got %s" % (tuple(basis.shape),))
         self._analysis = (int(n_fft), int(hop), basis)
+        self._analysis_rate = None if sample_rate is None else int(sample_rate)
 
-    def analyse(self, pcm, lengths=None):
+    def _at_model_rate(self, pcm, lengths, rate):
+        """(pcm, lengths) of analyse() resampled from `rate` to set_analysis' sample_rate; as given for rate None or
+        the model's own."""
+        if rate is None or int(rate) == getattr(self, "_analysis_rate", None):
+            return pcm, lengths
+        if getattr(self, "_analysis_rate", None) is None:
+            raise ValueError("rate= needs set_analysis(..., sample_rate=)")
+        L, M, _ = resample_taps(rate, self._analysis_rate)
+        out = self.resample(pcm, rate, self._analysis_rate, lengths=lengths)
+        return out, None if lengths is None else [-(-int(k) * L // M) for k in lengths]
+
+    def analyse(self, pcm, lengths=None, rate=None):
         """Audio to what scoring and priming take (nvw_analyse): pcm = int16 [batch][n] on the GPU; lengths: None (all
         n), or `batch` values in n_fft / 2 + 1 .. n.  Returns (mel [batch][n_mel][n // hop + 1] in the engine's precision, y
         [batch][n] int32), on the GPU, in one launch for the whole batch: utterance b's first lengths[b] // hop + 1 frames and
-        lengths[b] samples, zero past them.  Needs set_analysis; ValueError for a bad shape or length."""
+        lengths[b] samples, zero past them.  Needs set_analysis; ValueError for a bad shape or length.
+        rate: None, or the recording's rate in Hz: where it differs from set_analysis' sample_rate, what is analysed is
+        resample(pcm, rate, sample_rate, lengths) with its lengths, and n and lengths above are those after the conversion."""
         if getattr(self, "_analysis", None) is None:
             raise ValueError("analyse needs set_analysis")
+        pcm, lengths = self._at_model_rate(pcm, lengths, rate)
         n_fft, hop, basis = self._analysis
         if pcm.dim() != 2 or pcm.dtype != torch.int16 or not pcm.is_cuda:
             raise ValueError("pcm: an int16 CUDA tensor [batch][n], got %s %s" % (pcm.dtype, tuple(pcm.shape)))
@@ -611,14 +735,16 @@ class NVWaveNetEngine(NVWaveNet):
         return mel, y
 
     def score_audio(self, pcm, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, lengths=None, temperature=None,
-                    return_rows=False, chunk=None, return_state=False):
+                    return_rows=False, chunk=None, return_state=False, rate=None):
         """score_mel() of a recording: analyse(pcm, lengths), then score_mel on its frames and samples, and nothing else.  The
-        analysis' hop must be the upsampling's stride and its n_mel the upsampling's input channels (ValueError otherwise)."""
+        analysis' hop must be the upsampling's stride and its n_mel the upsampling's input channels (ValueError otherwise).
+        rate: as for analyse(): a recording at another rate is resampled to the model's first."""
         if getattr(self, "_analysis", None) is None:
             raise ValueError("score_audio needs set_analysis")
         if self._analysis[1] != int(upsample_stride) or self._analysis[2].size(0) != upsample_weight.size(0):
             raise ValueError("the analysis has hop %d and %d channels, the upsampling stride %d and %d" %
                              (self._analysis[1], self._analysis[2].size(0), int(upsample_stride), upsample_weight.size(0)))
+        pcm, lengths = self._at_model_rate(pcm, lengths, rate)
         mel, y = self.analyse(pcm, lengths)
         return self.score_mel(mel, upsample_weight, upsample_bias, upsample_stride, cond_weight, cond_bias, y, lengths=lengths,
                               temperature=temperature, return_rows=return_rows, chunk=chunk, return_state=return_state)
