@@ -815,6 +815,54 @@ int nvw_set_resampler(nvw_engine* e, int slot, int up, int down, const double* t
 long long nvw_resample_count(nvw_engine* e, int slot, long long n);
 int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int count, void* stream);
 
+/* SLOT MODE: RAGGED DELIVERY AT THE CALLER'S SAMPLE RATE (additive within ABI 7).  nvw_slots_step_ragged delivers PCM at the model's
+ * rate; a caller who delivers at 8, 16, 44.1 or 48 kHz would take every piece back and resample it per utterance and per step.  A
+ * rate step converts while it delivers: one launch writes, for every piece, the outputs of its utterance that this
+ * step's samples complete, and carries each utterance's filter history across steps, moves and suspensions.
+ * An utterance's stream is x[i] = PCM of its local sample i (nvw_slot_piece.first counts i), zero below 0 and, once the utterance is
+ * finished, from its end on; outputs follow the definition of nvw_resample with the taps of the chosen resampler slot, centre c.
+ * After k samples of an unfinished utterance D(k) = max(0, ceil((k L - c) / M)) outputs are deliverable (those whose every input is
+ * below k); a finished one of length n has ceil(n L / M).  The piece with first = f and n samples carries m0 = D(f) and count =
+ * D(f + n) - m0, or ceil((f + n) L / M) - m0 when it finishes the utterance; count may be 0.  An utterance's pieces, concatenated,
+ * are bit for bit nvw_resample of its whole PCM with last = 1, however the steps cut it.
+ * The history of a column is H = ceil(2 c / L) int16 values: the last H PCM values of its utterance, zero where it has none.
+ *   nvw_slots_set_delivery      resampler 0 .. 3: rate delivery through that slot of nvw_set_resampler; -1: off (the default;
+ *                               nvw_slots_begin and nvw_slots_end turn it off).  Every column's history starts at zero, a running
+ *                               column's too.  While it is on, nvw_slots_step and nvw_slots_step_ragged are refused (they would
+ *                               leave a hole in every history) and nvw_set_resampler refuses that slot.  Synchronises.  Returns 1;
+ *                               0 with nothing changed: not in slot mode, a slot that is not set, or a ragged step in flight.
+ *   nvw_slots_tail_len          H; -1 when delivery is off.
+ *   nvw_slots_rate_capacity     PCM elements that always suffice for a rate step of `count`; -1 when delivery is off.
+ *   nvw_slots_step_ragged_rate  nvw_slots_step_ragged with the PCM side converted: the same launches up to and including the
+ *                               generation, the same pieces, the same optional int32 `samples` (capacity elements; NULL: not wanted)
+ *                               at the pieces' offsets, the same ticket; never synchronises.  The PCM goes to `pcm` (int16, device
+ *                               or pinned, pcm_capacity elements): entry p of rate[0 .. *n_pieces) (host, parallel to pieces) says
+ *                               that piece p carries outputs m0 .. m0 + count - 1 at element `offset`; offsets are packed, each
+ *                               rounded up to 8 elements, the gaps are not written.  Returns the end of the last sample piece and
+ *                               *pcm_total the end of the last PCM piece; -2 as nvw_slots_step_ragged; -1 with nothing launched:
+ *                               what nvw_slots_step_ragged refuses, delivery off, pcm NULL or not device / pinned memory, or
+ *                               pcm_capacity too small (pieces and rate are then written, nothing else has changed).
+ *   nvw_slot_tail_get / _set    a column's history, H int16 values, to dst / from src (host or device memory): for save and resume.
+ *                               Get it after the step that nvw_slot_save follows; set it after nvw_slot_resume (any start puts
+ *                               the column's history back to zero).  A resumed column whose history is not set goes on with m0 =
+ *                               D(done) from a zero history: a discontinuity in the first H L / M + 1 outputs after the seam.
+ *                               nvw_slot_move carries the history (no launch).  Blocking copies on the null stream, ordered as the
+ *                               header read of nvw_slot_resume.  Return 1; 0: delivery off, or a column without an utterance. */
+typedef struct {
+    long long m0;
+    int count;
+    int pad;
+    long long offset;
+} nvw_slot_rate_piece;
+int nvw_slots_set_delivery(nvw_engine* e, int resampler);
+int nvw_slots_tail_len(nvw_engine* e);
+long long nvw_slots_rate_capacity(nvw_engine* e, int count);
+long long nvw_slots_step_ragged_rate(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                     nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces, long long* pcm_total,
+                                     unsigned long long* ticket, void* stream);
+int nvw_slot_tail_get(nvw_engine* e, int slot, short* dst);
+int nvw_slot_tail_set(nvw_engine* e, int slot, const short* src);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

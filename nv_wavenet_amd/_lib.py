@@ -98,7 +98,14 @@ SIGNATURES = {
     "nvw_slots_resume_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _fp, C.c_longlong]),
     "nvw_slots_step_ragged": (C.c_longlong, [C.c_void_p, C.c_int, _fp, _fp, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                              C.POINTER(C.c_ulonglong), C.c_void_p]),
-    "nvw_slots_time_outputs": (C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),
+    "nvw_slots_set_delivery": (C.c_int, [C.c_void_p, C.c_int]),
+    "nvw_slots_tail_len": (C.c_int, [C.c_void_p]),
+    "nvw_slots_rate_capacity": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "nvw_slots_step_ragged_rate": (C.c_longlong, [C.c_void_p, C.c_int, _fp, C.c_longlong, _fp, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_void_p]),
+    "nvw_slot_tail_get": (C.c_int, [C.c_void_p, C.c_int, _fp]),
+    "nvw_slot_tail_set": (C.c_int, [C.c_void_p, C.c_int, _fp]),
+    "nvw_slots_time_outputs":(C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),
     "nvw_slots_wait": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "nvw_slots_done": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "nvw_set_temperatures": (C.c_int, [C.c_void_p, _fp, C.c_int]),

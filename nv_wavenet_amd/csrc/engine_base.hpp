@@ -103,6 +103,10 @@ static_assert(sizeof(nvw_slot_piece) == sizeof(wn::SlotPiece) && offsetof(nvw_sl
               offsetof(nvw_slot_piece, first) == offsetof(wn::SlotPiece, first) &&
               offsetof(nvw_slot_piece, n) == offsetof(wn::SlotPiece, n) && offsetof(nvw_slot_piece, offset) == offsetof(wn::SlotPiece, offset),
               "nvw_slot_piece is wn::SlotPiece");
+static_assert(sizeof(nvw_slot_rate_piece) == sizeof(wn::SlotRatePiece) && offsetof(nvw_slot_rate_piece, m0) == offsetof(wn::SlotRatePiece, m0) &&
+              offsetof(nvw_slot_rate_piece, count) == offsetof(wn::SlotRatePiece, count) &&
+              offsetof(nvw_slot_rate_piece, offset) == offsetof(wn::SlotRatePiece, offset),
+              "nvw_slot_rate_piece is wn::SlotRatePiece");
 
 static_assert(sizeof(nvw_slot_saved) == sizeof(wn::SlotSaved) && offsetof(nvw_slot_saved, slot) == offsetof(wn::SlotSaved, slot) &&
               offsetof(nvw_slot_saved, uid) == offsetof(wn::SlotSaved, uid) && offsetof(nvw_slot_saved, done) == offsetof(wn::SlotSaved, done) &&

@@ -2,6 +2,8 @@
 // types are a conversion at the staging and at the store.
 #include "resample.hpp"
 
+#include "resample_core.hpp"
+
 #include <string.h>
 
 #include <vector>
@@ -10,31 +12,20 @@ namespace wn {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int kResampleWaves = 4, kResampleThreads = 64 * kResampleWaves;
-constexpr int kResampleTilesMax = 5;      // row tiles a wave holds at a time (G = 1): five accumulators, five operand fragments in flight
-
 inline int round16(long long v) { return (int)(16 * ((v + 15) / 16)); }
 
 struct ResampleArgs {
     const ResampleJob* jobs;
     int count;
-    const floatx4* tab;
-    int Q, hop;
-    int j0;
-    int nq;                  // W' / 16: operand fragments of a row tile
-    int rowTiles;
-    int spare;               // s
+    ResampleTab t;
 };
 
-// G: 16-block groups of a workgroup (4: every wave its own group and all CH = rowTiles row tiles; 1: row tile t belongs to wave t & 3,
-// CH of a wave's tiles per pass over the span).
+// G, CH: as resample_tile_gemm (resample_core.hpp)
 template <int G, int CH>
 __global__ __launch_bounds__(kResampleThreads) void resample_kernel(const ResampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) float span[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, fl = lane & 15;
-    const int hop = a.hop, spare = a.spare;
+    const int tid = threadIdx.x;
+    const int hop = a.t.hop, spare = a.t.spare;
 
     // this workgroup's request by bisection of the first tiles, and its tile of it
     int lo = 0, hi = a.count - 1;
@@ -48,8 +39,8 @@ __global__ __launch_bounds__(kResampleThreads) void resample_kernel(const Resamp
     // its blocks of the range: ti * 16 G + (0 .. live), and the span that they read: inputs i0 + (0 .. span_n)
     const int left = jb.blocks - ti * 16 * G, live = left < 16 * G ? left : 16 * G;
     const long long blk0 = jb.block0 + (long long)ti * 16 * G;
-    const long long i0 = blk0 * hop + a.j0;
-    const int span_n = (live - 1) * hop + 16 * a.nq;
+    const long long i0 = blk0 * hop + a.t.j0;
+    const int span_n = (live - 1) * hop + 16 * a.t.nq;
     for (int l = tid; l < span_n; l += kResampleThreads) {
         const long long rel = i0 + l - jb.first;      // (first >= 0: an index below zero is below first)
         float v = 0.f;
@@ -58,58 +49,13 @@ __global__ __launch_bounds__(kResampleThreads) void resample_kernel(const Resamp
     }
     __syncthreads();
 
-    const int grp = G == 4 ? w : 0;
-    if (grp * 16 >= live) return;
-    // (a block lane past the last live block reads the last one's inputs, and is not stored)
-    const int col = grp * 16 + fl, src = col < live ? col : live - 1;
-    const float* const bp = span + src * (hop + spare) + g;
-    const floatx4* const tab = a.tab + lane;
-    const int nq = a.nq, nrt = a.rowTiles;
-    const long long mBlock = (blk0 + col) * a.Q - jb.m0;      // the block's first output, relative to the range
-    for (int first = G == 4 ? 0 : w; first < nrt; first += (G == 4 ? 1 : 4) * CH) {
-        floatx4 acc[CH];
-        size_t at[CH];                                  // (a tile past the last repeats the last, and is not stored)
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-            acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
-            const int t = first + (G == 4 ? 1 : 4) * i;
-            at[i] = (size_t)(t < nrt ? t : nrt - 1) * nq * 64;
-        }
-        // input j = 16 qd + 4 e + g of the block lies pad = s (j / hop) words past bp[16 qd + 4 e]: rem = j mod hop, stepped by 4 <= hop
-        int rem = g, pad = 0;
-        for (int qd = 0; qd < nq; qd++) {
-            floatx4 af[CH];
-#pragma unroll
-            for (int i = 0; i < CH; i++) af[i] = tab[at[i] + (size_t)qd * 64];
-            float b[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                b[e] = bp[16 * qd + 4 * e + pad];
-                rem += 4;
-                const bool wrap = rem >= hop;
-                rem -= wrap ? hop : 0;
-                pad += wrap ? spare : 0;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-#pragma unroll
-                for (int i = 0; i < CH; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][e], b[e], acc[i], 0, 0, 0);
-        }
-        // outputs 16 t + 4 g + r of block `col`, those of the range only
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-            const int t = first + (G == 4 ? 1 : 4) * i;
-            if (t >= nrt || col >= live) continue;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int p = t * 16 + 4 * g + r;
-                const long long o = mBlock + p;
-                if (p >= a.Q || o < 0 || o >= jb.count) continue;
-                if (jb.outType == 16) ((short*)jb.out)[o] = (short)(int)fminf(fmaxf(rintf(acc[i][r]), -32768.f), 32767.f);
-                else ((float*)jb.out)[o] = acc[i][r];
-            }
-        }
-    }
+    // outputs of the range only
+    resample_tile_gemm<G, CH>(span, a.t, live, [&](int col, int p, float v) {
+        const long long o = (blk0 + col) * a.t.Q - jb.m0 + p;
+        if (o < 0 || o >= jb.count) return;
+        if (jb.outType == 16) ((short*)jb.out)[o] = resample_pcm16(v);
+        else ((float*)jb.out)[o] = v;
+    });
 }
 
 template <int G, int CH>
@@ -119,6 +65,15 @@ bool launchResample(const ResampleArgs& a, int tiles, size_t lds, hipStream_t st
     hipLaunchKernelGGL((resample_kernel<G, CH>), dim3(tiles), dim3(kResampleThreads), lds, stream, a);
     return hipGetLastError() == hipSuccess;
 }
+
+struct ResampleLaunch {
+    const ResampleArgs& a;
+    int tiles;
+    size_t lds;
+    hipStream_t stream;
+    bool optIn;
+    template <int G, int CH> bool run() const { return launchResample<G, CH>(a, tiles, lds, stream, optIn); }
+};
 
 int gcd(int a, int b) { return b == 0 ? a : gcd(b, a % b); }
 // floor and ceiling of a / b, b > 0, for a of either sign
@@ -187,6 +142,24 @@ bool Resampler::set(int up, int down, const double* taps, int nTaps) {
     return true;
 }
 
+ResampleTab Resampler::tab() const {
+    ResampleTab t;
+    t.tab = (const floatx4*)m_tab;
+    t.Q = m_g.Q;
+    t.hop = m_g.hop;
+    t.j0 = m_g.j0;
+    t.nq = m_g.wp / 16;
+    t.rowTiles = m_g.rowTiles;
+    t.spare = m_g.spare;
+    return t;
+}
+
+// G = 1: a wave's row tiles in the fewest passes of at most kResampleTilesMax, and evenly over those
+int Resampler::tilesPerPass() const {
+    const int perWave = (m_g.rowTiles + kResampleWaves - 1) / kResampleWaves, passes = (perWave + kResampleTilesMax - 1) / kResampleTilesMax;
+    return m_g.groups == 4 ? m_g.rowTiles : (perWave + passes - 1) / passes;
+}
+
 bool Resampler::acceptable(const ResampleReq* reqs, int count) const {
     if (!ready() || reqs == NULL || count < 1 || count > 65535) return false;
     const long long kIndexMax = 1LL << 50;      // (index x factor stays far from overflow)
@@ -247,31 +220,10 @@ bool Resampler::run(const ResampleReq* reqs, int count, hipStream_t stream) {
     ResampleArgs a;
     a.jobs = dev;
     a.count = count;
-    a.tab = (const floatx4*)m_tab;
-    a.Q = m_g.Q;
-    a.hop = m_g.hop;
-    a.j0 = m_g.j0;
-    a.nq = m_g.wp / 16;
-    a.rowTiles = m_g.rowTiles;
-    a.spare = m_g.spare;
+    a.t = tab();
     const size_t lds = 4 * (size_t)m_g.spanWords;
-    // G = 1: a wave's row tiles in the fewest passes of at most kResampleTilesMax, and evenly over those
-    const int perWave = (m_g.rowTiles + kResampleWaves - 1) / kResampleWaves, passes = (perWave + kResampleTilesMax - 1) / kResampleTilesMax;
-    const int ch = m_g.groups == 4 ? m_g.rowTiles : (perWave + passes - 1) / passes;
     const bool optIn = !m_ldsReady;      // (per engine, hence per device: the attribute belongs to the device's copy of the kernel)
-    bool ok = false;
-    if (m_g.groups == 4) switch (ch) {
-            case 1: ok = launchResample<4, 1>(a, tiles, lds, stream, optIn); break;
-            case 2: ok = launchResample<4, 2>(a, tiles, lds, stream, optIn); break;
-            default: ok = launchResample<4, 3>(a, tiles, lds, stream, optIn); break;
-        }
-    else switch (ch) {
-            case 1: ok = launchResample<1, 1>(a, tiles, lds, stream, optIn); break;
-            case 2: ok = launchResample<1, 2>(a, tiles, lds, stream, optIn); break;
-            case 3: ok = launchResample<1, 3>(a, tiles, lds, stream, optIn); break;
-            case 4: ok = launchResample<1, 4>(a, tiles, lds, stream, optIn); break;
-            default: ok = launchResample<1, 5>(a, tiles, lds, stream, optIn); break;
-        }
+    const bool ok = resample_dispatch(m_g.groups, tilesPerPass(), ResampleLaunch{a, tiles, lds, stream, optIn});
     if (ok) m_ldsReady = true;
     return ok;
 }

@@ -74,6 +74,7 @@ struct ResampleGeom {
     long long spanWords;     // words of LDS: (16 G - 1) hop + W' + s (that / hop + 1)
 };
 ResampleGeom resampleGeom(int up, int down, int nTaps);
+struct ResampleTab;      // (resample_core.hpp)
 
 // The engine-owned side: the table of one ratio and the requests' staging.  Calls of one engine are issued on one stream, or ordered
 // by the caller.
@@ -93,6 +94,14 @@ public:
     bool acceptable(const ResampleReq* reqs, int count) const;
     // count requests in one launch, asynchronously on `stream`.  false with nothing written or launched: a refused request.
     bool run(const ResampleReq* reqs, int count, hipStream_t stream);
+    // what another kernel over the same table needs (slot mode's rate delivery, slots_deliver_rate.hpp): the factors, the centre,
+    // the geometry, the table as the GEMM core reads it, and CH of the kernel variant (resample_core.hpp)
+    int up() const { return m_up; }
+    int down() const { return m_down; }
+    int centre() const { return m_centre; }
+    const ResampleGeom& geom() const { return m_g; }
+    ResampleTab tab() const;
+    int tilesPerPass() const;
 
 private:
     void clear();

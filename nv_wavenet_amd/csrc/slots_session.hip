@@ -1,6 +1,8 @@
 // slots_session.hip -- wn::SlotSession and wn::StageRing (slots_session.hpp): the host half of slot mode.  Compiled once.
 #include "slots_session.hpp"
 
+#include "resample.hpp"
+
 namespace wn {
 
 namespace {
@@ -99,6 +101,9 @@ bool SlotSession::begin(int window) {
     m_slotResume.assign(f.maxBatch, NULL);
     m_slotResumeDone.assign(f.maxBatch, 0);
     m_slotMoveEnd.assign(f.maxBatch, 0);
+    m_tailRow.resize(f.maxBatch);
+    for (int b = 0; b < f.maxBatch; b++) m_tailRow[b] = b;
+    m_tailZero.assign(f.maxBatch, 1);
     m_temps.reset(false);      // (every column at T = 1, floor 0 and no cut, a lockstep run's values included)
     m_primeY.clear();
     m_primeN.clear();
@@ -131,6 +136,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     d.uid = uid;
     d.precision = precision;
     d.active = 1;
+    m_tailZero[slot] = 1;      // (a new utterance has no history; a resumed one's is set after this: slotTailSet)
     slotMarkPending(slot, 1);
     slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
@@ -163,6 +169,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     melMarkDirty(slot);
     m_melTilesDirty = true;
     m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
+    m_tailZero[slot] = 1;
     slotMarkPending(slot, 1);
     slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
@@ -220,6 +227,8 @@ bool SlotSession::move(int from, int to) {
     m_slotMoveEnd[from] = 1;
     m_slotMoveEnd[to] = 2;
     m_slotMoves.push_back(SlotMove{from, to});
+    std::swap(m_tailRow[from], m_tailRow[to]);      // (the filter history goes with the utterance: two host integers, no launch)
+    std::swap(m_tailZero[from], m_tailZero[to]);
     slotSamplingSet(to, m_temps.get(from));
     slotSamplingSet(from, Sampling{});      // (as stop())
     if (primed(from)) {
@@ -363,7 +372,7 @@ bool SlotSession::getFeatures(void* dst, long long first, int count) {
     return true;
 }
 bool SlotSession::step(int count, int* yOut, short* pcm, hipStream_t stream) {
-    if (m_slotW <= 0 || count <= 0 || count > m_slotW) return false;
+    if (m_slotW <= 0 || count <= 0 || count > m_slotW || m_rate) return false;
     if (m_melColumns > 0 && (m_host.slotLive().upStride <= 0 || count > headroom())) return false;      // (mel columns short of frames)
     const int T = (int)(m_slotCounter % m_slotW);
     int cols = 0;
@@ -465,7 +474,7 @@ int SlotSession::slotPieces(int count, SlotPiece* out, int maxOut, long long& to
 long long SlotSession::stepRagged(int count, int* samples, short* pcm, long long capacity, SlotPiece* pieces, int maxPieces, int* nPieces,
                                   unsigned long long* ticket, hipStream_t stream) {
     if (m_slotW <= 0 || count <= 0 || count > m_slotW || (samples == NULL && pcm == NULL) || pieces == NULL || nPieces == NULL ||
-        ticket == NULL)
+        ticket == NULL || m_rate)
         return -1;
     const int upStride = m_host.slotLive().upStride;
     if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
@@ -486,6 +495,140 @@ long long SlotSession::stepRagged(int count, int* samples, short* pcm, long long
         gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(DeliverPiece), hipMemcpyHostToDevice, stream));
         ok = slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, dPcm) && ok;
     }
+    m_dlv.release(stream);
+    m_slotCounter += count;
+    *ticket = m_dlv.uses();
+    return ok ? total : -2;
+}
+// ---- ragged delivery at the caller's rate (slots_deliver_rate.hpp) ----
+void SlotSession::rateOff() {
+    freeDev(m_tails, m_rateDev);
+    m_rateStage.reset();
+    m_rate = NULL;
+    m_rateIndex = -1;
+    m_tailH = 0;
+}
+bool SlotSession::setDelivery(const Resampler* r, int index) {
+    if (m_slotW <= 0 || (r != NULL && !r->ready())) return false;
+    if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
+    if (r != NULL && !slots_deliver_rate_prepare(r->geom().groups, r->tilesPerPass())) return false;
+    gpuErrChk(hipDeviceSynchronize());
+    rateOff();
+    if (r == NULL) return true;
+    m_rate = r;
+    m_rateIndex = index;
+    m_tailH = rate_tail_len(r->up(), r->centre());
+    m_tailCur = 0;
+    allocZero(m_tails, 2 * (size_t)f.maxBatch * (m_tailH > 0 ? m_tailH : 1) * sizeof(short));
+    m_tailZero.assign(f.maxBatch, 1);
+    gpuErrChk(hipMalloc((void**)&m_rateDev, (size_t)f.maxBatch * sizeof(RatePiece)));
+    m_rateStage.make(kSlotTickets, (size_t)f.maxBatch * sizeof(RatePiece));
+    gpuErrChk(hipDeviceSynchronize());
+    return true;
+}
+long long SlotSession::rateCapacity(int count) const {
+    if (!m_rate || count <= 0 || count > m_slotW) return -1;
+    // a piece of n samples has at most ceil(n L / M) + 1 outputs, its utterance's last one ceil(c / M) more
+    const long long L = m_rate->up(), M = m_rate->down(), c = m_rate->centre();
+    const long long most = (count * L + M - 1) / M + (c + M - 1) / M + 2;
+    return f.maxBatch * ((most + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign);
+}
+bool SlotSession::tailGet(int slot, short* dst) {
+    if (!m_rate || !inBatch(slot) || !slotHolds(slot) || dst == NULL) return false;
+    if (m_tailH == 0) return true;
+    if (m_tailZero[slot]) {
+        const std::vector<short> zero(m_tailH, 0);
+        gpuErrChk(hipMemcpy(dst, zero.data(), (size_t)m_tailH * sizeof(short), hipMemcpyDefault));
+    } else {
+        gpuErrChk(hipMemcpy(dst, tailAt(m_tailCur, slot), (size_t)m_tailH * sizeof(short), hipMemcpyDefault));
+    }
+    return true;
+}
+bool SlotSession::tailSet(int slot, const short* src) {
+    if (!m_rate || !inBatch(slot) || !slotHolds(slot) || src == NULL) return false;
+    if (m_tailH > 0) gpuErrChk(hipMemcpy(tailAt(m_tailCur, slot), src, (size_t)m_tailH * sizeof(short), hipMemcpyDefault));
+    m_tailZero[slot] = 0;
+    return true;
+}
+long long SlotSession::stepRaggedRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                                      SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
+                                      hipStream_t stream) {
+    if (m_slotW <= 0 || !m_rate || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL || nPieces == NULL ||
+        pcmTotal == NULL || ticket == NULL)
+        return -1;
+    const int upStride = m_host.slotLive().upStride;
+    if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
+    int* const dSamples = samples ? (int*)deliverTarget(samples) : NULL;
+    short* const dPcm = (short*)deliverTarget(pcm);
+    if ((samples && !dSamples) || !dPcm) return -1;
+    long long total = 0;
+    const int n = slotPieces(count, NULL, 0, total, upStride);
+    if (n > maxPieces || (samples && total > capacity)) return -1;
+    slotPieces(count, pieces, maxPieces, total, upStride);
+    // the outputs every piece carries, from its sample piece: D(first) .. D(first + n), or up to the utterance's last one
+    const ResampleGeom& g = m_rate->geom();
+    const int L = m_rate->up(), M = m_rate->down(), c = m_rate->centre(), perTile = 16 * g.groups;
+    long long off = 0, pcmEnd = 0;
+    for (int i = 0; i < n; i++) {
+        const SlotPiece& p = pieces[i];
+        const long long m0 = rate_delivered(p.first, L, M, c);
+        const long long end = p.finished ? rate_ceil_div((p.first + p.n) * L, M) : rate_delivered(p.first + p.n, L, M, c);
+        rate[i] = SlotRatePiece{m0, (int)(end - m0), 0, off};
+        if (end > m0) {
+            pcmEnd = off + (end - m0);
+            off = (pcmEnd + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign;
+        }
+    }
+    if (pcmEnd > pcmCapacity) return -1;      // (pieces and rate have been written: nothing else has changed)
+    RatePiece* const rstage = (RatePiece*)m_rateStage.acquire();
+    int tiles = 0;
+    for (int i = 0; i < n; i++) {
+        RatePiece& r = rstage[i];
+        r.slot = pieces[i].slot;
+        r.tailRow = m_tailRow[r.slot];
+        r.n = pieces[i].n;
+        r.flags = m_tailZero[r.slot] ? kRateZeroTail : 0;
+        r.first = pieces[i].first;
+        r.m0 = rate[i].m0;
+        r.offset = rate[i].offset;
+        r.block0 = r.m0 / g.Q;
+        r.count = rate[i].count;
+        r.blocks = r.count > 0 ? (int)((r.m0 + r.count - 1) / g.Q - r.block0 + 1) : 0;
+        r.tile0 = tiles;
+        r.pad = 0;
+        tiles += r.blocks > 0 ? (r.blocks + perTile - 1) / perTile : 1;
+    }
+    *nPieces = n;
+    *pcmTotal = pcmEnd;
+    const int T = (int)(m_slotCounter % m_slotW);
+    DeliverPiece* const stage = (DeliverPiece*)m_dlv.acquire();
+    int cols = 0;
+    bool ok = generate(count, cols, stream);
+    if (n > 0) {
+        gpuErrChk(hipMemcpyAsync(m_rateDev, rstage, (size_t)n * sizeof(RatePiece), hipMemcpyHostToDevice, stream));
+        if (dSamples) {
+            for (int i = 0; i < n; i++) stage[i] = DeliverPiece{pieces[i].slot, pieces[i].n, pieces[i].offset};
+            gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(DeliverPiece), hipMemcpyHostToDevice, stream));
+            ok = slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, NULL) && ok;
+        }
+        RateLaunch a;
+        a.pieces = m_rateDev;
+        a.count = n;
+        a.tiles = tiles;
+        a.y = m_slotY;
+        a.table = m_mulaw;
+        a.T = T;
+        a.W = m_slotW;
+        a.tailIn = m_tails + (size_t)m_tailCur * f.maxBatch * m_tailH;
+        a.tailOut = m_tails + (size_t)(m_tailCur ^ 1) * f.maxBatch * m_tailH;
+        a.H = m_tailH;
+        a.pcm = dPcm;
+        a.t = m_rate->tab();
+        ok = slots_deliver_rate(stream, a, g.groups, m_rate->tilesPerPass(), 4 * (size_t)g.spanWords) && ok;
+        for (int i = 0; i < n; i++) m_tailZero[pieces[i].slot] = 0;      // (the image just written holds what the flag stood for)
+        m_tailCur ^= 1;
+    }
+    m_rateStage.release(stream);
     m_dlv.release(stream);
     m_slotCounter += count;
     *ticket = m_dlv.uses();
@@ -554,6 +697,7 @@ int SlotSession::done(unsigned long long ticket) {
 void SlotSession::end() {
     if (m_slotW <= 0) return;
     gpuErrChk(hipDeviceSynchronize());
+    rateOff();
     freeDev(m_slotDesc, m_slotFeat, m_slotSel, m_slotY, m_slotPcm, m_slotUpd, m_dlvDev, m_saveDev, m_scaleDev, m_primeDev, m_melDesc, m_melUpd,
             m_melColInfo, m_melStage);
     m_melStageBytes = 0;

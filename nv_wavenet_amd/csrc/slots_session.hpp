@@ -12,12 +12,15 @@
 #include "gpu_check.hpp"
 #include "slots.hpp"
 #include "slots_deliver.hpp"
+#include "slots_deliver_rate.hpp"
 #include "slots_mel.hpp"
 #include "slots_prime.hpp"
 #include "slots_sampler.hpp"
 #include "slots_state.hpp"
 
 namespace wn {
+
+class Resampler;      // (resample.hpp, which includes this header for StageRing)
 
 // what is fixed when the engine has been constructed
 struct SlotFacts {
@@ -221,6 +224,34 @@ public:
     // the step kSlotTickets before it: with at most that many steps in flight it waits for nothing.)
     long long stepRagged(int count, int* samples, short* pcm, long long capacity, SlotPiece* pieces, int maxPieces, int* nPieces,
                          unsigned long long* ticket, hipStream_t stream = 0);
+    // ---- ragged delivery at the caller's rate (slots_deliver_rate.hpp) ----
+    // Rate delivery through the resampler `r` (slot `index` of the handle; NULL, -1: off, the default): allocates the two tail
+    // images and the pieces' staging; every column's filter history starts at zero, that of a column already running too (a
+    // discontinuity there).  While it is on, slotsStep and slotsStepRagged are refused: they would leave a hole in every history.
+    // false (nothing changes): not in slot mode, a resampler that is not set, a ragged step in flight, or the kernel's LDS opt-in
+    // refused.  Synchronises.  slotsBegin and slotsEnd turn it off.
+    bool setDelivery(const Resampler* r, int index);
+    int delivery() const { return m_rate ? m_rateIndex : -1; }
+    // H = ceil(2 c / L), the int16 values of a column's filter history; -1 when delivery is off
+    int tailLen() const { return m_rate ? m_tailH : -1; }
+    // PCM elements that always suffice for a rate step of `count`; -1 when delivery is off or count is out of range
+    long long rateCapacity(int count) const;
+    // A column's filter history, H int16 values (the last H PCM values of its utterance, zero where it has none), from / to host
+    // or device memory, in the image the next step reads: a blocking copy on the null stream, ordered as the header read of
+    // slotResume is.  For save and resume: get after the step that the save follows, set after the resume (any start puts the
+    // column's history back to zero).  false: delivery off, slot outside the batch, a column without an utterance, NULL.
+    bool tailGet(int slot, short* dst);
+    bool tailSet(int slot, const short* src);
+    // slotsStepRagged with the PCM side converted: the same launches up to and including the generation, the same pieces, the same
+    // optional `samples` at the pieces' offsets (one slot_deliver_kernel launch), and ONE slot_deliver_rate_kernel launch that
+    // writes piece p's outputs rate[p].m0 .. m0 + count - 1 at element rate[p].offset of `pcm` (int16, device or pinned, pcmCapacity
+    // elements; offsets packed, each rounded up to 8, the gaps not written).  pieces and rate (host, maxPieces each) are filled
+    // before anything is launched.  Returns the end of the last sample piece and *pcmTotal the end of the last PCM piece; -2 and
+    // -1 as slotsStepRagged, -1 also when delivery is off, pcm is NULL or pcmCapacity is too small (then pieces and rate have been
+    // written, nothing else has changed).  Never synchronises.
+    long long stepRaggedRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                             SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
+                             hipStream_t stream = 0);
     // Measurement only (scripts/slots_perf.py --serve): `reps` back-to-back output passes over the last `count` samples generated,
     // timed with events on `stream`; returns milliseconds for all of them, < 0 when refused.  ragged = false: what slotsStep
     // issues after the generation -- the PCM launches and the 2-D copies into samples / pcm [maxBatch][count]; ragged = true: the
@@ -284,8 +315,18 @@ private:
     DeliverPiece* m_dlvDev = NULL;          // [maxBatch] on the device: the pieces of the step being delivered
     StageRing m_dlv;                        // pinned host staging of them, one per ticket in flight; its uses() is the last ticket
                                             // given out (they count from 1)
+    // ... and delivery at the caller's rate (slots_deliver_rate.hpp)
+    const Resampler* m_rate = NULL;         // the handle's resampler in use (NULL: off) and its slot
+    int m_rateIndex = -1;
+    int m_tailH = 0;
+    int m_tailCur = 0;                      // the tail image the next step reads; it writes the other
+    short* m_tails = NULL;                  // [2][maxBatch][H]
+    std::vector<int> m_tailRow;             // per column: its row of the images (a move swaps two entries)
+    std::vector<char> m_tailZero;           // per column: its history counts as zero (a start, or a resume whose tail was not set)
+    RatePiece* m_rateDev = NULL;            // [maxBatch] on the device: the rate pieces of the step being delivered
+    StageRing m_rateStage;                  // pinned host staging of them, as m_dlv
     // ... and the sampling temperatures (slots_sampler.hpp)
-    std::vector<char> m_tempDirty;          // the columns whose table entry the next step writes
+    std::vector<char> m_tempDirty;         // the columns whose table entry the next step writes
     std::vector<int> m_tempDirtyList;
     SlotScale* m_scaleDev = NULL;           // [4 maxBatch] on the device: a step's changed entries (made by the first step that needs it)
     StageRing m_scaleStage;                 // ... their pinned host staging: two halves
@@ -320,6 +361,8 @@ private:
         return left < m_slotW - row ? left : m_slotW - row;
     }
     int slotPieces(int count, SlotPiece* out, int maxOut, long long& total, int upStride) const;
+    void rateOff();
+    short* tailAt(int image, int slot) const { return m_tails + ((size_t)image * f.maxBatch + m_tailRow[slot]) * m_tailH; }
     // what slotStart / slotStartMel refuse (shared with slotsResumeList, which checks every request before it changes anything)
     bool slotStartOk(int slot, const void* x, int precision, long long cStride, long long tStride, int length) const;
     bool slotStartMelOk(int slot, const void* mel, int precision, long long cStride, long long fStride, int frames, int final, int upStride) const;

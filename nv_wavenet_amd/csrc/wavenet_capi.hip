@@ -519,9 +519,11 @@ int nvw_analyse(nvw_engine* e, const nvw_analysis_req* reqs, int count, void* st
 }
 // ---- sample-rate conversion: a polyphase FIR by request and output range (additive within ABI 7) ------------------------------------
 int nvw_set_resampler(nvw_engine* e, int slot, int up, int down, const double* taps, int n_taps) {
-    if (slot < 0 || slot > 3 || !e->resamplers[slot].set(up, down, taps, n_taps)) {
-        fprintf(stderr, "nvw_set_resampler: refused (slot %d: 0 .. 3; up %d and down %d: coprime, in 1 .. %d; %d taps: odd, in host memory; at "
-                "most %d bytes of LDS per workgroup)\n", slot, up, down, wn::kResampleFactorMax, n_taps, wn::kResampleLdsMax);
+    // (a slot that a slot session delivers through keeps its table: the columns' filter histories are that filter's)
+    if (slot < 0 || slot > 3 || e->slots().delivery() == slot || !e->resamplers[slot].set(up, down, taps, n_taps)) {
+        fprintf(stderr, "nvw_set_resampler: refused (slot %d: 0 .. 3, not the one of nvw_slots_set_delivery; up %d and down %d: coprime, in "
+                "1 .. %d; %d taps: odd, in host memory; at most %d bytes of LDS per workgroup)\n", slot, up, down, wn::kResampleFactorMax,
+                n_taps, wn::kResampleLdsMax);
         return 0;
     }
     return 1;
@@ -540,6 +542,32 @@ int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int coun
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {
     return e->slots().stepRagged(count, samples, pcm, capacity, (wn::SlotPiece*)pieces, max_pieces, n_pieces, ticket, (hipStream_t)stream);
+}
+// ---- slot mode: ragged delivery at the caller's sample rate (additive within ABI 7) -------------------------------------------------
+int nvw_slots_set_delivery(nvw_engine* e, int resampler) {
+    const bool off = resampler == -1;
+    if ((off || (resampler >= 0 && resampler <= 3)) && e->slots().setDelivery(off ? NULL : &e->resamplers[resampler], resampler)) return 1;
+    fprintf(stderr, "nvw_slots_set_delivery: refused, nothing changed (nvw_slots_begin first; resampler %d: -1, or a slot of "
+            "nvw_set_resampler that is set; no ragged step in flight)\n", resampler);
+    return 0;
+}
+int nvw_slots_tail_len(nvw_engine* e) { return e->slots().tailLen(); }
+long long nvw_slots_rate_capacity(nvw_engine* e, int count) { return e->slots().rateCapacity(count); }
+int nvw_slot_tail_get(nvw_engine* e, int slot, short* dst) {
+    if (e->slots().tailGet(slot, dst)) return 1;
+    fprintf(stderr, "nvw_slot_tail_get: refused (nvw_slots_set_delivery first; slot %d of %d: a column with an utterance)\n", slot, e->maxBatch());
+    return 0;
+}
+int nvw_slot_tail_set(nvw_engine* e, int slot, const short* src) {
+    if (e->slots().tailSet(slot, src)) return 1;
+    fprintf(stderr, "nvw_slot_tail_set: refused (nvw_slots_set_delivery first; slot %d of %d: a column with an utterance)\n", slot, e->maxBatch());
+    return 0;
+}
+long long nvw_slots_step_ragged_rate(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                     nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces, long long* pcm_total,
+                                     unsigned long long* ticket, void* stream) {
+    return e->slots().stepRaggedRate(count, samples, capacity, pcm, pcm_capacity, (wn::SlotPiece*)pieces, (wn::SlotRatePiece*)rate, max_pieces,
+                                     n_pieces, pcm_total, ticket, (hipStream_t)stream);
 }
 float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream) {
     return e->slots().timeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);

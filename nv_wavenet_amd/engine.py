@@ -13,6 +13,9 @@ from ._lib import lib, addr, CONSUME_FN
 # nvw_slot_piece of include/nv_wavenet_c.h: one delivered piece of a ragged slot step
 SLOT_PIECE = np.dtype([("slot", "<i4"), ("uid", "<u4"), ("first", "<i8"), ("n", "<i4"), ("finished", "<i4"), ("offset", "<i8")])
 assert SLOT_PIECE.itemsize == 32
+# ... nvw_slot_rate_piece, parallel to it in a rate step
+SLOT_RATE_PIECE = np.dtype([("m0", "<i8"), ("count", "<i4"), ("pad", "<i4"), ("offset", "<i8")])
+assert SLOT_RATE_PIECE.itemsize == 24
 # ... nvw_slot_saved and nvw_slot_resume_req of nvw_slots_save_list / nvw_slots_resume_list
 SLOT_SAVED = np.dtype([("slot", "<i4"), ("uid", "<u4"), ("done", "<i4"), ("mel", "<i4")])
 SLOT_RESUME_REQ = np.dtype({"names": ["slot", "mel", "src", "precision", "c_stride", "t_stride", "length", "final"],
@@ -445,6 +448,55 @@ class WavenetEngine:
         if total < 0:
             raise ValueError("nvw_slots_step_ragged refused a step of %d samples into %s elements" % (count, cap))
         return int(total), pieces[:n.value], int(ticket.value)
+
+    # ---- ragged delivery at the caller's sample rate (include/nv_wavenet_c.h, "AT THE CALLER'S SAMPLE RATE") ----
+    def slotsSetDelivery(self, resampler):
+        """Rate delivery in slot mode through resampler slot 0 .. 3 (setResampler first); None or -1: off.  ValueError when
+        refused (nothing changed): see nvw_slots_set_delivery."""
+        r = -1 if resampler is None else int(resampler)
+        if not lib.nvw_slots_set_delivery(self._h, r):
+            raise ValueError("nvw_slots_set_delivery refused resampler %d" % r)
+
+    def slotsTailLen(self):
+        """H, the int16 values of a column's filter history; -1 when delivery is off."""
+        return int(lib.nvw_slots_tail_len(self._h))
+
+    def slotsRateCapacity(self, count):
+        """PCM elements that always suffice for slotsStepRaggedRate(count); -1 when delivery is off."""
+        return int(lib.nvw_slots_rate_capacity(self._h, int(count)))
+
+    def slotTailGet(self, slot):
+        """The filter history of column `slot`: a numpy int16 array [H] (blocking; for save and resume)."""
+        tail = np.zeros(max(self.slotsTailLen(), 0), dtype=np.int16)
+        if not lib.nvw_slot_tail_get(self._h, int(slot), tail.ctypes.data):
+            raise ValueError("nvw_slot_tail_get refused slot %d" % slot)
+        return tail
+
+    def slotTailSet(self, slot, tail):
+        """Sets the filter history of column `slot` (H int16 values, numpy or a CPU tensor): after slotResume, before the step."""
+        tail = np.ascontiguousarray(tail.numpy() if hasattr(tail, "numpy") else tail, dtype=np.int16)
+        if tail.shape != (self.slotsTailLen(),) or not lib.nvw_slot_tail_set(self._h, int(slot), tail.ctypes.data):
+            raise ValueError("nvw_slot_tail_set refused slot %d, a tail of shape %s" % (slot, tail.shape))
+
+    def slotsStepRaggedRate(self, count, samples, pcm, stream=None):
+        """slotsStepRagged with the PCM converted to the delivery rate (nvw_slots_step_ragged_rate): samples int32 (or None) takes
+        the pieces' samples at the model's rate as before, pcm int16 (1-D CUDA or pinned tensors) piece p's outputs rate[p].m0 ..
+        m0 + count - 1 at element rate[p].offset.  Returns (total, pcm_total, pieces, rate, ticket) with rate a numpy structured
+        array (SLOT_RATE_PIECE: m0, count, offset) parallel to pieces.  ValueError when refused."""
+        for a, dt, name in ((samples, "int32", "samples"), (pcm, "int16", "pcm")):
+            if a is not None or name == "pcm":
+                assert hasattr(a, "data_ptr") and (a.is_cuda or a.is_pinned()) and a.is_contiguous() and str(a.dtype) == "torch." + dt, \
+                    "%s: a contiguous CUDA or pinned %s tensor" % (name, dt)
+        pieces, rate = np.empty(self.maxBatch, dtype=SLOT_PIECE), np.empty(self.maxBatch, dtype=SLOT_RATE_PIECE)
+        n, ticket, pcm_total = C.c_int(0), C.c_ulonglong(0), C.c_longlong(0)
+        total = lib.nvw_slots_step_ragged_rate(self._h, int(count), addr(samples), samples.numel() if samples is not None else 0, addr(pcm),
+                                               pcm.numel(), pieces.ctypes.data, rate.ctypes.data, self.maxBatch, C.byref(n),
+                                               C.byref(pcm_total), C.byref(ticket), stream)
+        if total == -2:
+            raise RuntimeError("nvw_slots_step_ragged_rate: a launch of the step of %d samples failed" % count)
+        if total < 0:
+            raise ValueError("nvw_slots_step_ragged_rate refused a step of %d samples into %d PCM elements" % (count, pcm.numel()))
+        return int(total), int(pcm_total.value), pieces[:n.value], rate[:n.value], int(ticket.value)
 
     def slotsWait(self, ticket):
         """Blocks until the outputs of the ragged step with that ticket are complete."""

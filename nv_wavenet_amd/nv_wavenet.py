@@ -454,7 +454,7 @@ class NVWaveNetEngine(NVWaveNet):
         return e
 
     def slot_stream(self, columns, window, cond_weight, cond_bias, seed=0, implementation=Impl.AUTO, pcm=True, upsample_weight=None,
-                    upsample_bias=None, upsample_stride=None, compact=False, prefill=False):
+                    upsample_bias=None, upsample_stride=None, compact=False, prefill=False, deliver_rate=None, deliver_taps=None):
         """Continuous batching (nv_wavenet_amd/slots.py): a SlotStream over an engine of its own with `columns` columns and a window of
         `window` samples (a multiple of max_dilation), the conditioning convolution in the kernel as infer_features has it
         (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
@@ -463,7 +463,10 @@ class NVWaveNetEngine(NVWaveNet):
         batch (SlotStream.compact).  prefill: submit(prime=) makes the state behind a prime with the engine's time-parallel pass and
         enters the request at sample n, unless the call says prefill=False (SlotStream.submit).  stream.step(n) waits for its samples; stream.step_async(n) issues the step and returns a
         PendingStep, two of which may be in flight (the pipelined service loop of INTEGRATION.md §2g).  close() the stream to free
-        the engine."""
+        the engine.  deliver_rate = (model rate, delivery rate) in Hz: step_async delivers every request's PCM at the delivery rate
+        (DESIGN.md §6q), converted in the delivery launch with the taps of resample_taps(*deliver_rate), or deliver_taps (an odd
+        number of float64 prototype taps at rate L x the model's); StepOutput.pcm_offsets / pcm_lengths / pcm_first describe it, and a
+        request's pieces concatenated are bit for bit resample() of its whole PCM."""
         from .slots import SlotStream
         e = self._new_engine(columns, window, implementation)
         e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
@@ -471,7 +474,12 @@ class NVWaveNetEngine(NVWaveNet):
             assert upsample_bias is not None and upsample_stride is not None, "upsampling needs its weight, bias and stride"
             e.setUpsampling(upsample_weight.float().contiguous(), upsample_bias.float().contiguous(), int(upsample_stride))
         e.setSelectorSeed(seed)
-        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact, prefill=prefill)
+        deliver = None
+        if deliver_rate is not None:
+            L, M, taps = resample_taps(*deliver_rate)
+            e.setResampler(0, L, M, taps if deliver_taps is None else deliver_taps)
+            deliver = 0
+        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact, prefill=prefill, deliver=deliver)
 
     def close(self):
         for e in self._engines.values():

@@ -270,6 +270,24 @@ def window_pieces(counter, count, window):
     return [(t, first)] if first == count else [(t, first), (0, count - first)]
 
 
+def rate_delivered(k, L, M, c):
+    """D(k) of rate delivery (DESIGN.md §6q; wn::rate_delivered): the outputs of an unfinished stream at rate L / M, filter centre c,
+    whose every input is below k -- max(0, ceil((k L - c) / M))."""
+    return max(0, -((c - k * L) // M))
+
+
+def rate_tail_len(L, c):
+    """H = ceil(2 c / L): the inputs below `first` that the first output of a piece may reach back over (wn::rate_tail_len)."""
+    return -(-2 * c // L)
+
+
+def rate_piece(first, n, finished, L, M, c):
+    """(m0, count) of the piece with local samples [first, first + n): outputs D(first) .. D(first + n) - 1, or up to the last of
+    the utterance's ceil((first + n) L / M) when the piece finishes it."""
+    m0 = rate_delivered(first, L, M, c)
+    return m0, (-(-(first + n) * L // M) if finished else rate_delivered(first + n, L, M, c)) - m0
+
+
 class SlotState:
     """A suspended request (SlotStream.suspend): blob = the column's state, a CUDA uint8 tensor of WavenetEngine.slotSave (None: the
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
@@ -277,7 +295,9 @@ class SlotState:
     the blob's header, word 10; a resume goes on at this attribute's value); prime = its prime (an int32 tensor [n], None: none; a
     resume applies it again when done < n); min_p = its probability floor (word 11 of the blob's header where the engine saved
     the blob; the blobs that prefill and scoring write leave the word zero, and the stream sets the floor after resuming); top_k,
-    top_p = its tail cuts (words 12 and 13, likewise)."""
+    top_p = its tail cuts (words 12 and 13, likewise); tail = its filter history at the delivery rate (a numpy int16 array [H] of a
+    stream made with deliver_rate; None: none -- a resume then goes on from a zero history, a discontinuity in the
+    first H L / M + 1 outputs after the seam)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -294,9 +314,13 @@ class SlotState:
     # to_bytes() of a state with done < n of its prime: behind the blob this record, then the n - done values y[done .. n) (int32)
     PRIME = struct.Struct("<4sII")           # magic, first (= done), count (= n - done)
     PRIME_MAGIC = b"NWSP"
+    # to_bytes() of a state with a filter history: last of all this record, then its H int16 values
+    TAIL = struct.Struct("<4sI")             # magic, H
+    TAIL_MAGIC = b"NWSR"
 
     def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0,
-                 top_k=0, top_p=1.0):
+                 top_k=0, top_p=1.0, tail=None):
+        self.tail = None if tail is None else np.ascontiguousarray(tail, dtype="<i2")
         self.prime = check_prime(prime)
         self.temperature, self.min_p, self.top_k, self.top_p = check_sampling(temperature, min_p, top_k, top_p)
         self._blob_sampling = self.sampling() if blob is not None else OFF      # (what the engine reads from the header on resume)
@@ -323,7 +347,7 @@ class SlotState:
         so that the values survive; a blob whose words 11 to 13 are not the state's floor and cuts (a prefilled state) is written
         with them.  A state
         still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
-        what they were before primes existed."""
+        what they were before primes existed.  A state with a filter history ends with the TAIL record and its values."""
         blob = b""
         s = self.sampling()
         if self.blob is None and s != OFF:
@@ -347,7 +371,8 @@ class SlotState:
                 blob = words.tobytes()
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
-                                1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob + self._prime_bytes()
+                                1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob + self._prime_bytes() + \
+            (b"" if self.tail is None else self.TAIL.pack(self.TAIL_MAGIC, self.tail.size) + self.tail.tobytes())
 
     def _prime_bytes(self):
         if self.prime is None or self.done >= self.prime.numel():
@@ -367,14 +392,21 @@ class SlotState:
         magic, version, kind, frames, final, uid, done, nblob = cls.RECORD.unpack_from(data)
         if magic != cls.RECORD_MAGIC or version != cls.RECORD_VERSION or kind not in (0, 1):
             raise ValueError("not a SlotState record (magic %r, version %d, kind %d)" % (magic, version, kind))
-        prime, tail = None, len(data) - cls.RECORD_BYTES - nblob
-        if tail >= cls.PRIME.size:
-            pmagic, first, count = cls.PRIME.unpack_from(data, cls.RECORD_BYTES + nblob)
-            if pmagic != cls.PRIME_MAGIC or first != done or count < 1 or tail != cls.PRIME.size + 4 * count:
+        prime, history, at = None, None, cls.RECORD_BYTES + nblob
+        tail = len(data) - at
+        if tail >= cls.PRIME.size and data[at:at + 4] != cls.TAIL_MAGIC:
+            pmagic, first, count = cls.PRIME.unpack_from(data, at)
+            if pmagic != cls.PRIME_MAGIC or first != done or count < 1 or tail < cls.PRIME.size + 4 * count:
                 raise ValueError("not a prime record behind the blob (magic %r, first %d, count %d, %d bytes)" % (pmagic, first, count, tail))
             y = np.zeros(first + count, dtype=np.int32)      # (the samples below done are never reached)
-            y[first:] = np.frombuffer(data, dtype="<i4", count=count, offset=cls.RECORD_BYTES + nblob + cls.PRIME.size)
-            prime, tail = torch.from_numpy(y), 0
+            y[first:] = np.frombuffer(data, dtype="<i4", count=count, offset=at + cls.PRIME.size)
+            prime, at = torch.from_numpy(y), at + cls.PRIME.size + 4 * count
+            tail = len(data) - at
+        if tail >= cls.TAIL.size:
+            tmagic, H = cls.TAIL.unpack_from(data, at)
+            if tmagic != cls.TAIL_MAGIC or tail != cls.TAIL.size + 2 * H:
+                raise ValueError("not a filter history behind the state (magic %r, H %d, %d bytes)" % (tmagic, H, tail))
+            history, tail = np.frombuffer(data, dtype="<i2", count=H, offset=at + cls.TAIL.size).copy(), 0
         if tail != 0 or (nblob and (nblob < 64 or nblob % 16)):
             raise ValueError("the record announces a blob of %d bytes, %d follow it" % (nblob, len(data) - cls.RECORD_BYTES))
         blob = buffer = None
@@ -397,17 +429,23 @@ class SlotState:
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   prime=prime, **s._asdict())
+                   prime=prime, tail=history, **s._asdict())
 
 
 class StepOutput:
     """What one step delivered (PendingStep.result): per delivering request, in ascending column order, handles[i], offsets[i] and
     lengths[i] (numpy) -- its samples are samples[offsets[i] : offsets[i] + lengths[i]], its PCM the same range of pcm (None when the
     stream was made with pcm=False) --, and finished, the handles whose last sample is in this step.  samples and pcm are views of a
-    pinned buffer of the stream, valid until the second step after this one is issued (the stream's two buffers take turns).  out[handle] and out.items() slice lazily."""
+    pinned buffer of the stream, valid until the second step after this one is issued (the stream's two buffers take turns).  out[handle] and out.items() slice lazily.
+    A stream made with deliver_rate delivers its PCM at that rate: request i's PCM is pcm[pcm_offsets[i] :
+    pcm_offsets[i] + pcm_lengths[i]], outputs pcm_first[i] .. of its utterance (a length may be 0); the samples stay at the model's
+    rate under offsets and lengths.  Without, the three are offsets, lengths and the pieces' first samples."""
 
-    def __init__(self, handles, offsets, lengths, samples, pcm, finished):
+    def __init__(self, handles, offsets, lengths, samples, pcm, finished, pcm_offsets=None, pcm_lengths=None, pcm_first=None):
         self.handles, self.offsets, self.lengths, self.samples, self.pcm, self.finished = handles, offsets, lengths, samples, pcm, finished
+        self.pcm_offsets = offsets if pcm_offsets is None else pcm_offsets
+        self.pcm_lengths = lengths if pcm_lengths is None else pcm_lengths
+        self.pcm_first = pcm_first
         self._index = None
 
     def __len__(self):
@@ -423,7 +461,8 @@ class StepOutput:
 
     def _slice(self, i):
         a, b = int(self.offsets[i]), int(self.offsets[i]) + int(self.lengths[i])
-        return self.samples[a:b], (self.pcm[a:b] if self.pcm is not None else None)
+        c, d = int(self.pcm_offsets[i]), int(self.pcm_offsets[i]) + int(self.pcm_lengths[i])
+        return self.samples[a:b], (self.pcm[c:d] if self.pcm is not None else None)
 
     def __getitem__(self, handle):
         i = self._at(handle)
@@ -440,9 +479,12 @@ class PendingStep:
     """A step that has been issued (SlotStream.step_async).  result() waits for its samples -- for nothing else -- and returns its
     StepOutput (the same one every time; a pending step issued before it is collected first); done() asks without waiting."""
 
-    def __init__(self, stream, ticket, buf, total, handles, offsets, lengths, finished):
+    def __init__(self, stream, ticket, buf, total, handles, offsets, lengths, finished, first=None, rate=None, pcm_total=None):
         self._stream, self._ticket, self._buf, self._total = stream, ticket, buf, total
         self._handles, self._offsets, self._lengths, self._finished = handles, offsets, lengths, finished
+        # what StepOutput adds for the PCM: the pieces' first samples, or the (offsets, lengths, first outputs) of a rate step
+        self._pcm = (None, None, first) if rate is None else rate
+        self._pcm_total = total if pcm_total is None else pcm_total
         self._out = None
 
     def done(self):
@@ -458,8 +500,8 @@ class PendingStep:
                     earlier.result()
                 st.engine.slotsWait(self._ticket)
                 y, pcm = st._bufs[self._buf]
-                self._out = StepOutput(self._handles, self._offsets, self._lengths, y[:self._total], pcm[:self._total] if pcm is not None else None,
-                                       self._finished)
+                self._out = StepOutput(self._handles, self._offsets, self._lengths, y[:self._total],
+                                       pcm[:self._pcm_total] if pcm is not None else None, self._finished, *self._pcm)
                 st._pending.remove(self)
                 st._done.extend(self._finished)
             else:      # (a step that generated nothing: step() returns {} there)
@@ -468,7 +510,7 @@ class PendingStep:
 
 
 class SlotStream:
-    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False, prefill=False):
+    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False, prefill=False, deliver=None):
         self.engine = engine
         self._prefill = bool(prefill)                  # what submit(prefill=None) does with a prime
         self.columns = engine.maxBatch
@@ -477,6 +519,12 @@ class SlotStream:
         self._owns = owns_engine
         self._compact = bool(compact)
         engine.slotsBegin(self.window)
+        # deliver: the engine's resampler slot through which step_async delivers its PCM at the caller's rate
+        self._rate = deliver is not None
+        if self._rate:
+            if not pcm:
+                raise ValueError("deliver needs pcm=True")
+            engine.slotsSetDelivery(deliver)
         self._free = list(range(self.columns))         # a heap: lowest free column first
         self._queue = deque()                          # (handle, features, uid, mel request or None[, SlotState]) waiting for a column
         self._src = {}                                 # handle -> (source tensor, uid) of the running requests
@@ -830,6 +878,10 @@ class SlotStream:
         blob, done = self.engine.slotSave(col)      # (first: a refusal leaves the stream as it was)
         return self._stopped(handle, col, blob, done)
 
+    def _tail(self, col):
+        """The filter history of a running column of a stream that delivers at a rate (None otherwise)."""
+        return self.engine.slotTailGet(col) if self._rate else None
+
     def _dequeued(self, item):
         """The state of a request taken out of the queue (an empty one unless it was itself resumed)."""
         handle, req = item[0], item[3]
@@ -848,6 +900,7 @@ class SlotStream:
 
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
+        tail = self._tail(col)
         self.engine.slotStop(col)
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
@@ -858,11 +911,11 @@ class SlotStream:
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, prime=prime, **s._asdict())
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, prime=prime, tail=tail, **s._asdict())
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, prime=prime, **s._asdict())
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, prime=prime, tail=tail, **s._asdict())
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -926,6 +979,8 @@ class SlotStream:
         if hasattr(state.blob, "numel") and state.blob.numel() != self.engine.slotStateBytes():
             raise ValueError("a state of %d bytes, this engine's are %d: another shape or precision" % (state.blob.numel(), self.engine.slotStateBytes()))
         s = state.sampling(getattr(self.engine, "A", None))      # (against this engine's alphabet, before anything is queued)
+        if self._rate and state.tail is not None and state.tail.size != self.engine.slotsTailLen():
+            raise ValueError("a filter history of %d values, this stream's filter has %d" % (state.tail.size, self.engine.slotsTailLen()))
         handle = self._next_handle
         self._next_handle += 1
         self._next_uid = max(self._next_uid, int(state.uid) + 1)
@@ -959,6 +1014,7 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
+        tails = []       # (column, filter history) of the resumed requests that carry one, where the stream delivers at a rate
         wanted = []      # (column, Sampling, what the start or the resume leaves) likewise, where the two differ: a start leaves OFF, a
                          # resume words 10 to 13 of the blob (11 to 13 zero in a prefilled or scored one)
         while self._queue and self._free and self._ready(self._queue[0], count):
@@ -970,6 +1026,8 @@ class SlotStream:
             # a row of a shared buffer, or a CPU tensor still to be uploaded: by list; a CUDA blob of its own (suspend()): singly
             by_list = blob is not None and (state.buffer is not None or not getattr(blob, "is_cuda", True))
             self._src[handle] = (x, uid)
+            if self._rate and blob is not None and state.tail is not None:
+                tails.append((col, state.tail))
             if handle in self._prime:
                 primed.append((col, handle))
             s, had = self._sampling.get(handle, OFF), (state._blob_sampling if blob is not None else OFF)
@@ -998,6 +1056,8 @@ class SlotStream:
                 self._deliv[col] = req[3] if req is not None else 0
         if listed:
             self._resume_listed(listed)
+        for col, tail in tails:      # (resume, then its history: a resume starts the column from a zero one)
+            self.engine.slotTailSet(col, tail)
         # start, then set (the engine applies both at the step that follows): every temperature, every floor, then the cuts by column
         order = [(f, it) for f in ("temperature", "min_p") for it in wanted] + [(f, it) for it in wanted for f in ("top_k", "top_p")]
         for field, (col, s, had) in order:
@@ -1031,6 +1091,8 @@ class SlotStream:
         when a running mel request has no frames beyond what it has delivered.  Not while steps of step_async are pending."""
         if self._pending:
             raise RuntimeError("%d pending steps: collect them (PendingStep.result) before a synchronous step" % len(self._pending))
+        if self._rate:
+            raise RuntimeError("a stream that delivers at a rate steps with step_async: a plain step would leave a hole in every filter history")
         self._use_arrays(False)
         if self._mel:
             count = min(count, self.engine.slotsHeadroom())
@@ -1105,12 +1167,21 @@ class SlotStream:
             return PendingStep(self, None, None, 0, empty, empty, empty, [])
         buf = self._last_buf ^ 1      # (never the buffer of a pending step: at most one is pending here, and it was issued last)
         need = len(self._running) * ((count + 7) & ~7)
-        if self._bufs[buf] is None or self._bufs[buf][0].size < need:
+        need_pcm = len(self._running) * (self.engine.slotsRateCapacity(count) // self.columns) if self._rate else need
+        if self._bufs[buf] is None or self._bufs[buf][0].size < need or (self._rate and self._bufs[buf][1].size < need_pcm):
             keep = self.engine.slotsPinned(max(need, 8), self.pcm)
+            if self._rate:
+                import torch
+                keep = (keep[0], torch.empty(max(need_pcm, 8), dtype=torch.int16, pin_memory=True))
             self._bufs_keep[buf] = keep
             self._bufs[buf] = tuple(a.numpy() if hasattr(a, "numpy") and not isinstance(a, np.ndarray) else a for a in keep)
         y, pcm = self._bufs_keep[buf]
-        total, pieces, ticket = self.engine.slotsStepRagged(count, y, pcm)
+        rate = pcm_total = None
+        if self._rate:
+            total, pcm_total, pieces, r, ticket = self.engine.slotsStepRaggedRate(count, y, pcm)
+            rate = (r["offset"].copy(), r["count"].astype(np.int64), r["m0"].copy())
+        else:
+            total, pieces, ticket = self.engine.slotsStepRagged(count, y, pcm)
         self._last_buf = buf
         self._inflight.clear()
         slots = pieces["slot"]
@@ -1118,7 +1189,8 @@ class SlotStream:
         self._left[slots] -= pieces["n"]
         self._deliv[slots] += pieces["n"]
         finished = [self._retire(int(col)) for col in slots[pieces["finished"] != 0]]
-        step = PendingStep(self, ticket, buf, total, handles, pieces["offset"].copy(), pieces["n"].astype(np.int64), finished)
+        step = PendingStep(self, ticket, buf, total, handles, pieces["offset"].copy(), pieces["n"].astype(np.int64), finished,
+                           pieces["first"].copy(), rate, pcm_total)
         self._pending.append(step)
         return step
 

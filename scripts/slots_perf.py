@@ -152,6 +152,7 @@ def main():
     ap.add_argument("--prefill-mel", action="store_true", help="time nvw_prefill_states_mel against nvw_prefill_states on rows upsampled beforehand and against mel columns of the parent")
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--analyse", action="store_true", help="time nvw_analyse beside nvw_score_samples_mel of the same audio")
+    ap.add_argument("--rate", action="store_true", help="time the ragged step with plain delivery against rate delivery at 2 / 1 and 147 / 80")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
     ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
@@ -166,6 +167,10 @@ def main():
     Wc, bc = bench.make_cond_layers()
     if args.analyse:
         print(json.dumps(time_analyse(args, w, Wc, bc)), flush=True)
+        return
+    if args.rate:
+        for chunk in [int(c) for c in args.chunks.split(",")]:
+            print(json.dumps(time_rate(args, w, Wc, bc, chunk)), flush=True)
         return
     if args.prefill_mel or args.score_mel:
         if args.prefill_mel:
@@ -1148,6 +1153,47 @@ def time_mel(args, w, Wc, bc, chunk, warm, steps, rng):
 
 def _stats(v):
     return {"median": round(float(np.median(v)), 4), "min": round(float(min(v)), 4), "max": round(float(max(v)), 4)}
+
+
+def time_rate(args, w, Wc, bc, chunk):
+    """The --rate measurement: one session with every column busy; per round, alternating, `steps` ragged steps of `chunk` samples
+    into pinned memory (events around them, one warm-up step first) with plain delivery (nvw_slots_step_ragged, the parent's path,
+    which this commit leaves as it was) and with rate delivery at 2 / 1 and 147 / 80 (nvw_slots_step_ragged_rate, the default
+    design of resample_taps); milliseconds per step."""
+    import torch
+    import bench
+    from nv_wavenet_amd.nv_wavenet import resample_taps
+    B, W, steps = args.batch, args.window, max(2, args.steps)
+    cases = {"plain": None, "rate_2_1": (1, 2), "rate_147_80": (80, 147)}
+    src = torch.randn(bench.N_COND, 65536, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)).half()
+    assert args.rounds * len(cases) * (steps + 1) * chunk <= src.size(1)
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    e.setSelectorSeed(5)
+    e.slotsBegin(W)
+    for slot, rates in enumerate(r for r in cases.values() if r):
+        e.setResampler(slot, *resample_taps(*rates))
+    for b in range(B):
+        e.slotStart(b, src, b)
+    y, _ = e.slotsPinned(B * chunk, pcm=False)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = {name: [] for name in cases}
+    for _ in range(args.rounds):
+        for slot, name in enumerate(cases, -1):
+            e.slotsSetDelivery(slot)
+            pcm = torch.empty(e.slotsRateCapacity(chunk) if slot >= 0 else B * chunk, dtype=torch.int16, pin_memory=True)
+            for k in range(steps + 1):
+                if k == 1:
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                e.slotsStepRaggedRate(chunk, y, pcm) if slot >= 0 else e.slotsStepRagged(chunk, y, pcm)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]) / steps)
+    e.slotsEnd()
+    e.close()
+    return {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
+            "ms_per_step": {name: _stats(v) for name, v in ms.items()}, "device": torch.cuda.get_device_name(0)}
 
 
 def time_serve(args, w, Wc, bc, load, chunk):
