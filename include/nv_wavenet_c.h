@@ -863,6 +863,54 @@ long long nvw_slots_step_ragged_rate(nvw_engine* e, int count, int* samples, lon
 int nvw_slot_tail_get(nvw_engine* e, int slot, short* dst);
 int nvw_slot_tail_set(nvw_engine* e, int slot, const short* src);
 
+/* DENOISER AT THE PCM BOUNDARY: STFT, SPECTRAL SUBTRACTION AND INVERSE STFT IN ONE KERNEL (additive within ABI 7).  A vocoder has a
+ * stationary noise floor -- for an 8-bit mu-law WaveNet the hiss it emits for silent conditioning.  Callers of this family of
+ * vocoders measure it once as a magnitude spectrum b[k] (generate from zero mel frames, take the STFT magnitude) and subtract
+ * strength * b[k] from the STFT magnitude of every delivered utterance, keeping the phase (the Denoiser beside Tacotron-2 /
+ * WaveGlow).  This pass does that on the engine's PCM, batched, in one launch per call.  With N = n_fft (= the window
+ * length), hop dividing N, O = N / hop, w the periodic Hann window, a stream x[0 .. n) in PCM units (nothing is divided by 32768):
+ *     xp     = x reflect-padded by N / 2 on both sides                                   (torch 'reflect'; n > N / 2)
+ *     X_f[k] = sum_j w[j] xp[f hop + j] e^{-2 pi i k j / N}              f = 0 .. n / hop, k = 0 .. N / 2
+ *     Y_f[k] = X_f[k] max(1 - strength b[k] / |X_f[k]|, 0)               (0 where |X_f[k]| = 0)
+ *     y_f[j] = w[j] / N sum_k c_k Re(Y_f[k] e^{+2 pi i k j / N})         c_0 = c_{N/2} = 1, otherwise 2
+ *     out[t] = sum_f y_f[t + N/2 - f hop] / sum_f w^2[t + N/2 - f hop]   t = 0 .. n - 1
+ * both sums of out[t] over the existing frames that cover t, in ascending f: torch.istft(gain * torch.stft(x, N, hop, N, w,
+ * center=True, pad_mode="reflect"), N, hop, N, w, center=True, length=n).  Everything is fp32 (matrix instructions against tables
+ * built in float64); an fp32 output is the quotient, an int16 output the quotient rounded to nearest-even and saturated.  strength
+ * = 0 is the identity up to fp32 rounding.  b is a weight of the caller's, as the mel basis is; strength is per request.
+ *   nvw_set_denoiser    the geometry and b (n_fft / 2 + 1 floats >= 0, host memory, copied).  Returns 1; 0 with the previous geometry
+ *                       kept: n_fft not a multiple of 4 in 64 .. 1024, hop not a multiple of 4 that divides n_fft, O outside 4 .. 16
+ *                       (with O >= 4 the window envelope stays >= 0.25 at an utterance's ends; at O = 2 it falls to 6e-6 for some
+ *                       lengths), no bias, a negative or non-finite one, or a geometry whose workgroup needs more than 160 KiB of
+ *                       LDS: 4 (32 K' + max(15 hop + J' + 4 ((15 hop + J') / hop + 1), 16 (J' + 4))) bytes, J' = n_fft rounded up
+ *                       to 16, K' = n_fft / 2 + 1 rounded up to 16.  1024 / 256 takes 130 KiB, 800 / 200 102 KiB.  Synchronises.
+ *   nvw_denoise_ready   the leading outputs computable from the first k samples of a stream: with last = 0 those whose every
+ *                       covering frame lies below k and needs no reflection at the end, max(0, ((k - N/2) / hop + 1) hop - N/2)
+ *                       for k > N / 2; with last = 1 (the stream ends at k) all k.  0 for k <= N / 2, or when no geometry is set.
+ *   nvw_denoise         `count` requests (1 .. 65535) in one launch.  in: n_in samples in device memory, int16 (in_type 16) or fp32
+ *                       (32), the samples of absolute index first .. first + n_in - 1; last: 1 when the stream ends at first + n_in.
+ *                       out: `count` samples in device memory, int16 or fp32 (out_type), the outputs t0 .. t0 + count - 1.  The range
+ *                       form is stateless, as nvw_resample is: a streaming caller keeps the tail of its input and asks for the
+ *                       outputs that have become computable, and gets bit for bit what the whole stream gives in one request.
+ *                       Output t needs the samples from max(0, ((t + N/2) / hop - O + 1) hop - N/2) on.  Nothing is written beyond
+ *                       out[count).  Asynchronous on `stream`: in and out stay alive until it has run.  Works inside and outside slot
+ *                       mode, touches no ring, column or session.  Returns count, or 0 with nothing written and nothing launched:
+ *                       no geometry set, count outside 1 .. 65535, a pointer not in device memory, a type other than 16 or 32, a
+ *                       non-positive n_in or count, a negative first or t0, first + n_in beyond 2^31 - 16, a negative or non-finite
+ *                       strength, a needed sample below `first`, or t0 + count beyond nvw_denoise_ready(first + n_in, last) (a
+ *                       whole stream must be longer than n_fft / 2). */
+typedef struct {
+    const void* in; int in_type;
+    long long first; int n_in;
+    int last;
+    void* out; int out_type;
+    long long t0; int count;
+    float strength;
+} nvw_denoise_req;
+int nvw_set_denoiser(nvw_engine* e, int n_fft, int hop, const float* bias);
+long long nvw_denoise_ready(nvw_engine* e, long long k, int last);
+int nvw_denoise(nvw_engine* e, const nvw_denoise_req* reqs, int count, void* stream);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

@@ -138,6 +138,9 @@ SIGNATURES = {
     "nvw_set_resampler": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "nvw_resample_count": (C.c_longlong, [C.c_void_p, C.c_int, C.c_longlong]),
     "nvw_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "nvw_set_denoiser": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "nvw_denoise_ready": (C.c_longlong, [C.c_void_p, C.c_longlong, C.c_int]),
+    "nvw_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_score_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_score_chunks_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "nvw_pinned_alloc": (C.c_void_p, [C.c_size_t]),

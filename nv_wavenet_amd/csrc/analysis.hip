@@ -2,6 +2,8 @@
 // precision is a conversion at the store.
 #include "analysis.hpp"
 
+#include "stft_core.hpp"
+
 #include <math.h>
 #include <string.h>
 
@@ -11,12 +13,10 @@ namespace wn {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int kAnalysisWaves = 4, kAnalysisThreads = 64 * kAnalysisWaves;
 constexpr int kAnalysisTilesMax = 5;      // bin tiles a wave holds at a time: ten accumulators, ten operand fragments in flight
 
-inline int round16(int v) { return 16 * ((v + 15) / 16); }
+inline int round16(int v) { return stft_round16(v); }
 
 struct AnalysisArgs {
     const AnalysisJob* jobs;
@@ -31,9 +31,6 @@ struct AnalysisArgs {
     int thresholds;          // of the mu-law table: the largest y
     float logFloor;          // the fp32 of log 1e-5
 };
-
-// where local position l of a tile's span lies in LDS: four spare words per hop (analysis.hpp, "frames")
-__device__ __forceinline__ unsigned span_at(const unsigned l, const unsigned hop) { return l + 4 * (l / hop); }
 
 // The samples [16 hop ti, 16 hop (ti + 1)) of a request, clipped to n: y = how many thresholds are <= p.
 __device__ __forceinline__ void mulaw_tile(const AnalysisJob& jb, const int ti, const short* thr, const int nthr, const int hop, const int tid) {
@@ -222,27 +219,10 @@ bool Analysis::set(int nFft, int hop, int nMel, const float* basis, int levels) 
     if (nFft < kAnalysisFftMin || nFft > kAnalysisFftMax || (nFft & 3) != 0 || hop < 1 || hop > nFft || nMel < 1 || nMel > kAnalysisMelMax ||
         basis == NULL || is_device_ptr(basis) || levels < 2 || levels > 65536 || ldsBytes(nFft, hop, levels) > (size_t)kAnalysisLdsMax)
         return false;
-    const int bins = nFft / 2 + 1, kp = round16(bins), jp = round16(nFft), nq = jp / 16, nk = kp / 16, nct = (nMel + 15) / 16;
-    const double kPi = 3.14159265358979323846;
-    // the windowed basis, in float64: the angle from k j mod nFft, so that its argument stays exact
-    std::vector<double> wnd(nFft), c(nFft), s(nFft);
-    for (int j = 0; j < nFft; j++) {
-        c[j] = cos(2 * kPi * j / nFft);
-        s[j] = sin(2 * kPi * j / nFft);
-        wnd[j] = 0.5 - 0.5 * c[j];
-    }
-    // A fragments: lane (row lane & 15, k-step column lane >> 4), element e = k-step 4 q + e, i.e. sample 16 q + 4 e + (lane >> 4)
-    std::vector<float> dft((size_t)nk * 2 * nq * 256, 0.f), mel((size_t)nct * nk * 256, 0.f);
-    for (int t = 0; t < nk; t++)
-        for (int q = 0; q < nq; q++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 4; e++) {
-                    const int k = t * 16 + (lane & 15), j = 16 * q + 4 * e + (lane >> 4);
-                    if (k >= bins || j >= nFft) continue;
-                    const int ph = (int)(((long long)k * j) % nFft);
-                    dft[(((size_t)t * 2 * nq + q) * 64 + lane) * 4 + e] = (float)(wnd[j] * c[ph]);
-                    dft[(((size_t)t * 2 * nq + nq + q) * 64 + lane) * 4 + e] = (float)(-wnd[j] * s[ph]);
-                }
+    const int bins = nFft / 2 + 1, nk = round16(bins) / 16, nct = (nMel + 15) / 16;
+    const std::vector<float> dft = stft_forward_table(nFft, StftBasis(nFft));
+    // the mel basis as A fragments: lane (row lane & 15, k-step column lane >> 4), element e = k-step 4 q + e, i.e. bin 16 q + 4 e + (lane >> 4)
+    std::vector<float> mel((size_t)nct * nk * 256, 0.f);
     for (int ct = 0; ct < nct; ct++)
         for (int q = 0; q < nk; q++)
             for (int lane = 0; lane < 64; lane++)

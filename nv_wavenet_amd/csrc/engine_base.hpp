@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/nv_wavenet_c.h"
 #include "analysis.hpp"
+#include "denoise.hpp"
 #include "nv_wavenet.hpp"
 #include "resample.hpp"
 
@@ -84,7 +85,17 @@ struct nvw_engine {
     int levels = 0;
     // ... and so do the sample-rate converters (resample.hpp), four to a handle
     wn::Resampler resamplers[4];
+    // ... and the bias denoiser (denoise.hpp)
+    wn::Denoiser denoiser;
 };
+static_assert(sizeof(nvw_denoise_req) == sizeof(wn::DenoiseReq) && offsetof(nvw_denoise_req, in) == offsetof(wn::DenoiseReq, in) &&
+              offsetof(nvw_denoise_req, in_type) == offsetof(wn::DenoiseReq, inType) &&
+              offsetof(nvw_denoise_req, first) == offsetof(wn::DenoiseReq, first) && offsetof(nvw_denoise_req, n_in) == offsetof(wn::DenoiseReq, nIn) &&
+              offsetof(nvw_denoise_req, last) == offsetof(wn::DenoiseReq, last) && offsetof(nvw_denoise_req, out) == offsetof(wn::DenoiseReq, out) &&
+              offsetof(nvw_denoise_req, out_type) == offsetof(wn::DenoiseReq, outType) &&
+              offsetof(nvw_denoise_req, t0) == offsetof(wn::DenoiseReq, t0) && offsetof(nvw_denoise_req, count) == offsetof(wn::DenoiseReq, count) &&
+              offsetof(nvw_denoise_req, strength) == offsetof(wn::DenoiseReq, strength),
+              "nvw_denoise_req is wn::DenoiseReq");
 static_assert(sizeof(nvw_resample_req) == sizeof(wn::ResampleReq) && offsetof(nvw_resample_req, in) == offsetof(wn::ResampleReq, in) &&
               offsetof(nvw_resample_req, in_type) == offsetof(wn::ResampleReq, inType) &&
               offsetof(nvw_resample_req, first) == offsetof(wn::ResampleReq, first) && offsetof(nvw_resample_req, n_in) == offsetof(wn::ResampleReq, nIn) &&

@@ -538,6 +538,26 @@ int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int coun
     }
     return count;
 }
+// ---- the bias denoiser: STFT, spectral subtraction, inverse STFT by request and output range (additive within ABI 7) ----------------
+int nvw_set_denoiser(nvw_engine* e, int n_fft, int hop, const float* bias) {
+    if (!e->denoiser.set(n_fft, hop, bias)) {
+        fprintf(stderr, "nvw_set_denoiser: refused (n_fft %d: a multiple of 4 in %d .. %d; hop %d: a multiple of 4 that divides n_fft, n_fft / "
+                "hop in %d .. %d; a host bias of n_fft / 2 + 1 finite values >= 0; at most %d bytes of LDS per workgroup)\n", n_fft,
+                wn::kDenoiseFftMin, wn::kDenoiseFftMax, hop, wn::kDenoiseOverlapMin, wn::kDenoiseOverlapMax, wn::kDenoiseLdsMax);
+        return 0;
+    }
+    return 1;
+}
+long long nvw_denoise_ready(nvw_engine* e, long long k, int last) { return e->denoiser.ready(k, last); }
+int nvw_denoise(nvw_engine* e, const nvw_denoise_req* reqs, int count, void* stream) {
+    if (!e->denoiser.run((const wn::DenoiseReq*)reqs, count, (hipStream_t)stream)) {
+        fprintf(stderr, "nvw_denoise: refused, nothing written (nvw_set_denoiser first; %d requests of 1 .. 65535; in and out in device "
+                "memory, types 16 or 32; n_in, count > 0, first, t0 >= 0; a finite strength >= 0; t0 + count within nvw_denoise_ready(first "
+                "+ n_in, last); every needed sample at or above first)\n", count);
+        return 0;
+    }
+    return count;
+}
 // ---- slot mode: ragged delivery, steps that never block (additive within ABI 7) ---------------------------------------------------
 long long nvw_slots_step_ragged(nvw_engine* e, int count, int* samples, short* pcm, long long capacity, nvw_slot_piece* pieces,
                                 int max_pieces, int* n_pieces, unsigned long long* ticket, void* stream) {

@@ -57,6 +57,10 @@ ANALYSIS_REQ = np.dtype({"names": ["pcm", "n", "mel", "precision", "c_stride", "
 RESAMPLE_REQ = np.dtype({"names": ["in", "in_type", "first", "n_in", "last", "out", "out_type", "m0", "count"],
                          "formats": ["<u8", "<i4", "<i8", "<i4", "<i4", "<u8", "<i4", "<i8", "<i4"],
                          "offsets": [0, 8, 16, 24, 28, 32, 40, 48, 56], "itemsize": 64})
+# ... nvw_denoise_req of nvw_denoise
+DENOISE_REQ = np.dtype({"names": ["in", "in_type", "first", "n_in", "last", "out", "out_type", "t0", "count", "strength"],
+                        "formats": ["<u8", "<i4", "<i8", "<i4", "<i4", "<u8", "<i4", "<i8", "<i4", "<f4"],
+                        "offsets": [0, 8, 16, 24, 28, 32, 40, 48, 56, 60], "itemsize": 64})
 
 
 class Impl:
@@ -1029,6 +1033,40 @@ class WavenetEngine:
             reqs[i] = (x.data_ptr(), bits[x.dtype], int(first), x.numel(), 1 if last else 0, out.data_ptr(), bits[out.dtype], int(m0), out.numel())
         if n == 0 or lib.nvw_resample(self._h, int(slot), reqs.ctypes.data, n, stream) != n:
             raise ValueError("nvw_resample refused %d requests" % n)
+
+    # ---- the bias denoiser (include/nv_wavenet_c.h, "DENOISER AT THE PCM BOUNDARY") ----
+    def setDenoiser(self, nFft, hop, bias):
+        """The geometry of denoise() and the bias spectrum [nFft / 2 + 1] (numpy or torch, >= 0, copied).  ValueError when refused
+        (the previous geometry stays): see nvw_set_denoiser."""
+        if bias is not None:
+            bias = np.ascontiguousarray(bias.detach().cpu().numpy() if hasattr(bias, "detach") else bias, dtype=np.float32)
+            if bias.shape != (int(nFft) // 2 + 1,):
+                raise ValueError("the bias spectrum is [nFft / 2 + 1], got %s" % (bias.shape,))
+        if not lib.nvw_set_denoiser(self._h, int(nFft), int(hop), None if bias is None else bias.ctypes.data):
+            raise ValueError("nvw_set_denoiser refused nFft %d, hop %d" % (nFft, hop))
+
+    def denoiseReady(self, k, last=False):
+        """Leading outputs computable from the first k samples of a stream (all k when it ends there); 0 without setDenoiser."""
+        return int(lib.nvw_denoise_ready(self._h, int(k), 1 if last else 0))
+
+    def denoise(self, requests, stream=None):
+        """Spectral subtraction, one launch: requests = [(x, first, last, out, t0, strength), ...] with x a contiguous 1-D int16 or
+        float32 CUDA tensor, the samples of absolute index first .. first + len(x) - 1 of its stream (last: the stream ends there),
+        and out a contiguous 1-D int16 or float32 CUDA tensor that receives the outputs t0 .. t0 + len(out) - 1.  Asynchronous on
+        `stream`.  ValueError when refused (nothing written): see nvw_denoise."""
+        import torch
+        bits = {torch.int16: 16, torch.float32: 32}
+        requests = list(requests)
+        n = len(requests)
+        reqs = np.zeros(max(n, 1), dtype=DENOISE_REQ)
+        for i, (x, first, last, out, t0, strength) in enumerate(requests):
+            for t in (x, out):
+                if not hasattr(t, "data_ptr") or t.dim() != 1 or t.dtype not in bits or not t.is_contiguous() or not t.is_cuda:
+                    raise ValueError("samples are contiguous 1-D int16 or float32 CUDA tensors")
+            reqs[i] = (x.data_ptr(), bits[x.dtype], int(first), x.numel(), 1 if last else 0, out.data_ptr(), bits[out.dtype], int(t0),
+                       out.numel(), float(strength))
+        if n == 0 or lib.nvw_denoise(self._h, reqs.ctypes.data, n, stream) != n:
+            raise ValueError("nvw_denoise refused %d requests" % n)
 
     # ---- scoring with carried state (include/nv_wavenet_c.h, "SCORING WITH CARRIED STATE"; DESIGN.md §6l) ----
     def _score_chunks(self, requests, mel, rows, states, pinned, stream, out=None):

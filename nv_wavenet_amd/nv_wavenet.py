@@ -402,6 +402,45 @@ class ResampleStream:
         return out
 
 
+class DenoiseStream:
+    """Streaming side of NVWaveNetEngine.denoise (denoise_stream makes it): feed(chunk, last=False) takes the next samples
+    [batch][k] (or [k] for a batch of 1) of `batch` streams that advance together and returns the outputs that have become
+    computable, [batch][count] (count may be 0).  Holds the tail of the input that later outputs still need and the two absolute
+    counters; any chunking of a signal gives the outputs of the whole-signal call bit for bit."""
+
+    def __init__(self, model, batch, strength, out_dtype):
+        self._model, self.batch, self.out_dtype = model, int(batch), out_dtype
+        self._strength = model._strengths(strength, self.batch)
+        self.fed = self.done = 0            # inputs taken, outputs given
+        self._tail, self._first = None, 0   # [batch][k]: the inputs of absolute index _first .. fed - 1
+        self.finished = False
+
+    def feed(self, chunk, last=False):
+        if self.finished:
+            raise ValueError("the stream has ended")
+        chunk = chunk.view(1, -1) if chunk.dim() == 1 else chunk
+        if chunk.dim() != 2 or chunk.size(0) != self.batch or not chunk.is_cuda or chunk.dtype not in (torch.int16, torch.float32):
+            raise ValueError("a chunk is an int16 or float32 CUDA tensor [batch = %d][k]" % self.batch)
+        buf = chunk if self._tail is None else torch.cat((self._tail, chunk), dim=1)
+        self.fed += chunk.size(1)
+        e, n_fft, hop = self._model._denoiser()
+        end = e.denoiseReady(self.fed, last)
+        if last and end != self.fed:
+            raise ValueError("a stream is longer than n_fft / 2 = %d samples" % (n_fft // 2))
+        count = max(0, end - self.done)
+        out = torch.zeros((self.batch, count), dtype=self.out_dtype, device=chunk.device)
+        if count:
+            buf = buf.contiguous()
+            e.denoise([(buf[b], self._first, last, out[b], self.done, self._strength[b]) for b in range(self.batch)],
+                      stream=torch.cuda.current_stream(chunk.device).cuda_stream)
+            self.done = end
+        self.finished = bool(last)
+        # the next output's first covering frame starts at ((done + N/2) / hop - O + 1) hop - N/2 (below 0: the reflection, from 0 on)
+        keep = min(self.fed, max(self._first, ((self.done + n_fft // 2) // hop + 1) * hop - n_fft - n_fft // 2))
+        self._tail, self._first = buf[:, keep - self._first:], keep
+        return out
+
+
 class NVWaveNetEngine(NVWaveNet):
     """The same wrapper with the engine kept alive: the reference rebuilds
     its nvWavenetInfer object and re-uploads every weight on each infer() (wavenet_infer.cu:124-143).
@@ -489,6 +528,12 @@ class NVWaveNetEngine(NVWaveNet):
             self._resample_engine.close()
             self._resample_engine = None
 
+    def _side_engine(self):
+        """The small engine that the conversions at the PCM boundary (resample, denoise) share; no generation evicts it."""
+        if getattr(self, "_resample_engine", None) is None:
+            self._resample_engine, self._resample_slots = self._new_engine(1, 64, Impl.AUTO), {}
+        return self._resample_engine
+
     def _resampler(self, rate_in, rate_out, taps=None):
         """(engine, slot, L, M, centre) of a ratio and its taps (None: resample_taps' default design).  The conversions have a
         small engine of their own, which no generation evicts; its four slots are cached per ratio, least recently used first out."""
@@ -497,9 +542,7 @@ class NVWaveNetEngine(NVWaveNet):
             import numpy as np
             design = np.ascontiguousarray(taps.detach().cpu().numpy() if hasattr(taps, "detach") else taps, dtype=np.float64)
         key = (L, M, None if taps is None else design.tobytes())
-        if getattr(self, "_resample_engine", None) is None:
-            self._resample_engine, self._resample_slots = self._new_engine(1, 64, Impl.AUTO), {}
-        e, slots = self._resample_engine, self._resample_slots
+        e, slots = self._side_engine(), self._resample_slots
         slot = slots.pop(key, None)
         if slot is None:
             slot = next(s for s in range(4) if s not in slots.values()) if len(slots) < 4 else slots.pop(next(iter(slots)))
@@ -532,6 +575,66 @@ class NVWaveNetEngine(NVWaveNet):
         feed(chunk, last=False) returns the outputs that have become computable; the concatenation over any chunking is bit for
         bit what resample() returns for the whole signal."""
         return ResampleStream(self, rate_in, rate_out, batch, out_dtype, taps)
+
+    # ---- the bias denoiser (DESIGN.md §6r) ----
+    @staticmethod
+    def denoiser_bias(pcm, n_fft=1024, hop=256):
+        """The bias spectrum of a recording of the model's noise floor (what it generates from zero mel frames), as WaveGlow's
+        Denoiser takes it: the magnitude of frame 0 of its STFT, [n_fft / 2 + 1] float32 on the CPU.  pcm: 1-D, in PCM units, longer
+        than n_fft / 2.  Computed in float64 on the host: it runs once per model, not on the hot path."""
+        x = pcm.detach().reshape(-1).to("cpu", torch.float64)
+        w = torch.hann_window(n_fft, periodic=True, dtype=torch.float64)
+        spec = torch.stft(x, n_fft, hop, n_fft, w, center=True, pad_mode="reflect", return_complex=True)
+        return spec[:, 0].abs().float()
+
+    def set_denoiser(self, n_fft, hop, bias):
+        """The geometry of denoise() and the bias spectrum [n_fft / 2 + 1] >= 0 (denoiser_bias measures it), in PCM units.  n_fft a
+        multiple of 4 in 64 .. 1024, hop a multiple of 4 dividing it with n_fft / hop in 4 .. 16: ValueError otherwise."""
+        self._denoise = (int(n_fft), int(hop), torch.as_tensor(bias).detach().float().cpu().contiguous())
+        self._denoiser()
+
+    def _denoiser(self):
+        """(engine, n_fft, hop) of set_denoiser, on the engine that the conversions share."""
+        if getattr(self, "_denoise", None) is None:
+            raise ValueError("denoise needs set_denoiser")
+        e = self._side_engine()
+        if getattr(e, "_denoise_key", None) is not self._denoise:
+            e.setDenoiser(*self._denoise)
+            e._denoise_key = self._denoise
+        return e, self._denoise[0], self._denoise[1]
+
+    @staticmethod
+    def _strengths(strength, batch):
+        s = [float(strength)] * batch if not hasattr(strength, "__len__") else [float(v) for v in strength]
+        if len(s) != batch:
+            raise ValueError("strength: a number, or one per utterance")
+        return s
+
+    def denoise(self, pcm, lengths=None, strength=0.1, out_dtype=torch.int16):
+        """Spectral subtraction of the bias spectrum on the GPU (nvw_denoise): pcm = int16 or float32 [batch][n] on
+        the GPU, in PCM units; lengths: None (all n), or `batch` values in n_fft / 2 + 1 .. n; strength: a number, or one per
+        utterance.  Returns [batch][n] of out_dtype (torch.int16: rounded to nearest-even and saturated; torch.float32) in one launch
+        for the whole batch: utterance b's lengths[b] outputs, zero past them.  ValueError for a bad shape, type or length."""
+        if pcm.dim() != 2 or pcm.dtype not in (torch.int16, torch.float32) or not pcm.is_cuda or out_dtype not in (torch.int16, torch.float32):
+            raise ValueError("pcm: an int16 or float32 CUDA tensor [batch][n], out_dtype torch.int16 or torch.float32")
+        e, n_fft, _ = self._denoiser()
+        batch_size, n = pcm.shape
+        lengths = [n] * batch_size if lengths is None else [int(k) for k in lengths]
+        if len(lengths) != batch_size or not all(n_fft // 2 < k <= n for k in lengths):
+            raise ValueError("lengths: %d values in %d .. %d" % (batch_size, n_fft // 2 + 1, n))
+        strength = self._strengths(strength, batch_size)
+        pcm = pcm.contiguous()
+        out = torch.zeros((batch_size, n), dtype=out_dtype, device=pcm.device)
+        e.denoise([(pcm[b, :lengths[b]], 0, True, out[b, :lengths[b]], 0, strength[b]) for b in range(batch_size)],
+                  stream=torch.cuda.current_stream(pcm.device).cuda_stream)
+        return out
+
+    def denoise_stream(self, batch=1, strength=0.1, out_dtype=torch.int16):
+        """A DenoiseStream: denoise() step by step, for callers that clean delivered PCM as it arrives (slot mode).  Its
+        feed(chunk, last=False) returns the outputs that have become computable; the concatenation over any chunking is bit for
+        bit what denoise() returns for the whole signal."""
+        self._denoiser()
+        return DenoiseStream(self, batch, strength, out_dtype)
 
     def cond_tiles(self, batch_size, sample_count, implementation=Impl.AUTO):
         """condTiles() of the engine that infer() will use for this batch and utterance length (for layout "packed")."""

@@ -104,7 +104,12 @@ results of the paths are checked to be equal bytes.  One JSON line each: median 
 24 000 int16 samples (frames in fp16 and samples, one launch) beside nvw_score_samples_mel of the frames and samples it wrote -- the
 claim to confirm is only that analysing a recording is a small share of scoring it.
 
+--denoise times the bias denoiser at n_fft 1024 / hop 256: one nvw_denoise launch for --batch one-second utterances
+(24 000 int16 samples in, int16 out, strength 0.1, a random bias spectrum), events around the launch, median of the rounds after one
+warm-up call.  The number to set it against is what generating that audio costs (bench.py).
+
     python scripts/slots_perf.py [--batch 12288] [--chunks 256,2048] [--steps 6] [--mel]
+    python scripts/slots_perf.py --denoise [--batch 12288] [--rounds 5]
     python scripts/slots_perf.py --prefill-mel [--parent-lib PATH] [--rounds 5]
     python scripts/slots_perf.py --score-mel [--rounds 5]
     python scripts/slots_perf.py --analyse [--rounds 5]
@@ -153,6 +158,7 @@ def main():
     ap.add_argument("--score-mel", action="store_true", help="time nvw_score_samples_mel against nvw_score_samples on rows upsampled beforehand")
     ap.add_argument("--analyse", action="store_true", help="time nvw_analyse beside nvw_score_samples_mel of the same audio")
     ap.add_argument("--rate", action="store_true", help="time the ragged step with plain delivery against rate delivery at 2 / 1 and 147 / 80")
+    ap.add_argument("--denoise", action="store_true", help="time one nvw_denoise launch for --batch one-second utterances at 1024 / 256")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
     ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
@@ -167,6 +173,9 @@ def main():
     Wc, bc = bench.make_cond_layers()
     if args.analyse:
         print(json.dumps(time_analyse(args, w, Wc, bc)), flush=True)
+        return
+    if args.denoise:
+        print(json.dumps(time_denoise(args, w)), flush=True)
         return
     if args.rate:
         for chunk in [int(c) for c in args.chunks.split(",")]:
@@ -1090,6 +1099,37 @@ def time_analyse(args, w, Wc, bc):
                                                "audio_seconds_per_second": round(count * n / 24000.0 / (1e-3 * med["analyse"]), 1)}
         e.close()
         torch.cuda.empty_cache()
+    return res
+
+
+def time_denoise(args, w):
+    """The --denoise measurement: one nvw_denoise launch for `batch` utterances of 24 000 samples (n_fft 1024 / hop 256, int16 in and out)."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import DENOISE_REQ
+    n_fft, hop, n, count = 1024, 256, 24000, args.batch
+    e = bench.build_engine(w, 1, 64)
+    e.setDenoiser(n_fft, hop, np.abs(np.random.default_rng(37).standard_normal(n_fft // 2 + 1)).astype(np.float32) * 2000 * 32)
+    g = torch.Generator(device="cuda")
+    g.manual_seed(41)
+    pcm = (8000 * torch.randn(count, n, device="cuda", generator=g)).clamp(-32768, 32767).to(torch.int16)
+    out = torch.zeros_like(pcm)
+    rq = np.zeros(count, dtype=DENOISE_REQ)
+    for b in range(count):
+        rq[b] = (pcm[b].data_ptr(), 16, 0, n, 1, out[b].data_ptr(), 16, 0, n, 0.1)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def denoise():
+        assert lib.nvw_denoise(e._h, rq.ctypes.data, count, s) == count
+
+    denoise()
+    ms = _timed_rounds([("denoise", denoise)], args.rounds)
+    assert bool(out.any())
+    med = float(np.median(ms["denoise"]))
+    res = {"denoise": "%d / %d" % (n_fft, hop), "batch": count, "n": n, "rounds": args.rounds, "device": torch.cuda.get_device_name(0),
+           "ms": _stats(ms["denoise"]), "audio_seconds_per_second": round(count * n / 24000.0 / (1e-3 * med), 1)}
+    e.close()
     return res
 
 
