@@ -911,6 +911,58 @@ int nvw_set_denoiser(nvw_engine* e, int n_fft, int hop, const float* bias);
 long long nvw_denoise_ready(nvw_engine* e, long long k, int last);
 int nvw_denoise(nvw_engine* e, const nvw_denoise_req* reqs, int count, void* stream);
 
+/* SLOT MODE: DENOISED DELIVERY, THE STFT STATE CARRIED ACROSS STEPS (additive within ABI 7).  nvw_denoise is stateless: a streaming
+ * caller who asks per step for what nvw_denoise_ready allows pays for sixteen frames to receive the one a step completes, and takes
+ * the PCM across the host boundary twice.  A denoised step cleans while it delivers: one launch computes the frames
+ * that this step's samples complete, gathered across columns, and carries each column's overlap-add across steps, moves and
+ * suspensions.
+ * A column's stream is x[i] = PCM of its local sample i from the stream origin s0 on: the `first` of the column's first piece after
+ * a start (0; the prime's length for a prefilled column), or after a resume whose denoise state was not set.  Outputs are those of
+ * nvw_denoise on x[s0 ..), numbered from s0, with n_fft, hop and bias of nvw_set_denoiser and a strength per column, int16.  After k
+ * samples of an unfinished stream D(k) = nvw_denoise_ready(k, 0) outputs are deliverable; a finished one of length n has all n.  The
+ * piece with first = f (relative to s0) and n samples carries m0 = D(f) and count = D(f + n) - m0, or f + n - m0 when it finishes
+ * the utterance; count may be 0.  An utterance's pieces, concatenated, are bit for bit nvw_denoise of its whole PCM with last = 1,
+ * however the steps cut it.  A stream that finishes at n_fft / 2 samples or fewer, which nvw_denoise refuses (the reflection is
+ * undefined), is delivered unchanged in its finishing piece.  A column stopped before its end delivers nothing more.
+ * The state of a column is its last n_fft PCM values (int16) and the n_fft - hop partial sums (fp32) of the overlap-add behind its
+ * last complete frame, then its strength (fp32), four spare bytes and s0 (int64): nvw_slots_denoise_state_bytes in all.
+ *   nvw_slots_set_denoise          on != 0: denoised delivery with `strength` for every column that does not set its own; 0: off (the
+ *                                  default; nvw_slots_begin and nvw_slots_end turn it off).  All state is zeroed: every column's
+ *                                  stream starts afresh at its next piece, a running column's too.  While it is on,
+ *                                  nvw_slots_step, nvw_slots_step_ragged and nvw_slots_step_ragged_rate are refused (they would
+ *                                  leave a hole in every stream) and so is nvw_set_denoiser.  Mutually exclusive with
+ *                                  nvw_slots_set_delivery: each refuses while the other is on (not built: both in one launch).
+ *                                  Synchronises.  Returns 1; 0 with nothing changed: not in slot mode, no nvw_set_denoiser, rate
+ *                                  delivery on, a negative or non-finite strength, or a ragged step in flight.
+ *   nvw_slot_set_denoise_strength  the strength of column `slot`, from the next frame computed on.  A frame is computed by the step
+ *                                  that completes it, and an output sums n_fft / hop frames: the outputs still waiting for a frame
+ *                                  mix both strengths.  nvw_slot_start* puts the column back to the session's value, so the order
+ *                                  is start, then set; nvw_slot_move carries it.  Returns 1; 0: off, a column without an
+ *                                  utterance, a bad value.
+ *   nvw_slots_denoise_capacity     PCM elements that always suffice for a denoised step of `count`; -1 when off.
+ *   nvw_slots_step_ragged_denoise  nvw_slots_step_ragged_rate with the denoiser in the resampler's place: the same arguments,
+ *                                  pieces, optional `samples`, ticket and return values, entry p of rate[] saying that piece p
+ *                                  carries outputs m0 .. m0 + count - 1 at element `offset` of pcm; never synchronises (a step
+ *                                  that completes more than 16 frames of some column is issued as several delivery launches, and
+ *                                  the first such step may grow their staging, which synchronises once).  -1 with nothing
+ *                                  launched: what nvw_slots_step_ragged refuses, denoised delivery off, pcm NULL or not device /
+ *                                  pinned memory, or pcm_capacity too small (pieces and rate are then written).
+ *   nvw_slots_denoise_state_bytes  bytes of a column's state; -1 when off.
+ *   nvw_slot_denoise_state_get / _set   a column's state to dst / from src (host or device memory), for save and resume, used and
+ *                                  ordered as nvw_slot_tail_get / _set: get after the step that nvw_slot_save follows, set after
+ *                                  nvw_slot_resume.  A resumed column whose state is not set starts a new stream at `done`: its
+ *                                  outputs are nvw_denoise of the remaining samples as a stream of their own.  Return 1; 0: off, a
+ *                                  column without an utterance, and for set an origin outside 0 .. the column's next sample. */
+int nvw_slots_set_denoise(nvw_engine* e, int on, float strength);
+int nvw_slot_set_denoise_strength(nvw_engine* e, int slot, float strength);
+long long nvw_slots_denoise_capacity(nvw_engine* e, int count);
+long long nvw_slots_step_ragged_denoise(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                        nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces,
+                                        long long* pcm_total, unsigned long long* ticket, void* stream);
+long long nvw_slots_denoise_state_bytes(nvw_engine* e);
+int nvw_slot_denoise_state_get(nvw_engine* e, int slot, void* dst);
+int nvw_slot_denoise_state_set(nvw_engine* e, int slot, const void* src);
+
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);
 /* time `reps` back-to-back nvw_run() launches with HIP events on `stream`; returns milliseconds

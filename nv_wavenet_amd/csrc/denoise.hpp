@@ -84,6 +84,13 @@ public:
     // nFft / hop in 4 .. 16, no bias or one in device memory, a negative or non-finite bias, or more LDS than a workgroup has.
     bool set(int nFft, int hop, const float* bias);
     bool isSet() const { return m_nFft > 0; }
+    // the geometry and the tables on the device, for the kernel that shares them (slots_deliver_denoise.hpp)
+    int nFft() const { return m_nFft; }
+    int hop() const { return m_hop; }
+    const float* forwardTable() const { return m_fwdTab; }
+    const float* inverseTable() const { return m_invTab; }
+    const float* biasTable() const { return m_bias; }
+    const float* envelopeTable() const { return m_wnd2; }
     // bytes of LDS a workgroup of this geometry takes
     static size_t ldsBytes(int nFft, int hop);
     // the leading outputs computable from the first k samples: k itself for a stream that ends there (0 for one that run() refuses,

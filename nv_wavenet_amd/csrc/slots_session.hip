@@ -1,6 +1,7 @@
 // slots_session.hip -- wn::SlotSession and wn::StageRing (slots_session.hpp): the host half of slot mode.  Compiled once.
 #include "slots_session.hpp"
 
+#include "denoise.hpp"
 #include "resample.hpp"
 
 namespace wn {
@@ -136,7 +137,7 @@ bool SlotSession::start(int slot, const void* x, int precision, long long cStrid
     d.uid = uid;
     d.precision = precision;
     d.active = 1;
-    m_tailZero[slot] = 1;      // (a new utterance has no history; a resumed one's is set after this: slotTailSet)
+    slotFresh(slot);      // (a new utterance has no history; a resumed one's is set after this: slotTailSet)
     slotMarkPending(slot, 1);
     slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
@@ -169,7 +170,7 @@ bool SlotSession::startMel(int slot, const void* mel, int precision, long long c
     melMarkDirty(slot);
     m_melTilesDirty = true;
     m_slotHost[slot].active = 0;      // (its SlotDesc goes idle: the feed writes zeros into its lanes, the mel feed overwrites them)
-    m_tailZero[slot] = 1;
+    slotFresh(slot);
     slotMarkPending(slot, 1);
     slotSamplingSet(slot, Sampling{});
     slotPrimeSet(slot, NULL, 0);
@@ -229,6 +230,10 @@ bool SlotSession::move(int from, int to) {
     m_slotMoves.push_back(SlotMove{from, to});
     std::swap(m_tailRow[from], m_tailRow[to]);      // (the filter history goes with the utterance: two host integers, no launch)
     std::swap(m_tailZero[from], m_tailZero[to]);
+    if (m_dn) {      // (... and so does the STFT state, with its origin and strength)
+        std::swap(m_dnOrigin[from], m_dnOrigin[to]);
+        std::swap(m_dnStrength[from], m_dnStrength[to]);
+    }
     slotSamplingSet(to, m_temps.get(from));
     slotSamplingSet(from, Sampling{});      // (as stop())
     if (primed(from)) {
@@ -372,7 +377,7 @@ bool SlotSession::getFeatures(void* dst, long long first, int count) {
     return true;
 }
 bool SlotSession::step(int count, int* yOut, short* pcm, hipStream_t stream) {
-    if (m_slotW <= 0 || count <= 0 || count > m_slotW || m_rate) return false;
+    if (m_slotW <= 0 || count <= 0 || count > m_slotW || m_rate || m_dn) return false;
     if (m_melColumns > 0 && (m_host.slotLive().upStride <= 0 || count > headroom())) return false;      // (mel columns short of frames)
     const int T = (int)(m_slotCounter % m_slotW);
     int cols = 0;
@@ -474,7 +479,7 @@ int SlotSession::slotPieces(int count, SlotPiece* out, int maxOut, long long& to
 long long SlotSession::stepRagged(int count, int* samples, short* pcm, long long capacity, SlotPiece* pieces, int maxPieces, int* nPieces,
                                   unsigned long long* ticket, hipStream_t stream) {
     if (m_slotW <= 0 || count <= 0 || count > m_slotW || (samples == NULL && pcm == NULL) || pieces == NULL || nPieces == NULL ||
-        ticket == NULL || m_rate)
+        ticket == NULL || m_rate || m_dn)
         return -1;
     const int upStride = m_host.slotLive().upStride;
     if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
@@ -509,7 +514,7 @@ void SlotSession::rateOff() {
     m_tailH = 0;
 }
 bool SlotSession::setDelivery(const Resampler* r, int index) {
-    if (m_slotW <= 0 || (r != NULL && !r->ready())) return false;
+    if (m_slotW <= 0 || (r != NULL && (!r->ready() || m_dn))) return false;
     if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
     if (r != NULL && !slots_deliver_rate_prepare(r->geom().groups, r->tilesPerPass())) return false;
     gpuErrChk(hipDeviceSynchronize());
@@ -634,6 +639,250 @@ long long SlotSession::stepRaggedRate(int count, int* samples, long long capacit
     *ticket = m_dlv.uses();
     return ok ? total : -2;
 }
+// ---- ragged delivery through the bias denoiser (slots_deliver_denoise.hpp) ----
+namespace {
+bool strengthOk(float s) { return s >= 0.f && s <= 3.0e38f; }      // (finite, not negative, not a NaN)
+// what follows a column's history and accumulator in its state as a value
+struct DenoiseStateTrailer {
+    float strength;
+    int pad;
+    long long origin;
+};
+}  // namespace
+void SlotSession::slotFresh(int slot) {
+    m_tailZero[slot] = 1;
+    if (m_dn) m_dnStrength[slot] = m_dnDefault;
+}
+void SlotSession::denoiseOff() {
+    freeDev(m_dnHist, m_dnAcc, m_dnDev);
+    m_dnStage.reset();
+    m_dnStageBytes = 0;
+    m_dn = NULL;
+}
+bool SlotSession::setDenoise(const Denoiser* d, float strength) {
+    if (m_slotW <= 0 || (d != NULL && (!d->isSet() || m_rate || !strengthOk(strength)))) return false;
+    if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
+    if (d != NULL && !slots_deliver_denoise_prepare(d->nFft(), d->hop())) return false;
+    gpuErrChk(hipDeviceSynchronize());
+    denoiseOff();
+    if (d == NULL) return true;
+    m_dn = d;
+    m_dnDefault = strength;
+    m_dnCur = 0;
+    allocZero(m_dnHist, 2 * (size_t)f.maxBatch * denoise_hist_len(d->nFft()) * sizeof(short));
+    allocZero(m_dnAcc, 2 * (size_t)f.maxBatch * denoise_acc_len(d->nFft(), d->hop()) * sizeof(float));
+    m_tailZero.assign(f.maxBatch, 1);
+    m_dnOrigin.assign(f.maxBatch, 0);
+    m_dnStrength.assign(f.maxBatch, strength);
+    gpuErrChk(hipMalloc((void**)&m_dnDev, dnLaunchBytes()));
+    m_dnStageBytes = 2 * dnLaunchBytes();
+    m_dnStage.make(kSlotTickets, m_dnStageBytes);
+    gpuErrChk(hipDeviceSynchronize());
+    return true;
+}
+bool SlotSession::setDenoiseStrength(int slot, float strength) {
+    if (!m_dn || !inBatch(slot) || !slotHolds(slot) || !strengthOk(strength)) return false;
+    m_dnStrength[slot] = strength;
+    return true;
+}
+long long SlotSession::denoiseCapacity(int count) const {
+    if (!m_dn || count <= 0 || count > m_slotW) return -1;
+    // a piece of n samples completes at most n / hop + 1 hops of outputs; the one that finishes adds the at most N / 2 + hop held back
+    const long long most = (long long)count + m_dn->nFft() / 2 + 2 * m_dn->hop();
+    return f.maxBatch * ((most + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign);
+}
+long long SlotSession::denoiseStateBytes() const {
+    if (!m_dn) return -1;
+    return (long long)(denoise_hist_len(m_dn->nFft()) * sizeof(short) + denoise_acc_len(m_dn->nFft(), m_dn->hop()) * sizeof(float) +
+                       sizeof(DenoiseStateTrailer));
+}
+bool SlotSession::denoiseStateGet(int slot, void* dst) {
+    if (!m_dn || !inBatch(slot) || !slotHolds(slot) || dst == NULL) return false;
+    const size_t hist = denoise_hist_len(m_dn->nFft()) * sizeof(short), acc = denoise_acc_len(m_dn->nFft(), m_dn->hop()) * sizeof(float);
+    const size_t row = m_tailRow[slot];
+    const bool mel = m_melHost[slot].state != 0;
+    const long long next = m_slotPending[slot] == 1 ? m_slotResumeDone[slot] : m_slotCounter - (mel ? m_melHost[slot].start : m_slotHost[slot].start);
+    DenoiseStateTrailer t = {m_dnStrength[slot], 0, m_tailZero[slot] ? next : m_dnOrigin[slot]};
+    if (m_tailZero[slot]) {      // (the stream starts at the column's next sample: nothing behind it)
+        const std::vector<char> zero(hist + acc, 0);
+        gpuErrChk(hipMemcpy(dst, zero.data(), hist + acc, hipMemcpyDefault));
+    } else {
+        gpuErrChk(hipMemcpy(dst, (const char*)m_dnHist + ((size_t)m_dnCur * f.maxBatch + row) * hist, hist, hipMemcpyDefault));
+        gpuErrChk(hipMemcpy((char*)dst + hist, (const char*)m_dnAcc + ((size_t)m_dnCur * f.maxBatch + row) * acc, acc, hipMemcpyDefault));
+    }
+    gpuErrChk(hipMemcpy((char*)dst + hist + acc, &t, sizeof(t), hipMemcpyDefault));
+    return true;
+}
+bool SlotSession::denoiseStateSet(int slot, const void* src) {
+    if (!m_dn || !inBatch(slot) || !slotHolds(slot) || src == NULL) return false;
+    const size_t hist = denoise_hist_len(m_dn->nFft()) * sizeof(short), acc = denoise_acc_len(m_dn->nFft(), m_dn->hop()) * sizeof(float);
+    const size_t row = m_tailRow[slot];
+    const bool mel = m_melHost[slot].state != 0;
+    const long long next = m_slotPending[slot] == 1 ? m_slotResumeDone[slot] : m_slotCounter - (mel ? m_melHost[slot].start : m_slotHost[slot].start);
+    DenoiseStateTrailer t;
+    gpuErrChk(hipMemcpy(&t, (const char*)src + hist + acc, sizeof(t), hipMemcpyDefault));
+    if (t.origin < 0 || t.origin > next || !strengthOk(t.strength)) return false;
+    gpuErrChk(hipMemcpy((char*)m_dnHist + ((size_t)m_dnCur * f.maxBatch + row) * hist, src, hist, hipMemcpyDefault));
+    gpuErrChk(hipMemcpy((char*)m_dnAcc + ((size_t)m_dnCur * f.maxBatch + row) * acc, (const char*)src + hist, acc, hipMemcpyDefault));
+    m_dnOrigin[slot] = t.origin;
+    m_dnStrength[slot] = t.strength;
+    m_tailZero[slot] = 0;
+    return true;
+}
+long long SlotSession::stepRaggedDenoise(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                                         SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
+                                         hipStream_t stream) {
+    if (m_slotW <= 0 || !m_dn || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL || nPieces == NULL ||
+        pcmTotal == NULL || ticket == NULL)
+        return -1;
+    const int upStride = m_host.slotLive().upStride;
+    if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
+    int* const dSamples = samples ? (int*)deliverTarget(samples) : NULL;
+    short* const dPcm = (short*)deliverTarget(pcm);
+    if ((samples && !dSamples) || !dPcm) return -1;
+    long long total = 0;
+    const int n = slotPieces(count, NULL, 0, total, upStride);
+    if (n > maxPieces || (samples && total > capacity)) return -1;
+    slotPieces(count, pieces, maxPieces, total, upStride);
+    // the outputs every piece carries, from its sample piece: D(k0) .. D(k0 + n) of its stream, or up to the stream's last one
+    const int N = m_dn->nFft(), hop = m_dn->hop(), half = N / 2;
+    const auto origin = [&](const SlotPiece& p) { return m_tailZero[p.slot] ? p.first : m_dnOrigin[p.slot]; };
+    // frames of a stream of k samples: complete ones, or all of one that ends there (none: it is delivered unchanged)
+    const auto frames = [&](long long k, bool fin) { return !fin ? denoise_frames(k, N, hop) : k > half ? k / hop + 1 : 0; };
+    long long off = 0, pcmEnd = 0, most = 0;
+    for (int i = 0; i < n; i++) {
+        const SlotPiece& p = pieces[i];
+        const long long k0 = p.first - origin(p), t0 = denoise_delivered(k0, N, hop);
+        const long long end = p.finished ? k0 + p.n : denoise_delivered(k0 + p.n, N, hop);
+        rate[i] = SlotRatePiece{t0, (int)(end - t0), 0, off};
+        if (end > t0) {
+            pcmEnd = off + (end - t0);
+            off = (pcmEnd + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign;
+        }
+        const long long nf = frames(k0 + p.n, p.finished != 0) - denoise_frames(k0, N, hop);
+        if (nf > most) most = nf;
+    }
+    if (pcmEnd > pcmCapacity) return -1;      // (pieces and rate have been written: nothing else has changed)
+    // The launches: the whole step where no piece completes more than 16 frames, otherwise sub-ranges of 6 hop samples, which
+    // complete at most 6 + 1 and, where a stream ends, N / 2 / hop + 1 <= 9 more.  Per launch the pieces with new frames in tile
+    // order, then the others; a tile takes pieces while their frames fit its 16 N-columns.
+    const int chunk = most <= 16 ? count : 6 * hop;
+    m_dnPieces.clear();
+    m_dnPairs.clear();
+    m_dnPlan.clear();
+    size_t stageBytes = 0;
+    for (int a = 0; a < count; a += chunk) {
+        const int b = a + chunk < count ? a + chunk : count;
+        const size_t pieceBase = m_dnPieces.size(), pairBase = m_dnPairs.size();
+        int col = 16, framed = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            for (int i = 0; i < n; i++) {
+                const SlotPiece& p = pieces[i];
+                if (p.n <= a) continue;
+                DenoisePiece r = {};
+                const bool fin = p.finished && p.n <= b;
+                r.n = (p.n < b ? p.n : b) - a;
+                r.k0 = p.first - origin(p) + a;
+                r.q0 = (int)denoise_frames(r.k0, N, hop);
+                r.nf = (int)frames(r.k0 + r.n, fin) - r.q0;
+                if ((r.nf > 0) != (pass == 0)) continue;
+                if (r.nf > 16) return -1;      // (never: the bound above)
+                const long long t0 = denoise_delivered(r.k0, N, hop);
+                r.slot = p.slot;
+                r.row = m_tailRow[p.slot];
+                r.flags = fin ? kDenoiseFin : 0;
+                r.offset = rate[i].offset + (t0 - rate[i].m0);
+                r.count = (int)((fin ? r.k0 + r.n : denoise_delivered(r.k0 + r.n, N, hop)) - t0);
+                r.strength = m_dnStrength[p.slot];
+                if (pass == 0) {
+                    if (col + r.nf > 16) {
+                        m_dnPairs.resize(pairBase + (m_dnPairs.size() - pairBase + 15) / 16 * 16, DenoisePair{-1, 0});
+                        col = 0;
+                    }
+                    r.col0 = col;
+                    for (int k = 0; k < r.nf; k++) m_dnPairs.push_back(DenoisePair{(int)(m_dnPieces.size() - pieceBase), r.q0 + k});
+                    col += r.nf;
+                    framed++;
+                }
+                m_dnPieces.push_back(r);
+            }
+            if (pass == 0) m_dnPairs.resize(pairBase + (m_dnPairs.size() - pairBase + 15) / 16 * 16, DenoisePair{-1, 0});
+        }
+        const int launched = (int)(m_dnPieces.size() - pieceBase), tiles = (int)((m_dnPairs.size() - pairBase) / 16);
+        for (int v : {a, launched, framed, tiles}) m_dnPlan.push_back(v);
+        stageBytes += (size_t)launched * sizeof(DenoisePiece) + (size_t)tiles * 16 * sizeof(DenoisePair);
+    }
+    if (stageBytes > m_dnStageBytes) {
+        gpuErrChk(hipDeviceSynchronize());      // (earlier steps may still be reading what is replaced)
+        m_dnStageBytes = 2 * stageBytes;
+        m_dnStage.make(kSlotTickets, m_dnStageBytes);
+    }
+    *nPieces = n;
+    *pcmTotal = pcmEnd;
+    const int T = (int)(m_slotCounter % m_slotW);
+    char* const dstage = (char*)m_dnStage.acquire();
+    DeliverPiece* const stage = (DeliverPiece*)m_dlv.acquire();
+    int cols = 0;
+    bool ok = generate(count, cols, stream);
+    if (n > 0) {
+        if (dSamples) {
+            for (int i = 0; i < n; i++) stage[i] = DeliverPiece{pieces[i].slot, pieces[i].n, pieces[i].offset};
+            gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(DeliverPiece), hipMemcpyHostToDevice, stream));
+            ok = slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, NULL) && ok;
+        }
+        const size_t histImage = (size_t)f.maxBatch * denoise_hist_len(N), accImage = (size_t)f.maxBatch * denoise_acc_len(N, hop);
+        DenoisePiece* const devPieces = (DenoisePiece*)m_dnDev;
+        DenoisePair* const devPairs = (DenoisePair*)(m_dnDev + (size_t)f.maxBatch * sizeof(DenoisePiece));
+        size_t at = 0, pieceAt = 0, pairAt = 0;
+        for (size_t l = 0; l < m_dnPlan.size(); l += 4) {
+            const int a0 = m_dnPlan[l], launched = m_dnPlan[l + 1], framed = m_dnPlan[l + 2], tiles = m_dnPlan[l + 3];
+            if (launched == 0) continue;      // (every piece ended below this sub-range)
+            const size_t pieceBytes = (size_t)launched * sizeof(DenoisePiece), pairBytes = (size_t)tiles * 16 * sizeof(DenoisePair);
+            memcpy(dstage + at, &m_dnPieces[pieceAt], pieceBytes);
+            gpuErrChk(hipMemcpyAsync(devPieces, dstage + at, pieceBytes, hipMemcpyHostToDevice, stream));
+            if (tiles > 0) {
+                memcpy(dstage + at + pieceBytes, &m_dnPairs[pairAt], pairBytes);
+                gpuErrChk(hipMemcpyAsync(devPairs, dstage + at + pieceBytes, pairBytes, hipMemcpyHostToDevice, stream));
+            }
+            at += pieceBytes + pairBytes;
+            pieceAt += launched;
+            pairAt += (size_t)tiles * 16;
+            DenoiseLaunch d;
+            d.pieces = devPieces;
+            d.pairs = devPairs;
+            d.count = launched;
+            d.framed = framed;
+            d.tiles = tiles;
+            d.y = m_slotY;
+            d.table = m_mulaw;
+            d.T = (T + a0) % m_slotW;
+            d.W = m_slotW;
+            d.histIn = m_dnHist + (size_t)m_dnCur * histImage;
+            d.histOut = m_dnHist + (size_t)(m_dnCur ^ 1) * histImage;
+            d.accIn = m_dnAcc + (size_t)m_dnCur * accImage;
+            d.accOut = m_dnAcc + (size_t)(m_dnCur ^ 1) * accImage;
+            d.pcm = dPcm;
+            d.fwdTab = m_dn->forwardTable();
+            d.invTab = m_dn->inverseTable();
+            d.bias = m_dn->biasTable();
+            d.wnd2 = m_dn->envelopeTable();
+            d.nFft = N;
+            d.hop = hop;
+            ok = slots_deliver_denoise(stream, d) && ok;
+            m_dnCur ^= 1;
+        }
+        for (int i = 0; i < n; i++)
+            if (m_tailZero[pieces[i].slot]) {      // (its stream has begun: the images hold what the flag stood for)
+                m_dnOrigin[pieces[i].slot] = pieces[i].first;
+                m_tailZero[pieces[i].slot] = 0;
+            }
+    }
+    m_dnStage.release(stream);
+    m_dlv.release(stream);
+    m_slotCounter += count;
+    *ticket = m_dlv.uses();
+    return ok ? total : -2;
+}
 float SlotSession::timeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t stream) {
     if (m_slotW <= 0 || count <= 0 || count > m_slotW || count > m_slotCounter || samples == NULL || pcm == NULL || reps <= 0) return -1.f;
     int* const dSamples = (int*)deliverTarget(samples);
@@ -698,6 +947,7 @@ void SlotSession::end() {
     if (m_slotW <= 0) return;
     gpuErrChk(hipDeviceSynchronize());
     rateOff();
+    denoiseOff();
     freeDev(m_slotDesc, m_slotFeat, m_slotSel, m_slotY, m_slotPcm, m_slotUpd, m_dlvDev, m_saveDev, m_scaleDev, m_primeDev, m_melDesc, m_melUpd,
             m_melColInfo, m_melStage);
     m_melStageBytes = 0;

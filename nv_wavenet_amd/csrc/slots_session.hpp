@@ -12,6 +12,7 @@
 #include "gpu_check.hpp"
 #include "slots.hpp"
 #include "slots_deliver.hpp"
+#include "slots_deliver_denoise.hpp"
 #include "slots_deliver_rate.hpp"
 #include "slots_mel.hpp"
 #include "slots_prime.hpp"
@@ -21,6 +22,7 @@
 namespace wn {
 
 class Resampler;      // (resample.hpp, which includes this header for StageRing)
+class Denoiser;       // (denoise.hpp, likewise)
 
 // what is fixed when the engine has been constructed
 struct SlotFacts {
@@ -252,6 +254,37 @@ public:
     long long stepRaggedRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
                              SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
                              hipStream_t stream = 0);
+    // ---- ragged delivery through the bias denoiser (slots_deliver_denoise.hpp) ----
+    // Denoised delivery with the geometry, bias and tables of `d` (NULL: off, the default) and `strength` for every column that
+    // does not set its own: allocates the two images of the columns' STFT state (zeroed) and the staging; every column's stream
+    // starts afresh at its next piece, that of a column already running too.  While it is on, slotsStep, slotsStepRagged and
+    // slotsStepRaggedRate are refused (they would leave a hole in every stream), and so is a new geometry of `d`.  false (nothing
+    // changes): not in slot mode, a denoiser that is not set, rate delivery on (not built: both in one launch), a bad strength, a
+    // ragged step in flight, or the kernel's LDS opt-in refused.  Synchronises.  slotsBegin and slotsEnd turn it off.
+    bool setDenoise(const Denoiser* d, float strength);
+    bool denoiseOn() const { return m_dn != NULL; }
+    // The strength of column `slot`, from the next frame computed on: a frame is computed by the step that completes it, so the
+    // outputs still waiting for a frame mix frames of both strengths.  A start puts the column back to the session's default; a
+    // move carries the value.  false: off, slot outside the batch, a column without an utterance, a bad value.
+    bool setDenoiseStrength(int slot, float strength);
+    // PCM elements that always suffice for a denoised step of `count`; -1 when off or count is out of range
+    long long denoiseCapacity(int count) const;
+    // bytes of a column's state as a value: N int16 of history, N - hop fp32 of accumulator, then the strength (fp32), four spare
+    // bytes and the stream origin (int64); -1 when off
+    long long denoiseStateBytes() const;
+    // A column's state from / to host or device memory, in the images the next step reads: blocking copies on the null stream,
+    // ordered and used as slotTailGet / slotTailSet.  A resumed column whose state is not set starts a new stream at `done`.
+    // false: off, slot outside the batch, a column without an utterance, NULL; set: an origin beyond the column's next sample.
+    bool denoiseStateGet(int slot, void* dst);
+    bool denoiseStateSet(int slot, const void* src);
+    // slotsStepRaggedRate with the denoiser in the resampler's place: the same launches up to and including the generation, the
+    // same pieces and optional `samples`, and one slot_deliver_denoise_kernel launch (several, over sub-ranges of the step, when
+    // some piece completes more than 16 frames) that writes piece p's outputs rate[p].m0 .. m0 + count - 1 at element
+    // rate[p].offset of `pcm`.  Returns, refuses and never synchronises as slotsStepRaggedRate; a step whose sub-ranges need more
+    // staging than two full launches grows it once, and that synchronises.
+    long long stepRaggedDenoise(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                                SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
+                                hipStream_t stream = 0);
     // Measurement only (scripts/slots_perf.py --serve): `reps` back-to-back output passes over the last `count` samples generated,
     // timed with events on `stream`; returns milliseconds for all of them, < 0 when refused.  ragged = false: what slotsStep
     // issues after the generation -- the PCM launches and the 2-D copies into samples / pcm [maxBatch][count]; ragged = true: the
@@ -325,6 +358,21 @@ private:
     std::vector<char> m_tailZero;           // per column: its history counts as zero (a start, or a resume whose tail was not set)
     RatePiece* m_rateDev = NULL;            // [maxBatch] on the device: the rate pieces of the step being delivered
     StageRing m_rateStage;                  // pinned host staging of them, as m_dlv
+    // ... and delivery through the denoiser (slots_deliver_denoise.hpp); state rows and "starts afresh" are m_tailRow
+    // and m_tailZero, which rate delivery, never on at the same time, uses for its tails
+    const Denoiser* m_dn = NULL;            // the handle's denoiser in use (NULL: off)
+    float m_dnDefault = 0.f;                // the strength of a column that has not set its own
+    int m_dnCur = 0;                        // the state images the next launch reads; it writes the others
+    short* m_dnHist = NULL;                 // [2][maxBatch][N]
+    float* m_dnAcc = NULL;                  // [2][maxBatch][N - hop]
+    std::vector<long long> m_dnOrigin;      // per column: s0, the local index its stream counts from
+    std::vector<float> m_dnStrength;
+    char* m_dnDev = NULL;                   // one launch's pieces [maxBatch], then its pairs [16 maxBatch], on the device
+    StageRing m_dnStage;                    // pinned host staging of a step's launches, as m_dlv
+    size_t m_dnStageBytes = 0;
+    std::vector<DenoisePiece> m_dnPieces;   // (scratch of a step: the records of all its launches ...
+    std::vector<DenoisePair> m_dnPairs;
+    std::vector<int> m_dnPlan;              //  ... and per launch: first sample, pieces, those with frames, tiles)
     // ... and the sampling temperatures (slots_sampler.hpp)
     std::vector<char> m_tempDirty;         // the columns whose table entry the next step writes
     std::vector<int> m_tempDirtyList;
@@ -362,6 +410,9 @@ private:
     }
     int slotPieces(int count, SlotPiece* out, int maxOut, long long& total, int upStride) const;
     void rateOff();
+    void denoiseOff();
+    void slotFresh(int slot);      // a start: no filter history, no STFT state, the default strength
+    size_t dnLaunchBytes() const { return (size_t)f.maxBatch * (sizeof(DenoisePiece) + 16 * sizeof(DenoisePair)); }
     short* tailAt(int image, int slot) const { return m_tails + ((size_t)image * f.maxBatch + m_tailRow[slot]) * m_tailH; }
     // what slotStart / slotStartMel refuse (shared with slotsResumeList, which checks every request before it changes anything)
     bool slotStartOk(int slot, const void* x, int precision, long long cStride, long long tStride, int length) const;

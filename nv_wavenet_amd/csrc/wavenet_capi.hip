@@ -540,8 +540,9 @@ int nvw_resample(nvw_engine* e, int slot, const nvw_resample_req* reqs, int coun
 }
 // ---- the bias denoiser: STFT, spectral subtraction, inverse STFT by request and output range (additive within ABI 7) ----------------
 int nvw_set_denoiser(nvw_engine* e, int n_fft, int hop, const float* bias) {
-    if (!e->denoiser.set(n_fft, hop, bias)) {
-        fprintf(stderr, "nvw_set_denoiser: refused (n_fft %d: a multiple of 4 in %d .. %d; hop %d: a multiple of 4 that divides n_fft, n_fft / "
+    // (a geometry that a slot session delivers through keeps its tables: the columns' STFT states are that geometry's)
+    if (e->slots().denoiseOn() || !e->denoiser.set(n_fft, hop, bias)) {
+        fprintf(stderr, "nvw_set_denoiser: refused (not while nvw_slots_set_denoise is on; n_fft %d: a multiple of 4 in %d .. %d; hop %d: a multiple of 4 that divides n_fft, n_fft / "
                 "hop in %d .. %d; a host bias of n_fft / 2 + 1 finite values >= 0; at most %d bytes of LDS per workgroup)\n", n_fft,
                 wn::kDenoiseFftMin, wn::kDenoiseFftMax, hop, wn::kDenoiseOverlapMin, wn::kDenoiseOverlapMax, wn::kDenoiseLdsMax);
         return 0;
@@ -588,6 +589,39 @@ long long nvw_slots_step_ragged_rate(nvw_engine* e, int count, int* samples, lon
                                      unsigned long long* ticket, void* stream) {
     return e->slots().stepRaggedRate(count, samples, capacity, pcm, pcm_capacity, (wn::SlotPiece*)pieces, (wn::SlotRatePiece*)rate, max_pieces,
                                      n_pieces, pcm_total, ticket, (hipStream_t)stream);
+}
+// ---- slot mode: denoised delivery, the STFT state carried across steps (additive within ABI 7) --------------------------------------
+int nvw_slots_set_denoise(nvw_engine* e, int on, float strength) {
+    if (e->slots().setDenoise(on ? &e->denoiser : NULL, strength)) return 1;
+    fprintf(stderr, "nvw_slots_set_denoise: refused, nothing changed (nvw_slots_begin and nvw_set_denoiser first; not with "
+            "nvw_slots_set_delivery on; a finite strength >= 0; no ragged step in flight)\n");
+    return 0;
+}
+int nvw_slot_set_denoise_strength(nvw_engine* e, int slot, float strength) {
+    if (e->slots().setDenoiseStrength(slot, strength)) return 1;
+    fprintf(stderr, "nvw_slot_set_denoise_strength: refused (nvw_slots_set_denoise first; slot %d of %d: a column with an utterance; a "
+            "finite strength >= 0)\n", slot, e->maxBatch());
+    return 0;
+}
+long long nvw_slots_denoise_capacity(nvw_engine* e, int count) { return e->slots().denoiseCapacity(count); }
+long long nvw_slots_denoise_state_bytes(nvw_engine* e) { return e->slots().denoiseStateBytes(); }
+int nvw_slot_denoise_state_get(nvw_engine* e, int slot, void* dst) {
+    if (e->slots().denoiseStateGet(slot, dst)) return 1;
+    fprintf(stderr, "nvw_slot_denoise_state_get: refused (nvw_slots_set_denoise first; slot %d of %d: a column with an utterance)\n", slot,
+            e->maxBatch());
+    return 0;
+}
+int nvw_slot_denoise_state_set(nvw_engine* e, int slot, const void* src) {
+    if (e->slots().denoiseStateSet(slot, src)) return 1;
+    fprintf(stderr, "nvw_slot_denoise_state_set: refused (nvw_slots_set_denoise first; slot %d of %d: a column with an utterance; an "
+            "origin in 0 .. the column's next sample, a finite strength >= 0)\n", slot, e->maxBatch());
+    return 0;
+}
+long long nvw_slots_step_ragged_denoise(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                        nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces,
+                                        long long* pcm_total, unsigned long long* ticket, void* stream) {
+    return e->slots().stepRaggedDenoise(count, samples, capacity, pcm, pcm_capacity, (wn::SlotPiece*)pieces, (wn::SlotRatePiece*)rate,
+                                        max_pieces, n_pieces, pcm_total, ticket, (hipStream_t)stream);
 }
 float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream) {
     return e->slots().timeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);

@@ -502,6 +502,57 @@ class WavenetEngine:
             raise ValueError("nvw_slots_step_ragged_rate refused a step of %d samples into %d PCM elements" % (count, pcm.numel()))
         return int(total), int(pcm_total.value), pieces[:n.value], rate[:n.value], int(ticket.value)
 
+    # ---- denoised delivery (include/nv_wavenet_c.h, "DENOISED DELIVERY") ----
+    def slotsSetDenoise(self, strength):
+        """Denoised delivery in slot mode with `strength` for every column that does not set its own (setDenoiser first); None:
+        off.  ValueError when refused (nothing changed): see nvw_slots_set_denoise."""
+        if not lib.nvw_slots_set_denoise(self._h, 0 if strength is None else 1, float(strength or 0)):
+            raise ValueError("nvw_slots_set_denoise refused strength %s" % (strength,))
+
+    def slotSetDenoiseStrength(self, slot, strength):
+        """The strength of column `slot`, from the next frame computed on (after slotStart / slotResume)."""
+        if not lib.nvw_slot_set_denoise_strength(self._h, int(slot), float(strength)):
+            raise ValueError("nvw_slot_set_denoise_strength refused slot %d, strength %s" % (slot, strength))
+
+    def slotsDenoiseCapacity(self, count):
+        """PCM elements that always suffice for slotsStepRaggedDenoise(count); -1 when denoised delivery is off."""
+        return int(lib.nvw_slots_denoise_capacity(self._h, int(count)))
+
+    def slotsDenoiseStateBytes(self):
+        """Bytes of a column's denoise state (history, accumulator, strength, stream origin); -1 when denoised delivery is off."""
+        return int(lib.nvw_slots_denoise_state_bytes(self._h))
+
+    def slotDenoiseStateGet(self, slot):
+        """The denoise state of column `slot`: a numpy uint8 array (blocking; for save and resume)."""
+        state = np.zeros(max(self.slotsDenoiseStateBytes(), 0), dtype=np.uint8)
+        if not lib.nvw_slot_denoise_state_get(self._h, int(slot), state.ctypes.data):
+            raise ValueError("nvw_slot_denoise_state_get refused slot %d" % slot)
+        return state
+
+    def slotDenoiseStateSet(self, slot, state):
+        """Sets the denoise state of column `slot` (a uint8 array of slotsDenoiseStateBytes()): after slotResume, before the step."""
+        state = np.ascontiguousarray(state, dtype=np.uint8)
+        if state.shape != (self.slotsDenoiseStateBytes(),) or not lib.nvw_slot_denoise_state_set(self._h, int(slot), state.ctypes.data):
+            raise ValueError("nvw_slot_denoise_state_set refused slot %d, a state of shape %s" % (slot, state.shape))
+
+    def slotsStepRaggedDenoise(self, count, samples, pcm, stream=None):
+        """slotsStepRaggedRate with the denoiser in the resampler's place (nvw_slots_step_ragged_denoise): the same arguments and
+        the same (total, pcm_total, pieces, rate, ticket), rate[p] = (m0, count, offset) of piece p's denoised outputs in pcm."""
+        for a, dt, name in ((samples, "int32", "samples"), (pcm, "int16", "pcm")):
+            if a is not None or name == "pcm":
+                assert hasattr(a, "data_ptr") and (a.is_cuda or a.is_pinned()) and a.is_contiguous() and str(a.dtype) == "torch." + dt, \
+                    "%s: a contiguous CUDA or pinned %s tensor" % (name, dt)
+        pieces, rate = np.empty(self.maxBatch, dtype=SLOT_PIECE), np.empty(self.maxBatch, dtype=SLOT_RATE_PIECE)
+        n, ticket, pcm_total = C.c_int(0), C.c_ulonglong(0), C.c_longlong(0)
+        total = lib.nvw_slots_step_ragged_denoise(self._h, int(count), addr(samples), samples.numel() if samples is not None else 0,
+                                                  addr(pcm), pcm.numel(), pieces.ctypes.data, rate.ctypes.data, self.maxBatch, C.byref(n),
+                                                  C.byref(pcm_total), C.byref(ticket), stream)
+        if total == -2:
+            raise RuntimeError("nvw_slots_step_ragged_denoise: a launch of the step of %d samples failed" % count)
+        if total < 0:
+            raise ValueError("nvw_slots_step_ragged_denoise refused a step of %d samples into %d PCM elements" % (count, pcm.numel()))
+        return int(total), int(pcm_total.value), pieces[:n.value], rate[:n.value], int(ticket.value)
+
     def slotsWait(self, ticket):
         """Blocks until the outputs of the ragged step with that ticket are complete."""
         if not lib.nvw_slots_wait(self._h, int(ticket)):

@@ -493,7 +493,7 @@ class NVWaveNetEngine(NVWaveNet):
         return e
 
     def slot_stream(self, columns, window, cond_weight, cond_bias, seed=0, implementation=Impl.AUTO, pcm=True, upsample_weight=None,
-                    upsample_bias=None, upsample_stride=None, compact=False, prefill=False, deliver_rate=None, deliver_taps=None):
+                    upsample_bias=None, upsample_stride=None, compact=False, prefill=False, deliver_rate=None, deliver_taps=None, denoise=None):
         """Continuous batching (nv_wavenet_amd/slots.py): a SlotStream over an engine of its own with `columns` columns and a window of
         `window` samples (a multiple of max_dilation), the conditioning convolution in the kernel as infer_features has it
         (cond_weight / cond_bias = the model's cond_layers), selectors from `seed`.  Submit upsampled features [n_cond][T] per
@@ -505,7 +505,10 @@ class NVWaveNetEngine(NVWaveNet):
         the engine.  deliver_rate = (model rate, delivery rate) in Hz: step_async delivers every request's PCM at the delivery rate
         (DESIGN.md §6q), converted in the delivery launch with the taps of resample_taps(*deliver_rate), or deliver_taps (an odd
         number of float64 prototype taps at rate L x the model's); StepOutput.pcm_offsets / pcm_lengths / pcm_first describe it, and a
-        request's pieces concatenated are bit for bit resample() of its whole PCM."""
+        request's pieces concatenated are bit for bit resample() of its whole PCM.  denoise = strength: step_async delivers every
+        request's PCM through the denoiser of set_denoiser, the STFT state carried from step to step; described by
+        the same three arrays, and a request's pieces concatenated are bit for bit denoise() of its whole PCM (a request of n_fft / 2
+        samples or fewer comes unchanged).  submit(denoise_strength=) gives a request its own.  Not together with deliver_rate."""
         from .slots import SlotStream
         e = self._new_engine(columns, window, implementation)
         e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())
@@ -518,7 +521,11 @@ class NVWaveNetEngine(NVWaveNet):
             L, M, taps = resample_taps(*deliver_rate)
             e.setResampler(0, L, M, taps if deliver_taps is None else deliver_taps)
             deliver = 0
-        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact, prefill=prefill, deliver=deliver)
+        if denoise is not None:
+            if getattr(self, "_denoise", None) is None:
+                raise ValueError("denoise needs set_denoiser")
+            e.setDenoiser(*self._denoise)
+        return SlotStream(e, window, pcm=pcm, owns_engine=True, compact=compact, prefill=prefill, deliver=deliver, denoise=denoise)
 
     def close(self):
         for e in self._engines.values():

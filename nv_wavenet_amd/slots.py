@@ -288,6 +288,24 @@ def rate_piece(first, n, finished, L, M, c):
     return m0, (-(-(first + n) * L // M) if finished else rate_delivered(first + n, L, M, c)) - m0
 
 
+def denoise_delivered(k, n_fft, hop):
+    """D(k) of denoised delivery (DESIGN.md §6s; wn::denoise_delivered, nvw_denoise_ready(k, 0)): the outputs of an unfinished
+    stream of k samples whose every covering frame is complete -- max(0, q hop - n_fft / 2) with q = (k - n_fft / 2) // hop + 1
+    complete frames for k > n_fft / 2, none before."""
+    q = (k - n_fft // 2) // hop + 1 if k > n_fft // 2 else 0
+    return max(0, q * hop - n_fft // 2)
+
+
+def denoise_hist_len(n_fft):
+    """The PCM values of a column's input history: the first incomplete frame starts less than n_fft samples back (wn::denoise_hist_len)."""
+    return n_fft
+
+
+def denoise_acc_len(n_fft, hop):
+    """The partial sums of a column's overlap-add behind its last complete frame's hop (wn::denoise_acc_len)."""
+    return n_fft - hop
+
+
 class SlotState:
     """A suspended request (SlotStream.suspend): blob = the column's state, a CUDA uint8 tensor of WavenetEngine.slotSave (None: the
     request had not started); source = its features or mel tensor; uid; done = samples delivered so far; kind = "features" | "mel";
@@ -297,7 +315,8 @@ class SlotState:
     the blob; the blobs that prefill and scoring write leave the word zero, and the stream sets the floor after resuming); top_k,
     top_p = its tail cuts (words 12 and 13, likewise); tail = its filter history at the delivery rate (a numpy int16 array [H] of a
     stream made with deliver_rate; None: none -- a resume then goes on from a zero history, a discontinuity in the
-    first H L / M + 1 outputs after the seam)."""
+    first H L / M + 1 outputs after the seam); denoise = its STFT state (a numpy uint8 array of nvw_slot_denoise_state_get of a stream
+    made with denoise=; None: none -- a resume then starts a new stream origin at done)."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -317,10 +336,14 @@ class SlotState:
     # to_bytes() of a state with a filter history: last of all this record, then its H int16 values
     TAIL = struct.Struct("<4sI")             # magic, H
     TAIL_MAGIC = b"NWSR"
+    # to_bytes() of a state with a denoise state: last of all this record, then its bytes
+    DENOISE = struct.Struct("<4sI")          # magic, bytes
+    DENOISE_MAGIC = b"NWSD"
 
     def __init__(self, blob, source, uid, done, kind, frames=None, final=None, buffer=None, row=0, temperature=1.0, prime=None, min_p=0.0,
-                 top_k=0, top_p=1.0, tail=None):
+                 top_k=0, top_p=1.0, tail=None, denoise=None):
         self.tail = None if tail is None else np.ascontiguousarray(tail, dtype="<i2")
+        self.denoise = None if denoise is None else np.ascontiguousarray(denoise, dtype=np.uint8)
         self.prime = check_prime(prime)
         self.temperature, self.min_p, self.top_k, self.top_p = check_sampling(temperature, min_p, top_k, top_p)
         self._blob_sampling = self.sampling() if blob is not None else OFF      # (what the engine reads from the header on resume)
@@ -347,7 +370,8 @@ class SlotState:
         so that the values survive; a blob whose words 11 to 13 are not the state's floor and cuts (a prefilled state) is written
         with them.  A state
         still inside its prime (done < n) ends with the PRIME record and the values y[done .. n); every other state's bytes are
-        what they were before primes existed.  A state with a filter history ends with the TAIL record and its values."""
+        what they were before primes existed.  A state with a filter history ends with the TAIL record and its values, one with a
+        denoise state with the DENOISE record and its bytes."""
         blob = b""
         s = self.sampling()
         if self.blob is None and s != OFF:
@@ -372,7 +396,8 @@ class SlotState:
         mel = self.kind == "mel"
         return self.RECORD.pack(self.RECORD_MAGIC, self.RECORD_VERSION, 1 if mel else 0, int(self.frames) if mel else 0,
                                 1 if (mel and self.final) else 0, int(self.uid) & 0xFFFFFFFF, int(self.done), len(blob)) + blob + self._prime_bytes() + \
-            (b"" if self.tail is None else self.TAIL.pack(self.TAIL_MAGIC, self.tail.size) + self.tail.tobytes())
+            (b"" if self.tail is None else self.TAIL.pack(self.TAIL_MAGIC, self.tail.size) + self.tail.tobytes()) + \
+            (b"" if self.denoise is None else self.DENOISE.pack(self.DENOISE_MAGIC, self.denoise.size) + self.denoise.tobytes())
 
     def _prime_bytes(self):
         if self.prime is None or self.done >= self.prime.numel():
@@ -392,9 +417,9 @@ class SlotState:
         magic, version, kind, frames, final, uid, done, nblob = cls.RECORD.unpack_from(data)
         if magic != cls.RECORD_MAGIC or version != cls.RECORD_VERSION or kind not in (0, 1):
             raise ValueError("not a SlotState record (magic %r, version %d, kind %d)" % (magic, version, kind))
-        prime, history, at = None, None, cls.RECORD_BYTES + nblob
+        prime, history, denoise, at = None, None, None, cls.RECORD_BYTES + nblob
         tail = len(data) - at
-        if tail >= cls.PRIME.size and data[at:at + 4] != cls.TAIL_MAGIC:
+        if tail >= cls.PRIME.size and data[at:at + 4] not in (cls.TAIL_MAGIC, cls.DENOISE_MAGIC):
             pmagic, first, count = cls.PRIME.unpack_from(data, at)
             if pmagic != cls.PRIME_MAGIC or first != done or count < 1 or tail < cls.PRIME.size + 4 * count:
                 raise ValueError("not a prime record behind the blob (magic %r, first %d, count %d, %d bytes)" % (pmagic, first, count, tail))
@@ -402,6 +427,11 @@ class SlotState:
             y[first:] = np.frombuffer(data, dtype="<i4", count=count, offset=at + cls.PRIME.size)
             prime, at = torch.from_numpy(y), at + cls.PRIME.size + 4 * count
             tail = len(data) - at
+        if tail >= cls.DENOISE.size and data[at:at + 4] == cls.DENOISE_MAGIC:
+            size = cls.DENOISE.unpack_from(data, at)[1]
+            if tail != cls.DENOISE.size + size:
+                raise ValueError("not a denoise state behind the state (%d bytes announced, %d follow)" % (size, tail - cls.DENOISE.size))
+            denoise, tail = np.frombuffer(data, dtype=np.uint8, count=size, offset=at + cls.DENOISE.size).copy(), 0
         if tail >= cls.TAIL.size:
             tmagic, H = cls.TAIL.unpack_from(data, at)
             if tmagic != cls.TAIL_MAGIC or tail != cls.TAIL.size + 2 * H:
@@ -429,7 +459,7 @@ class SlotState:
             blob, buffer = host[0], host if pinned else None
         mel = kind == 1
         return cls(blob, source, uid, done, "mel" if mel else "features", frames if mel else None, bool(final) if mel else None, buffer, 0,
-                   prime=prime, tail=history, **s._asdict())
+                   prime=prime, tail=history, denoise=denoise, **s._asdict())
 
 
 class StepOutput:
@@ -439,7 +469,9 @@ class StepOutput:
     pinned buffer of the stream, valid until the second step after this one is issued (the stream's two buffers take turns).  out[handle] and out.items() slice lazily.
     A stream made with deliver_rate delivers its PCM at that rate: request i's PCM is pcm[pcm_offsets[i] :
     pcm_offsets[i] + pcm_lengths[i]], outputs pcm_first[i] .. of its utterance (a length may be 0); the samples stay at the model's
-    rate under offsets and lengths.  Without, the three are offsets, lengths and the pieces' first samples."""
+    rate under offsets and lengths.  A stream made with denoise delivers its PCM through the denoiser, described
+    in the same way: outputs pcm_first[i] .. of the request's denoised stream.  Without either, the three are offsets, lengths and
+    the pieces' first samples."""
 
     def __init__(self, handles, offsets, lengths, samples, pcm, finished, pcm_offsets=None, pcm_lengths=None, pcm_first=None):
         self.handles, self.offsets, self.lengths, self.samples, self.pcm, self.finished = handles, offsets, lengths, samples, pcm, finished
@@ -510,7 +542,7 @@ class PendingStep:
 
 
 class SlotStream:
-    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False, prefill=False, deliver=None):
+    def __init__(self, engine, window, pcm=True, owns_engine=False, compact=False, prefill=False, deliver=None, denoise=None):
         self.engine = engine
         self._prefill = bool(prefill)                  # what submit(prefill=None) does with a prime
         self.columns = engine.maxBatch
@@ -525,6 +557,13 @@ class SlotStream:
             if not pcm:
                 raise ValueError("deliver needs pcm=True")
             engine.slotsSetDelivery(deliver)
+        # denoise: the strength at which step_async delivers its PCM through the engine's denoiser (setDenoiser)
+        self._dn = denoise is not None
+        if self._dn:
+            if not pcm or self._rate:
+                raise ValueError("denoise needs pcm=True and no deliver: the two deliveries exclude each other")
+            engine.slotsSetDenoise(denoise)
+        self._dn_strength = {}                         # handle -> strength of the requests (queued or running) submitted with one
         self._free = list(range(self.columns))         # a heap: lowest free column first
         self._queue = deque()                          # (handle, features, uid, mel request or None[, SlotState]) waiting for a column
         self._src = {}                                 # handle -> (source tensor, uid) of the running requests
@@ -669,7 +708,7 @@ class SlotStream:
             raise ValueError("score needs samples")
         return self.engine.scoreSamplesMel([(y if y.is_cuda else y.cuda(), mel, temperature, n)])[0]
 
-    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None, min_p=0.0, top_k=0, top_p=1.0):
+    def submit(self, features, uid=None, temperature=1.0, prime=None, prefill=None, min_p=0.0, top_k=0, top_p=1.0, denoise_strength=None):
         """Queues one utterance (features [n_cond][T]); returns its handle.  uid: the Philox counter word of its selectors
         (default: 0, 1, 2, ... in submission order) -- the same features, uid and temperature give the same samples whenever they
         run.  temperature: its samples are drawn from softmax(logits / temperature) (ValueError unless finite and in
@@ -683,10 +722,15 @@ class SlotStream:
         probable bin (ValueError unless finite and in [0, 0.5]); forced samples stay forced.  top_k, top_p: its samples are drawn
         from its top_k most probable bins (0: off; 1: greedy) and from the smallest set of most probable bins whose mass reaches
         top_p (1: off), on the tempered distribution, intersected with each other and with the floor (ValueError unless top_k is
-        an integer in [0, A] and top_p finite and in (0, 1])."""
+        an integer in [0, A] and top_p finite and in (0, 1]).  denoise_strength: on a stream made with denoise, the strength of this
+        request in place of the stream's (ValueError on any other stream, or unless finite and >= 0)."""
         assert features.dim() == 2 and features.size(1) > 0, "features: [n_cond][samples]"
         s = self._check(temperature, min_p, top_k, top_p)
         prime = check_prime(prime, features.size(1))
+        if denoise_strength is not None:
+            if not self._dn or not 0 <= float(denoise_strength) < float("inf"):
+                raise ValueError("denoise_strength: a finite value >= 0, on a stream made with denoise")
+            self._dn_strength[self._next_handle] = float(denoise_strength)
         if (self._prefill if prefill is None else prefill) and prime is not None:
             if prime.numel() >= features.size(1):
                 raise ValueError("prefill: a prime of %d samples leaves nothing of an utterance of %d to generate" % (prime.numel(), features.size(1)))
@@ -901,6 +945,8 @@ class SlotStream:
     def _stopped(self, handle, col, blob, done, buffer=None, row=0):
         """Stops the saved request of column `col` and frees the column; its state."""
         tail = self._tail(col)
+        denoise = self.engine.slotDenoiseStateGet(col) if self._dn else None
+        self._dn_strength.pop(handle, None)      # (the state carries it)
         self.engine.slotStop(col)
         rec = self._running.pop(col)
         x, uid = self._src.pop(handle)
@@ -911,11 +957,11 @@ class SlotStream:
         if rec[1] is not None:
             left = int(self._left[col]) if self._arrays else rec[1]
             assert done == x.size(1) - left, (done, x.size(1), left)
-            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, prime=prime, tail=tail, **s._asdict())
+            return SlotState(blob, x, uid, done, "features", buffer=buffer, row=row, prime=prime, tail=tail, denoise=denoise, **s._asdict())
         req = self._mel.pop(handle)
         delivered = int(self._deliv[col]) if self._arrays else req[3]
         assert done == delivered, (done, delivered)
-        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, prime=prime, tail=tail, **s._asdict())
+        return SlotState(blob, x, uid, done, "mel", req[0], req[1], buffer, row, prime=prime, tail=tail, denoise=denoise, **s._asdict())
 
     def suspend_many(self, handles=None, pinned=False):
         """suspend() for a list of requests (None: all of them, running ones first, each group in handle order), with ONE engine
@@ -981,6 +1027,8 @@ class SlotStream:
         s = state.sampling(getattr(self.engine, "A", None))      # (against this engine's alphabet, before anything is queued)
         if self._rate and state.tail is not None and state.tail.size != self.engine.slotsTailLen():
             raise ValueError("a filter history of %d values, this stream's filter has %d" % (state.tail.size, self.engine.slotsTailLen()))
+        if self._dn and state.denoise is not None and state.denoise.size != self.engine.slotsDenoiseStateBytes():
+            raise ValueError("a denoise state of %d bytes, this stream's are %d" % (state.denoise.size, self.engine.slotsDenoiseStateBytes()))
         handle = self._next_handle
         self._next_handle += 1
         self._next_uid = max(self._next_uid, int(state.uid) + 1)
@@ -1014,7 +1062,9 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
-        tails = []       # (column, filter history) of the resumed requests that carry one, where the stream delivers at a rate
+        tails = []       # (column, filter history) of the resumed requests that carry one, where the stream delivers at a rate; where it
+                         # denoises, (column, denoise state)
+        strengths = []   # (column, strength) of the admitted requests submitted with a denoise strength
         wanted = []      # (column, Sampling, what the start or the resume leaves) likewise, where the two differ: a start leaves OFF, a
                          # resume words 10 to 13 of the blob (11 to 13 zero in a prefilled or scored one)
         while self._queue and self._free and self._ready(self._queue[0], count):
@@ -1028,6 +1078,10 @@ class SlotStream:
             self._src[handle] = (x, uid)
             if self._rate and blob is not None and state.tail is not None:
                 tails.append((col, state.tail))
+            if self._dn and blob is not None and state.denoise is not None:
+                tails.append((col, state.denoise))
+            elif handle in self._dn_strength:
+                strengths.append((col, self._dn_strength[handle]))
             if handle in self._prime:
                 primed.append((col, handle))
             s, had = self._sampling.get(handle, OFF), (state._blob_sampling if blob is not None else OFF)
@@ -1057,7 +1111,9 @@ class SlotStream:
         if listed:
             self._resume_listed(listed)
         for col, tail in tails:      # (resume, then its history: a resume starts the column from a zero one)
-            self.engine.slotTailSet(col, tail)
+            (self.engine.slotDenoiseStateSet if self._dn else self.engine.slotTailSet)(col, tail)
+        for col, strength in strengths:
+            self.engine.slotSetDenoiseStrength(col, strength)
         # start, then set (the engine applies both at the step that follows): every temperature, every floor, then the cuts by column
         order = [(f, it) for f in ("temperature", "min_p") for it in wanted] + [(f, it) for it in wanted for f in ("top_k", "top_p")]
         for field, (col, s, had) in order:
@@ -1091,8 +1147,8 @@ class SlotStream:
         when a running mel request has no frames beyond what it has delivered.  Not while steps of step_async are pending."""
         if self._pending:
             raise RuntimeError("%d pending steps: collect them (PendingStep.result) before a synchronous step" % len(self._pending))
-        if self._rate:
-            raise RuntimeError("a stream that delivers at a rate steps with step_async: a plain step would leave a hole in every filter history")
+        if self._rate or self._dn:
+            raise RuntimeError("a stream that delivers at a rate or denoised steps with step_async: a plain step would leave a hole in every history")
         self._use_arrays(False)
         if self._mel:
             count = min(count, self.engine.slotsHeadroom())
@@ -1137,6 +1193,7 @@ class SlotStream:
         self._mel.pop(handle, None)
         self._sampling.pop(handle, None)
         self._prime.pop(handle, None)
+        self._dn_strength.pop(handle, None)
         del self._src[handle]
         self._ch[col] = -1
         self.engine.slotStop(col)
@@ -1167,18 +1224,20 @@ class SlotStream:
             return PendingStep(self, None, None, 0, empty, empty, empty, [])
         buf = self._last_buf ^ 1      # (never the buffer of a pending step: at most one is pending here, and it was issued last)
         need = len(self._running) * ((count + 7) & ~7)
-        need_pcm = len(self._running) * (self.engine.slotsRateCapacity(count) // self.columns) if self._rate else need
-        if self._bufs[buf] is None or self._bufs[buf][0].size < need or (self._rate and self._bufs[buf][1].size < need_pcm):
+        own = self._rate or self._dn      # (the PCM has lengths of its own)
+        most = self.engine.slotsRateCapacity(count) if self._rate else self.engine.slotsDenoiseCapacity(count) if self._dn else 0
+        need_pcm = len(self._running) * (most // self.columns) if own else need
+        if self._bufs[buf] is None or self._bufs[buf][0].size < need or (own and self._bufs[buf][1].size < need_pcm):
             keep = self.engine.slotsPinned(max(need, 8), self.pcm)
-            if self._rate:
+            if own:
                 import torch
                 keep = (keep[0], torch.empty(max(need_pcm, 8), dtype=torch.int16, pin_memory=True))
             self._bufs_keep[buf] = keep
             self._bufs[buf] = tuple(a.numpy() if hasattr(a, "numpy") and not isinstance(a, np.ndarray) else a for a in keep)
         y, pcm = self._bufs_keep[buf]
         rate = pcm_total = None
-        if self._rate:
-            total, pcm_total, pieces, r, ticket = self.engine.slotsStepRaggedRate(count, y, pcm)
+        if own:
+            total, pcm_total, pieces, r, ticket = (self.engine.slotsStepRaggedRate if self._rate else self.engine.slotsStepRaggedDenoise)(count, y, pcm)
             rate = (r["offset"].copy(), r["count"].astype(np.int64), r["m0"].copy())
         else:
             total, pieces, ticket = self.engine.slotsStepRagged(count, y, pcm)

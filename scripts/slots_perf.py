@@ -159,6 +159,7 @@ def main():
     ap.add_argument("--analyse", action="store_true", help="time nvw_analyse beside nvw_score_samples_mel of the same audio")
     ap.add_argument("--rate", action="store_true", help="time the ragged step with plain delivery against rate delivery at 2 / 1 and 147 / 80")
     ap.add_argument("--denoise", action="store_true", help="time one nvw_denoise launch for --batch one-second utterances at 1024 / 256")
+    ap.add_argument("--denoise-deliver", action="store_true", help="time the ragged step with plain delivery, with denoised delivery at 1024 / 256, and with plain delivery followed by a per-step nvw_denoise")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
     ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
@@ -176,6 +177,10 @@ def main():
         return
     if args.denoise:
         print(json.dumps(time_denoise(args, w)), flush=True)
+        return
+    if args.denoise_deliver:
+        for chunk in [int(c) for c in args.chunks.split(",")]:
+            print(json.dumps(time_denoise_deliver(args, w, Wc, bc, chunk)), flush=True)
         return
     if args.rate:
         for chunk in [int(c) for c in args.chunks.split(",")]:
@@ -1233,6 +1238,68 @@ def time_rate(args, w, Wc, bc, chunk):
     e.slotsEnd()
     e.close()
     return {"batch": B, "chunk": chunk, "window": W, "rounds": args.rounds, "steps_per_round": steps,
+            "ms_per_step": {name: _stats(v) for name, v in ms.items()}, "device": torch.cuda.get_device_name(0)}
+
+
+def time_denoise_deliver(args, w, Wc, bc, chunk):
+    """The --denoise-deliver measurement: one session with every column busy, n_fft 1024 / hop 256; per round, alternating, `steps`
+    ragged steps of `chunk` samples (events around them, one warm-up step first) with plain delivery into pinned memory
+    (nvw_slots_step_ragged), with denoised delivery into pinned memory (nvw_slots_step_ragged_denoise), and with the path that
+    denoised delivery replaces: plain delivery into device memory, the pieces appended to per-column streams, one nvw_denoise launch
+    for the outputs that nvw_denoise_ready has newly allowed, and their copy into pinned memory; milliseconds per step."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import DENOISE_REQ
+    from nv_wavenet_amd.slots import denoise_delivered
+    B, W, steps, n_fft, hop = args.batch, args.window, max(2, args.steps), 1024, 256
+    cases = ("plain", "denoised", "plain_then_denoise")
+    src = torch.randn(bench.N_COND, 65536, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)).half()
+    assert args.rounds * len(cases) * (steps + 1) * chunk <= src.size(1)
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    e.setSelectorSeed(5)
+    e.setDenoiser(n_fft, hop, np.abs(np.random.default_rng(37).standard_normal(n_fft // 2 + 1)).astype(np.float32) * 2000 * 32)
+    e.slotsBegin(W)
+    for b in range(B):
+        e.slotStart(b, src, b)
+    y, _ = e.slotsPinned(B * chunk, pcm=False)
+    pitch = (steps + 1) * chunk
+    streams = torch.zeros(B, pitch, dtype=torch.int16, device="cuda")
+    pieces_dev = torch.empty(B * chunk, dtype=torch.int16, device="cuda")
+    cleaned = torch.empty(B, chunk + hop, dtype=torch.int16, device="cuda")
+    cleaned_host = torch.empty(B, chunk + hop, dtype=torch.int16, pin_memory=True)
+    reqs = np.zeros(B, dtype=DENOISE_REQ)
+    reqs["in"], reqs["out"] = streams.data_ptr() + 2 * pitch * np.arange(B), cleaned.data_ptr() + 2 * (chunk + hop) * np.arange(B)
+    reqs["in_type"], reqs["out_type"], reqs["strength"] = 16, 16, 0.1
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = {name: [] for name in cases}
+    for _ in range(args.rounds):
+        for name in cases:
+            e.slotsSetDenoise(0.1 if name == "denoised" else None)
+            pcm = torch.empty(e.slotsDenoiseCapacity(chunk) if name == "denoised" else B * chunk, dtype=torch.int16, pin_memory=True)
+            for k in range(steps + 1):
+                if k == 1:
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                if name == "denoised":
+                    e.slotsStepRaggedDenoise(chunk, y, pcm)
+                elif name == "plain":
+                    e.slotsStepRagged(chunk, y, pcm)
+                else:
+                    e.slotsStepRagged(chunk, y, pieces_dev)      # (every column delivers `chunk` samples: the pieces are rows)
+                    streams[:, k * chunk:(k + 1) * chunk].copy_(pieces_dev.view(B, chunk))
+                    t0, t1 = denoise_delivered(k * chunk, n_fft, hop), denoise_delivered((k + 1) * chunk, n_fft, hop)
+                    if t1 > t0:
+                        reqs["n_in"], reqs["t0"], reqs["count"] = (k + 1) * chunk, t0, t1 - t0
+                        assert lib.nvw_denoise(e._h, reqs.ctypes.data, B, None) == B
+                        cleaned_host[:, :t1 - t0].copy_(cleaned[:, :t1 - t0], non_blocking=True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]) / steps)
+    e.slotsEnd()
+    e.close()
+    return {"batch": B, "chunk": chunk, "window": W, "n_fft": n_fft, "hop": hop, "rounds": args.rounds, "steps_per_round": steps,
             "ms_per_step": {name: _stats(v) for name, v in ms.items()}, "device": torch.cuda.get_device_name(0)}
 
 
