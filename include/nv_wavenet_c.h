@@ -931,7 +931,7 @@ int nvw_denoise(nvw_engine* e, const nvw_denoise_req* reqs, int count, void* str
  *                                  stream starts afresh at its next piece, a running column's too.  While it is on,
  *                                  nvw_slots_step, nvw_slots_step_ragged and nvw_slots_step_ragged_rate are refused (they would
  *                                  leave a hole in every stream) and so is nvw_set_denoiser.  Mutually exclusive with
- *                                  nvw_slots_set_delivery: each refuses while the other is on (not built: both in one launch).
+ *                                  nvw_slots_set_delivery: each refuses while the other is on (both: nvw_slots_set_denoise_rate).
  *                                  Synchronises.  Returns 1; 0 with nothing changed: not in slot mode, no nvw_set_denoiser, rate
  *                                  delivery on, a negative or non-finite strength, or a ragged step in flight.
  *   nvw_slot_set_denoise_strength  the strength of column `slot`, from the next frame computed on.  A frame is computed by the step
@@ -962,6 +962,42 @@ long long nvw_slots_step_ragged_denoise(nvw_engine* e, int count, int* samples, 
 long long nvw_slots_denoise_state_bytes(nvw_engine* e);
 int nvw_slot_denoise_state_get(nvw_engine* e, int slot, void* dst);
 int nvw_slot_denoise_state_set(nvw_engine* e, int slot, const void* src);
+
+/* SLOT MODE: DENOISED DELIVERY AT THE CALLER'S RATE IN ONE LAUNCH (additive within ABI 7).  The configuration a deployment runs: a
+ * vocoder's output cleaned and handed to a sink at another rate.  The two deliveries above exclude each other; this third mode
+ * chains them inside the delivery launch: the cleaned samples go from the overlap-add to the rate conversion through
+ * on-chip memory and cross the host boundary once, at the caller's rate.
+ * A column's stream x from its origin s0 (as under nvw_slots_set_denoise) is cleaned into the int16 stream z = nvw_denoise(x) (z = x
+ * for a stream that finishes at n_fft / 2 samples or fewer), z is converted at L / M with the taps of resampler `slot`, and the
+ * outputs are numbered from 0 at s0.  After k samples of an unfinished stream R(D(k)) outputs are out, with D = nvw_denoise_ready(k,
+ * 0) and R(t) = max(0, ceil((t L - c) / M)); the finishing piece carries the rest up to ceil(n L / M); a count may be 0.  An
+ * utterance's pieces, concatenated, are bit for bit nvw_resample (int16 in, int16 out, last = 1) of nvw_denoise (int16 out, last =
+ * 1) of its whole PCM, however the steps cut it.
+ *   nvw_slots_set_denoise_rate          slot = 0 .. 3: the mode with resampler `slot` and `strength` for every column that does not
+ *                                       set its own; slot < 0: off (the default; nvw_slots_begin and nvw_slots_end turn it off; 1
+ *                                       when it was off already).  Needs nvw_set_denoiser and nvw_set_resampler(slot).  All three
+ *                                       states of every column are zeroed (the STFT history and accumulator, the tail of z): every
+ *                                       stream starts afresh at its next piece.  Excludes nvw_slots_set_delivery and
+ *                                       nvw_slots_set_denoise and is excluded by them: each of the three refuses while another is
+ *                                       on, and the other two setters refuse any value while this mode is on.  While it is on,
+ *                                       nvw_set_denoiser, nvw_set_resampler(slot) and every other step entry are refused.
+ *                                       Synchronises.  Returns 1; 0 with nothing changed: not in slot mode, denoiser or resampler
+ *                                       not set, another delivery on, a bad strength, a ragged step in flight, or a geometry and
+ *                                       ratio whose tile needs more on-chip memory than a workgroup has.
+ *   nvw_slots_denoise_rate_capacity     PCM elements that always suffice for such a step of `count`; -1 when off.
+ *   nvw_slots_step_ragged_denoise_rate  the argument list, piece records (nvw_slot_rate_piece), ticket, return values and refusals
+ *                                       of nvw_slots_step_ragged_rate; a step that completes more than 16 frames of some column is
+ *                                       issued as several delivery launches, as nvw_slots_step_ragged_denoise does.
+ * While the mode is on, nvw_slot_set_denoise_strength, nvw_slots_denoise_state_bytes and nvw_slot_denoise_state_get / _set work as
+ * under nvw_slots_set_denoise, and nvw_slots_tail_len and nvw_slot_tail_get / _set as under nvw_slots_set_delivery, the tail being
+ * the last H values of z.  A resumed column whose denoise state is not set starts a new stream at `done`: its tail is ignored and
+ * its outputs are numbered from 0 again.  One whose denoise state is set but whose tail is not goes on from a zero history of z: a
+ * discontinuity in the first H L / M + 1 outputs after the seam. */
+int nvw_slots_set_denoise_rate(nvw_engine* e, int slot, float strength);
+long long nvw_slots_denoise_rate_capacity(nvw_engine* e, int count);
+long long nvw_slots_step_ragged_denoise_rate(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                             nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces,
+                                             long long* pcm_total, unsigned long long* ticket, void* stream);
 
 /* hipDeviceSynchronize() for hosts without a HIP binding */
 void nvw_device_synchronize(void);

@@ -114,6 +114,11 @@ SIGNATURES = {
     "nvw_slots_denoise_state_bytes": (C.c_longlong, [C.c_void_p]),
     "nvw_slot_denoise_state_get": (C.c_int, [C.c_void_p, C.c_int, _fp]),
     "nvw_slot_denoise_state_set": (C.c_int, [C.c_void_p, C.c_int, _fp]),
+    "nvw_slots_set_denoise_rate": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "nvw_slots_denoise_rate_capacity": (C.c_longlong, [C.c_void_p, C.c_int]),
+    "nvw_slots_step_ragged_denoise_rate": (C.c_longlong, [C.c_void_p, C.c_int, _fp, C.c_longlong, _fp, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                          C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong),
+                                                          C.c_void_p]),
     "nvw_slots_time_outputs":(C.c_float, [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_longlong, C.c_int, C.c_void_p]),
     "nvw_slots_wait": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "nvw_slots_done": (C.c_int, [C.c_void_p, C.c_ulonglong]),

@@ -81,6 +81,58 @@ __device__ __forceinline__ void resample_tile_gemm(const float* span, const Resa
     }
 }
 
+// The same product with the N dimension gathered (slots_deliver_denoise_rate.hpp): block lane fl of the wave is a block of any span
+// staged in LDS, its input j at bp[j - g + s (j / hop)] -- bp = that span's block base + g; the caller has synchronised, and hands a
+// dead lane a live lane's base.  The k-step order per accumulator is resample_tile_gemm's, so an output has its bits.  G = 4: the
+// wave holds all CH = rowTiles row tiles (the caller gives every wave a group of 16 lanes of its own); G = 1: row tile t belongs to
+// wave t & 3.  store(p, v): output p < Q of this lane's block has the sum v (live lanes only).
+template <int G, int CH, class Store>
+__device__ __forceinline__ void resample_gather_gemm(const float* bp, const ResampleTab& a, bool live, Store store) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
+    const int hop = a.hop, spare = a.spare;
+    const floatx4* const tab = a.tab + lane;
+    const int nq = a.nq, nrt = a.rowTiles;
+    for (int first = G == 4 ? 0 : w; first < nrt; first += (G == 4 ? 1 : 4) * CH) {
+        floatx4 acc[CH];
+        size_t at[CH];                                  // (a tile past the last repeats the last, and is not stored)
+#pragma unroll
+        for (int i = 0; i < CH; i++) {
+            acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+            const int t = first + (G == 4 ? 1 : 4) * i;
+            at[i] = (size_t)(t < nrt ? t : nrt - 1) * nq * 64;
+        }
+        int rem = g, pad = 0;
+        for (int qd = 0; qd < nq; qd++) {
+            floatx4 af[CH];
+#pragma unroll
+            for (int i = 0; i < CH; i++) af[i] = tab[at[i] + (size_t)qd * 64];
+            float b[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                b[e] = bp[16 * qd + 4 * e + pad];
+                rem += 4;
+                const bool wrap = rem >= hop;
+                rem -= wrap ? hop : 0;
+                pad += wrap ? spare : 0;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+#pragma unroll
+                for (int i = 0; i < CH; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][e], b[e], acc[i], 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < CH; i++) {
+            const int t = first + (G == 4 ? 1 : 4) * i;
+            if (t >= nrt || !live) continue;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int p = t * 16 + 4 * g + r;
+                if (p < a.Q) store(p, acc[i][r]);
+            }
+        }
+    }
+}
+
 // int16 PCM of a sum: nearest-even, saturated
 __device__ __forceinline__ short resample_pcm16(float v) { return (short)(int)fminf(fmaxf(rintf(v), -32768.f), 32767.f); }
 

@@ -234,6 +234,7 @@ bool SlotSession::move(int from, int to) {
         std::swap(m_dnOrigin[from], m_dnOrigin[to]);
         std::swap(m_dnStrength[from], m_dnStrength[to]);
     }
+    if (m_chain) std::swap(m_zTailZero[from], m_zTailZero[to]);
     slotSamplingSet(to, m_temps.get(from));
     slotSamplingSet(from, Sampling{});      // (as stop())
     if (primed(from)) {
@@ -514,7 +515,7 @@ void SlotSession::rateOff() {
     m_tailH = 0;
 }
 bool SlotSession::setDelivery(const Resampler* r, int index) {
-    if (m_slotW <= 0 || (r != NULL && (!r->ready() || m_dn))) return false;
+    if (m_slotW <= 0 || m_chain || (r != NULL && (!r->ready() || m_dn))) return false;
     if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
     if (r != NULL && !slots_deliver_rate_prepare(r->geom().groups, r->tilesPerPass())) return false;
     gpuErrChk(hipDeviceSynchronize());
@@ -532,7 +533,7 @@ bool SlotSession::setDelivery(const Resampler* r, int index) {
     return true;
 }
 long long SlotSession::rateCapacity(int count) const {
-    if (!m_rate || count <= 0 || count > m_slotW) return -1;
+    if (!m_rate || m_chain || count <= 0 || count > m_slotW) return -1;
     // a piece of n samples has at most ceil(n L / M) + 1 outputs, its utterance's last one ceil(c / M) more
     const long long L = m_rate->up(), M = m_rate->down(), c = m_rate->centre();
     const long long most = (count * L + M - 1) / M + (c + M - 1) / M + 2;
@@ -541,7 +542,7 @@ long long SlotSession::rateCapacity(int count) const {
 bool SlotSession::tailGet(int slot, short* dst) {
     if (!m_rate || !inBatch(slot) || !slotHolds(slot) || dst == NULL) return false;
     if (m_tailH == 0) return true;
-    if (m_tailZero[slot]) {
+    if (m_tailZero[slot] || (m_chain && m_zTailZero[slot])) {
         const std::vector<short> zero(m_tailH, 0);
         gpuErrChk(hipMemcpy(dst, zero.data(), (size_t)m_tailH * sizeof(short), hipMemcpyDefault));
     } else {
@@ -552,14 +553,14 @@ bool SlotSession::tailGet(int slot, short* dst) {
 bool SlotSession::tailSet(int slot, const short* src) {
     if (!m_rate || !inBatch(slot) || !slotHolds(slot) || src == NULL) return false;
     if (m_tailH > 0) gpuErrChk(hipMemcpy(tailAt(m_tailCur, slot), src, (size_t)m_tailH * sizeof(short), hipMemcpyDefault));
-    m_tailZero[slot] = 0;
+    (m_chain ? m_zTailZero : m_tailZero)[slot] = 0;      // (under both stages the stream's origin is the denoise state's matter)
     return true;
 }
 long long SlotSession::stepRaggedRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
                                       SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
                                       hipStream_t stream) {
-    if (m_slotW <= 0 || !m_rate || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL || nPieces == NULL ||
-        pcmTotal == NULL || ticket == NULL)
+    if (m_slotW <= 0 || !m_rate || m_chain || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL ||
+        nPieces == NULL || pcmTotal == NULL || ticket == NULL)
         return -1;
     const int upStride = m_host.slotLive().upStride;
     if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
@@ -652,6 +653,7 @@ struct DenoiseStateTrailer {
 void SlotSession::slotFresh(int slot) {
     m_tailZero[slot] = 1;
     if (m_dn) m_dnStrength[slot] = m_dnDefault;
+    if (m_chain) m_zTailZero[slot] = 1;
 }
 void SlotSession::denoiseOff() {
     freeDev(m_dnHist, m_dnAcc, m_dnDev);
@@ -660,7 +662,7 @@ void SlotSession::denoiseOff() {
     m_dn = NULL;
 }
 bool SlotSession::setDenoise(const Denoiser* d, float strength) {
-    if (m_slotW <= 0 || (d != NULL && (!d->isSet() || m_rate || !strengthOk(strength)))) return false;
+    if (m_slotW <= 0 || m_chain || (d != NULL && (!d->isSet() || m_rate || !strengthOk(strength)))) return false;
     if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
     if (d != NULL && !slots_deliver_denoise_prepare(d->nFft(), d->hop())) return false;
     gpuErrChk(hipDeviceSynchronize());
@@ -686,7 +688,7 @@ bool SlotSession::setDenoiseStrength(int slot, float strength) {
     return true;
 }
 long long SlotSession::denoiseCapacity(int count) const {
-    if (!m_dn || count <= 0 || count > m_slotW) return -1;
+    if (!m_dn || m_chain || count <= 0 || count > m_slotW) return -1;
     // a piece of n samples completes at most n / hop + 1 hops of outputs; the one that finishes adds the at most N / 2 + hop held back
     const long long most = (long long)count + m_dn->nFft() / 2 + 2 * m_dn->hop();
     return f.maxBatch * ((most + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign);
@@ -732,8 +734,8 @@ bool SlotSession::denoiseStateSet(int slot, const void* src) {
 long long SlotSession::stepRaggedDenoise(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
                                          SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
                                          hipStream_t stream) {
-    if (m_slotW <= 0 || !m_dn || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL || nPieces == NULL ||
-        pcmTotal == NULL || ticket == NULL)
+    if (m_slotW <= 0 || !m_dn || m_chain || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL ||
+        nPieces == NULL || pcmTotal == NULL || ticket == NULL)
         return -1;
     const int upStride = m_host.slotLive().upStride;
     if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
@@ -883,6 +885,247 @@ long long SlotSession::stepRaggedDenoise(int count, int* samples, long long capa
     *ticket = m_dlv.uses();
     return ok ? total : -2;
 }
+// ---- ragged delivery through the denoiser and at the caller's rate (slots_deliver_denoise_rate.hpp) ----
+bool SlotSession::setDenoiseRate(const Denoiser* d, const Resampler* r, int index, float strength) {
+    if (m_slotW <= 0) return false;
+    if (r == NULL && !m_chain) return true;      // (off already: the single modes are not this call's to turn off)
+    if (r != NULL && ((!m_chain && (m_dn || m_rate)) || d == NULL || !d->isSet() || !r->ready() || !strengthOk(strength))) return false;
+    if (m_dlv.uses() > 0 && done(m_dlv.uses()) == 0) return false;      // (the last step issued is the last to complete)
+    DenoiseRateGeom g = {};
+    long long span = 0;
+    if (r != NULL) {
+        const ResampleGeom& rg = r->geom();
+        g = DenoiseRateGeom{d->nFft(), d->hop(), r->up(), r->down(), r->centre(), rg.Q, rg.hop, rg.spare, rg.wp};
+        span = slots_deliver_denoise_rate_span_words(g);
+        if (!slots_deliver_denoise_rate_prepare(g.nFft, span, rg.groups, r->tilesPerPass())) return false;
+    }
+    gpuErrChk(hipDeviceSynchronize());
+    rateOff();
+    denoiseOff();
+    m_chain = false;
+    if (r == NULL) return true;
+    m_chain = true;
+    m_chainGeom = g;
+    m_chainSpan = span;
+    m_chainPairsMost = denoise_rate_blocks_most(g, 16LL * g.hop + g.nFft / 2);
+    m_dn = d;
+    m_dnDefault = strength;
+    m_dnCur = 0;
+    m_rate = r;
+    m_rateIndex = index;
+    m_tailH = rate_tail_len(g.up, g.centre);
+    m_tailCur = 0;
+    allocZero(m_dnHist, 2 * (size_t)f.maxBatch * denoise_hist_len(g.nFft) * sizeof(short));
+    allocZero(m_dnAcc, 2 * (size_t)f.maxBatch * denoise_acc_len(g.nFft, g.hop) * sizeof(float));
+    allocZero(m_tails, 2 * (size_t)f.maxBatch * (m_tailH > 0 ? m_tailH : 1) * sizeof(short));
+    m_tailZero.assign(f.maxBatch, 1);
+    m_zTailZero.assign(f.maxBatch, 1);
+    m_dnOrigin.assign(f.maxBatch, 0);
+    m_dnStrength.assign(f.maxBatch, strength);
+    // one launch's pieces [maxBatch], its frame pairs [16 maxBatch], its blocks [maxBatch][the most of a piece]
+    const size_t launchBytes = (size_t)f.maxBatch * (sizeof(DenoiseRatePiece) + 16 * sizeof(DenoisePair) + (size_t)m_chainPairsMost * sizeof(RatePair));
+    gpuErrChk(hipMalloc((void**)&m_dnDev, launchBytes));
+    m_dnStageBytes = 2 * launchBytes;
+    m_dnStage.make(kSlotTickets, m_dnStageBytes);
+    gpuErrChk(hipDeviceSynchronize());
+    return true;
+}
+long long SlotSession::denoiseRateCapacity(int count) const {
+    if (!m_chain || count <= 0 || count > m_slotW) return -1;
+    // denoiseCapacity's cleaned samples of a piece, and what (z L + c) / M + 2 outputs they become at the most
+    const DenoiseRateGeom& g = m_chainGeom;
+    const long long z = (long long)count + g.nFft / 2 + 2 * g.hop, most = (z * g.up + g.centre) / g.down + 2;
+    return f.maxBatch * ((most + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign);
+}
+long long SlotSession::stepRaggedDenoiseRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                                             SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal,
+                                             unsigned long long* ticket, hipStream_t stream) {
+    if (m_slotW <= 0 || !m_chain || count <= 0 || count > m_slotW || pcm == NULL || pieces == NULL || rate == NULL || nPieces == NULL ||
+        pcmTotal == NULL || ticket == NULL)
+        return -1;
+    const int upStride = m_host.slotLive().upStride;
+    if (m_melColumns > 0 && (upStride <= 0 || count > headroom())) return -1;
+    int* const dSamples = samples ? (int*)deliverTarget(samples) : NULL;
+    short* const dPcm = (short*)deliverTarget(pcm);
+    if ((samples && !dSamples) || !dPcm) return -1;
+    long long total = 0;
+    const int n = slotPieces(count, NULL, 0, total, upStride);
+    if (n > maxPieces || (samples && total > capacity)) return -1;
+    slotPieces(count, pieces, maxPieces, total, upStride);
+    // the outputs every piece carries, from its sample piece: R(D(k0)) .. R(D(k0 + n)) of its stream, or up to ceil(len L / M)
+    const DenoiseRateGeom& g = m_chainGeom;
+    const int N = g.nFft, hop = g.hop, half = N / 2;
+    const auto origin = [&](const SlotPiece& p) { return m_tailZero[p.slot] ? p.first : m_dnOrigin[p.slot]; };
+    const auto frames = [&](long long k, bool fin) { return !fin ? denoise_frames(k, N, hop) : k > half ? k / hop + 1 : 0; };
+    const auto cleaned = [&](long long k, bool fin) { return fin ? k : denoise_delivered(k, N, hop); };
+    const auto outputs = [&](long long k, bool fin) { return fin ? rate_ceil_div(k * g.up, g.down) : denoise_rate_delivered(k, g); };
+    long long off = 0, pcmEnd = 0, most = 0;
+    for (int i = 0; i < n; i++) {
+        const SlotPiece& p = pieces[i];
+        const long long k0 = p.first - origin(p), m0 = outputs(k0, false), end = outputs(k0 + p.n, p.finished != 0);
+        rate[i] = SlotRatePiece{m0, (int)(end - m0), 0, off};
+        if (end > m0) {
+            pcmEnd = off + (end - m0);
+            off = (pcmEnd + kDeliverAlign - 1) / kDeliverAlign * kDeliverAlign;
+        }
+        const long long nf = frames(k0 + p.n, p.finished != 0) - denoise_frames(k0, N, hop);
+        if (nf > most) most = nf;
+    }
+    if (pcmEnd > pcmCapacity) return -1;      // (pieces and rate have been written: nothing else has changed)
+    // The launches, pieces and tiles of stepRaggedDenoise; next to them every piece's blocks of the rate GEMM and, per tile, its
+    // pieces' spans one behind the other.
+    const int chunk = most <= 16 ? count : 6 * hop;
+    m_chainPieces.clear();
+    m_dnPairs.clear();
+    m_chainPairs.clear();
+    m_dnPlan.clear();
+    size_t stageBytes = 0;
+    for (int a = 0; a < count; a += chunk) {
+        const int b = a + chunk < count ? a + chunk : count;
+        const size_t pieceBase = m_chainPieces.size(), pairBase = m_dnPairs.size(), blockBase = m_chainPairs.size();
+        int col = 16, framed = 0;
+        long long spanAt = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            for (int i = 0; i < n; i++) {
+                const SlotPiece& p = pieces[i];
+                if (p.n <= a) continue;
+                DenoiseRatePiece c = {};
+                DenoisePiece& r = c.d;
+                const bool fin = p.finished && p.n <= b;
+                r.n = (p.n < b ? p.n : b) - a;
+                r.k0 = p.first - origin(p) + a;
+                r.q0 = (int)denoise_frames(r.k0, N, hop);
+                r.nf = (int)frames(r.k0 + r.n, fin) - r.q0;
+                if ((r.nf > 0) != (pass == 0)) continue;
+                if (r.nf > 16) return -1;      // (never: the bound of stepRaggedDenoise)
+                const long long t0 = denoise_delivered(r.k0, N, hop), m1 = outputs(r.k0 + r.n, fin);
+                c.m0 = outputs(r.k0, false);
+                c.count = (int)(m1 - c.m0);
+                c.block0 = c.m0 / g.Q;
+                c.blocks = c.count > 0 ? (int)((m1 - 1) / g.Q - c.block0 + 1) : 0;
+                c.pair0 = (int)(m_chainPairs.size() - blockBase);
+                r.slot = p.slot;
+                r.row = m_tailRow[p.slot];
+                // (the tail counts as zero in the column's first launch after a start or a resume without one; that launch writes it)
+                r.flags = (fin ? kDenoiseFin : 0) | (a == 0 && (m_tailZero[p.slot] || m_zTailZero[p.slot]) ? kDenoiseRateZeroTail : 0);
+                r.offset = rate[i].offset + (c.m0 - rate[i].m0);
+                r.count = (int)(cleaned(r.k0 + r.n, fin) - t0);
+                r.strength = m_dnStrength[p.slot];
+                const long long words = c.blocks > 0 ? denoise_rate_span_of(g, c.blocks) : 0;
+                if (pass == 0) {
+                    if (col + r.nf > 16) {
+                        m_dnPairs.resize(pairBase + (m_dnPairs.size() - pairBase + 15) / 16 * 16, DenoisePair{-1, 0});
+                        col = 0;
+                        spanAt = 0;
+                    }
+                    r.col0 = col;
+                    for (int k = 0; k < r.nf; k++) m_dnPairs.push_back(DenoisePair{(int)(m_chainPieces.size() - pieceBase), r.q0 + k});
+                    col += r.nf;
+                    framed++;
+                } else {
+                    spanAt = 0;      // (a workgroup of its own)
+                }
+                c.span = (int)spanAt;
+                spanAt += words;
+                if (spanAt > m_chainSpan || c.blocks > m_chainPairsMost) return -1;      // (never: the bounds of slots_deliver_denoise_rate.hpp)
+                for (int k = 0; k < c.blocks; k++) m_chainPairs.push_back(RatePair{(int)(m_chainPieces.size() - pieceBase), k});
+                m_chainPieces.push_back(c);
+            }
+            if (pass == 0) m_dnPairs.resize(pairBase + (m_dnPairs.size() - pairBase + 15) / 16 * 16, DenoisePair{-1, 0});
+        }
+        const int launched = (int)(m_chainPieces.size() - pieceBase), tiles = (int)((m_dnPairs.size() - pairBase) / 16);
+        const int blocks = (int)(m_chainPairs.size() - blockBase);
+        for (int v : {a, launched, framed, tiles, blocks}) m_dnPlan.push_back(v);
+        stageBytes += (size_t)launched * sizeof(DenoiseRatePiece) + (size_t)tiles * 16 * sizeof(DenoisePair) + (size_t)blocks * sizeof(RatePair);
+    }
+    if (stageBytes > m_dnStageBytes) {
+        gpuErrChk(hipDeviceSynchronize());      // (earlier steps may still be reading what is replaced)
+        m_dnStageBytes = 2 * stageBytes;
+        m_dnStage.make(kSlotTickets, m_dnStageBytes);
+    }
+    *nPieces = n;
+    *pcmTotal = pcmEnd;
+    const int T = (int)(m_slotCounter % m_slotW);
+    char* const dstage = (char*)m_dnStage.acquire();
+    DeliverPiece* const stage = (DeliverPiece*)m_dlv.acquire();
+    int cols = 0;
+    bool ok = generate(count, cols, stream);
+    if (n > 0) {
+        if (dSamples) {
+            for (int i = 0; i < n; i++) stage[i] = DeliverPiece{pieces[i].slot, pieces[i].n, pieces[i].offset};
+            gpuErrChk(hipMemcpyAsync(m_dlvDev, stage, (size_t)n * sizeof(DeliverPiece), hipMemcpyHostToDevice, stream));
+            ok = slots_deliver(stream, m_slotY, m_mulaw, T, m_slotW, count, m_dlvDev, n, dSamples, NULL) && ok;
+        }
+        const size_t histImage = (size_t)f.maxBatch * denoise_hist_len(N), accImage = (size_t)f.maxBatch * denoise_acc_len(N, hop);
+        const size_t tailImage = (size_t)f.maxBatch * m_tailH;
+        DenoiseRatePiece* const devPieces = (DenoiseRatePiece*)m_dnDev;
+        DenoisePair* const devPairs = (DenoisePair*)(devPieces + f.maxBatch);
+        RatePair* const devBlocks = (RatePair*)(devPairs + (size_t)16 * f.maxBatch);
+        size_t at = 0, pieceAt = 0, pairAt = 0, blockAt = 0;
+        for (size_t l = 0; l < m_dnPlan.size(); l += 5) {
+            const int a0 = m_dnPlan[l], launched = m_dnPlan[l + 1], framed = m_dnPlan[l + 2], tiles = m_dnPlan[l + 3], blocks = m_dnPlan[l + 4];
+            if (launched == 0) continue;      // (every piece ended below this sub-range)
+            const struct {
+                void* dev;
+                const void* src;
+                size_t bytes;
+            } parts[3] = {{devPieces, &m_chainPieces[pieceAt], (size_t)launched * sizeof(DenoiseRatePiece)},
+                          {devPairs, m_dnPairs.data() + pairAt, (size_t)tiles * 16 * sizeof(DenoisePair)},
+                          {devBlocks, m_chainPairs.data() + blockAt, (size_t)blocks * sizeof(RatePair)}};
+            for (const auto& part : parts) {
+                if (part.bytes == 0) continue;
+                memcpy(dstage + at, part.src, part.bytes);
+                gpuErrChk(hipMemcpyAsync(part.dev, dstage + at, part.bytes, hipMemcpyHostToDevice, stream));
+                at += part.bytes;
+            }
+            pieceAt += launched;
+            pairAt += (size_t)tiles * 16;
+            blockAt += blocks;
+            DenoiseRateLaunch c;
+            c.pieces = devPieces;
+            c.pairs = devPairs;
+            c.ratePairs = devBlocks;
+            DenoiseLaunch& d = c.l;
+            d.pieces = NULL;
+            d.pairs = NULL;
+            d.count = launched;
+            d.framed = framed;
+            d.tiles = tiles;
+            d.y = m_slotY;
+            d.table = m_mulaw;
+            d.T = (T + a0) % m_slotW;
+            d.W = m_slotW;
+            d.histIn = m_dnHist + (size_t)m_dnCur * histImage;
+            d.histOut = m_dnHist + (size_t)(m_dnCur ^ 1) * histImage;
+            d.accIn = m_dnAcc + (size_t)m_dnCur * accImage;
+            d.accOut = m_dnAcc + (size_t)(m_dnCur ^ 1) * accImage;
+            d.pcm = dPcm;
+            d.fwdTab = m_dn->forwardTable();
+            d.invTab = m_dn->inverseTable();
+            d.bias = m_dn->biasTable();
+            d.wnd2 = m_dn->envelopeTable();
+            d.nFft = N;
+            d.hop = hop;
+            c.tailIn = m_tails + (size_t)m_tailCur * tailImage;
+            c.tailOut = m_tails + (size_t)(m_tailCur ^ 1) * tailImage;
+            c.H = m_tailH;
+            c.t = m_rate->tab();
+            ok = slots_deliver_denoise_rate(stream, c, m_chainSpan, m_rate->geom().groups, m_rate->tilesPerPass()) && ok;
+            m_dnCur ^= 1;      // (the three states flip together)
+            m_tailCur ^= 1;
+        }
+        for (int i = 0; i < n; i++) {
+            const int slot = pieces[i].slot;
+            if (m_tailZero[slot]) m_dnOrigin[slot] = pieces[i].first;      // (its stream has begun: the images hold what the flags stood for)
+            m_tailZero[slot] = m_zTailZero[slot] = 0;
+        }
+    }
+    m_dnStage.release(stream);
+    m_dlv.release(stream);
+    m_slotCounter += count;
+    *ticket = m_dlv.uses();
+    return ok ? total : -2;
+}
 float SlotSession::timeOutputs(bool ragged, int count, int* samples, short* pcm, long long capacity, int reps, hipStream_t stream) {
     if (m_slotW <= 0 || count <= 0 || count > m_slotW || count > m_slotCounter || samples == NULL || pcm == NULL || reps <= 0) return -1.f;
     int* const dSamples = (int*)deliverTarget(samples);
@@ -948,6 +1191,7 @@ void SlotSession::end() {
     gpuErrChk(hipDeviceSynchronize());
     rateOff();
     denoiseOff();
+    m_chain = false;
     freeDev(m_slotDesc, m_slotFeat, m_slotSel, m_slotY, m_slotPcm, m_slotUpd, m_dlvDev, m_saveDev, m_scaleDev, m_primeDev, m_melDesc, m_melUpd,
             m_melColInfo, m_melStage);
     m_melStageBytes = 0;

@@ -13,6 +13,7 @@
 #include "slots.hpp"
 #include "slots_deliver.hpp"
 #include "slots_deliver_denoise.hpp"
+#include "slots_deliver_denoise_rate.hpp"
 #include "slots_deliver_rate.hpp"
 #include "slots_mel.hpp"
 #include "slots_prime.hpp"
@@ -259,7 +260,7 @@ public:
     // does not set its own: allocates the two images of the columns' STFT state (zeroed) and the staging; every column's stream
     // starts afresh at its next piece, that of a column already running too.  While it is on, slotsStep, slotsStepRagged and
     // slotsStepRaggedRate are refused (they would leave a hole in every stream), and so is a new geometry of `d`.  false (nothing
-    // changes): not in slot mode, a denoiser that is not set, rate delivery on (not built: both in one launch), a bad strength, a
+    // changes): not in slot mode, a denoiser that is not set, rate delivery on (both in one launch: setDenoiseRate), a bad strength, a
     // ragged step in flight, or the kernel's LDS opt-in refused.  Synchronises.  slotsBegin and slotsEnd turn it off.
     bool setDenoise(const Denoiser* d, float strength);
     bool denoiseOn() const { return m_dn != NULL; }
@@ -285,6 +286,25 @@ public:
     long long stepRaggedDenoise(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
                                 SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
                                 hipStream_t stream = 0);
+    // ---- ragged delivery through the denoiser and at the caller's rate (slots_deliver_denoise_rate.hpp) ----
+    // Both stages in one delivery launch: the denoiser `d` with `strength` as setDenoise has it, the resampler `r` (slot `index`
+    // of the handle) as setDelivery has it; r = NULL: off.  Allocates and zeroes the three state images (history, accumulator,
+    // tail of the cleaned stream), whose rows the other two modes share, and the staging; every column's stream starts afresh at
+    // its next piece.  While it is on, delivery(), tailLen(), tailGet / tailSet, denoiseOn(), setDenoiseStrength,
+    // denoiseStateBytes and denoiseStateGet / Set answer as under the single modes, every other step is refused, and so are
+    // setDelivery and setDenoise (either would leave half a mode).  false (nothing changes): not in slot mode, d or r not set,
+    // one of the single modes on, a bad strength, a ragged step in flight, more LDS than a workgroup has
+    // (slots_deliver_denoise_rate_lds), or the LDS opt-in refused.  Synchronises.  slotsBegin and slotsEnd turn it off.
+    bool setDenoiseRate(const Denoiser* d, const Resampler* r, int index, float strength);
+    bool denoiseRateOn() const { return m_chain; }
+    // PCM elements that always suffice for such a step of `count`; -1 when off or count is out of range
+    long long denoiseRateCapacity(int count) const;
+    // stepRaggedDenoise with the cleaned samples converted before they leave the chip: the same launches (sub-ranges included,
+    // all three state images flipping after each), piece p's outputs rate[p].m0 .. m0 + count - 1 of resample(denoise(stream)),
+    // numbered from the stream origin, at element rate[p].offset of `pcm`.  Returns and refuses as stepRaggedRate.
+    long long stepRaggedDenoiseRate(int count, int* samples, long long capacity, short* pcm, long long pcmCapacity, SlotPiece* pieces,
+                                    SlotRatePiece* rate, int maxPieces, int* nPieces, long long* pcmTotal, unsigned long long* ticket,
+                                    hipStream_t stream = 0);
     // Measurement only (scripts/slots_perf.py --serve): `reps` back-to-back output passes over the last `count` samples generated,
     // timed with events on `stream`; returns milliseconds for all of them, < 0 when refused.  ragged = false: what slotsStep
     // issues after the generation -- the PCM launches and the 2-D copies into samples / pcm [maxBatch][count]; ragged = true: the
@@ -359,7 +379,8 @@ private:
     RatePiece* m_rateDev = NULL;            // [maxBatch] on the device: the rate pieces of the step being delivered
     StageRing m_rateStage;                  // pinned host staging of them, as m_dlv
     // ... and delivery through the denoiser (slots_deliver_denoise.hpp); state rows and "starts afresh" are m_tailRow
-    // and m_tailZero, which rate delivery, never on at the same time, uses for its tails
+    // and m_tailZero, which rate delivery uses for its tails (the two are on together only under §6t, where m_tailZero is the
+    // stream's and the tails have m_zTailZero)
     const Denoiser* m_dn = NULL;            // the handle's denoiser in use (NULL: off)
     float m_dnDefault = 0.f;                // the strength of a column that has not set its own
     int m_dnCur = 0;                        // the state images the next launch reads; it writes the others
@@ -373,6 +394,14 @@ private:
     std::vector<DenoisePiece> m_dnPieces;   // (scratch of a step: the records of all its launches ...
     std::vector<DenoisePair> m_dnPairs;
     std::vector<int> m_dnPlan;              //  ... and per launch: first sample, pieces, those with frames, tiles)
+    // ... and through both (slots_deliver_denoise_rate.hpp): m_dn and m_rate are both set, the state is theirs
+    bool m_chain = false;
+    DenoiseRateGeom m_chainGeom = {};
+    long long m_chainSpan = 0;              // S: the span words of a tile
+    long long m_chainPairsMost = 0;         // the most (piece, block) pairs of one piece of one launch
+    std::vector<char> m_zTailZero;          // per column: the tail of its cleaned stream counts as zero (a resume whose tail was not set)
+    std::vector<DenoiseRatePiece> m_chainPieces;      // (scratch of a step, as m_dnPieces ...
+    std::vector<RatePair> m_chainPairs;               //  ... and the blocks of all its launches; m_dnPlan gets a fifth entry: these)
     // ... and the sampling temperatures (slots_sampler.hpp)
     std::vector<char> m_tempDirty;         // the columns whose table entry the next step writes
     std::vector<int> m_tempDirtyList;

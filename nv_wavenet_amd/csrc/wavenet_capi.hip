@@ -623,6 +623,21 @@ long long nvw_slots_step_ragged_denoise(nvw_engine* e, int count, int* samples, 
     return e->slots().stepRaggedDenoise(count, samples, capacity, pcm, pcm_capacity, (wn::SlotPiece*)pieces, (wn::SlotRatePiece*)rate,
                                         max_pieces, n_pieces, pcm_total, ticket, (hipStream_t)stream);
 }
+// ---- slot mode: denoised delivery at the caller's rate in one launch (additive within ABI 7) ----------------------------------------
+int nvw_slots_set_denoise_rate(nvw_engine* e, int slot, float strength) {
+    if (slot <= 3 && e->slots().setDenoiseRate(&e->denoiser, slot < 0 ? NULL : &e->resamplers[slot], slot < 0 ? -1 : slot, strength)) return 1;
+    fprintf(stderr, "nvw_slots_set_denoise_rate: refused, nothing changed (nvw_slots_begin, nvw_set_denoiser and nvw_set_resampler on slot %d "
+            "first; not with nvw_slots_set_delivery or nvw_slots_set_denoise on; a finite strength >= 0; no ragged step in flight; at most "
+            "%d bytes of LDS per workgroup)\n", slot, wn::kResampleLdsMax);
+    return 0;
+}
+long long nvw_slots_denoise_rate_capacity(nvw_engine* e, int count) { return e->slots().denoiseRateCapacity(count); }
+long long nvw_slots_step_ragged_denoise_rate(nvw_engine* e, int count, int* samples, long long capacity, short* pcm, long long pcm_capacity,
+                                             nvw_slot_piece* pieces, nvw_slot_rate_piece* rate, int max_pieces, int* n_pieces,
+                                             long long* pcm_total, unsigned long long* ticket, void* stream) {
+    return e->slots().stepRaggedDenoiseRate(count, samples, capacity, pcm, pcm_capacity, (wn::SlotPiece*)pieces, (wn::SlotRatePiece*)rate,
+                                            max_pieces, n_pieces, pcm_total, ticket, (hipStream_t)stream);
+}
 float nvw_slots_time_outputs(nvw_engine* e, int ragged, int count, int* samples, short* pcm, long long capacity, int reps, void* stream) {
     return e->slots().timeOutputs(ragged != 0, count, samples, pcm, capacity, reps, (hipStream_t)stream);
 }

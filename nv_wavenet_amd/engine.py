@@ -553,6 +553,36 @@ class WavenetEngine:
             raise ValueError("nvw_slots_step_ragged_denoise refused a step of %d samples into %d PCM elements" % (count, pcm.numel()))
         return int(total), int(pcm_total.value), pieces[:n.value], rate[:n.value], int(ticket.value)
 
+    # ---- denoised delivery at the caller's rate (include/nv_wavenet_c.h, "DENOISED DELIVERY AT THE CALLER'S RATE") ----
+    def slotsSetDenoiseRate(self, slot, strength=0.0):
+        """Denoised delivery at the rate of resampler `slot` in one launch, with `strength` for every column that does not set its
+        own (setDenoiser and setResampler(slot) first); slot None: off.  ValueError when refused (nothing changed): see
+        nvw_slots_set_denoise_rate."""
+        if not lib.nvw_slots_set_denoise_rate(self._h, -1 if slot is None else int(slot), float(strength or 0)):
+            raise ValueError("nvw_slots_set_denoise_rate refused slot %s, strength %s" % (slot, strength))
+
+    def slotsDenoiseRateCapacity(self, count):
+        """PCM elements that always suffice for slotsStepRaggedDenoiseRate(count); -1 when the mode is off."""
+        return int(lib.nvw_slots_denoise_rate_capacity(self._h, int(count)))
+
+    def slotsStepRaggedDenoiseRate(self, count, samples, pcm, stream=None):
+        """slotsStepRaggedRate with the denoiser in front of the resampler (nvw_slots_step_ragged_denoise_rate): the same arguments
+        and the same (total, pcm_total, pieces, rate, ticket), rate[p] = (m0, count, offset) of piece p's outputs in pcm."""
+        for a, dt, name in ((samples, "int32", "samples"), (pcm, "int16", "pcm")):
+            if a is not None or name == "pcm":
+                assert hasattr(a, "data_ptr") and (a.is_cuda or a.is_pinned()) and a.is_contiguous() and str(a.dtype) == "torch." + dt, \
+                    "%s: a contiguous CUDA or pinned %s tensor" % (name, dt)
+        pieces, rate = np.empty(self.maxBatch, dtype=SLOT_PIECE), np.empty(self.maxBatch, dtype=SLOT_RATE_PIECE)
+        n, ticket, pcm_total = C.c_int(0), C.c_ulonglong(0), C.c_longlong(0)
+        total = lib.nvw_slots_step_ragged_denoise_rate(self._h, int(count), addr(samples), samples.numel() if samples is not None else 0,
+                                                       addr(pcm), pcm.numel(), pieces.ctypes.data, rate.ctypes.data, self.maxBatch,
+                                                       C.byref(n), C.byref(pcm_total), C.byref(ticket), stream)
+        if total == -2:
+            raise RuntimeError("nvw_slots_step_ragged_denoise_rate: a launch of the step of %d samples failed" % count)
+        if total < 0:
+            raise ValueError("nvw_slots_step_ragged_denoise_rate refused a step of %d samples into %d PCM elements" % (count, pcm.numel()))
+        return int(total), int(pcm_total.value), pieces[:n.value], rate[:n.value], int(ticket.value)
+
     def slotsWait(self, ticket):
         """Blocks until the outputs of the ragged step with that ticket are complete."""
         if not lib.nvw_slots_wait(self._h, int(ticket)):

@@ -508,7 +508,9 @@ class NVWaveNetEngine(NVWaveNet):
         request's pieces concatenated are bit for bit resample() of its whole PCM.  denoise = strength: step_async delivers every
         request's PCM through the denoiser of set_denoiser, the STFT state carried from step to step; described by
         the same three arrays, and a request's pieces concatenated are bit for bit denoise() of its whole PCM (a request of n_fft / 2
-        samples or fewer comes unchanged).  submit(denoise_strength=) gives a request its own.  Not together with deliver_rate."""
+        samples or fewer comes unchanged).  submit(denoise_strength=) gives a request its own.  Both together: cleaned, then
+        converted, in one delivery launch; a request's pieces concatenated are bit for bit resample() of denoise() of
+        its whole PCM."""
         from .slots import SlotStream
         e = self._new_engine(columns, window, implementation)
         e.setConditioningWeights(cond_weight.float().contiguous(), cond_bias.float().contiguous())

@@ -296,6 +296,12 @@ def denoise_delivered(k, n_fft, hop):
     return max(0, q * hop - n_fft // 2)
 
 
+def denoise_rate_delivered(k, n_fft, hop, L, M, c):
+    """The composed count of denoised delivery at a rate (DESIGN.md §6t; wn::denoise_rate_delivered): the outputs that are out after
+    k samples of an unfinished stream -- those of the D(k) cleaned samples whose every input is among them."""
+    return rate_delivered(denoise_delivered(k, n_fft, hop), L, M, c)
+
+
 def denoise_hist_len(n_fft):
     """The PCM values of a column's input history: the first incomplete frame starts less than n_fft samples back (wn::denoise_hist_len)."""
     return n_fft
@@ -316,7 +322,9 @@ class SlotState:
     top_p = its tail cuts (words 12 and 13, likewise); tail = its filter history at the delivery rate (a numpy int16 array [H] of a
     stream made with deliver_rate; None: none -- a resume then goes on from a zero history, a discontinuity in the
     first H L / M + 1 outputs after the seam); denoise = its STFT state (a numpy uint8 array of nvw_slot_denoise_state_get of a stream
-    made with denoise=; None: none -- a resume then starts a new stream origin at done)."""
+    made with denoise=; None: none -- a resume then starts a new stream origin at done).  A stream made with both
+     carries both: tail is then the last H values of the cleaned stream, ignored in a resume without denoise (the
+    outputs are numbered from 0 again); with denoise but without tail the resume goes on from a zero history of the cleaned stream."""
 
     # to_bytes(): this record, then the blob's bytes (blob_bytes of them; 0: the request had not started)
     RECORD = struct.Struct("<4sIIiiIiI")     # magic, version, kind (0 features, 1 mel), frames, final, uid, done, blob_bytes
@@ -427,6 +435,11 @@ class SlotState:
             y[first:] = np.frombuffer(data, dtype="<i4", count=count, offset=at + cls.PRIME.size)
             prime, at = torch.from_numpy(y), at + cls.PRIME.size + 4 * count
             tail = len(data) - at
+        if tail >= cls.TAIL.size and data[at:at + 4] == cls.TAIL_MAGIC:
+            end = at + cls.TAIL.size + 2 * cls.TAIL.unpack_from(data, at)[1]
+            if data[end:end + 4] == cls.DENOISE_MAGIC:      # (a state with both, DESIGN.md §6t: the history, then the denoise state)
+                history = np.frombuffer(data, dtype="<i2", count=(end - at - cls.TAIL.size) // 2, offset=at + cls.TAIL.size).copy()
+                at, tail = end, len(data) - end
         if tail >= cls.DENOISE.size and data[at:at + 4] == cls.DENOISE_MAGIC:
             size = cls.DENOISE.unpack_from(data, at)[1]
             if tail != cls.DENOISE.size + size:
@@ -470,8 +483,8 @@ class StepOutput:
     A stream made with deliver_rate delivers its PCM at that rate: request i's PCM is pcm[pcm_offsets[i] :
     pcm_offsets[i] + pcm_lengths[i]], outputs pcm_first[i] .. of its utterance (a length may be 0); the samples stay at the model's
     rate under offsets and lengths.  A stream made with denoise delivers its PCM through the denoiser, described
-    in the same way: outputs pcm_first[i] .. of the request's denoised stream.  Without either, the three are offsets, lengths and
-    the pieces' first samples."""
+    in the same way: outputs pcm_first[i] .. of the request's denoised stream; one made with both the denoised
+    stream at the delivery rate.  Without either, the three are offsets, lengths and the pieces' first samples."""
 
     def __init__(self, handles, offsets, lengths, samples, pcm, finished, pcm_offsets=None, pcm_lengths=None, pcm_first=None):
         self.handles, self.offsets, self.lengths, self.samples, self.pcm, self.finished = handles, offsets, lengths, samples, pcm, finished
@@ -552,16 +565,16 @@ class SlotStream:
         self._compact = bool(compact)
         engine.slotsBegin(self.window)
         # deliver: the engine's resampler slot through which step_async delivers its PCM at the caller's rate
-        self._rate = deliver is not None
-        if self._rate:
-            if not pcm:
-                raise ValueError("deliver needs pcm=True")
-            engine.slotsSetDelivery(deliver)
         # denoise: the strength at which step_async delivers its PCM through the engine's denoiser (setDenoiser)
-        self._dn = denoise is not None
-        if self._dn:
-            if not pcm or self._rate:
-                raise ValueError("denoise needs pcm=True and no deliver: the two deliveries exclude each other")
+        # both: cleaned, then converted, in one delivery launch
+        self._rate, self._dn = deliver is not None, denoise is not None
+        if (self._rate or self._dn) and not pcm:
+            raise ValueError("deliver and denoise need pcm=True")
+        if self._rate and self._dn:
+            engine.slotsSetDenoiseRate(deliver, denoise)
+        elif self._rate:
+            engine.slotsSetDelivery(deliver)
+        elif self._dn:
             engine.slotsSetDenoise(denoise)
         self._dn_strength = {}                         # handle -> strength of the requests (queued or running) submitted with one
         self._free = list(range(self.columns))         # a heap: lowest free column first
@@ -1062,8 +1075,8 @@ class SlotStream:
         """Queued requests into free columns, lowest first, while the head of the queue is ready for a step of `count` samples."""
         listed = []      # (column, state, source, samples | frames, final | None) of the resumes that go to the engine as lists
         primed = []      # (column, handle) of the admitted requests that carry a prime
-        tails = []       # (column, filter history) of the resumed requests that carry one, where the stream delivers at a rate; where it
-                         # denoises, (column, denoise state)
+        tails = []       # (setter, column, filter history) of the resumed requests that carry one, where the stream delivers at a rate;
+                         # where it denoises, (setter, column, denoise state); where it does both, either
         strengths = []   # (column, strength) of the admitted requests submitted with a denoise strength
         wanted = []      # (column, Sampling, what the start or the resume leaves) likewise, where the two differ: a start leaves OFF, a
                          # resume words 10 to 13 of the blob (11 to 13 zero in a prefilled or scored one)
@@ -1077,9 +1090,9 @@ class SlotStream:
             by_list = blob is not None and (state.buffer is not None or not getattr(blob, "is_cuda", True))
             self._src[handle] = (x, uid)
             if self._rate and blob is not None and state.tail is not None:
-                tails.append((col, state.tail))
+                tails.append((self.engine.slotTailSet, col, state.tail))
             if self._dn and blob is not None and state.denoise is not None:
-                tails.append((col, state.denoise))
+                tails.append((self.engine.slotDenoiseStateSet, col, state.denoise))
             elif handle in self._dn_strength:
                 strengths.append((col, self._dn_strength[handle]))
             if handle in self._prime:
@@ -1110,8 +1123,8 @@ class SlotStream:
                 self._deliv[col] = req[3] if req is not None else 0
         if listed:
             self._resume_listed(listed)
-        for col, tail in tails:      # (resume, then its history: a resume starts the column from a zero one)
-            (self.engine.slotDenoiseStateSet if self._dn else self.engine.slotTailSet)(col, tail)
+        for setter, col, tail in tails:      # (resume, then its history: a resume starts the column from a zero one)
+            setter(col, tail)
         for col, strength in strengths:
             self.engine.slotSetDenoiseStrength(col, strength)
         # start, then set (the engine applies both at the step that follows): every temperature, every floor, then the cuts by column
@@ -1225,7 +1238,9 @@ class SlotStream:
         buf = self._last_buf ^ 1      # (never the buffer of a pending step: at most one is pending here, and it was issued last)
         need = len(self._running) * ((count + 7) & ~7)
         own = self._rate or self._dn      # (the PCM has lengths of its own)
-        most = self.engine.slotsRateCapacity(count) if self._rate else self.engine.slotsDenoiseCapacity(count) if self._dn else 0
+        e = self.engine
+        most = e.slotsDenoiseRateCapacity(count) if self._rate and self._dn else e.slotsRateCapacity(count) if self._rate else \
+            e.slotsDenoiseCapacity(count) if self._dn else 0
         need_pcm = len(self._running) * (most // self.columns) if own else need
         if self._bufs[buf] is None or self._bufs[buf][0].size < need or (own and self._bufs[buf][1].size < need_pcm):
             keep = self.engine.slotsPinned(max(need, 8), self.pcm)
@@ -1237,7 +1252,8 @@ class SlotStream:
         y, pcm = self._bufs_keep[buf]
         rate = pcm_total = None
         if own:
-            total, pcm_total, pieces, r, ticket = (self.engine.slotsStepRaggedRate if self._rate else self.engine.slotsStepRaggedDenoise)(count, y, pcm)
+            step = e.slotsStepRaggedDenoiseRate if self._rate and self._dn else e.slotsStepRaggedRate if self._rate else e.slotsStepRaggedDenoise
+            total, pcm_total, pieces, r, ticket = step(count, y, pcm)
             rate = (r["offset"].copy(), r["count"].astype(np.int64), r["m0"].copy())
         else:
             total, pieces, ticket = self.engine.slotsStepRagged(count, y, pcm)

@@ -160,6 +160,7 @@ def main():
     ap.add_argument("--rate", action="store_true", help="time the ragged step with plain delivery against rate delivery at 2 / 1 and 147 / 80")
     ap.add_argument("--denoise", action="store_true", help="time one nvw_denoise launch for --batch one-second utterances at 1024 / 256")
     ap.add_argument("--denoise-deliver", action="store_true", help="time the ragged step with plain delivery, with denoised delivery at 1024 / 256, and with plain delivery followed by a per-step nvw_denoise")
+    ap.add_argument("--denoise-rate", action="store_true", help="time the ragged step with denoised delivery at 1024 / 256, with denoised delivery at 320 / 147 in one launch, and with denoised delivery followed by a per-step nvw_resample")
     ap.add_argument("--parent", action="store_true", help="time the plain and the ragged slot step of the parent commit and of this one")
     ap.add_argument("--min-p", action="store_true", help="time the slot step of the parent commit, of this one at floor 0 and at mixed probability floors")
     ap.add_argument("--cut", action="store_true", help="time the slot step of the parent commit (plain, mixed floors) and of this one with everything off, floors only, top-k, top-p and both")
@@ -181,6 +182,10 @@ def main():
     if args.denoise_deliver:
         for chunk in [int(c) for c in args.chunks.split(",")]:
             print(json.dumps(time_denoise_deliver(args, w, Wc, bc, chunk)), flush=True)
+        return
+    if args.denoise_rate:
+        for chunk in [int(c) for c in args.chunks.split(",")]:
+            print(json.dumps(time_denoise_rate(args, w, Wc, bc, chunk)), flush=True)
         return
     if args.rate:
         for chunk in [int(c) for c in args.chunks.split(",")]:
@@ -1301,6 +1306,81 @@ def time_denoise_deliver(args, w, Wc, bc, chunk):
     e.close()
     return {"batch": B, "chunk": chunk, "window": W, "n_fft": n_fft, "hop": hop, "rounds": args.rounds, "steps_per_round": steps,
             "ms_per_step": {name: _stats(v) for name, v in ms.items()}, "device": torch.cuda.get_device_name(0)}
+
+
+def time_denoise_rate(args, w, Wc, bc, chunk):
+    """The --denoise-rate measurement: one session with every column busy, n_fft 1024 / hop 256, 22.05 kHz to 48 kHz (320 / 147); per
+    round, alternating, `steps` ragged steps of `chunk` samples (events around them, one warm-up step first) with denoised delivery
+    into pinned memory (nvw_slots_step_ragged_denoise, the parent's path), with denoised delivery at the rate in one launch
+    (nvw_slots_step_ragged_denoise_rate), and with the path that replaces: denoised delivery into device memory, the pieces appended
+    to per-column streams, one nvw_resample launch for the outputs that the cleaned samples newly allow, and their copy into pinned
+    memory; milliseconds per step."""
+    import torch
+    import bench
+    from nv_wavenet_amd._lib import lib
+    from nv_wavenet_amd.engine import RESAMPLE_REQ
+    from nv_wavenet_amd.nv_wavenet import resample_taps
+    from nv_wavenet_amd.slots import denoise_delivered, rate_delivered
+    B, W, steps, n_fft, hop = args.batch, args.window, max(2, args.steps), 1024, 256
+    L, M, taps = resample_taps(22050, 48000)
+    c = (len(taps) - 1) // 2
+    cases = ("denoised", "denoised_rate", "denoised_then_resample")
+    src = torch.randn(bench.N_COND, 65536, device="cuda", generator=torch.Generator(device="cuda").manual_seed(7)).half()
+    assert args.rounds * len(cases) * (steps + 1) * chunk <= src.size(1)
+    e = bench.build_engine(w, B, W)
+    e.setConditioningWeights(Wc, bc)
+    e.setSelectorSeed(5)
+    e.setDenoiser(n_fft, hop, np.abs(np.random.default_rng(37).standard_normal(n_fft // 2 + 1)).astype(np.float32) * 2000 * 32)
+    e.setResampler(0, L, M, taps)
+    e.slotsBegin(W)
+    for b in range(B):
+        e.slotStart(b, src, b)
+    y, _ = e.slotsPinned(B * chunk, pcm=False)
+    pitch, most = (steps + 1) * chunk, -(-(chunk + hop) * L // M) + 1
+    streams = torch.zeros(B, pitch, dtype=torch.int16, device="cuda")
+    converted = torch.empty(B, most, dtype=torch.int16, device="cuda")
+    converted_host = torch.empty(B, most, dtype=torch.int16, pin_memory=True)
+    reqs = np.zeros(B, dtype=RESAMPLE_REQ)
+    reqs["in"], reqs["out"] = streams.data_ptr() + 2 * pitch * np.arange(B), converted.data_ptr() + 2 * most * np.arange(B)
+    reqs["in_type"], reqs["out_type"] = 16, 16
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = {name: [] for name in cases}
+    for _ in range(args.rounds):
+        for name in cases:
+            e.slotsSetDenoiseRate(None)
+            e.slotsSetDenoise(None)
+            if name == "denoised_rate":
+                e.slotsSetDenoiseRate(0, 0.1)
+                pcm = torch.empty(e.slotsDenoiseRateCapacity(chunk), dtype=torch.int16, pin_memory=True)
+            else:
+                e.slotsSetDenoise(0.1)
+                pcm = torch.empty(e.slotsDenoiseCapacity(chunk), dtype=torch.int16, **({"pin_memory": True} if name == "denoised" else {"device": "cuda"}))
+            for k in range(steps + 1):
+                if k == 1:
+                    torch.cuda.synchronize()
+                    ev[0].record()
+                if name == "denoised_rate":
+                    e.slotsStepRaggedDenoiseRate(chunk, y, pcm)
+                    continue
+                e.slotsStepRaggedDenoise(chunk, y, pcm)
+                if name == "denoised_then_resample":      # (every column delivers the same outputs: the pieces are rows, 8-aligned)
+                    t0, t1 = denoise_delivered(k * chunk, n_fft, hop), denoise_delivered((k + 1) * chunk, n_fft, hop)
+                    m0, m1 = rate_delivered(t0, L, M, c), rate_delivered(t1, L, M, c)
+                    if t1 > t0:
+                        row = (t1 - t0 + 7) & ~7
+                        streams[:, t0:t1].copy_(pcm[:B * row].view(B, row)[:, :t1 - t0])
+                    if m1 > m0:
+                        reqs["n_in"], reqs["m0"], reqs["count"] = t1, m0, m1 - m0
+                        assert lib.nvw_resample(e._h, 0, reqs.ctypes.data, B, None) == B
+                        converted_host[:, :m1 - m0].copy_(converted[:, :m1 - m0], non_blocking=True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms[name].append(ev[0].elapsed_time(ev[1]) / steps)
+    e.slotsSetDenoiseRate(None)
+    e.slotsEnd()
+    e.close()
+    return {"batch": B, "chunk": chunk, "window": W, "n_fft": n_fft, "hop": hop, "up": L, "down": M, "rounds": args.rounds,
+            "steps_per_round": steps, "ms_per_step": {name: _stats(v) for name, v in ms.items()}, "device": torch.cuda.get_device_name(0)}
 
 
 def time_serve(args, w, Wc, bc, load, chunk):
